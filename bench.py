@@ -10,6 +10,9 @@ packets, the full RP2350 11-channel chain (preamp, loudness, 10-band master PEQ,
     python bench.py --gpus N                N ranks on one node: spawned here (torchrun) when not already under a launcher
     python bench.py --scaling strong        65 536 streams in total, split over the ranks (dspi_amd/shard.py)
     python bench.py --config {2,2b,5,perstream,perstream_eq,pdm,spdif,i2s}     the other BASELINE configs / SURVEY section 8f consumers, same JSON shape
+    python bench.py --dump-outputs DIR      also write the last timed step's outputs (a fixed, seeded sample) as DIR/<name>.npy, float64
+    python bench.py --full                  everything the line can carry (below); without it a run sets up, warms up, times --steps
+                                            steps and prints the headline
 
 Multi-GPU: one process per GPU, streams sharded per rank, no data-path collective; RCCL only for the barrier and the
 max-over-ranks time.  DSPI_BENCH_BACKEND=gloo lets the ranks share GPUs (control-flow smoke test on a 1-GPU box).
@@ -18,7 +21,7 @@ What a line says (config 3):
   value       frames/s x 11 channels, whole job, on the PRIMARY variant: float contract `--contract` (default fma = the firmware
               as built: GCC's contracted multiply-adds, include/dspi.h DSPI_FLOAT_CONTRACT_FMA), word layout `--out-layout`,
               input = SURVEY section 8d's synthetic mix (70 % noise / 10 % sweep / 10 % bursts / 5 % silence / 5 % square)
-  also        the same step measured on the other variants (other contract, other layout, white-noise input), N=1 only
+  also        (--full) the same step measured on the other variants (other contract, other layout, white-noise input), N=1 only
   roofline    algorithmic HBM bytes / measured kernel time against 8 TB/s.  `frac` is the STRICT figure: the bytes a launch of T frames must
               move when the lines keep the reference's history exactly — compulsory I/O + 4 B per delayed output for the launch's first
               min(dly, T) frames (line reads) + 4 B for its last min(line length, T) frames (line writes): 77 B/frame for config 3 at 50
@@ -26,10 +29,11 @@ What a line says (config 3):
               read) and `frac_launch_span` (8d's lower figure, 8 * min(dly, T) / T: 59.4 B).  `traffic_ratio` = counter bytes / the
               strict bytes.  The chain is on the VALU side of the ridge: `valu_fraction_at_sclk` is the issue fraction at the clock the
               socket's power limit allows; `binds` says "power" when that clock is below 0.9 x the part's maximum.
-  configs     (default run, N=1) short driver-timed runs of BASELINE configs 2, 2b and 5, each with its own roofline and its own
+  configs     (--full, default configuration, N=1) short driver-timed runs of BASELINE configs 2, 2b and 5, each with its own roofline and its own
               post-run oracle check; `value` stays config 3
-  cpu_baseline  the reference C path on this box's host cores (a reported baseline, not the target)
-  realtime_call  (default configuration, N=1) the call as the firmware makes it: ONE packet per dspi_process(), host buffers, one stream
+  cpu_baseline  (--full) the reference C path on the host cores (a reported baseline, not the target)
+  parity_checked  (--full) streams of the timed context checked bit-for-bit against the CPU oracle after the run; 0 without --full
+  realtime_call  (--full, default configuration, N=1) the call as the firmware makes it: ONE packet per dspi_process(), host buffers, one stream
               of the same preset, through the C host (dspi_host -rt): p50 / p99 us per call, every word of every call checked against
               the oracle.  Reported beside the batched figure; never part of `value`.  `realtime_call_q28`: the same for the RP2040 Q28
               flavour (one 48-frame packet at 48 kHz, BASELINE config 5's preset).
@@ -146,7 +150,7 @@ class PowerSampler:
 
     def window(self, t0, t1):
         """mean / max over the samples taken in [t0, t1] (perf_counter times) plus the first one after it.  The caller has kept the device
-        under the same load for >= 0.6 s before t0 (timed_steps: untimed pre-load steps), so the whole window is the settled state."""
+        under the same load for >= 0.6 s before t0 at the BASELINE configs' sizes (preload_steps), so the whole window is the settled state."""
         w = [x for x in self.samples if t0 <= x[0] <= t1 + 0.02]
         if not w: return None
         pw = [x[1] for x in w]; ck = [x[2] for x in w if x[2]]
@@ -329,7 +333,7 @@ def latest_power_model():
 
 def side_run(extra, env=None, timeout=600):
     """bench.py run again as a child (same box, minutes apart) for one more variant of config 3: returns the child's line (dict) or an error record."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-variants", "--no-realtime", "--no-configs", "--no-side-runs"] + extra
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-variants", "--no-realtime", "--no-configs", "--no-side-runs"] + extra
     e = dict(os.environ, **(env or {}))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DSPI_BENCH_FORCE_DIST"): e.pop(k, None)
     try:
@@ -357,6 +361,60 @@ def rt_record(what, r):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step, for output-for-output comparison of two builds
+# ---------------------------------------------------------------------------------------------------------------------
+DUMP_BYTES = 60_000_000      # float64 bytes per dump, below the 64 MB cap
+DUMP_SEED = 20240
+
+
+def dump_chain_outputs(out_dir, torch, pairs, sub, peaks, tiled, R, S, P, frames, nb, n_out):
+    """A fixed, seeded sample of streams (at most 128, as many as DUMP_BYTES allows), stream-major whatever the word layout:
+    pairs [k][pair][frame][2], sub [k][frame], peaks [k][packet][2 + outputs], streams [k] (the context's stream indices), packets [m]
+    (the packets dumped: all of them, or the launch's last m when one stream's words alone would exceed DUMP_BYTES)."""
+    B = frames // nb
+    per_packet = 8 * (B * (2 * P + 1) + 2 + n_out)
+    m = min(nb, DUMP_BYTES // per_packet)
+    assert m >= 1, "one packet of one stream exceeds the dump's cap"
+    k = min(S, 128, DUMP_BYTES // (m * per_packet))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(S, size=k, replace=False))
+    f0 = (nb - m) * B
+    dev = pairs.device
+    if tiled:      # [tile][output][frame][R] -> [k][pair][frame][2]; [tile][frame][R] -> [k][frame]
+        t = torch.as_tensor(idx // R, device=dev); r = torch.as_tensor(idx % R, device=dev)
+        p = pairs[t, :, f0:, r].reshape(k, P, 2, m * B).transpose(2, 3)
+        s = sub[t, f0:, r]
+    else:
+        i = torch.as_tensor(idx, device=dev)
+        p, s = pairs[i, :, f0:], sub[i, f0:]
+    arrays = {"pairs": p, "sub": s, "peaks": peaks[torch.as_tensor(idx, device=dev), nb - m:], "streams": torch.as_tensor(idx),
+              "packets": torch.arange(nb - m, nb)}
+    write_dump(out_dir, arrays)
+
+
+def dump_flat_output(out_dir, torch, words, name):
+    """A fixed, seeded sample of the words of a flat output buffer: DIR/<name>.npy and the sampled positions, DIR/<name>_index.npy."""
+    n = min(words.numel(), DUMP_BYTES // 16)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, words.numel(), size=n))
+    write_dump(out_dir, {name: words.reshape(-1)[torch.as_tensor(idx, device=words.device)], name + "_index": torch.as_tensor(idx)})
+
+
+def write_dump(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float64))      # (int32 words and int64 indices are exact in float64)
+
+
+def config_args(args, name, steps, warm):
+    """The arguments of one of the short BASELINE config runs that follow config 3 in a --full line.  They never dump: --dump-outputs is
+    the headline's last timed step, and these runs would overwrite it."""
+    a2 = argparse.Namespace(**vars(args))
+    a2.config, a2.steps, a2.warmup, a2.no_variants, a2.no_realtime, a2.no_cpu_baseline = name, steps, warm, True, True, True
+    a2.contract, a2.out_layout, a2.input = "fma", "stream", "mix"
+    a2.dump_outputs = None
+    return a2
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 def free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close()
     return p
@@ -381,7 +439,16 @@ def main():
     ap.add_argument("--no-parity", action="store_true", help="skip the post-run oracle check of the timed context (profiling runs)")
     ap.add_argument("--no-configs", action="store_true", help="default run: skip the short runs of BASELINE configs 2, 2b and 5 that follow config 3")
     ap.add_argument("--no-side-runs", action="store_true", help="default run: skip the child runs (200 packets per launch on tiled words; the previous round's library on this box)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the other variants, BASELINE configs 2 / 2b / 5, the child runs, the one-packet-per-call "
+                         "figures, the CPU baseline and the post-run oracle check (each still subject to its --no-* switch).  Off: the run sets up, "
+                         "warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64; a fixed, seeded "
+                         "sample of streams or words, at most 64 MB in all)")
     args = ap.parse_args()
+    if not args.full:      # a plain run: only what the headline figure needs
+        args.no_cpu_baseline = args.no_variants = args.no_realtime = args.no_parity = args.no_configs = args.no_side_runs = True
 
     # ---- N ranks without an external launcher: become the launcher ----
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -428,9 +495,7 @@ def main():
     if args.config == "3" and world == 1 and out is not None and not args.no_configs and not args.streams and not args.blocks_per_step:
         out["configs"] = {}
         for name, steps, warm in (("2", 5, 2), ("2b", 5, 2), ("5", 20, 3)):
-            a2 = argparse.Namespace(**vars(args))
-            a2.config, a2.steps, a2.warmup, a2.no_variants, a2.no_realtime, a2.no_cpu_baseline = name, steps, warm, True, True, True
-            a2.contract, a2.out_layout, a2.input = "fma", "stream", "mix"
+            a2 = config_args(args, name, steps, warm)
             try:
                 r = bench_chain(a2, torch, dev, rank, world, None, backend, Dspi, W, stream_range)
                 out["configs"][name] = {"workload": r["config"]["workload"], "dtype": r["dtype"], "steps": steps, "warmup": warm, "preload_steps": r["config"].get("preload_steps", 0),
@@ -453,23 +518,26 @@ def main():
         dist.destroy_process_group()
 
 
-def timed_steps(args, torch, dist, backend, dev, ctx, step, min_load_s=0.0):
-    """W untimed steps, then exactly K steps between barrier + synchronize on both sides; MAX over ranks.
-    min_load_s: when the W warm-up steps are shorter than this, further UNTIMED steps follow them ("preload_steps") until the device has
-    been under this load for that long — socket power and shader clock need ~0.5 s to settle, and the sampler's window is the timed region."""
-    tw = time.perf_counter()
-    for _ in range(args.warmup):
+PRELOAD_FRAMES = 2.7e10      # stream-frames of warm-up + pre-load: >= 0.6 s for BASELINE configs 3, 2 and 2b on one MI355X (see preload_steps)
+
+
+def preload_steps(stream_frames_per_step, warmup):
+    """UNTIMED steps after the W warm-up steps, so that the device has been under the timed load for >= 0.6 s before the timed region
+    (socket power and shader clock need ~0.5 s to settle, and the power sampler's window is the timed region).  A count fixed by the
+    workload's size, not by a clock: the chain carries state from launch to launch, so the timed context's history, and with it
+    every word its last step writes (--dump-outputs), is the same on every run with the same arguments.  At the step times measured
+    for them (DESIGN.md section 6): config 3, 86 launches of 9.65 ms = 0.83 s; configs 2 / 2b, 69 launches of 9.8 / 8.8 ms = 0.68 / 0.61 s;
+    config 5, the cap of 400 steps at 3.46 ms = 1.4 s.  Contexts of a few thousand streams reach the cap well before 0.6 s, as they
+    did when the count was timed (the same cap)."""
+    return min(400, max(0, -(-int(PRELOAD_FRAMES) // int(stream_frames_per_step)) - warmup))
+
+
+def timed_steps(args, torch, dist, backend, dev, ctx, step, preload=0):
+    """W untimed steps and `preload` more (preload_steps), then exactly K steps between barrier + synchronize on both sides; MAX over ranks."""
+    for _ in range(args.warmup + preload):
         step()
     ctx.sync()
-    tw = time.perf_counter() - tw
-    extra = 0
-    if min_load_s > 0.0 and tw < min_load_s:
-        per = tw / max(1, args.warmup) if args.warmup else 0.01
-        extra = min(400, int((min_load_s - tw) / max(per, 1e-4)) + 1)
-        for _ in range(extra):
-            step()
-        ctx.sync()
-    timed_steps.preload_steps = extra
+    timed_steps.preload_steps = preload
     ev = HipEvents(ctx.hip_stream())
     e0, e1 = ev.new(), ev.new()
     if dist: dist.barrier()
@@ -562,7 +630,7 @@ def bench_chain(args, torch, dev, rank, world, dist, backend, Dspi, W, stream_ra
         return {"parity_checked": len(sample), "parity_streams": [first + s for s in sample], "parity_launches_replayed": launches,
                 "parity_what": "every pair word, sub word, peak of the timed context's last launch + the status bytes, bit-exact vs the CPU oracle", "parity_s": time.perf_counter() - t0}
 
-    def measure(contract, layout, inp, check=False, enabled_only=None):
+    def measure(contract, layout, inp, check=False, enabled_only=None, dump=None):
         fma = (contract == "fma") and flavor == 1
         ctx = Dspi(flavor, S, device=dev.index, fma=fma)
         ctx.set_rate(FS); ctx.set_volume(w["vol"])
@@ -576,13 +644,14 @@ def bench_chain(args, torch, dev, rank, world, dist, backend, Dspi, W, stream_ra
         pcm = pcm_cache[inp]
         tiled = layout == "tiled"
         R = ctx.tile_streams(); tiles = (S + R - 1) // R
+        alloc = torch.zeros if dump else torch.empty      # (a dump must not carry the words a launch leaves unwritten: DSPI_OUT_ENABLED_ONLY, no peaks)
         if tiled:      # [tile][output][frame][R] / [tile][frame][R]  (include/dspi.h, DSPI_OUT_TILED)
-            pairs = torch.empty((tiles, 2 * P, frames, R), dtype=torch.int32, device=dev)
-            sub = torch.empty((tiles, frames, R), dtype=torch.int32, device=dev)
+            pairs = alloc((tiles, 2 * P, frames, R), dtype=torch.int32, device=dev)
+            sub = alloc((tiles, frames, R), dtype=torch.int32, device=dev)
         else:          # [stream][pair][frame][2] / [stream][frame]  (usb_audio.c:934-940)
-            pairs = torch.empty((S, P, frames, 2), dtype=torch.int32, device=dev)
-            sub = torch.empty((S, frames), dtype=torch.int32, device=dev)
-        peaks = torch.empty((S, NB, 2 + N), dtype=torch.int16, device=dev)
+            pairs = alloc((S, P, frames, 2), dtype=torch.int32, device=dev)
+            sub = alloc((S, frames), dtype=torch.int32, device=dev)
+        peaks = alloc((S, NB, 2 + N), dtype=torch.int16, device=dev)
         no_peaks = os.environ.get("DSPI_BENCH_NO_PEAKS") == "1"      # development: the per-packet peak array not requested (traffic accounting)
         torch.cuda.synchronize()
         smi = PowerSampler(dev.index) if check else None
@@ -590,9 +659,11 @@ def bench_chain(args, torch, dev, rank, world, dist, backend, Dspi, W, stream_ra
         elapsed, kernel_ms = timed_steps(args, torch, dist, backend, dev, ctx,
                                          lambda: ctx.process_device(pcm.data_ptr(), NB, B, 16, pairs.data_ptr(), sub.data_ptr(), 0 if no_peaks else peaks.data_ptr(), tiled=tiled,
                                                                     enabled_only=bool(w.get("enabled_only")) if enabled_only is None else enabled_only),
-                                         min_load_s=0.6 if (smi and smi.ok) else 0.0)
+                                         preload=preload_steps(S * frames, args.warmup) if check else 0)
         preload = timed_steps.preload_steps
         if smi: smi.stop()
+        if dump and rank == 0:
+            dump_chain_outputs(dump, torch, pairs, sub, peaks, tiled, R, S, P, frames, NB, N)
         plan = ctx.launch_plan()
         # whole job: frames of all ranks / the slowest rank's time — sum and max over ranks, 2 x 8 bytes over RCCL
         from dspi_amd.shard import reduce_throughput, gather_ranks
@@ -628,7 +699,7 @@ def bench_chain(args, torch, dev, rank, world, dist, backend, Dspi, W, stream_ra
         torch.cuda.empty_cache()
         return m
 
-    primary = measure(args.contract, args.out_layout, args.input, check=True)
+    primary = measure(args.contract, args.out_layout, args.input, check=True, dump=args.dump_outputs)
     also = []
     if world == 1 and not args.no_variants:
         other_contract = [("canonical" if args.contract == "fma" else "fma")] if flavor == 1 else []
@@ -812,30 +883,35 @@ def bench_consumer(args, torch, dev, rank, world, dist, backend):
     ctx.set_rate(96000)
     R = ctx.tile_streams(); nt = (S + R - 1) // R
     tiled = args.out_layout == "tiled"
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234 + rank)      # the same inputs on every run with the same arguments (--dump-outputs compares builds)
+    alloc = torch.zeros if args.dump_outputs else torch.empty
     if args.config == "pdm":
-        sub = torch.randint(-(1 << 27), 1 << 27, (nt, F, R) if tiled else (S, F), dtype=torch.int32, device=dev)
-        words = torch.empty((nt * R if tiled else S) * F * 8, dtype=torch.int32, device=dev)
+        sub = torch.randint(-(1 << 27), 1 << 27, (nt, F, R) if tiled else (S, F), dtype=torch.int32, device=dev, generator=g)
+        words = alloc((nt * R if tiled else S) * F * 8, dtype=torch.int32, device=dev)
         step = lambda: ctx.pdm_device(sub.data_ptr(), F, words.data_ptr(), tiled=tiled)
         per_unit_bytes, unit_name, units = 36.0, "sub samples", S * F
         text = "SURVEY 8f-2: PDM sigma-delta modulator (256x oversampled, 2nd order, noise-shaped dither), 65 536 streams x 2 400 Q28 samples per call"
         kernel, bound = "pdm_kernel", "valu (integer)"
     elif args.config == "i2s":
         n_in = (nt * R if tiled else S) * 4 * F * 2
-        pairs = torch.randint(-(1 << 23), 1 << 23, (n_in,), dtype=torch.int32, device=dev)
-        outb = torch.empty(n_in, dtype=torch.int32, device=dev)
+        pairs = torch.randint(-(1 << 23), 1 << 23, (n_in,), dtype=torch.int32, device=dev, generator=g)
+        outb = alloc(n_in, dtype=torch.int32, device=dev)
         step = lambda: ctx.i2s_device(pairs.data_ptr(), F, 0xF, outb.data_ptr(), tiled=tiled)
         per_unit_bytes, unit_name, units = 64.0, "stream-frames (4 pairs)", S * F
         text = "SURVEY 8f-3: I2S slot words (left-justified 24-bit in 32-bit slots), 65 536 streams x 4 pairs x 2 400 frames per call"
         kernel, bound = "i2s_kernel", "hbm"
     else:
         n_in = (nt * R if tiled else S) * 4 * F * 2
-        pairs = torch.randint(-(1 << 23), 1 << 23, (n_in,), dtype=torch.int32, device=dev)
-        outb = torch.empty(n_in * 2, dtype=torch.int32, device=dev)
+        pairs = torch.randint(-(1 << 23), 1 << 23, (n_in,), dtype=torch.int32, device=dev, generator=g)
+        outb = alloc(n_in * 2, dtype=torch.int32, device=dev)
         step = lambda: ctx.spdif_device(pairs.data_ptr(), F, 0, outb.data_ptr(), tiled=tiled)
         per_unit_bytes, unit_name, units = 96.0, "stream-frames (4 pairs)", S * F
         text = "SURVEY 8f-3: IEC-60958 subframe encoder, 65 536 streams x 4 pairs x 2 400 frames per call"
         kernel, bound = "spdif_kernel", "hbm"
     elapsed, kernel_ms = timed_steps(args, torch, dist, backend, dev, ctx, step)
+    if args.dump_outputs and rank == 0:
+        dump_flat_output(args.dump_outputs, torch, words if args.config == "pdm" else outb, args.config)
     ctx.close()
     if rank != 0:
         return None

@@ -78,3 +78,76 @@ def test_source_fingerprint_tracks_the_kernel_sources(tmp_path):
     assert len({f0, f1, host.source_fingerprint(pkg), a}) == 4
     p = bench.latest_profile("chain3", "fma", "stream")
     if p is not None: assert "src_sha16" in p
+
+
+def test_dump_outputs_sample_is_layout_independent_and_capped(tmp_path):
+    """--dump-outputs: the same seeded streams, stream-major, whichever word layout the timed path wrote; float64; under 64 MB."""
+    S, P, R, frames, nb, n_out = 300, 4, 64, 96, 2, 9
+    g = torch.Generator().manual_seed(5)
+    pairs = torch.randint(-(1 << 23), 1 << 23, (S, P, frames, 2), dtype=torch.int32, generator=g)
+    sub = torch.randint(-(1 << 30), 1 << 30, (S, frames), dtype=torch.int32, generator=g)
+    peaks = torch.randint(0, 1 << 15, (S, nb, 2 + n_out), dtype=torch.int16, generator=g)
+    tiles = (S + R - 1) // R
+    tp = torch.zeros((tiles * R, P, frames, 2), dtype=torch.int32); tp[:S] = pairs      # [tile][output][frame][R]
+    tp = tp.reshape(tiles, R, P, frames, 2).permute(0, 2, 4, 3, 1).reshape(tiles, 2 * P, frames, R).contiguous()
+    ts = torch.zeros((tiles * R, frames), dtype=torch.int32); ts[:S] = sub
+    ts = ts.reshape(tiles, R, frames).permute(0, 2, 1).contiguous()                       # [tile][frame][R]
+    bench.dump_chain_outputs(str(tmp_path / "s"), torch, pairs, sub, peaks, False, R, S, P, frames, nb, n_out)
+    bench.dump_chain_outputs(str(tmp_path / "t"), torch, tp, ts, peaks, True, R, S, P, frames, nb, n_out)
+    names = sorted(p.name for p in (tmp_path / "s").iterdir())
+    assert names == ["packets.npy", "pairs.npy", "peaks.npy", "streams.npy", "sub.npy"]
+    idx = np.load(tmp_path / "s" / "streams.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "s" / "packets.npy"), np.arange(nb))
+    assert len(idx) == 128 and len(set(idx)) == 128 and idx.max() < S
+    for n in names:
+        a, b = np.load(tmp_path / "s" / n), np.load(tmp_path / "t" / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+    assert np.array_equal(np.load(tmp_path / "s" / "pairs.npy"), pairs.numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "s" / "sub.npy"), sub.numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "s" / "peaks.npy"), peaks.numpy()[idx])
+    # the full-size headline (65 536 streams x 4 800 frames) stays under the cap
+    per_stream = 8 * (P * 4800 * 2 + 4800 + 50 * (2 + n_out))
+    assert min(128, bench.DUMP_BYTES // per_stream) * per_stream + 1024 < 64e6
+    bench.dump_flat_output(str(tmp_path / "f"), torch, torch.arange(10 ** 6, dtype=torch.int32), "words")
+    w, i = np.load(tmp_path / "f" / "words.npy"), np.load(tmp_path / "f" / "words_index.npy")
+    assert np.array_equal(w, i) and w.dtype == np.float64
+
+
+def test_preload_is_fixed_by_the_workload():
+    """The untimed pre-load is a step count set by the launch's size (~52 launches of the headline before its timed region), never by a
+    clock: the chain's state carries over, so only a fixed history makes the last step's words reproducible (--dump-outputs)."""
+    assert bench.preload_steps(65536 * 4800, 10) == 76 and bench.preload_steps(65536 * 4800, 5) == 81      # 86 launches of config 3: 0.83 s
+    assert bench.preload_steps(4096 * 96000, 2) == 67                                  # configs 2 / 2b: 69 launches, >= 0.6 s at 8.8 ms
+    assert bench.preload_steps(65536 * 4800, 100) == 0
+    assert bench.preload_steps(2048 * 4800, 1) == 400                                  # capped
+
+
+def test_dump_outputs_cap_holds_for_any_launch_length(tmp_path):
+    """A launch whose words for one stream alone exceed the cap: the dump keeps the launch's last packets that fit, and says which."""
+    S, P, R, B, nb, n_out = 4, 4, 64, 96, 9000, 9
+    frames = nb * B
+    pairs = torch.arange(S * P * frames * 2, dtype=torch.int32).reshape(S, P, frames, 2)
+    sub = torch.arange(S * frames, dtype=torch.int32).reshape(S, frames)
+    peaks = torch.arange(S * nb * (2 + n_out), dtype=torch.int32).reshape(S, nb, 2 + n_out).to(torch.int16)
+    bench.dump_chain_outputs(str(tmp_path), torch, pairs, sub, peaks, False, R, S, P, frames, nb, n_out)
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) < 64e6
+    pk = np.load(tmp_path / "packets.npy").astype(np.int64)
+    m = len(pk)
+    assert 0 < m < nb and np.array_equal(pk, np.arange(nb - m, nb))
+    idx = np.load(tmp_path / "streams.npy").astype(np.int64)
+    assert len(idx) == 1
+    assert np.array_equal(np.load(tmp_path / "pairs.npy"), pairs.numpy()[idx][:, :, (nb - m) * B:])
+    assert np.array_equal(np.load(tmp_path / "sub.npy"), sub.numpy()[idx][:, (nb - m) * B:])
+    assert np.array_equal(np.load(tmp_path / "peaks.npy"), peaks.numpy()[idx][:, nb - m:])
+
+
+def test_config_runs_of_a_full_line_never_dump():
+    """--full --dump-outputs: the short config 2 / 2b / 5 runs after config 3 must not overwrite the headline's dump."""
+    import argparse
+    args = argparse.Namespace(config="3", steps=50, warmup=10, dump_outputs="/some/dir", contract="canonical", out_layout="tiled", input="noise",
+                              no_variants=False, no_realtime=False, no_cpu_baseline=False, full=True)
+    for name in ("2", "2b", "5"):
+        a2 = bench.config_args(args, name, 5, 2)
+        assert a2.dump_outputs is None and a2.config == name and (a2.steps, a2.warmup) == (5, 2)
+        assert (a2.contract, a2.out_layout, a2.input) == ("fma", "stream", "mix")
+    assert args.dump_outputs == "/some/dir" and args.config == "3"

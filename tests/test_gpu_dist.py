@@ -80,7 +80,7 @@ def test_bench_self_spawn_two_ranks(scaling):
     env = dict(os.environ, DSPI_BENCH_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"): env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--streams", "2048", "--scaling", scaling,
-                        "--no-cpu-baseline", "--no-variants"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-variants"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -101,7 +101,7 @@ def test_bench_two_ranks_carry_the_cpu_baseline():
     """... and the reference's C path on the host cores sits next to the N > 1 figure (north_star), timed by rank 0 after the GPU work."""
     env = dict(os.environ, DSPI_BENCH_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"): env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--streams", "1024", "--no-variants", "--no-parity"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--streams", "1024", "--full", "--no-variants", "--no-parity"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -116,7 +116,7 @@ def test_bench_rccl_branch_world_size_one():
     env = dict(os.environ, DSPI_BENCH_FORCE_DIST="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "DSPI_BENCH_BACKEND", "MASTER_PORT"): env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--streams", "2048",
-                        "--no-cpu-baseline", "--no-variants"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-variants"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

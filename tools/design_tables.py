@@ -61,7 +61,7 @@ def headline():
     extra = []
     if d:
         r = d["roofline"]
-        extra.append(f"- `bench.py` (no flags, `profiles/bench_{TAG}_default.json`): **{d['ms_per_step']:.2f} ms** per launch = {d['config']['frames_per_s']:.3e} frames/s = "
+        extra.append(f"- `bench.py --full` (`profiles/bench_{TAG}_default.json`): **{d['ms_per_step']:.2f} ms** per launch = {d['config']['frames_per_s']:.3e} frames/s = "
                      f"**{d['value']:.3e} samples/s**; `roofline.frac` **{r['frac']:.3f}** (STRICT: {r['algorithmic_bytes_per_frame']:.1f} B/frame, {r['achieved']:.0f} GB/s), "
                      f"`frac_hbm_resident` {r['frac_hbm_resident']:.3f} (104 B), `frac_launch_span` {r['frac_launch_span']:.3f} (59.4 B); {r['power_w']:.0f} W of "
                      f"{r['power_cap_w']:.0f} W at {r['sclk_mhz']:.0f} of {r.get('sclk_max_mhz') or 0:.0f} MHz -> binds: {r['binds']}; {d.get('parity_checked', 0)} streams of the timed context checked against the oracle.")

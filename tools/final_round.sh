@@ -16,24 +16,24 @@ bash tools/probe/probe11_run.sh > $O/config2_calibration.md 2>&1
 bash tools/prof_all.sh $R > $O/prof_all.log 2>&1
 cp gpurun_out/profsum/${R}[a-r]_summary.md gpurun_out/profsum/traffic_${R}[a-r].json profiles/ 2>/dev/null
 [ -f $O/power_model.json ] && cp $O/power_model.json profiles/power_model_$R.json
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --steps 200 --no-cpu-baseline --no-variants > $O/bench_steps200.json 2>/dev/null
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --steps 200 --no-cpu-baseline --no-variants > $O/bench_steps200.json 2>/dev/null
 b() { local name=$1; shift; env "$@" > /dev/null 2>&1; }
 run() { local name=$1; shift; "$@" > $O/bench_$name.json 2>/dev/null; }
-run config_2 python bench.py --config 2 --no-cpu-baseline
-run config_2b python bench.py --config 2b --no-cpu-baseline
-run config_5 python bench.py --config 5 --no-cpu-baseline
-run config_5_64k python bench.py --config 5 --streams 65536 --no-cpu-baseline
-run config3_512streams python bench.py --config 3 --streams 512 --no-cpu-baseline --no-variants
-run config_5_1024streams python bench.py --config 5 --streams 1024 --no-cpu-baseline
+run config_2 python bench.py --full --config 2 --no-cpu-baseline
+run config_2b python bench.py --full --config 2b --no-cpu-baseline
+run config_5 python bench.py --full --config 5 --no-cpu-baseline
+run config_5_64k python bench.py --full --config 5 --streams 65536 --no-cpu-baseline
+run config3_512streams python bench.py --full --config 3 --streams 512 --no-cpu-baseline --no-variants
+run config_5_1024streams python bench.py --full --config 5 --streams 1024 --no-cpu-baseline
 python tools/bench_q28_layouts.py > $O/q28_layouts.jsonl 2>/dev/null
-run perstream python bench.py --config perstream --no-cpu-baseline
-run perstream_eq python bench.py --config perstream_eq --no-cpu-baseline
-DSPI_DEBUG=1 python bench.py --config perstream_eq --no-cpu-baseline > $O/bench_perstream_eq_every_band.json 2>/dev/null
+run perstream python bench.py --full --config perstream --no-cpu-baseline
+run perstream_eq python bench.py --full --config perstream_eq --no-cpu-baseline
+DSPI_DEBUG=1 python bench.py --full --config perstream_eq --no-cpu-baseline > $O/bench_perstream_eq_every_band.json 2>/dev/null
 run pdm python bench.py --config pdm --out-layout tiled
 run spdif python bench.py --config spdif
 run i2s python bench.py --config i2s
-run blocks200_tiled python bench.py --out-layout tiled --blocks-per-step 200 --no-cpu-baseline --no-variants
+run blocks200_tiled python bench.py --full --out-layout tiled --blocks-per-step 200 --no-cpu-baseline --no-variants
 python tools/bench_realtime.py --calls 30000 --presets config3,config3_leveller_off,config2 --out $O/realtime.json > $O/realtime.log 2>&1
 DSPI_Q28_LAYOUT=chain python tools/bench_realtime.py --calls 3000 --flavors q28 --out $O/realtime_q28_chain_kernel.json > $O/realtime_q28_chain_kernel.log 2>&1
 # the thin C host's node-level mode on the one GPU of this box: one context + feeder thread, the reduction through ncclCommInitAll / ncclAllReduce
