@@ -14,7 +14,6 @@
 #include <new>
 #include <cstdlib>
 #include <string>
-#include <map>
 #include <unordered_map>
 #include <type_traits>
 #include <vector>
@@ -29,6 +28,7 @@
 #include "dspi_image.h"
 #include "dspi_kernels.h"
 #include "dspi_params.h"
+#include "dspi_plan.h"
 
 using namespace dspi;
 
@@ -43,14 +43,13 @@ struct dspi_ctx {
     std::vector<int32_t> stream_image;
     bool assignment_dirty = true;
     bool merge_hint = false;       // a broadcast call ran while several images were live: equal images fold back into one (merge_images)
-    // per image, four work lists (dspi_image.h:WgItem): 0 = all streams of the image (state ops; the Q28 chain launch),
-    // 1 = lanes whose two streams both belong (float: packed kernel), 2/3 = lanes where only stream 0 / 1 belongs
-    std::vector<std::vector<WgItem>> image_items[4];
-    std::vector<uint32_t> image_item_offset[4];
-    // chain launches: the same work lists concatenated over images, grouped by what the kernels are specialised on
-    // (float: leveller on/off), so a dspi_process is a handful of launches however many presets are in play
-    std::vector<WgItem> launch_items[2][9];      // [leveller off / on][list]; lists 5, 6: the latency layout (dspi_chain_skew.inc) without / with output rows;
-    uint32_t launch_item_offset[2][9] = {};      // 7, 8: the same with paired presets (workgroups whose stream slots hold different images of one structure)
+    // per image, the rows that hold its streams (dspi_plan.h image_rows): the state mutations' work lists, uploaded to d_items
+    std::vector<std::vector<WgItem>> image_rows;
+    std::vector<uint32_t> image_rows_offset;
+    // chain launches (dspi_plan.h): one list per kernel path, each covering every image, so a dspi_process is a handful of launches
+    // however many presets are in play; uploaded to d_litems at plan.offset
+    PlanInput plan_in;             // its sig / bands: per image, what the last upload built (commit_params)
+    LaunchPlan plan;
     WgItem *d_litems = nullptr; size_t d_litems_cap = 0;
     uint32_t *d_stream_image = nullptr; size_t d_stream_image_cap = 0;   // image index per stream (per-lane parameter kernel)
     bool launch_dirty = true;
@@ -72,18 +71,6 @@ struct dspi_ctx {
     uint32_t *d_xwords = nullptr; size_t d_xwords_cap = 0;      // exchange area of the packed kernel's copy wave (stream-major output)
     DevImage *d_images = nullptr;
     std::vector<uint32_t> image_flags;             // DevImage::flags of each uploaded image (kernel variant selection)
-    // float flavour, per-lane VALUES: a row whose streams carry several presets of one structure runs the packed kernel with
-    // its numbers in a value tile (dspi_image.h); ImageSig = what has to agree for that
-    struct ImageSig {
-        uint32_t flags, ch_bypassed, out_enabled, out_mute, fs_hz, mute_transition, mix_nz, i2s_pairs;
-        int32_t delay[kMaxOut];
-        uint8_t kinds[kPvBandSlots];
-    };
-    struct BandHash { uint64_t a, b; };            // two independent 64-bit hashes of an image's band coefficient words: rows whose
-    std::vector<BandHash> image_bands;             // images agree in both run the shared band loops (row_pv = 2), the rest of the
-                                                   // numbers per lane
-    std::vector<ImageSig> image_sig;
-    std::vector<uint8_t> row_pv;                   // [n_wg] the row is a per-lane-value row
     std::vector<uint8_t> image_touched;            // images uploaded since the tiles were last built
     float *d_vals = nullptr; size_t d_vals_cap = 0;
     uint32_t *d_pv_rows = nullptr; size_t d_pv_rows_cap = 0;
@@ -211,7 +198,7 @@ void merge_images(dspi_ctx *c) {
     c->image_refs.assign(keep.size(), 0);
     for (auto &si : c->stream_image) { si = remap[(size_t)si]; c->image_refs[(size_t)si]++; }
     // per-image caches describe the old numbering: drop them, every image goes up again
-    c->image_flags.clear(); c->image_sig.clear(); c->image_bands.clear(); c->image_touched.clear();
+    c->image_flags.clear(); c->plan_in.sig.clear(); c->plan_in.bands.clear(); c->image_touched.clear();
     c->assignment_dirty = true; c->launch_dirty = true;
 }
 
@@ -232,40 +219,17 @@ int ensure(dspi_ctx *c, P *&ptr, size_t &cap, size_t bytes) {
 
 int rebuild_assignment(dspi_ctx *c) {
     const size_t ni = c->images.size();
-    const uint32_t row = (uint32_t)c->sm.row;
-    const bool two = c->flavor != 0;                 // float flavour: two streams per lane
-    struct Acc { uint32_t wg; uint64_t m0, m1; };
-    std::vector<std::vector<Acc>> acc(ni);
-    for (uint32_t s = 0; s < c->n_streams; s++) {
-        const size_t im = (size_t)c->stream_image[s];
-        const uint32_t wg = s / row, col = s % row;
-        auto &v = acc[im];
-        if (v.empty() || v.back().wg != wg) v.push_back(Acc{wg, 0ull, 0ull});
-        if (two) { if (col & 1u) v.back().m1 |= 1ull << (col >> 1); else v.back().m0 |= 1ull << (col >> 1); }
-        else v.back().m0 |= 1ull << col;
-    }
+    c->image_rows = image_rows(c->flavor, (uint32_t)c->sm.row, c->stream_image.data(), c->n_streams, ni);
+    c->image_rows_offset.assign(ni, 0);
     size_t total = 0;
-    for (int k = 0; k < 4; k++) { c->image_items[k].assign(ni, {}); c->image_item_offset[k].assign(ni, 0); }
-    for (size_t i = 0; i < ni; i++)
-        for (const Acc &x : acc[i]) {
-            c->image_items[0][i].push_back(WgItem{x.wg, 0u, x.m0, x.m1});
-            if (two) {
-                const uint64_t both = x.m0 & x.m1, only0 = x.m0 & ~x.m1, only1 = x.m1 & ~x.m0;
-                if (both) c->image_items[1][i].push_back(WgItem{x.wg, 0u, both, both});
-                if (only0) c->image_items[2][i].push_back(WgItem{x.wg, 0u, only0, 0ull});
-                if (only1) c->image_items[3][i].push_back(WgItem{x.wg, 0u, only1, 0ull});
-            }
-        }
-    for (int k = 0; k < 4; k++)
-        for (size_t i = 0; i < ni; i++) { c->image_item_offset[k][i] = (uint32_t)total; total += c->image_items[k][i].size(); }
+    for (size_t i = 0; i < ni; i++) { c->image_rows_offset[i] = (uint32_t)total; total += c->image_rows[i].size(); }
     int rc = ensure(c, c->d_items, c->d_items_cap, total * sizeof(WgItem));
     if (rc) return rc;
     HIPCK(c, hipStreamSynchronize(c->hs));      // no state_ops launch may still be reading the list
     {   // one upload (per-stream presets: tens of thousands of one-item lists)
         std::vector<WgItem> all;
         all.reserve(total);
-        for (int k = 0; k < 4; k++)
-            for (size_t i = 0; i < ni; i++) all.insert(all.end(), c->image_items[k][i].begin(), c->image_items[k][i].end());
+        for (const auto &v : c->image_rows) all.insert(all.end(), v.begin(), v.end());
         if (!all.empty()) HIPCK(c, hipMemcpy(c->d_items, all.data(), all.size() * sizeof(WgItem), hipMemcpyHostToDevice));
     }
     c->assignment_dirty = false;
@@ -273,281 +237,33 @@ int rebuild_assignment(dspi_ctx *c) {
     return 0;
 }
 
-dspi_ctx::ImageSig make_sig(const DevImage &img) {
-    dspi_ctx::ImageSig g;
-    memset(&g, 0, sizeof g);
-    g.flags = img.flags; g.ch_bypassed = img.ch_bypassed; g.out_enabled = img.out_enabled; g.out_mute = img.out_mute;
-    g.fs_hz = img.fs_hz; g.mute_transition = img.mute_transition; g.i2s_pairs = img.i2s_pairs;
-    for (int o = 0; o < kMaxOut; o++) {
-        g.delay[o] = img.delay_samples[o];
-        if (img.mix[0][o].f != 0.0f) g.mix_nz |= 1u << o;
-        if (img.mix[1][o].f != 0.0f) g.mix_nz |= 1u << (kMaxOut + o);
-    }
-    for (int ch = 0; ch < kMaxCh; ch++) for (int b = 0; b < kBands; b++) g.kinds[ch * kBands + b] = (uint8_t)img.eq[ch][b].kind;
-    g.kinds[kMaxCh * kBands] = (uint8_t)img.loud[0].kind; g.kinds[kMaxCh * kBands + 1] = (uint8_t)img.loud[1].kind;
-    return g;
-}
-
-// The latency layout of the float chain (dspi_chain_skew.inc) serves images with the leveller off.  Class 1: no output runs an EQ
-// (disabled, muted, every band flat, or the sub in EQ-worker mode: exactly the cases in which output_item_pk skips the band loops) —
-// eight stream pairs per workgroup, the outputs frame-parallel.  Class 2: some output does — two pairs per workgroup, every output a
-// systolic row of its own.  Class 3: the leveller is on — the same two pairs and output rows, the groups of the workgroup passing frames
-// through rings (dspi_chain_skew_lev.inc).
-int skew_class(const dspi_ctx::ImageSig &g) {
-    if (g.flags & IF_LEVELLER_ON) return 3;
-    for (int o = 0; o < kMaxOut; o++) {
-        const bool enabled = (g.out_enabled >> o) & 1u, muted = (g.out_mute >> o) & 1u, flat = (g.ch_bypassed >> (2 + o)) & 1u;
-        const bool processed = o != kMaxOut - 1 || (g.flags & IF_SUB_ACTIVE);
-        if (processed && enabled && !muted && !flat) return 2;
-    }
-    return 1;
-}
-// ... for launches that leave the chip underfilled: class 1 up to one of its eight-pair workgroups per CU (84 KB of LDS each), class 2
-// up to two of its two-pair workgroups per CU (79 KB each); beyond that the packed kernel's throughput layout wins
-// (tools/probe/probe8.hip, tools/bench_skew.py).  DSPI_F32_LAYOUT=skew|packed forces one (tests, development).
-uint32_t skew_pair_limit(int device, int cls) {
-    if (const char *e = getenv("DSPI_F32_LAYOUT")) { if (!strcmp(e, "skew")) return 0xffffffffu; if (!strcmp(e, "packed")) return 0u; }
-    int cus = 0;
-    if (device < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-    return (cls == 1 ? 8u : 4u) * (uint32_t)cus;
-}
-
-dspi_ctx::BandHash hash_bands(const DevImage &img) {
-    uint64_t a = 0xcbf29ce484222325ull, b = 0x9e3779b97f4a7c15ull;      // FNV-1a and a multiply-xorshift mix over the same words
-    auto feed = [&](uint32_t w) { a = (a ^ w) * 0x100000001b3ull; b = (b + w) * 0xff51afd7ed558ccdull; b ^= b >> 29; };
-    for (int ch = 0; ch < kMaxCh; ch++) for (int k = 0; k < kBands; k++) for (int j = 0; j < 6; j++) feed(img.eq[ch][k].c[j].u);
-    for (int k = 0; k < 2; k++) for (int j = 0; j < 6; j++) feed(img.loud[k].c[j].u);
-    return dspi_ctx::BandHash{a, b};
-}
-
 int rebuild_launch_lists(dspi_ctx *c) {
-    // lists 0 (Q28) and 1 (float lanes whose two streams share an image): one item per (row, image), grouped by leveller
-    // on/off for the float kernel variants.  List 2 (float lanes with ONE stream of an image — image_items 2 / 3 = first /
-    // second stream, WgItem::image = which; Q28: rows holding several images): the per-lane parameter kernels read every
-    // lane's own image, so all images of a row merge into one item.  Launch list 3 stays empty.
-    size_t total = 0;
-    // float: rows holding several images of ONE structure -> per-lane-value rows (launch list 3, packed kernel + value tile)
-    struct RowAcc { uint64_t m0 = 0, m1 = 0; int n = 0; uint32_t first = 0; bool same = true, same_bands = true; };
-    std::map<uint32_t, RowAcc> rows_f;
-    c->row_pv.assign(c->n_wg, 0);
-    if (c->flavor && c->image_sig.size() >= c->images.size()) {
-        for (size_t i = 0; i < c->images.size(); i++)
-            for (const WgItem &it : c->image_items[0][i]) {
-                RowAcc &r = rows_f[it.wg];
-                if (r.n++ == 0) r.first = (uint32_t)i;
-                else {
-                    if (memcmp(&c->image_sig[r.first], &c->image_sig[i], sizeof(dspi_ctx::ImageSig)) != 0) r.same = false;
-                    if (c->image_bands[r.first].a != c->image_bands[i].a || c->image_bands[r.first].b != c->image_bands[i].b) r.same_bands = false;
-                }
-                r.m0 |= it.mask; r.m1 |= it.mask1;
-            }
-        for (const auto &r : rows_f)
-            if (r.second.n > 1 && r.second.same && (r.second.m0 & r.second.m1)) c->row_pv[r.first] = r.second.same_bands ? 2 : 1;
-        // "identical filters" (row_pv 2: the kernel takes the band coefficients of the row's first image for every stream) was decided
-        // on two 64-bit hashes; back it with the words themselves before it can cost bit-exactness
-        std::unique_ptr<DevImage> ref(new DevImage), cur(new DevImage);
-        uint32_t ref_row = 0xffffffffu;
-        for (size_t i = 0; i < c->images.size(); i++)
-            for (const WgItem &it : c->image_items[0][i]) {
-                if (c->row_pv[it.wg] != 2) continue;
-                const RowAcc &r = rows_f[it.wg];
-                if (r.first == i) continue;
-                if (ref_row != it.wg) { c->images[r.first]->build_image(*ref); ref_row = it.wg; }
-                c->images[i]->build_image(*cur);
-                if (memcmp(ref->eq, cur->eq, sizeof ref->eq) != 0 || memcmp(ref->loud, cur->loud, sizeof ref->loud) != 0) c->row_pv[it.wg] = 1;
-            }
-    }
-    for (int lev = 0; lev < 2; lev++) for (int k = 5; k <= 8; k++) c->launch_items[lev][k].clear();
-    for (int lev = 0; lev < 2; lev++)
-        for (int k = 0; k < 5; k++) {
-            auto &v = c->launch_items[lev][k];
-            v.clear();
-            if (k >= 3) {      // list 3: per-lane values incl. band coefficients; list 4: identical filters, the other numbers per lane
-                for (const auto &r : rows_f) {
-                    if (c->row_pv[r.first] != (k == 3 ? 1 : 2)) continue;
-                    const int ilev = (c->image_flags[r.second.first] & IF_LEVELLER_ON) ? 1 : 0;
-                    if (ilev == lev) v.push_back(WgItem{r.first, r.second.first, r.second.m0 & r.second.m1, 0ull});
-                }
-            } else if (k >= 2) {
-                // float: lanes with one stream of an image (k = 2 first, 3 second stream); Q28 (k = 2): rows that hold
-                // several images.  Per-lane parameter kernel: all images of a row merge into one item.
-                // Float: both lane components go into list 2 (WgItem::image = component), one launch.
-                if (lev == 0 && k == 2) {
-                    for (int comp = 0; comp < (c->flavor ? 2 : 1); comp++) {
-                        std::map<uint32_t, std::pair<uint64_t, int>> rows;      // row -> (lane mask, number of images)
-                        const int src = c->flavor ? 2 + comp : 0;
-                        for (size_t i = 0; i < c->images.size(); i++)
-                            if (c->image_refs[i] > 0)
-                                for (const WgItem &it : c->image_items[src][i]) {
-                                    if (c->flavor && c->row_pv[it.wg]) continue;      // per-lane-value row: only its half-filled lanes come here (below)
-                                    auto &r = rows[it.wg]; r.first |= it.mask; r.second++;
-                                }
-                        if (c->flavor)
-                            for (const auto &rf : rows_f) {
-                                if (!c->row_pv[rf.first]) continue;
-                                const uint64_t only = comp ? (rf.second.m1 & ~rf.second.m0) : (rf.second.m0 & ~rf.second.m1);
-                                if (only) { auto &r = rows[rf.first]; r.first |= only; r.second++; }
-                            }
-                        for (const auto &r : rows)
-                            if (c->flavor || r.second.second > 1) v.push_back(WgItem{r.first, (uint32_t)comp, r.second.first, 0ull});
-                    }
-                }
-            } else {
-                std::map<uint32_t, int> per_row;       // Q28: rows with one image keep the workgroup-uniform path
-                if (!c->flavor && k == 0)
-                    for (size_t i = 0; i < c->images.size(); i++)
-                        if (c->image_refs[i] > 0)
-                            for (const WgItem &it : c->image_items[0][i]) per_row[it.wg]++;
-                for (size_t i = 0; i < c->images.size(); i++) {
-                    if (c->image_refs[i] == 0) continue;
-                    const int ilev = (c->flavor && (c->image_flags[i] & IF_LEVELLER_ON)) ? 1 : 0;
-                    if (ilev != lev) continue;
-                    for (WgItem it : c->image_items[k][i]) {
-                        if (!c->flavor && k == 0 && per_row[it.wg] > 1) continue;
-                        if (c->flavor && k == 1 && c->row_pv[it.wg]) continue;
-                        it.image = (uint32_t)i; v.push_back(it);
-                    }
-                }
-            }
-            // by row: a range of rows is then a contiguous run of every list (dspi_process stages host buffers row chunk by row chunk)
-            std::stable_sort(v.begin(), v.end(), [](const WgItem &x, const WgItem &y) { return x.wg < y.wg; });
-        }
-    // float, shared-preset lanes with the leveller off: those whose image suits the latency layout move to list 5 / 6 (by class) when
-    // the launch is small enough to leave the chip underfilled
-    if (c->flavor && c->image_sig.size() >= c->images.size()) {
-        uint64_t pairs[4] = {0, 0, 0, 0};
-        for (int lev = 0; lev < 2; lev++)
-            for (const WgItem &it : c->launch_items[lev][1]) pairs[skew_class(c->image_sig[it.image])] += (uint64_t)__builtin_popcountll(it.mask);
-        // the context's last stream when the stream count is odd: a lane that holds one stream.  The packed kernel leaves such lanes to the
-        // one-stream kernel (list 2); the latency layout serves them (its stores check the second stream) — a context of ONE stream is this case
-        const bool odd = (c->n_streams & 1u) != 0;
-        const uint32_t last = c->n_streams - 1u, h_row = last / (uint32_t)c->sm.row, h_lane = (last % (uint32_t)c->sm.row) / 2u;
-        const uint32_t h_img = odd ? c->stream_image[last] : 0u;
-        const int h_cls = (odd && !c->row_pv[h_row]) ? skew_class(c->image_sig[h_img]) : 0;
-        if (h_cls) pairs[h_cls]++;
-        bool take[4] = {false, false, false, false};
-        for (int cls = 1; cls <= 3; cls++) take[cls] = pairs[cls] > 0 && pairs[cls] <= skew_pair_limit(c->device, cls);
-        // The whole context small — the lanes of every class within its limit: EVERY float lane takes the latency layout, whatever the
-        // presets: no per-lane-value tiles, no one-stream kernel, any mix of structures.  A workgroup = one part of a row (8 or 2 stream
-        // pairs).  The images that hold streams there: one -> a shared-preset item; several of ONE structure (ImageSig) -> one paired-preset
-        // item (lists 7 / 8: the kernel reads every slot's numbers from its own image, args.stream_image; the item names the first image, for
-        // the structure); several structures -> one item per image, the other images' slots inactive (the kernels store per half).  The
-        // limit counts lanes, a lane of the last kind once per image.  DSPI_SKEW_PAIRED=0 keeps to the last form (development, tests).
-        {
-            const char *ppe = getenv("DSPI_SKEW_PAIRED");
-            const bool pp_on = !(ppe && !strcmp(ppe, "0"));
-            struct Slot { uint32_t image; uint64_t m0, m1; };
-            struct Cell { std::vector<Slot> v; bool same = false; };
-            std::map<std::pair<uint32_t, uint32_t>, Cell> cells[4];      // [class]: (row, part) -> images
-            uint64_t slots[4] = {0, 0, 0, 0};
-            {   // a first bound: the lanes in use, whatever their images
-                std::map<uint32_t, uint64_t> used[4];
-                for (size_t i = 0; i < c->images.size(); i++)
-                    if (c->image_refs[i] > 0)
-                        for (const WgItem &it : c->image_items[0][i]) used[skew_class(c->image_sig[i])][it.wg] |= it.mask | it.mask1;
-                for (int cls = 1; cls <= 3; cls++) for (const auto &u : used[cls]) slots[cls] += (uint64_t)__builtin_popcountll(u.second);
-            }
-            bool all_small = slots[1] + slots[2] + slots[3] > 0;
-            for (int cls = 1; cls <= 3; cls++) if (slots[cls] > (uint64_t)skew_pair_limit(c->device, cls) * (cls == 2 ? 2u : 1u)) all_small = false;      // (class 2: see below)
-            if (all_small) {
-                for (size_t i = 0; i < c->images.size(); i++) {
-                    if (c->image_refs[i] == 0) continue;
-                    const int cls = skew_class(c->image_sig[i]);
-                    for (const WgItem &it : c->image_items[0][i])
-                        for (uint32_t ppw = cls == 1 ? 8u : 2u, part = 0; part < 64u / ppw; part++) {
-                            const uint64_t pm = ((1ull << ppw) - 1ull) << (part * ppw);
-                            if ((it.mask | it.mask1) & pm) cells[cls][{it.wg, part}].v.push_back(Slot{(uint32_t)i, it.mask & pm, it.mask1 & pm});
-                        }
-                }
-                for (int cls = 1; cls <= 3; cls++) {
-                    slots[cls] = 0;
-                    size_t paired = 0;
-                    for (auto &cell : cells[cls]) {
-                        std::vector<Slot> &v = cell.second.v;
-                        bool same = pp_on && v.size() > 1;
-                        for (size_t j = 1; same && j < v.size(); j++)
-                            if (memcmp(&c->image_sig[v[0].image], &c->image_sig[v[j].image], sizeof(dspi_ctx::ImageSig)) != 0) same = false;
-                        cell.second.same = same;
-                        paired += same ? 1 : 0;
-                        uint64_t u = 0;
-                        for (const Slot &sl : v) { if (same) u |= sl.m0 | sl.m1; else slots[cls] += (uint64_t)__builtin_popcountll(sl.m0 | sl.m1); }
-                        slots[cls] += (uint64_t)__builtin_popcountll(u);
-                    }
-                    // Presets with output EQ and no leveller, mostly paired workgroups (every stream its own preset): the alternative is the packed
-                    // per-lane-filter kernel on an underfilled chip, and the layout wins up to twice its shared-preset limit (4 096 distinct
-                    // presets: 13.9 against 22.6 ms per 200 packets, profiles/r04_small_contexts_per_stream_leveller_off.jsonl).
-                    if (slots[cls] > (uint64_t)skew_pair_limit(c->device, cls) * ((cls == 2 && paired * 2 > cells[cls].size()) ? 2u : 1u)) all_small = false;
-                }
-            }
-            if (all_small) {
-                for (int lev = 0; lev < 2; lev++) for (int k = 1; k <= 4; k++) c->launch_items[lev][k].clear();
-                for (int cls = 1; cls <= 3; cls++)
-                    for (const auto &cell : cells[cls]) {
-                        const uint32_t row = cell.first.first, part = cell.first.second;
-                        const std::vector<Slot> &v = cell.second.v;
-                        if (cell.second.same) {
-                            uint64_t m0 = 0, m1 = 0;
-                            for (const Slot &sl : v) { m0 |= sl.m0; m1 |= sl.m1; }
-                            c->launch_items[cls == 3 ? 1 : 0][cls == 2 ? 8 : 7].push_back(WgItem{row, v[0].image | (part << 26), m0, m1});
-                        } else
-                            for (const Slot &sl : v) c->launch_items[cls == 3 ? 1 : 0][cls == 2 ? 6 : 5].push_back(WgItem{row, sl.image | (part << 26), sl.m0, sl.m1});
-                    }
-                for (int lev = 0; lev < 2; lev++)
-                    for (int k = 5; k <= 8; k++)
-                        std::stable_sort(c->launch_items[lev][k].begin(), c->launch_items[lev][k].end(), [](const WgItem &x, const WgItem &y) { return x.wg < y.wg; });
-                take[1] = take[2] = take[3] = false;      // (nothing left for the shared-preset rule below)
-            }
-        }
-        // a latency-layout item is ONE workgroup: a row's item is cut into its non-empty parts (8 or 2 stream pairs each), the part rides in
-        // the image field's top bits (kSkPartShift = 26, dspi_chain_skew.inc); mask / mask1 = the lanes whose first / second stream take part
-        auto push_parts = [&](std::vector<WgItem> &dst, uint32_t row, uint32_t image, uint64_t m0, uint64_t m1, int cls) {
-            const uint32_t ppw = cls == 1 ? 8u : 2u;
-            for (uint32_t part = 0; part < 64u / ppw; part++)
-                if (((m0 | m1) >> (part * ppw)) & ((1ull << ppw) - 1ull)) dst.push_back(WgItem{row, image | (part << 26), m0, m1});
-        };
-        for (int lev = 0; lev < 2; lev++) {
-            auto &v = c->launch_items[lev][1];
-            std::vector<WgItem> keep;
-            for (const WgItem &it : v) {
-                const int cls = skew_class(c->image_sig[it.image]);
-                // (class 3 sits in the leveller-on lists: list 5 there is the third shape)
-                if (take[cls]) push_parts(c->launch_items[lev][cls == 2 ? 6 : 5], it.wg, it.image, it.mask, it.mask, cls);
-                else keep.push_back(it);
-            }
-            v.swap(keep);
-        }
-        if (h_cls && take[h_cls]) {
-            auto &l2 = c->launch_items[0][2];
-            for (size_t i = 0; i < l2.size(); i++)
-                if (l2[i].wg == h_row && l2[i].image == 0u && ((l2[i].mask >> h_lane) & 1ull)) {      // (list 2: image = lane component, 0 = first stream)
-                    l2[i].mask &= ~(1ull << h_lane);
-                    if (l2[i].mask == 0) l2.erase(l2.begin() + (long)i);
-                    auto &dst = c->launch_items[h_cls == 3 ? 1 : 0][h_cls == 2 ? 6 : 5];
-                    const uint32_t ppw = h_cls == 1 ? 8u : 2u, h_part = h_lane / ppw;
-                    bool merged = false;
-                    for (WgItem &d : dst) if (d.wg == h_row && d.image == (h_img | (h_part << 26))) { d.mask |= 1ull << h_lane; merged = true; break; }
-                    if (!merged) {
-                        dst.push_back(WgItem{h_row, h_img | (h_part << 26), 1ull << h_lane, 0ull});
-                        std::stable_sort(dst.begin(), dst.end(), [](const WgItem &x, const WgItem &y) { return x.wg < y.wg; });
-                    }
-                    break;
-                }
-        }
-    }
-    for (int lev = 0; lev < 2; lev++)
-        for (int k = 0; k < 9; k++) {
-            c->launch_item_offset[lev][k] = (uint32_t)total;
-            total += c->launch_items[lev][k].size();
-        }
-    int rc = ensure(c, c->d_litems, c->d_litems_cap, total * sizeof(WgItem));
+    PlanInput &in = c->plan_in;
+    in.flavor = c->flavor; in.n_streams = c->n_streams; in.row = (uint32_t)c->sm.row;
+    in.stream_image = c->stream_image; in.refs = c->image_refs;
+    int cus = 0;
+    if (c->device < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0) cus = 256;
+    in.cus = (uint32_t)cus;
+    const char *layout = getenv("DSPI_F32_LAYOUT"), *paired = getenv("DSPI_SKEW_PAIRED");
+    in.layout = layout && !strcmp(layout, "skew") ? F32Layout::Skew : layout && !strcmp(layout, "packed") ? F32Layout::Packed : F32Layout::Auto;
+    in.paired = !(paired && !strcmp(paired, "0"));
+    // the word-by-word check of "identical filters": the rows come image after image, the row's first image is built once per run
+    std::unique_ptr<DevImage> ref(new DevImage), cur(new DevImage);
+    uint32_t ref_image = 0xffffffffu;
+    in.same_filters = [&](uint32_t a, uint32_t b) {
+        if (ref_image != a) { c->images[a]->build_image(*ref); ref_image = a; }
+        c->images[b]->build_image(*cur);
+        return memcmp(ref->eq, cur->eq, sizeof ref->eq) == 0 && memcmp(ref->loud, cur->loud, sizeof ref->loud) == 0;
+    };
+    c->plan = plan_launches(in);
+    in.same_filters = nullptr;
+    int rc = ensure(c, c->d_litems, c->d_litems_cap, c->plan.total * sizeof(WgItem));
     if (rc) return rc;
     if ((rc = ensure(c, c->d_stream_image, c->d_stream_image_cap, (size_t)c->n_streams * 4))) return rc;
     HIPCK(c, hipStreamSynchronize(c->hs));      // no launch may still be reading the lists we overwrite
-    for (int lev = 0; lev < 2; lev++)
-        for (int k = 0; k < 9; k++)
-            if (!c->launch_items[lev][k].empty())
-                HIPCK(c, hipMemcpy(c->d_litems + c->launch_item_offset[lev][k], c->launch_items[lev][k].data(),
-                                   c->launch_items[lev][k].size() * sizeof(WgItem), hipMemcpyHostToDevice));
+    for (int p = 0; p < kNumPaths; p++)
+        if (!c->plan.items[p].empty())
+            HIPCK(c, hipMemcpy(c->d_litems + c->plan.offset[p], c->plan.items[p].data(), c->plan.items[p].size() * sizeof(WgItem), hipMemcpyHostToDevice));
     HIPCK(c, hipMemcpy(c->d_stream_image, c->stream_image.data(), (size_t)c->n_streams * 4, hipMemcpyHostToDevice));
     // every per-lane-value row gets its tile rebuilt (commit_params)
     for (size_t i = 0; i < c->image_touched.size(); i++) c->image_touched[i] = 1;
@@ -579,15 +295,15 @@ int commit_params(dspi_ctx *c) {
     }
     // dirty images go up in contiguous runs (per-stream presets dirty thousands at once)
     if (c->image_flags.size() < ni) c->image_flags.resize(ni, 0u);
-    if (c->flavor && c->image_sig.size() < ni) {
-        dspi_ctx::ImageSig none; memset(&none, 0xff, sizeof none);
-        c->image_sig.resize(ni, none); c->image_bands.resize(ni, dspi_ctx::BandHash{0, 0}); c->image_touched.resize(ni, 1); c->launch_dirty = true;
+    if (c->flavor && c->plan_in.sig.size() < ni) {
+        ImageSig none; memset(&none, 0xff, sizeof none);
+        c->plan_in.sig.resize(ni, none); c->plan_in.bands.resize(ni, BandHash{0, 0}); c->image_touched.resize(ni, 1); c->launch_dirty = true;
     }
     // a run of dirty images: built on all host threads when it is long (every stream its own preset: tens of thousands at once),
     // compared with what the launch lists were built from, uploaded with one copy
     std::vector<DevImage> run;
-    std::vector<dspi_ctx::ImageSig> run_sig;
-    std::vector<dspi_ctx::BandHash> run_bands;
+    std::vector<ImageSig> run_sig;
+    std::vector<BandHash> run_bands;
     for (size_t i = 0; i < ni;) {
         if (!c->images[i]->dirty) { i++; continue; }
         size_t j = i;
@@ -618,8 +334,8 @@ int commit_params(dspi_ctx *c) {
                 if (std::find(c->lv_alphas.begin(), c->lv_alphas.end(), bits) == c->lv_alphas.end()) c->lv_alphas.push_back(bits);
             }
             if (c->flavor) {
-                if (memcmp(&run_sig[k], &c->image_sig[ii], sizeof(dspi_ctx::ImageSig)) != 0) { c->image_sig[ii] = run_sig[k]; c->launch_dirty = true; }
-                if (run_bands[k].a != c->image_bands[ii].a || run_bands[k].b != c->image_bands[ii].b) { c->image_bands[ii] = run_bands[k]; c->launch_dirty = true; }
+                if (memcmp(&run_sig[k], &c->plan_in.sig[ii], sizeof(ImageSig)) != 0) { c->plan_in.sig[ii] = run_sig[k]; c->launch_dirty = true; }
+                if (run_bands[k].a != c->plan_in.bands[ii].a || run_bands[k].b != c->plan_in.bands[ii].b) { c->plan_in.bands[ii] = run_bands[k]; c->launch_dirty = true; }
                 c->image_touched[ii] = 1;
             }
             c->images[ii]->dirty = false;
@@ -628,14 +344,14 @@ int commit_params(dspi_ctx *c) {
         i = j;
     }
     // pending state mutations: consecutive images with the same mutation share one launch (their workgroup items are
-    // consecutive in d_items, list 0)
+    // consecutive in d_items)
     for (size_t i = 0; i < ni;) {
         Params &p = *c->images[i];
         if (!ops_pending(p.ops)) { i++; continue; }
         size_t j = i + 1;
         while (j < ni && memcmp(&c->images[j]->ops, &p.ops, sizeof(StateOps)) == 0) j++;
-        const uint32_t first = c->image_item_offset[0][i];
-        const uint32_t count = (uint32_t)((j < ni ? c->image_item_offset[0][j] : c->image_item_offset[0][ni - 1] + (uint32_t)c->image_items[0][ni - 1].size()) - first);
+        const uint32_t first = c->image_rows_offset[i];
+        const uint32_t count = (uint32_t)((j < ni ? c->image_rows_offset[j] : c->image_rows_offset[ni - 1] + (uint32_t)c->image_rows[ni - 1].size()) - first);
         if (count)
             HIPCK(c, launch_state_ops(c->flavor, c->d_items + first, count, p.ops, c->d_state, c->d_dlines, c->d_ring, c->n_streams, c->hs));
         for (size_t k = i; k < j; k++) c->images[k]->ops = StateOps{};
@@ -648,8 +364,8 @@ int commit_params(dspi_ctx *c) {
         for (size_t i = 0; i < ni; i++) {
             if (!c->image_touched[i]) continue;
             c->image_touched[i] = 0;
-            for (const WgItem &it : c->image_items[0][i])
-                if (c->row_pv[it.wg] && !seen[it.wg]) { seen[it.wg] = 1; rows.push_back(it.wg); }
+            for (const WgItem &it : c->image_rows[i])
+                if (c->plan.row_pv[it.wg] && !seen[it.wg]) { seen[it.wg] = 1; rows.push_back(it.wg); }
         }
         if (!rows.empty()) {
             int rc = ensure(c, c->d_vals, c->d_vals_cap, (size_t)c->n_wg * kPvTileFloats * sizeof(float));
@@ -887,11 +603,14 @@ int dspi_debug_image(dspi_ctx *c, int32_t stream, void *buf, size_t cap) {
 
 int dspi_debug_launch_plan(dspi_ctx *c, uint32_t *counts, size_t n_counts) {
     if (!c || !counts || n_counts < 5) return DSPI_E_INVAL;
-    const int n = n_counts >= 7 ? 7 : n_counts >= 6 ? 6 : 5;      // [5]: items of the latency layout (dspi_chain_skew.inc), [6]: those of them with paired presets
-    for (int k = 0; k < 5; k++) counts[k] = (uint32_t)(c->launch_items[0][k].size() + c->launch_items[1][k].size());
-    if (n >= 6) { counts[5] = 0; for (int k = 5; k <= 8; k++) counts[5] += (uint32_t)(c->launch_items[0][k].size() + c->launch_items[1][k].size()); }      // every shape of the latency layout
-    if (n >= 7) { counts[6] = 0; for (int k = 7; k <= 8; k++) counts[6] += (uint32_t)(c->launch_items[0][k].size() + c->launch_items[1][k].size()); }
-    if (c->flavor) counts[0] = 0;      // (list 0 of a float context is bookkeeping for the state mutations, never launched)
+    const int n = n_counts >= 7 ? 7 : n_counts >= 6 ? 6 : 5;      // [0..5]: items per PathGroup, [6]: the latency layout's items with paired presets
+    uint32_t all[7] = {};
+    for (const PathInfo &pi : kPaths) {
+        const uint32_t k = (uint32_t)c->plan.items[(int)pi.path].size();
+        all[(int)pi.group] += k;
+        if (pi.paired) all[6] += k;
+    }
+    for (int k = 0; k < n; k++) counts[k] = all[k];
     return n;
 }
 
@@ -1098,8 +817,8 @@ int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_bloc
         // property of the output, not of the stream count) runs the chain into a scratch buffer of pair words, row chunk by row chunk,
         // and the subframe encoder from there into `pairs`: the same words, the block position carried the same way.
         bool all_latency = c->flavor != 0;
-        for (int lev = 0; lev < 2 && all_latency; lev++)
-            for (int k = 1; k <= 4; k++) if (!c->launch_items[lev][k].empty()) all_latency = false;
+        for (const PathInfo &pi : kPaths)
+            if (pi.group != PathGroup::Latency && !c->plan.items[(int)pi.path].empty()) all_latency = false;
         spdif_two_pass = !all_latency && out->pairs != nullptr;
     }
     const size_t padded = (size_t)c->n_wg * c->sm.row;          // tiled buffers cover whole tiles
@@ -1180,31 +899,22 @@ int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_bloc
     }
     a.img = c->d_images;
     a.stream_image = c->d_stream_image;
-    // float flavour: lanes with both streams on one image go to the packed kernel (list 1), every other lane to the
-    // per-lane-parameter kernel for both lane components in one launch (list 2).  Q28: rows with one image run workgroup-uniform
-    // (list 0), rows with several in per-lane-parameter mode (list 2).  A launch covers every image.
-    struct Launch { int list; int packed; };
-    static const Launch kF32[] = {{1, 1}, {5, 5}, {6, 6}, {7, 7}, {8, 8}, {3, 3}, {4, 4}, {2, 2}};      // lists 3 / 4: per-lane-value rows (packed kernel + value tiles); 5 - 8: latency layout
-    static const Launch kQ28[] = {{0, 0}, {2, 2}};
-    const Launch *ls = c->flavor ? kF32 : kQ28;
-    const int nl = c->flavor ? 8 : 2;
     a.vals = c->d_vals;
-    // the chain launches for the rows [r0, r1) (the lists are sorted by row)
+    // the chain launches for the rows [r0, r1): every non-empty path of the plan, in launch order (the lists are sorted by row)
     auto launch_rows_1 = [&](uint32_t r0, uint32_t r1) -> int {
-        for (int lev = 0; lev < 2; lev++)
-            for (int l = 0; l < nl; l++) {
-                const auto &items = c->launch_items[lev][ls[l].list];
-                if (items.empty()) continue;
-                auto by_row = [](const WgItem &it, uint32_t r) { return it.wg < r; };
-                const size_t lo = (size_t)(std::lower_bound(items.begin(), items.end(), r0, by_row) - items.begin());
-                const size_t hi = (size_t)(std::lower_bound(items.begin(), items.end(), r1, by_row) - items.begin());
-                if (hi == lo) continue;
-                a.items = c->d_litems + c->launch_item_offset[lev][ls[l].list] + lo;
-                hipError_t e = launch_chain(c->flavor, ls[l].packed, lev != 0, a, (uint32_t)(hi - lo), c->hs);
-                if (e == hipErrorNotSupported) return fail(c, DSPI_E_UNSUPPORTED, "this flavour has no HIP kernel yet");
-                if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string("chain kernel launch: ") + hipGetErrorString(e));
-                c->audio_started = true;      // only now: a call refused for its arguments, or one that could not allocate, leaves a booting device booting (dspi_load_flash_dump)
-            }
+        for (const PathInfo &pi : kPaths) {
+            const auto &items = c->plan.items[(int)pi.path];
+            if (items.empty()) continue;
+            auto by_row = [](const WgItem &it, uint32_t r) { return it.wg < r; };
+            const size_t lo = (size_t)(std::lower_bound(items.begin(), items.end(), r0, by_row) - items.begin());
+            const size_t hi = (size_t)(std::lower_bound(items.begin(), items.end(), r1, by_row) - items.begin());
+            if (hi == lo) continue;
+            a.items = c->d_litems + c->plan.offset[(int)pi.path] + lo;
+            hipError_t e = launch_chain(pi.path, a, (uint32_t)(hi - lo), c->hs);
+            if (e == hipErrorNotSupported) return fail(c, DSPI_E_UNSUPPORTED, "this flavour has no HIP kernel yet");
+            if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string("chain kernel launch: ") + hipGetErrorString(e));
+            c->audio_started = true;      // only now: a call refused for its arguments, or one that could not allocate, leaves a booting device booting (dspi_load_flash_dump)
+        }
         return 0;
     };
     const uint32_t row_ = (uint32_t)c->sm.row;

@@ -20,7 +20,7 @@
 // gain, delay line, peaks, words, one lane per frame, so a stream's S/PDIF pair buffer is written as whole coalesced lines.  One
 // barrier per batch; the post-crossfeed rows are double-buffered.
 //
-// Scope (dspi_capi.cpp skew_class / skew_pair_limit): float lanes in launches small enough to leave the chip underfilled.  A workgroup runs
+// Scope (dspi_plan.cpp skew_class / skew_pair_limit): float lanes in launches small enough to leave the chip underfilled.  A workgroup runs
 // one parameter image; a lane whose two streams carry different images runs in two workgroups, once per image, with the other half
 // inactive (sk_ha / sk_hb: every store is per half) — so any assignment of presets to streams is served.  Three shapes by the image's class: no output runs an EQ (this file, EQO = false: the output side is
 // frame-parallel), outputs with EQs (this file, EQO = true: every output a systolic row), leveller on (dspi_chain_skew_lev.inc).  Same
@@ -45,7 +45,6 @@ template <bool EQO> struct SkCfg {
 };
 static_assert(SkCfg<false>::waves == 8 && SkCfg<true>::waves == 8, "one block size");
 constexpr int kSkWaves = 8;
-constexpr uint32_t kSkPartShift = 26;  // WgItem::image of a latency-layout item: image index | part of the row << 26
 constexpr int kSkDepth = 14;           // stage 14 finishes frame t - 14 in step t
 constexpr int kSkOutDepth = 11;        // an output row's stage 11 hands on frame t - 11 in step t
 constexpr int kSkMaxB = 192;           // DSPI_MAX_BLOCK_LEN
@@ -98,7 +97,7 @@ __device__ __forceinline__ float sk_wave_max(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
-// ---- paired presets (PP): the stream slots of a workgroup hold DIFFERENT parameter images of ONE structure (dspi_capi.cpp ImageSig: what
+// ---- paired presets (PP): the stream slots of a workgroup hold DIFFERENT parameter images of ONE structure (dspi_plan.h ImageSig: what
 // steers control flow — flags, band forms, bypasses, enables, the crosspoints' zero pattern, delays in samples, rate — is equal), the case
 // of a small context in which every stream has a preset of its own.  Structural reads keep coming from the item's image; every NUMBER
 // (band coefficients, preamps, volumes, crosspoint and output gains, the leveller's and the crossfeed's constants) becomes a

@@ -149,11 +149,27 @@ struct StateOps {
     uint32_t clear_clips;          // REQ_CLEAR_CLIPS
 };
 
+// One work item: a row of streams (a workgroup of the chain kernels, or a part of one) and the lanes of it that a launch serves.  Float
+// lane l of row `wg` holds streams wg*128 + 2l (its first stream) and + 2l + 1 (its second); a Q28 lane holds stream wg*64 + l.
+// What `image`, `mask` and `mask1` mean, by list (dspi_plan.h Path):
+//   state mutations (dspi_plan.h image_rows): image unused (0); mask / mask1 = lanes whose first / second stream is on the image
+//   F32Packed(Lev)      image = the image of both streams; mask = lanes whose two streams run; mask1 = mask (unread)
+//   F32Pv{Bands,Shared}(Lev)  one item per row: image = the row's first image (read for the structure; the numbers come from the value
+//                       tile); mask = lanes whose two streams run; mask1 = 0
+//   F32OneStream        image = the lane component c (0 / 1); mask = lanes whose stream 2l + c runs, on that stream's own image
+//                       (KArgs::stream_image); mask1 = 0.  A row has one item per component.
+//   F32Skew*            ONE workgroup: image = image index | part << kSkPartShift; the part holds lanes [part*P, part*P + P) with P = 8
+//                       stream pairs (shape 1) or 2 (shapes 2, 3); mask / mask1 = lanes whose first / second stream run, read inside the
+//                       part only (items of the size rule carry the whole row's masks).  Plain: every such stream is on the image; paired
+//                       (*PP): on images of one ImageSig, each slot reading its own (KArgs::stream_image), `image` names the first
+//   Q28Uniform          image = the image of every listed lane; mask = lanes; mask1 = 0
+//   Q28PerLane          one item per row, image unused (0); mask = lanes, each on its own image (KArgs::stream_image); mask1 = 0
 struct WgItem {
     uint32_t wg;
-    uint32_t image;  // chain launches: index of the workgroup's parameter image (one launch covers every image)
-    uint64_t mask;   // lanes of this workgroup that take part in the launch
-    uint64_t mask1;  // state_ops only (float flavour): second stream of each lane; chain launches ignore it
+    uint32_t image;
+    uint64_t mask;
+    uint64_t mask1;
 };
+constexpr uint32_t kSkPartShift = 26;      // latency-layout items: image index | part of the row << kSkPartShift
 
 }  // namespace dspi

@@ -1689,7 +1689,7 @@ static hipError_t launch_chain_skew_lev(const KArgs &args, uint32_t n_items, hip
 }
 #endif
 #if !defined(DSPI_PART) || DSPI_PART == 7
-hipError_t launch_chain_skew(const KArgs &args, uint32_t n_items, int shape, hipStream_t stream) {      // shape 1 / 2 / 3: dspi_capi.cpp skew_class
+hipError_t launch_chain_skew(const KArgs &args, uint32_t n_items, int shape, hipStream_t stream) {      // shape 1 / 2 / 3: dspi_plan.cpp skew_class
     if (shape == 3) return launch_chain_skew_lev<false>(args, n_items, stream);
     return shape == 2 ? launch_chain_skew_t<true, false>(args, n_items, stream) : launch_chain_skew_t<false, false>(args, n_items, stream);
 }
@@ -1756,17 +1756,27 @@ hipError_t launch_pv_build(const DevImage *img, const uint32_t *stream_image, co
     return hipGetLastError();
 }
 
-hipError_t launch_chain(int flavor, int packed, bool leveller_on, const KArgs &args, uint32_t n_items, hipStream_t stream) {
-    // packed: 0 = one stream per lane, workgroup-uniform image (Q28) | 1 = packed float kernel | 2 = one stream per lane,
-    // per-lane images (float always; Q28 rows with several presets)
-    if (!flavor) return packed == 2 ? launch_chain_t<0, true>(args, n_items, stream) : launch_chain_t<0, false>(args, n_items, stream);
+hipError_t launch_chain(Path path, const KArgs &args, uint32_t n_items, hipStream_t stream) {
     // float: the context's contract (DSPI_FLOAT_CONTRACT_FMA) picks the kernel family
-    if (packed == 5 || packed == 6) return launch_chain_skew(args, n_items, leveller_on ? 3 : (packed == 6 ? 2 : 1), stream);
-    if (packed == 7 || packed == 8) return launch_chain_skew_pp(args, n_items, leveller_on ? 3 : (packed == 8 ? 2 : 1), stream);
-    if (packed != 1 && packed != 3 && packed != 4) return args.fma ? launch_chain_t<1, false, true>(args, n_items, stream) : launch_chain_t<1, false, false>(args, n_items, stream);
-    if (packed == 3) return args.fma ? launch_chain_pk_f5(args, leveller_on, n_items, stream) : launch_chain_pk_f2(args, leveller_on, n_items, stream);
-    if (packed == 4) return args.fma ? launch_chain_pk_f4(args, leveller_on, n_items, stream) : launch_chain_pk_f1(args, leveller_on, n_items, stream);
-    return args.fma ? launch_chain_pk_f3(args, leveller_on, n_items, stream) : launch_chain_pk_f0(args, leveller_on, n_items, stream);
+    const bool fma = args.fma != 0;
+    switch (path) {      // (the order in which the cases first name a template is the order of the kernels in the code object)
+        case Path::Q28PerLane: return launch_chain_t<0, true>(args, n_items, stream);
+        case Path::Q28Uniform: return launch_chain_t<0, false>(args, n_items, stream);
+        case Path::F32Skew1: return launch_chain_skew(args, n_items, 1, stream);
+        case Path::F32Skew2: return launch_chain_skew(args, n_items, 2, stream);
+        case Path::F32Skew3: return launch_chain_skew(args, n_items, 3, stream);
+        case Path::F32Skew1PP: return launch_chain_skew_pp(args, n_items, 1, stream);
+        case Path::F32Skew2PP: return launch_chain_skew_pp(args, n_items, 2, stream);
+        case Path::F32Skew3PP: return launch_chain_skew_pp(args, n_items, 3, stream);
+        case Path::F32OneStream: return fma ? launch_chain_t<1, false, true>(args, n_items, stream) : launch_chain_t<1, false, false>(args, n_items, stream);
+        case Path::F32PvBands: return fma ? launch_chain_pk_f5(args, false, n_items, stream) : launch_chain_pk_f2(args, false, n_items, stream);
+        case Path::F32PvBandsLev: return fma ? launch_chain_pk_f5(args, true, n_items, stream) : launch_chain_pk_f2(args, true, n_items, stream);
+        case Path::F32PvShared: return fma ? launch_chain_pk_f4(args, false, n_items, stream) : launch_chain_pk_f1(args, false, n_items, stream);
+        case Path::F32PvSharedLev: return fma ? launch_chain_pk_f4(args, true, n_items, stream) : launch_chain_pk_f1(args, true, n_items, stream);
+        case Path::F32Packed: return fma ? launch_chain_pk_f3(args, false, n_items, stream) : launch_chain_pk_f0(args, false, n_items, stream);
+        case Path::F32PackedLev: return fma ? launch_chain_pk_f3(args, true, n_items, stream) : launch_chain_pk_f0(args, true, n_items, stream);
+    }
+    return hipErrorInvalidValue;
 }
 
 // ---- debug: per-band taps of one float EQ channel (include/dspi.h dspi_debug_eq_taps) ----

@@ -1322,7 +1322,7 @@ def test_i2s_slot_words_fused_into_the_chain(flavor, tiled, monkeypatch):
 def test_paired_presets_widen_the_size_rule():
     """The library's own choice: 4 096 streams with output EQ and no leveller take the packed kernel when they share a preset (the chip is
     filled enough) and the latency layout when every stream has its own (the alternative being the packed per-lane-filter kernel:
-    13.9 against 22.6 ms per 200 packets) — dspi_capi.cpp rebuild_launch_lists.  Sampled streams against their oracles either way."""
+    13.9 against 22.6 ms per 200 packets) — dspi_plan.cpp all_small_rule.  Sampled streams against their oracles either way."""
     S, B, blocks, fs = 4096, 48, 4, 48000
     blob = WL.full_chain_blob(1); blob["leveller"]["enabled"] = 0
     pcm = WL.synth_pcm16(S, B * blocks, fs)
