@@ -783,263 +783,205 @@ int dspi_sync(dspi_ctx *c) {
     return DSPI_OK;
 }
 
-int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t flags) {
-    if (!c || !pcm_in || !out) return DSPI_E_INVAL;
-    // undefined flag bits are refused, not ignored: a later ABI may give them a meaning that reads further members of dspi_out
-    constexpr uint32_t kKnownFlags = DSPI_MEM_DEVICE | DSPI_OUT_TILED | DSPI_OUT_ENABLED_ONLY | DSPI_OUT_I2S_SLOTS | DSPI_OUT_SPDIF | DSPI_OUT_CLIP_FLAGS;
-    if (flags & ~kKnownFlags) return fail(c, DSPI_E_INVAL, "dspi_process: undefined flag bits");
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
-    if ((bit_depth != 16 && bit_depth != 24) || n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN)
-        return fail(c, DSPI_E_INVAL, "bit_depth must be 16/24, 1 <= block_len <= 192, n_blocks >= 1");
-    const auto call_t0 = std::chrono::steady_clock::now();
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = commit_params(c);
-    if (rc) return rc;
-    // alpha^count (leveller.c:200) on the device = step 1 of include/dspi_detmath.h's powf + its exception table; proven equal to the exact form
-    // for the firmware's alphas and every block length by tools/gen_detmath_tables.c — and checked here for the pairs this context really uses
-    if (c->lv_checked_count != block_len || c->lv_checked_n != c->lv_alphas.size()) {
-        for (const uint32_t bits : c->lv_alphas) {
-            float al; memcpy(&al, &bits, 4);
-            const float t = dspi_det_powf_tab(al, (float)block_len), e = dspi_det_powf(al, (float)block_len);
-            if (memcmp(&t, &e, 4) != 0) return fail(c, DSPI_E_UNSUPPORTED, "leveller alpha^count: this (alpha, block length) is not covered by the device's exception table (include/dspi_detmath_tables.h)");
-        }
-        c->lv_checked_count = block_len; c->lv_checked_n = c->lv_alphas.size();
-    }
+// ---- dspi_process: the call's layout (dspi_plan.h plan_call), then one of three memory paths ----
 
-    const size_t frames = (size_t)n_blocks * block_len;
-    const size_t in_b = (size_t)c->n_streams * frames * (bit_depth == 24 ? 6 : 4);
-    const bool tiled = flags & DSPI_OUT_TILED;
-    const bool spdif = flags & DSPI_OUT_SPDIF;
-    bool spdif_two_pass = false;
-    if (spdif) {
-        if (tiled || (flags & DSPI_OUT_I2S_SLOTS)) return fail(c, DSPI_E_INVAL, "DSPI_OUT_SPDIF goes with neither DSPI_OUT_TILED nor DSPI_OUT_I2S_SLOTS");
-        // The latency layout's output waves encode the subframes themselves.  A launch with lanes on any other kernel (the flag is a
-        // property of the output, not of the stream count) runs the chain into a scratch buffer of pair words, row chunk by row chunk,
-        // and the subframe encoder from there into `pairs`: the same words, the block position carried the same way.
-        bool all_latency = c->flavor != 0;
-        for (const PathInfo &pi : kPaths)
-            if (pi.group != PathGroup::Latency && !c->plan.items[(int)pi.path].empty()) all_latency = false;
-        spdif_two_pass = !all_latency && out->pairs != nullptr;
+// alpha^count (leveller.c:200) on the device = step 1 of include/dspi_detmath.h's powf + its exception table; proven equal to the exact form
+// for the firmware's alphas and every block length by tools/gen_detmath_tables.c — and checked here for the alphas this context has built
+// into its images (every one it ever built, leveller on or off), once per block length and set of alphas
+static int check_leveller_alphas(dspi_ctx *c, uint32_t block_len) {
+    if (c->lv_checked_count == block_len && c->lv_checked_n == c->lv_alphas.size()) return 0;
+    for (const uint32_t bits : c->lv_alphas) {
+        float al; memcpy(&al, &bits, 4);
+        const float t = dspi_det_powf_tab(al, (float)block_len), e = dspi_det_powf(al, (float)block_len);
+        if (memcmp(&t, &e, 4) != 0) return fail(c, DSPI_E_UNSUPPORTED, "leveller alpha^count: this (alpha, block length) is not covered by the device's exception table (include/dspi_detmath_tables.h)");
     }
-    const size_t padded = (size_t)c->n_wg * c->sm.row;          // tiled buffers cover whole tiles
-    const size_t pairs_b = tiled ? padded * (c->sm.n_out - 1) * frames * 4 : (size_t)c->n_streams * c->sm.n_pairs * frames * (spdif ? 16 : 8);
-    const size_t sub_b = (tiled ? padded : (size_t)c->n_streams) * frames * 4;
-    const size_t peaks_b = (size_t)c->n_streams * n_blocks * c->sm.n_ch * 2;
-    const bool dev = flags & DSPI_MEM_DEVICE;
-    // DSPI_OUT_CLIP_FLAGS: the caller's dspi_out has the ABI-7 member `clip_flags`
-    uint16_t *const clip_out = (flags & DSPI_OUT_CLIP_FLAGS) ? out->clip_flags : nullptr;
+    c->lv_checked_count = block_len; c->lv_checked_n = c->lv_alphas.size();
+    return 0;
+}
 
-    KArgs a{};
-    a.state = c->d_state; a.dlines = c->d_dlines; a.ring = c->d_ring;
-    a.n_streams = c->n_streams; a.n_blocks = n_blocks; a.block_len = block_len; a.bit_depth = (uint32_t)bit_depth;
-    a.tiled_out = tiled ? 1u : 0u;
-    a.fma = c->fma ? 1u : 0u;
-    // (two-pass S/PDIF: the encoder reads the WHOLE scratch chunk, so the chain must write the silent pairs' zero words there as well)
-    a.skip_silent = ((flags & DSPI_OUT_ENABLED_ONLY) && !spdif_two_pass) ? 1u : 0u;
-    a.i2s_slots = (flags & DSPI_OUT_I2S_SLOTS) ? 1u : 0u;
-    if (spdif) { a.spdif = spdif_two_pass ? 0u : 1u; a.spdif_pos = c->spdif_pos; }
-    if (c->flavor && !tiled) {      // stream-major layout, packed kernel: the mini lines of the outputs whose rows do not reach the emit wave through their delay line (dspi_chain_pk.inc)
-        const size_t xb = (size_t)c->n_wg * 3 * kMaxOut * kChunk * c->sm.row * 4;
-        if ((rc = ensure(c, c->d_xwords, c->d_xwords_cap, xb))) return rc;
-        a.xwords = c->d_xwords;
+// the chain launches for the rows [r0, r1): every non-empty path of the plan, in launch order (the lists are sorted by row)
+static int launch_paths(dspi_ctx *c, KArgs &a, uint32_t r0, uint32_t r1) {
+    for (const PathInfo &pi : kPaths) {
+        const auto &items = c->plan.items[(int)pi.path];
+        if (items.empty()) continue;
+        auto by_row = [](const WgItem &it, uint32_t r) { return it.wg < r; };
+        const size_t lo = (size_t)(std::lower_bound(items.begin(), items.end(), r0, by_row) - items.begin());
+        const size_t hi = (size_t)(std::lower_bound(items.begin(), items.end(), r1, by_row) - items.begin());
+        if (hi == lo) continue;
+        a.items = c->d_litems + c->plan.offset[(int)pi.path] + lo;
+        hipError_t e = launch_chain(pi.path, a, (uint32_t)(hi - lo), c->hs);
+        if (e == hipErrorNotSupported) return fail(c, DSPI_E_UNSUPPORTED, "this flavour has no HIP kernel yet");
+        if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string("chain kernel launch: ") + hipGetErrorString(e));
+        c->audio_started = true;      // only now: a call refused for its arguments, or one that could not allocate, leaves a booting device booting (dspi_load_flash_dump)
     }
-    // ---- small calls on host buffers: the drop-in as the firmware's main loop makes it, ONE packet per call (usb_audio_drain_ring,
-    // usb_audio.c:1326-1332).  Staged copies would cost four DMA round trips (~100 us) for a few KB; instead the kernels read the packet
-    // from, and write their words to, a pinned host area directly (fine-grained, GPU-visible: hipHostMalloc), so the call is two memcpys on
-    // the CPU, the launches, and a spin on the stream: its latency is the kernel's. ----
-    constexpr size_t kDirectBytes = 2u << 20;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t off_pairs = up(in_b), off_sub = off_pairs + up(out->pairs ? pairs_b : 0), off_peaks = off_sub + up(out->sub ? sub_b : 0),
-                 off_clip = off_peaks + up(out->peaks ? peaks_b : 0), direct_b = off_clip + up(clip_out ? (size_t)c->n_streams * 2 : 0);
-    const bool direct = !dev && direct_b <= kDirectBytes && !c->no_direct;
-    if (direct && direct_b > c->direct_cap) {
-        if (c->h_direct) { HIPCK(c, hipStreamSynchronize(c->hs)); (void)hipHostFree(c->h_direct); c->h_direct = nullptr; c->direct_cap = 0; }
-        const size_t want = std::max<size_t>(direct_b, 64u << 10);
-        void *hp = nullptr, *dp = nullptr;
-        if (hipHostMalloc(&hp, want, hipHostMallocDefault) != hipSuccess) return fail(c, DSPI_E_NOMEM, "hipHostMalloc failed (direct host area)");
-        if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { (void)hipHostFree(hp); return fail(c, DSPI_E_HIP, "hipHostGetDevicePointer failed"); }
-        c->h_direct = (char *)hp; c->d_direct = (char *)dp; c->direct_cap = want;
-    }
-    if (dev) {
-        a.pcm = pcm_in; a.pairs = out->pairs; a.sub = out->sub; a.peaks = out->peaks;
-    } else if (direct) {
-        memcpy(c->h_direct, pcm_in, in_b);
-        a.pcm = c->d_direct;
-        if (out->pairs) a.pairs = reinterpret_cast<int32_t *>(c->d_direct + off_pairs);
-        if (out->sub) a.sub = reinterpret_cast<int32_t *>(c->d_direct + off_sub);
-        if (out->peaks) a.peaks = reinterpret_cast<uint16_t *>(c->d_direct + off_peaks);
-        if (flags & DSPI_OUT_ENABLED_ONLY) {      // (silent parts stay unwritten by the kernels: the caller finds zeros, the firmware's own fill)
-            if (out->pairs) memset(c->h_direct + off_pairs, 0, pairs_b);
-            if (out->sub) memset(c->h_direct + off_sub, 0, sub_b);
-        }
-    } else {
-        if ((rc = ensure(c, c->d_in, c->d_in_cap, in_b))) return rc;
-        a.pcm = c->d_in;
-        if (out->pairs) { if ((rc = ensure(c, c->d_pairs, c->d_pairs_cap, pairs_b))) return rc; a.pairs = c->d_pairs; }
-        if (out->sub) { if ((rc = ensure(c, c->d_sub, c->d_sub_cap, sub_b))) return rc; a.sub = c->d_sub; }
-        if (out->peaks) { if ((rc = ensure(c, c->d_peaks, c->d_peaks_cap, peaks_b))) return rc; a.peaks = c->d_peaks; }
-        if (clip_out && (rc = ensure(c, c->d_clip, c->d_clip_cap, (size_t)c->n_streams * 2))) return rc;
-        // DSPI_OUT_ENABLED_ONLY leaves the silent parts of pairs / sub unwritten: the staging buffers are copied back whole, so what the
-        // caller finds there is zeros (the firmware's own fill), not stale staging memory
-        if (flags & DSPI_OUT_ENABLED_ONLY) {
-            if (a.pairs) HIPCK(c, hipMemsetAsync(a.pairs, 0, pairs_b, c->hs));
-            if (a.sub) HIPCK(c, hipMemsetAsync(a.sub, 0, sub_b, c->hs));
-        }
-    }
-    int32_t *const final_pairs = a.pairs;      // where the caller's pair words / subframes end up (device side)
-    uint32_t two_pass_rows = 0;
-    if (spdif_two_pass) {
-        // scratch for the chain's pair words of a row chunk, capped by BYTES: ~1 GiB worth of rows; one workgroup per CU (256 rows) only
-        // while that stays within 2 GiB; never less than one row
-        const size_t row_b = (size_t)c->sm.row * c->sm.n_pairs * frames * 8;
-        size_t rows = std::max<size_t>(1, ((size_t)1 << 30) / row_b);
-        if (rows < 256 && 256 * row_b <= ((size_t)2 << 30)) rows = 256;
-        two_pass_rows = (uint32_t)std::min<size_t>(c->n_wg, rows);
-        if ((rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, (size_t)two_pass_rows * row_b))) return rc;
-    }
-    a.img = c->d_images;
-    a.stream_image = c->d_stream_image;
-    a.vals = c->d_vals;
-    // the chain launches for the rows [r0, r1): every non-empty path of the plan, in launch order (the lists are sorted by row)
-    auto launch_rows_1 = [&](uint32_t r0, uint32_t r1) -> int {
-        for (const PathInfo &pi : kPaths) {
-            const auto &items = c->plan.items[(int)pi.path];
-            if (items.empty()) continue;
-            auto by_row = [](const WgItem &it, uint32_t r) { return it.wg < r; };
-            const size_t lo = (size_t)(std::lower_bound(items.begin(), items.end(), r0, by_row) - items.begin());
-            const size_t hi = (size_t)(std::lower_bound(items.begin(), items.end(), r1, by_row) - items.begin());
-            if (hi == lo) continue;
-            a.items = c->d_litems + c->plan.offset[(int)pi.path] + lo;
-            hipError_t e = launch_chain(pi.path, a, (uint32_t)(hi - lo), c->hs);
-            if (e == hipErrorNotSupported) return fail(c, DSPI_E_UNSUPPORTED, "this flavour has no HIP kernel yet");
-            if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string("chain kernel launch: ") + hipGetErrorString(e));
-            c->audio_started = true;      // only now: a call refused for its arguments, or one that could not allocate, leaves a booting device booting (dspi_load_flash_dump)
-        }
-        return 0;
-    };
-    const uint32_t row_ = (uint32_t)c->sm.row;
-    auto launch_rows = [&](uint32_t r0, uint32_t r1) -> int {
-        if (!spdif_two_pass) return launch_rows_1(r0, r1);
-        const size_t per_stream = (size_t)c->sm.n_pairs * frames;      // frames of pair words per stream
-        for (uint32_t q0 = r0; q0 < r1; q0 += two_pass_rows) {
-            const uint32_t q1 = std::min(r1, q0 + two_pass_rows);
-            const size_t s0 = (size_t)q0 * row_, s1 = std::min((size_t)q1 * row_, (size_t)c->n_streams);
-            a.pairs = c->d_spdif_words; a.pairs_stream0 = (uint32_t)s0;      // the kernels index by absolute stream: stream s0 lands at the scratch's start
-            int r = launch_rows_1(q0, q1);
-            if (r) return r;
-            hipError_t e = launch_spdif(false, c->d_spdif_words, reinterpret_cast<uint32_t *>(final_pairs) + s0 * per_stream * 4, (uint32_t)(s1 - s0), (uint32_t)c->sm.n_pairs,
-                                        (uint32_t)frames, row_, q1 - q0, c->spdif_pos, 0u, SpdifRates{c->d_images, c->d_stream_image, (uint32_t)s0}, c->hs);
-            if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string("spdif encoder launch: ") + hipGetErrorString(e));
-        }
-        return 0;
-    };
-    // sticky clip flags of every stream (global_status.clip_flags, usb_audio.c:2427-2443), after the chain on the same stream
-    auto gather_clip = [&](uint16_t *dst) -> int {
-        hipError_t e = launch_clip_gather(c->d_state, c->n_streams, row_, (uint32_t)c->sm.n_slots, (uint32_t)c->sm.clip, dst, c->hs);
-        return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("clip gather launch: ") + hipGetErrorString(e));
-    };
-    if (dev) {
-        if ((rc = launch_rows(0, c->n_wg))) return rc;
-        if (clip_out && (rc = gather_clip(clip_out))) return rc;
-        if (spdif) c->spdif_pos = (uint32_t)((c->spdif_pos + frames) % 192u);      // only once everything is enqueued: a failed call leaves the block position alone
-        return DSPI_OK;
-    }
-    if (direct) {
-        if ((rc = launch_rows(0, c->n_wg))) return rc;
-        if (clip_out && (rc = gather_clip(reinterpret_cast<uint16_t *>(c->d_direct + off_clip)))) return rc;
-        // the launches take tens of microseconds: polling answers within a microsecond of their end, a blocking wait adds a wake-up — but only
-        // for as long as such launches can take: past the budget the call falls back to the blocking wait (a hung queue, or a host running
-        // many contexts, must not pin a core).  The budget: the audio time the call carries (a caller in the firmware's rhythm has exactly
-        // that long per call), never less than 300 us, never more than 50 ms; DSPI_DIRECT_SPIN_US (read at dspi_create) overrides it.
-        // (The rare 0.5-10 ms calls — BENCH_r05 had one — are not this loop's: its clock check does not fire during them, the thread is off
-        //  its core; profiles/r06_realtime_polling.md.)
-        // What is polled (round 6): a word in pinned host memory that the stream itself sets to this call's sequence number behind the launches
-        // (hipStreamWriteValue32) — a load per poll, no call into the runtime while waiting; hipStreamQuery where that is not available
-        // (DSPI_DIRECT_POLL=query forces it).
-        if (c->direct_flag < 0) {
-            const char *e = getenv("DSPI_DIRECT_POLL");
-            c->direct_flag = 0;
-            if (!(e && !strcmp(e, "query"))) {
-                void *hp = nullptr, *dp = nullptr;
-                if (hipHostMalloc(&hp, 64, hipHostMallocDefault) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-                    c->h_done = (uint32_t *)hp; c->d_done = (uint32_t *)dp; *c->h_done = 0u; c->direct_flag = 1;
-                } else { if (hp) (void)hipHostFree(hp); (void)hipGetLastError(); }
-            }
-        }
-        bool flagged = false;
-        if (c->direct_flag == 1) {
-            ++c->direct_seq;
-            if (hipStreamWriteValue32(c->hs, c->d_done, c->direct_seq, 0) == hipSuccess) flagged = true;
-            else { (void)hipGetLastError(); c->direct_flag = 0; }      // (this runtime / device cannot: the stream is polled from here on)
-        }
-        hipError_t q = hipSuccess;
-        const auto spin_t0 = std::chrono::steady_clock::now();
-        const uint64_t audio_us = (uint64_t)frames * 1000000u / 44100u;      // (the slowest rate the firmware runs: an upper bound of the packet's time)
-        const auto budget = std::chrono::microseconds(c->direct_spin_us ? (uint64_t)c->direct_spin_us : std::min<uint64_t>(50000u, std::max<uint64_t>(300u, audio_us)));
-        uint32_t polls = 0;
-        bool fell_back = false;
-        if (flagged) {
-            volatile const uint32_t *done = c->h_done;
-            const uint32_t want = c->direct_seq;
-            while (*done != want) {
-                __builtin_ia32_pause();
-                if ((++polls & 1023u) == 0 && std::chrono::steady_clock::now() - spin_t0 > budget) { q = hipStreamSynchronize(c->hs); fell_back = true; break; }
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);      // the words the kernels wrote are read after the flag
-        } else {
-            while ((q = hipStreamQuery(c->hs)) == hipErrorNotReady) {
-                if ((++polls & 63u) == 0 && std::chrono::steady_clock::now() - spin_t0 > budget) { q = hipStreamSynchronize(c->hs); fell_back = true; break; }
-            }
-        }
-        {
-            const auto t_end = std::chrono::steady_clock::now();
-            const uint64_t enq = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(spin_t0 - call_t0).count();
-            const uint64_t wait = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(t_end - spin_t0).count();
-            c->direct_stats[0]++;
-            if (c->direct_stats[0] > 8) {      // (the context's first calls allocate the pinned area, build the launch lists, load the code objects: not the steady state)
-                c->direct_stats[1] += fell_back ? 1u : 0u;
-                c->direct_stats[2] = std::max(c->direct_stats[2], enq); c->direct_stats[3] = std::max(c->direct_stats[3], wait);
-            }
-            c->direct_stats[4] = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(budget).count();
-        }
-        if (q != hipSuccess) return fail(c, DSPI_E_HIP, std::string("stream: ") + hipGetErrorString(q));
-        if (out->pairs) memcpy(out->pairs, c->h_direct + off_pairs, pairs_b);
-        if (out->sub) memcpy(out->sub, c->h_direct + off_sub, sub_b);
-        if (out->peaks) memcpy(out->peaks, c->h_direct + off_peaks, peaks_b);
-        if (clip_out) memcpy(clip_out, c->h_direct + off_clip, (size_t)c->n_streams * 2);
-        if (spdif) c->spdif_pos = (uint32_t)((c->spdif_pos + frames) % 192u);
-        return DSPI_OK;
-    }
+    return 0;
+}
 
-    // ---- host buffers (the caller of usb_audio.c:1326-1332 is a host feeding packets): staged through device buffers.  The link moves
-    // 4 + 36 bytes per frame, the chain 100 times that, so the call is link-bound; what can be saved is the serialisation: the rows are
-    // cut into chunks and chunk i's D2H runs while chunk i+1 computes and chunk i+2 uploads (three streams, events).  The caller's
-    // buffers are pinned for the duration of the call (hipHostRegister: ~8 ms per GiB) so that the copies are asynchronous DMA; when
-    // that is refused (already registered, read-only mapping ...) the copies still work, just synchronously. ----
+// ... of a call (a: its arguments, a.pairs the caller's words).  Two-pass S/PDIF: L.two_pass_rows rows at a time into the scratch of pair
+// words, then the subframe encoder from there into a.pairs
+static int launch_rows(dspi_ctx *c, KArgs a, const CallLayout &L, uint32_t r0, uint32_t r1) {
+    if (!L.spdif_two_pass) return launch_paths(c, a, r0, r1);
+    char *const subframes = reinterpret_cast<char *>(a.pairs);
     const uint32_t row = (uint32_t)c->sm.row;
-    const size_t out_b = (out->pairs ? pairs_b : 0) + (out->sub ? sub_b : 0) + (out->peaks ? peaks_b : 0);
-    uint32_t n_chunks = 1;
-    if (out_b + in_b >= (32u << 20) && c->n_wg >= 2) {
-        n_chunks = (uint32_t)std::min<size_t>({(size_t)8, (size_t)c->n_wg, (out_b + in_b) / (16u << 20)});
-        if (n_chunks < 1) n_chunks = 1;
+    for (uint32_t q0 = r0; q0 < r1; q0 += L.two_pass_rows) {
+        const uint32_t q1 = std::min(r1, q0 + L.two_pass_rows);
+        const size_t s0 = (size_t)q0 * row, s1 = std::min((size_t)q1 * row, (size_t)c->n_streams);
+        a.pairs = c->d_spdif_words; a.pairs_stream0 = (uint32_t)s0;      // the kernels index by absolute stream: stream s0 lands at the scratch's start
+        int rc = launch_paths(c, a, q0, q1);
+        if (rc) return rc;
+        hipError_t e = launch_spdif(false, c->d_spdif_words, reinterpret_cast<uint32_t *>(subframes + s0 * L.pairs.per), (uint32_t)(s1 - s0), (uint32_t)c->sm.n_pairs,
+                                    (uint32_t)L.frames, row, q1 - q0, c->spdif_pos, 0u, SpdifRates{c->d_images, c->d_stream_image, (uint32_t)s0}, c->hs);
+        if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string("spdif encoder launch: ") + hipGetErrorString(e));
     }
-    const uint32_t rows_per = (c->n_wg + n_chunks - 1) / n_chunks;
-    n_chunks = (c->n_wg + rows_per - 1) / rows_per;
-    struct Pin { void *p; bool on; };
-    Pin pins[4] = {{const_cast<void *>(pcm_in), false}, {out->pairs, false}, {out->sub, false}, {out->peaks, false}};
-    const size_t pin_b[4] = {in_b, pairs_b, sub_b, peaks_b};
+    return 0;
+}
+
+// sticky clip flags of every stream (global_status.clip_flags, usb_audio.c:2427-2443), after the chain on the same stream
+static int gather_clip(dspi_ctx *c, uint16_t *dst) {
+    hipError_t e = launch_clip_gather(c->d_state, c->n_streams, (uint32_t)c->sm.row, (uint32_t)c->sm.n_slots, (uint32_t)c->sm.clip, dst, c->hs);
+    return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("clip gather launch: ") + hipGetErrorString(e));
+}
+
+// ---- device buffers: the caller's own, asynchronous on the context's stream ----
+static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out) {
+    a.pcm = pcm_in; a.pairs = out->pairs; a.sub = out->sub; a.peaks = out->peaks;
+    int rc = 0;
+    if ((L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) || (rc = launch_rows(c, a, L, 0, c->n_wg))) return rc;
+    return clip_out ? gather_clip(c, clip_out) : DSPI_OK;
+}
+
+// ---- small calls on host buffers: the drop-in as the firmware's main loop makes it, ONE packet per call (usb_audio_drain_ring,
+// usb_audio.c:1326-1332).  Staged copies would cost four DMA round trips (~100 us) for a few KB; instead the kernels read the packet
+// from, and write their words to, a pinned host area directly (fine-grained, GPU-visible: hipHostMalloc), so the call is two memcpys on
+// the CPU, the launches, and a spin on the stream: its latency is the kernel's. ----
+static int direct_area(dspi_ctx *c, size_t bytes) {
+    if (bytes <= c->direct_cap) return 0;
+    if (c->h_direct) { HIPCK(c, hipStreamSynchronize(c->hs)); (void)hipHostFree(c->h_direct); c->h_direct = nullptr; c->direct_cap = 0; }
+    const size_t want = std::max<size_t>(bytes, 64u << 10);
+    void *hp = nullptr, *dp = nullptr;
+    if (hipHostMalloc(&hp, want, hipHostMallocDefault) != hipSuccess) return fail(c, DSPI_E_NOMEM, "hipHostMalloc failed (direct host area)");
+    if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { (void)hipHostFree(hp); return fail(c, DSPI_E_HIP, "hipHostGetDevicePointer failed"); }
+    c->h_direct = (char *)hp; c->d_direct = (char *)dp; c->direct_cap = want;
+    return 0;
+}
+
+// What a direct call polls (round 6): a word in pinned host memory that the stream itself sets to the call's sequence number behind the
+// launches (hipStreamWriteValue32) — a load per poll, no call into the runtime while waiting; hipStreamQuery where that is not available
+// (DSPI_DIRECT_POLL=query forces it).  Allocated by the first direct call.
+static void completion_word(dspi_ctx *c) {
+    const char *e = getenv("DSPI_DIRECT_POLL");
+    c->direct_flag = 0;
+    if (e && !strcmp(e, "query")) return;
+    void *hp = nullptr, *dp = nullptr;
+    if (hipHostMalloc(&hp, 64, hipHostMallocDefault) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+        c->h_done = (uint32_t *)hp; c->d_done = (uint32_t *)dp; *c->h_done = 0u; c->direct_flag = 1;
+    } else { if (hp) (void)hipHostFree(hp); (void)hipGetLastError(); }
+}
+
+static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags,
+                          std::chrono::steady_clock::time_point call_t0) {
+    int rc = direct_area(c, L.direct_bytes);
+    if (rc) return rc;
+    char *const h = c->h_direct, *const d = c->d_direct;
+    memcpy(h, pcm_in, L.pcm.bytes);
+    a.pcm = d;
+    if (out->pairs) a.pairs = reinterpret_cast<int32_t *>(d + L.pairs.off);
+    if (out->sub) a.sub = reinterpret_cast<int32_t *>(d + L.sub.off);
+    if (out->peaks) a.peaks = reinterpret_cast<uint16_t *>(d + L.peaks.off);
+    if (flags & DSPI_OUT_ENABLED_ONLY) {      // (silent parts stay unwritten by the kernels: the caller finds zeros, the firmware's own fill)
+        if (out->pairs) memset(h + L.pairs.off, 0, L.pairs.bytes);
+        if (out->sub) memset(h + L.sub.off, 0, L.sub.bytes);
+    }
+    if ((L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) || (rc = launch_rows(c, a, L, 0, c->n_wg)) ||
+        (clip_out && (rc = gather_clip(c, reinterpret_cast<uint16_t *>(d + L.clip.off))))) return rc;
+    // the launches take tens of microseconds: polling answers within a microsecond of their end, a blocking wait adds a wake-up — but only
+    // for as long as such launches can take: past the budget the call falls back to the blocking wait (a hung queue, or a host running
+    // many contexts, must not pin a core).  The budget: the audio time the call carries (a caller in the firmware's rhythm has exactly
+    // that long per call), never less than 300 us, never more than 50 ms; DSPI_DIRECT_SPIN_US (read at dspi_create) overrides it.
+    // (The rare 0.5-10 ms calls — BENCH_r05 had one — are not this loop's: its clock check does not fire during them, the thread is off
+    //  its core; profiles/r06_realtime_polling.md.)
+    if (c->direct_flag < 0) completion_word(c);
+    bool flagged = false;
+    if (c->direct_flag == 1) {
+        ++c->direct_seq;
+        if (hipStreamWriteValue32(c->hs, c->d_done, c->direct_seq, 0) == hipSuccess) flagged = true;
+        else { (void)hipGetLastError(); c->direct_flag = 0; }      // (this runtime / device cannot: the stream is polled from here on)
+    }
+    hipError_t q = hipSuccess;
+    const auto spin_t0 = std::chrono::steady_clock::now();
+    const uint64_t audio_us = (uint64_t)L.frames * 1000000u / 44100u;      // (the slowest rate the firmware runs: an upper bound of the packet's time)
+    const auto budget = std::chrono::microseconds(c->direct_spin_us ? (uint64_t)c->direct_spin_us : std::min<uint64_t>(50000u, std::max<uint64_t>(300u, audio_us)));
+    uint32_t polls = 0;
+    bool fell_back = false;
+    if (flagged) {
+        volatile const uint32_t *done = c->h_done;
+        const uint32_t want = c->direct_seq;
+        while (*done != want) {
+            __builtin_ia32_pause();
+            if ((++polls & 1023u) == 0 && std::chrono::steady_clock::now() - spin_t0 > budget) { q = hipStreamSynchronize(c->hs); fell_back = true; break; }
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);      // the words the kernels wrote are read after the flag
+    } else {
+        while ((q = hipStreamQuery(c->hs)) == hipErrorNotReady) {
+            if ((++polls & 63u) == 0 && std::chrono::steady_clock::now() - spin_t0 > budget) { q = hipStreamSynchronize(c->hs); fell_back = true; break; }
+        }
+    }
+    {
+        const auto t_end = std::chrono::steady_clock::now();
+        const uint64_t enq = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(spin_t0 - call_t0).count();
+        const uint64_t wait = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(t_end - spin_t0).count();
+        c->direct_stats[0]++;
+        if (c->direct_stats[0] > 8) {      // (the context's first calls allocate the pinned area, build the launch lists, load the code objects: not the steady state)
+            c->direct_stats[1] += fell_back ? 1u : 0u;
+            c->direct_stats[2] = std::max(c->direct_stats[2], enq); c->direct_stats[3] = std::max(c->direct_stats[3], wait);
+        }
+        c->direct_stats[4] = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(budget).count();
+    }
+    if (q != hipSuccess) return fail(c, DSPI_E_HIP, std::string("stream: ") + hipGetErrorString(q));
+    if (out->pairs) memcpy(out->pairs, h + L.pairs.off, L.pairs.bytes);
+    if (out->sub) memcpy(out->sub, h + L.sub.off, L.sub.bytes);
+    if (out->peaks) memcpy(out->peaks, h + L.peaks.off, L.peaks.bytes);
+    if (clip_out) memcpy(clip_out, h + L.clip.off, L.clip.bytes);
+    return DSPI_OK;
+}
+
+// ---- host buffers (the caller of usb_audio.c:1326-1332 is a host feeding packets): staged through device buffers.  The link moves
+// 4 + 36 bytes per frame, the chain 100 times that, so the call is link-bound; what can be saved is the serialisation: the rows are
+// cut into chunks and chunk i's D2H runs while chunk i+1 computes and chunk i+2 uploads (three streams, events).  The caller's
+// buffers are pinned for the duration of the call (hipHostRegister: ~8 ms per GiB) so that the copies are asynchronous DMA; when
+// that is refused (already registered, read-only mapping ...) the copies still work, just synchronously. ----
+static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags) {
+    int rc;
+    if ((rc = ensure(c, c->d_in, c->d_in_cap, L.pcm.bytes))) return rc;
+    a.pcm = c->d_in;
+    if (out->pairs) { if ((rc = ensure(c, c->d_pairs, c->d_pairs_cap, L.pairs.bytes))) return rc; a.pairs = c->d_pairs; }
+    if (out->sub) { if ((rc = ensure(c, c->d_sub, c->d_sub_cap, L.sub.bytes))) return rc; a.sub = c->d_sub; }
+    if (out->peaks) { if ((rc = ensure(c, c->d_peaks, c->d_peaks_cap, L.peaks.bytes))) return rc; a.peaks = c->d_peaks; }
+    if (clip_out && (rc = ensure(c, c->d_clip, c->d_clip_cap, L.clip.bytes))) return rc;
+    // DSPI_OUT_ENABLED_ONLY leaves the silent parts of pairs / sub unwritten: the staging buffers are copied back whole, so what the
+    // caller finds there is zeros (the firmware's own fill), not stale staging memory
+    if (flags & DSPI_OUT_ENABLED_ONLY) {
+        if (a.pairs) HIPCK(c, hipMemsetAsync(a.pairs, 0, L.pairs.bytes, c->hs));
+        if (a.sub) HIPCK(c, hipMemsetAsync(a.sub, 0, L.sub.bytes, c->hs));
+    }
+    if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) return rc;
+    const uint32_t n_chunks = L.n_chunks, row = (uint32_t)c->sm.row;
+    // the caller's buffers and the staging buffers: a row range is one contiguous piece of each (tiled words: whole tiles; else streams)
+    struct Buf { void *host; void *dev; const CallBuffer &b; const char *what; bool pinned; };
+    Buf bufs[4] = {{const_cast<void *>(pcm_in), c->d_in, L.pcm, "H2D", false}, {out->pairs, a.pairs, L.pairs, "D2H pairs", false},
+                   {out->sub, a.sub, L.sub, "D2H sub", false}, {out->peaks, a.peaks, L.peaks, "D2H peaks", false}};
     if (n_chunks > 1)
-        for (int i = 0; i < 4; i++)
-            if (pins[i].p && pin_b[i] >= (1u << 20)) {
-                pins[i].on = hipHostRegister(pins[i].p, pin_b[i], hipHostRegisterDefault) == hipSuccess;
-                if (!pins[i].on) (void)hipGetLastError();
+        for (Buf &bf : bufs)
+            if (bf.host && bf.b.bytes >= (1u << 20)) {
+                bf.pinned = hipHostRegister(bf.host, bf.b.bytes, hipHostRegisterDefault) == hipSuccess;
+                if (!bf.pinned) (void)hipGetLastError();
             }
     // (error paths too: no copy or kernel may still be in flight on memory that is about to be unregistered)
     auto unpin = [&]() {
         if (c->hs_in) (void)hipStreamSynchronize(c->hs_in);
         (void)hipStreamSynchronize(c->hs);
         if (c->hs_out) (void)hipStreamSynchronize(c->hs_out);
-        for (auto &pn : pins) if (pn.on) { (void)hipHostUnregister(pn.p); pn.on = false; }
+        for (Buf &bf : bufs) if (bf.pinned) { (void)hipHostUnregister(bf.host); bf.pinned = false; }
     };
     if (n_chunks > 1 && !c->hs_in) {
         if (hipStreamCreateWithFlags(&c->hs_in, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&c->hs_out, hipStreamNonBlocking) != hipSuccess) {
@@ -1051,40 +993,31 @@ int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_bloc
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { unpin(); return fail(c, DSPI_E_HIP, "event creation failed"); }
         c->pipe_events.push_back(e);
     }
-    const size_t bpf = bit_depth == 24 ? 6 : 4;
     auto fail_hip = [&](hipError_t e, const char *what) { unpin(); return fail(c, DSPI_E_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
     hipError_t he;
     for (uint32_t ch = 0; ch < n_chunks; ch++) {
-        const uint32_t r0 = ch * rows_per, r1 = std::min(c->n_wg, r0 + rows_per);
+        const uint32_t r0 = ch * L.rows_per_chunk, r1 = std::min(c->n_wg, r0 + L.rows_per_chunk);
         const size_t s0 = (size_t)r0 * row, s1 = std::min((size_t)r1 * row, (size_t)c->n_streams);      // streams of the chunk
+        auto copy = [&](const Buf &bf, hipMemcpyKind kind, hipStream_t s) {      // the chunk's piece of a buffer
+            const size_t at = s0 * bf.b.per, n = ((bf.b.tile_cols ? (size_t)r1 * row : s1) - s0) * bf.b.per;
+            char *h = static_cast<char *>(bf.host) + at, *d = static_cast<char *>(bf.dev) + at;
+            return kind == hipMemcpyHostToDevice ? hipMemcpyAsync(d, h, n, kind, s) : hipMemcpyAsync(h, d, n, kind, s);
+        };
         hipStream_t sin = n_chunks > 1 ? c->hs_in : c->hs, sout = n_chunks > 1 ? c->hs_out : c->hs;
-        if ((he = hipMemcpyAsync(static_cast<char *>(c->d_in) + s0 * frames * bpf, static_cast<const char *>(pcm_in) + s0 * frames * bpf, (s1 - s0) * frames * bpf,
-                                 hipMemcpyHostToDevice, sin)) != hipSuccess) return fail_hip(he, "H2D");
+        if ((he = copy(bufs[0], hipMemcpyHostToDevice, sin)) != hipSuccess) return fail_hip(he, bufs[0].what);
         if (n_chunks > 1) {
             if ((he = hipEventRecord(c->pipe_events[2 * ch], sin)) != hipSuccess || (he = hipStreamWaitEvent(c->hs, c->pipe_events[2 * ch], 0)) != hipSuccess) return fail_hip(he, "event");
         }
-        if ((rc = launch_rows(r0, r1))) { unpin(); return rc; }
+        if ((rc = launch_rows(c, a, L, r0, r1))) { unpin(); return rc; }
         if (n_chunks > 1) {
             if ((he = hipEventRecord(c->pipe_events[2 * ch + 1], c->hs)) != hipSuccess || (he = hipStreamWaitEvent(sout, c->pipe_events[2 * ch + 1], 0)) != hipSuccess) return fail_hip(he, "event");
         }
-        // tiled words: whole tiles [tile][...]; stream-major: [stream][...] — either way a row range is one contiguous piece
-        const size_t t0 = tiled ? (size_t)r0 * row : s0, t1 = tiled ? (size_t)r1 * row : s1;
-        if (out->pairs) {
-            const size_t per = tiled ? (size_t)(c->sm.n_out - 1) * frames * 4 : (size_t)c->sm.n_pairs * frames * (spdif ? 16 : 8);
-            if ((he = hipMemcpyAsync(reinterpret_cast<char *>(out->pairs) + t0 * per, reinterpret_cast<char *>(final_pairs) + t0 * per, (t1 - t0) * per, hipMemcpyDeviceToHost, sout)) != hipSuccess) return fail_hip(he, "D2H pairs");
-        }
-        if (out->sub) {
-            const size_t per = frames * 4;
-            if ((he = hipMemcpyAsync(reinterpret_cast<char *>(out->sub) + t0 * per, reinterpret_cast<char *>(c->d_sub) + t0 * per, (t1 - t0) * per, hipMemcpyDeviceToHost, sout)) != hipSuccess) return fail_hip(he, "D2H sub");
-        }
-        if (out->peaks) {
-            const size_t per = (size_t)n_blocks * c->sm.n_ch * 2;
-            if ((he = hipMemcpyAsync(reinterpret_cast<char *>(out->peaks) + s0 * per, reinterpret_cast<char *>(c->d_peaks) + s0 * per, (s1 - s0) * per, hipMemcpyDeviceToHost, sout)) != hipSuccess) return fail_hip(he, "D2H peaks");
-        }
+        for (int k = 1; k < 4; k++)
+            if (bufs[k].host && (he = copy(bufs[k], hipMemcpyDeviceToHost, sout)) != hipSuccess) return fail_hip(he, bufs[k].what);
     }
     if (clip_out) {
-        if ((rc = gather_clip(c->d_clip))) { unpin(); return rc; }
-        if ((he = hipMemcpyAsync(clip_out, c->d_clip, (size_t)c->n_streams * 2, hipMemcpyDeviceToHost, c->hs)) != hipSuccess) return fail_hip(he, "D2H clip flags");
+        if ((rc = gather_clip(c, c->d_clip))) { unpin(); return rc; }
+        if ((he = hipMemcpyAsync(clip_out, c->d_clip, L.clip.bytes, hipMemcpyDeviceToHost, c->hs)) != hipSuccess) return fail_hip(he, "D2H clip flags");
     }
     if (n_chunks > 1) {
         if ((he = hipStreamSynchronize(c->hs_out)) != hipSuccess) return fail_hip(he, "sync");
@@ -1092,8 +1025,58 @@ int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_bloc
     }
     if ((he = hipStreamSynchronize(c->hs)) != hipSuccess) return fail_hip(he, "sync");
     unpin();
-    if (spdif) c->spdif_pos = (uint32_t)((c->spdif_pos + frames) % 192u);
     return DSPI_OK;
+}
+
+int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t flags) {
+    if (!c || !pcm_in || !out) return DSPI_E_INVAL;
+    // undefined flag bits are refused, not ignored: a later ABI may give them a meaning that reads further members of dspi_out
+    constexpr uint32_t kKnownFlags = DSPI_MEM_DEVICE | DSPI_OUT_TILED | DSPI_OUT_ENABLED_ONLY | DSPI_OUT_I2S_SLOTS | DSPI_OUT_SPDIF | DSPI_OUT_CLIP_FLAGS;
+    if (flags & ~kKnownFlags) return fail(c, DSPI_E_INVAL, "dspi_process: undefined flag bits");
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if ((bit_depth != 16 && bit_depth != 24) || n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN)
+        return fail(c, DSPI_E_INVAL, "bit_depth must be 16/24, 1 <= block_len <= 192, n_blocks >= 1");
+    const auto call_t0 = std::chrono::steady_clock::now();
+    HIPCK(c, hipSetDevice(c->device));
+    int rc = commit_params(c);
+    if (rc || (rc = check_leveller_alphas(c, block_len))) return rc;
+
+    // DSPI_OUT_CLIP_FLAGS: the caller's dspi_out has the ABI-7 member `clip_flags`
+    uint16_t *const clip_out = (flags & DSPI_OUT_CLIP_FLAGS) ? out->clip_flags : nullptr;
+    CallInput in;
+    in.n_streams = c->n_streams; in.n_wg = c->n_wg; in.row = (uint32_t)c->sm.row; in.n_ch = (uint32_t)c->sm.n_ch; in.n_out = (uint32_t)c->sm.n_out;
+    in.n_pairs = (uint32_t)c->sm.n_pairs; in.n_blocks = n_blocks; in.block_len = block_len; in.bit_depth = (uint32_t)bit_depth; in.flags = flags;
+    in.pairs = out->pairs; in.sub = out->sub; in.peaks = out->peaks; in.clip = clip_out; in.no_direct = c->no_direct;
+    in.all_latency = c->flavor != 0;
+    for (const PathInfo &pi : kPaths)
+        if (pi.group != PathGroup::Latency && !c->plan.items[(int)pi.path].empty()) in.all_latency = false;
+    const CallLayout L = plan_call(in);
+    const bool tiled = flags & DSPI_OUT_TILED, spdif = flags & DSPI_OUT_SPDIF;
+    if (spdif && (tiled || (flags & DSPI_OUT_I2S_SLOTS))) return fail(c, DSPI_E_INVAL, "DSPI_OUT_SPDIF goes with neither DSPI_OUT_TILED nor DSPI_OUT_I2S_SLOTS");
+
+    KArgs a{};
+    a.img = c->d_images; a.stream_image = c->d_stream_image; a.vals = c->d_vals;
+    a.state = c->d_state; a.dlines = c->d_dlines; a.ring = c->d_ring;
+    a.n_streams = c->n_streams; a.n_blocks = n_blocks; a.block_len = block_len; a.bit_depth = (uint32_t)bit_depth;
+    a.tiled_out = tiled ? 1u : 0u;
+    a.fma = c->fma ? 1u : 0u;
+    // (two-pass S/PDIF: the encoder reads the WHOLE scratch chunk, so the chain must write the silent pairs' zero words there as well)
+    a.skip_silent = ((flags & DSPI_OUT_ENABLED_ONLY) && !L.spdif_two_pass) ? 1u : 0u;
+    a.i2s_slots = (flags & DSPI_OUT_I2S_SLOTS) ? 1u : 0u;
+    if (spdif) { a.spdif = L.spdif_two_pass ? 0u : 1u; a.spdif_pos = c->spdif_pos; }
+    if (c->flavor && !tiled) {      // stream-major layout, packed kernel: the mini lines of the outputs whose rows do not reach the emit wave through their delay line (dspi_chain_pk.inc)
+        const size_t xb = (size_t)c->n_wg * 3 * kMaxOut * kChunk * c->sm.row * 4;
+        if ((rc = ensure(c, c->d_xwords, c->d_xwords_cap, xb))) return rc;
+        a.xwords = c->d_xwords;
+    }
+
+    switch (L.mem) {
+    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out); break;
+    case CallMem::Direct: rc = process_direct(c, L, a, pcm_in, out, clip_out, flags, call_t0); break;
+    case CallMem::Staged: rc = process_staged(c, L, a, pcm_in, out, clip_out, flags); break;
+    }
+    if (rc == DSPI_OK && spdif) c->spdif_pos = (uint32_t)((c->spdif_pos + L.frames) % 192u);      // a failed call leaves the block position alone
+    return rc;
 }
 
 }  // extern "C"

@@ -1,5 +1,7 @@
-// dspi_plan.cpp — the launch plan: which lanes of which workgroup run on which chain kernel (dspi_plan.h).
+// dspi_plan.cpp — the launch plan: which lanes of which workgroup run on which chain kernel, and the layout of one call (dspi_plan.h).
 #include "dspi_plan.h"
+
+#include "../../include/dspi.h"
 
 #include <string.h>
 
@@ -302,6 +304,46 @@ LaunchPlan plan_launches(const PlanInput &in) {
     }
     for (int p = 0; p < kNumPaths; p++) { plan.offset[p] = (uint32_t)plan.total; plan.total += plan.items[p].size(); }
     return plan;
+}
+
+CallLayout plan_call(const CallInput &in) {
+    CallLayout L;
+    const size_t F = L.frames = (size_t)in.n_blocks * in.block_len;
+    const bool tiled = in.flags & DSPI_OUT_TILED, spdif = in.flags & DSPI_OUT_SPDIF;
+    auto buffer = [&](bool passed, bool tile_cols, size_t per) {
+        return CallBuffer{passed ? (tile_cols ? (size_t)in.n_wg * in.row : (size_t)in.n_streams) * per : 0, per, tile_cols, 0};
+    };
+    L.pcm = buffer(true, false, F * (in.bit_depth == 24 ? 6 : 4));
+    L.pairs = buffer(in.pairs, tiled, tiled ? (size_t)(in.n_out - 1) * F * 4 : (size_t)in.n_pairs * F * (spdif ? 16 : 8));
+    L.sub = buffer(in.sub, tiled, F * 4);
+    L.peaks = buffer(in.peaks, false, (size_t)in.n_blocks * in.n_ch * 2);
+    L.clip = buffer(in.clip, false, 2);
+
+    // The latency layout's output waves encode the subframes themselves.  A launch with lanes on any other kernel (the flag is a property
+    // of the output, not of the stream count) runs the chain into a scratch buffer of pair words, row chunk by row chunk, and the subframe
+    // encoder from there into `pairs`: the same words, the block position carried the same way.  The scratch is capped by BYTES: ~1 GiB
+    // worth of rows; one workgroup per CU (256 rows) only while that stays within 2 GiB; never less than one row.
+    L.spdif_two_pass = spdif && !in.all_latency && in.pairs;
+    if (L.spdif_two_pass) {
+        const size_t row_b = (size_t)in.row * in.n_pairs * F * 8;
+        size_t rows = std::max<size_t>(1, ((size_t)1 << 30) / row_b);
+        if (rows < 256 && 256 * row_b <= ((size_t)2 << 30)) rows = 256;
+        L.two_pass_rows = (uint32_t)std::min<size_t>(in.n_wg, rows);
+        L.two_pass_bytes = L.two_pass_rows * row_b;
+    }
+
+    // the direct area: every buffer of the call at a 256-byte boundary, up to 2 MiB
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    L.pairs.off = up(L.pcm.bytes); L.sub.off = L.pairs.off + up(L.pairs.bytes); L.peaks.off = L.sub.off + up(L.sub.bytes);
+    L.clip.off = L.peaks.off + up(L.peaks.bytes); L.direct_bytes = L.clip.off + up(L.clip.bytes);
+    L.mem = (in.flags & DSPI_MEM_DEVICE) ? CallMem::Device : !in.no_direct && L.direct_bytes <= (2u << 20) ? CallMem::Direct : CallMem::Staged;
+
+    // staged: from 32 MiB through the link, one chunk per 16 MiB, at most 8, and none without rows
+    const size_t moved = L.pcm.bytes + L.pairs.bytes + L.sub.bytes + L.peaks.bytes;
+    if (moved >= (32u << 20) && in.n_wg >= 2) L.n_chunks = (uint32_t)std::min<size_t>({(size_t)8, (size_t)in.n_wg, moved / (16u << 20)});
+    L.rows_per_chunk = (in.n_wg + L.n_chunks - 1) / L.n_chunks;
+    L.n_chunks = (in.n_wg + L.rows_per_chunk - 1) / L.rows_per_chunk;
+    return L;
 }
 
 }  // namespace dspi

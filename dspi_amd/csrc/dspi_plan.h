@@ -2,6 +2,7 @@
 //
 // Host only, no HIP: dspi_capi.cpp builds a PlanInput from the committed images at each rebuild, calls plan_launches and uploads
 // the lists; tests/test_launch_plan_cpu.py drives plan_launches on the CPU.  What an item of each path means: WgItem, dspi_image.h.
+// The layout of one dspi_process call (plan_call, below) lives here as well, under the same rule and the same test driver.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -101,5 +102,38 @@ struct LaunchPlan {
 };
 
 LaunchPlan plan_launches(const PlanInput &in);
+
+// ---- one dspi_process call: the sizes of its buffers and how it moves them (dspi_capi.cpp dspi_process runs it) ----
+struct CallInput {
+    uint32_t n_streams = 0, n_wg = 0, row = 128;      // StateMap::row: streams per workgroup row, = per tile of DSPI_OUT_TILED
+    uint32_t n_ch = 11, n_out = 9, n_pairs = 4;      // StateMap
+    uint32_t n_blocks = 1, block_len = 1, bit_depth = 16;
+    uint32_t flags = 0;                               // DSPI_MEM_DEVICE, DSPI_OUT_* (include/dspi.h)
+    bool pairs = false, sub = false, peaks = false, clip = false;      // the outputs the caller passed (clip: with DSPI_OUT_CLIP_FLAGS)
+    bool no_direct = false;                           // DSPI_NO_DIRECT
+    bool all_latency = false;                         // float, and every non-empty path of the launch plan is on the latency layout
+};
+
+struct CallBuffer {
+    size_t bytes = 0;          // 0: the caller did not pass it
+    size_t per = 0;            // bytes per unit
+    bool tile_cols = false;    // the unit: a tile column (DSPI_OUT_TILED words cover whole tiles) or a stream
+    size_t off = 0;            // in the direct area
+};
+
+// the caller's device buffers; a pinned host area the kernels use directly (small host calls); device buffers, copies by row chunk
+enum class CallMem : uint8_t { Device, Direct, Staged };
+
+struct CallLayout {
+    size_t frames = 0;
+    CallBuffer pcm, pairs, sub, peaks, clip;
+    bool spdif_two_pass = false;                      // DSPI_OUT_SPDIF off the latency layout: the chain's pair words, then the encoder
+    uint32_t two_pass_rows = 0; size_t two_pass_bytes = 0;      // rows per pass, their scratch of pair words
+    CallMem mem = CallMem::Staged;
+    size_t direct_bytes = 0;                          // the direct area: pcm, pairs, sub, peaks, clip at their `off`
+    uint32_t n_chunks = 1, rows_per_chunk = 0;        // staged: chunk k = rows [k * rows_per_chunk, min(n_wg, (k + 1) * rows_per_chunk))
+};
+
+CallLayout plan_call(const CallInput &in);
 
 }  // namespace dspi

@@ -317,7 +317,7 @@ DSPI_DM_FN float dspi_det_powf(float a, float b) {
  * the correctly rounded result either way, the same float the two-step functions above return (tests/test_detmath.py re-walks both ranges).
  * a^b in general has no such table; the leveller's a^count has 18 bases (three speeds x attack / release x three rates, leveller.c:37-89)
  * and counts 1 .. 192: the generator walks those, +-8 ulps around every base; a context whose actual (alpha, count) falls outside is
- * refused by the host, which compares the two forms when it builds the parameter image (dspi_params.cpp).
+ * refused by the host, which compares the two forms for its images' alphas before a call (dspi_capi.cpp check_leveller_alphas).
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct { uint32_t in, out; } dspi_dm_exc;
 typedef struct { uint32_t a, b, out; } dspi_dm_exc2;

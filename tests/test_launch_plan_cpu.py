@@ -1,7 +1,9 @@
 """The launch plan (dspi_amd/csrc/dspi_plan.cpp) on the CPU: seeded scenarios of both flavours go through plan_launches (driver:
 tests/launch_plan_driver.cpp, built with g++), and every plan is held to the WgItem contract (dspi_amd/csrc/dspi_image.h):
 every stream served exactly once, on its own image (or, per-lane values and paired presets, on images of one ImageSig); every list
-sorted by row; latency items inside their part; the DSPI_F32_LAYOUT overrides respected."""
+sorted by row; latency items inside their part; the DSPI_F32_LAYOUT overrides respected.  The same driver runs plan_call on seeded
+dspi_process calls, whose buffer sizes are held to the arrays dspi_amd/host.py process_host allocates (test_call_layout)."""
+import math
 import os
 import random
 import subprocess
@@ -150,3 +152,120 @@ def test_launch_plan_contract(driver):
         seen |= {nm for nm, items in plan["items"].items() if items}
     # the scenarios reach every path
     assert seen == {nm for nm, _, _ in PATHS}, sorted({nm for nm, _, _ in PATHS} - seen)
+
+
+# ---- the layout of one dspi_process call (plan_call), held to the buffers host.py process_host allocates for the same call ----
+STATE_MAP = {0: dict(C=7, P=2, R=64), 1: dict(C=11, P=4, R=128)}      # channels, output pairs, streams per row (dspi_image.h make_state_map)
+MEM_DEVICE, OUT_TILED, OUT_ENABLED_ONLY, OUT_I2S_SLOTS, OUT_SPDIF, OUT_CLIP_FLAGS = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20      # include/dspi.h
+ACCEPTED_FLAGS = [f for f in range(64) if not (f & OUT_SPDIF and f & (OUT_TILED | OUT_I2S_SLOTS))]
+DEVICE, DIRECT, STAGED = 0, 1, 2
+MIB, GIB = 1 << 20, 1 << 30
+N_CALLS = 800
+BUFFERS = ("pcm", "pairs", "sub", "peaks", "clip")
+
+
+def call(seed):
+    r = random.Random(seed)
+    flavor = r.choice((0, 1))
+    n = r.choice((1, 2, r.randrange(1, 300), r.randrange(300, 3000), r.randrange(3000, 70000), r.choice((65536, 65537, 65600))))
+    n_blocks = r.choice((1, 1, 2, r.randrange(1, 20), r.randrange(1, 2001)))
+    block_len = r.choice((1, 48, 96, 192, r.randrange(1, 193)))
+    flags = ACCEPTED_FLAGS[seed % len(ACCEPTED_FLAGS)]          # every combination dspi_process accepts, N_CALLS / 40 times each
+    passed = dict(pcm=True, pairs=r.random() < 0.7, sub=r.random() < 0.6, peaks=r.random() < 0.6,
+                  clip=bool(flags & OUT_CLIP_FLAGS) and r.random() < 0.8)
+    return dict(flavor=flavor, n=n, n_blocks=n_blocks, block_len=block_len, bit_depth=r.choice((16, 24)), flags=flags, passed=passed,
+                no_direct=r.random() < 0.3, all_latency=flavor == 1 and r.random() < 0.4)
+
+
+def render_call(c):
+    sm, O = STATE_MAP[c["flavor"]], 9 if c["flavor"] else 5
+    n_wg = -(-c["n"] // sm["R"])
+    p = c["passed"]
+    f = (c["n"], n_wg, sm["R"], sm["C"], O, sm["P"], c["n_blocks"], c["block_len"], c["bit_depth"], c["flags"],
+         p["pairs"], p["sub"], p["peaks"], p["clip"], c["no_direct"], c["all_latency"])
+    return "C " + " ".join(str(int(x)) for x in f) + "\n"
+
+
+def parse_call(line):
+    f = line.split()
+    assert f[0] == "L", line
+    v = [int(x) for x in f[1:]]
+    lay = dict(zip(("frames", "mem", "two_pass", "two_pass_rows", "two_pass_bytes", "direct_bytes", "n_chunks", "rows_per_chunk"), v[:8]))
+    for k, name in enumerate(BUFFERS):
+        lay[name] = dict(zip(("bytes", "per", "tile_cols", "off"), v[8 + 4 * k:12 + 4 * k]))
+    return lay
+
+
+def host_buffers(c):
+    """(shape, item size, tile columns?) of each buffer, as process_host (dspi_amd/host.py) allocates them for this call."""
+    sm = STATE_MAP[c["flavor"]]
+    S, F, R, P, C = c["n"], c["n_blocks"] * c["block_len"], sm["R"], sm["P"], sm["C"]
+    nt, tiled = -(-S // R), bool(c["flags"] & OUT_TILED)
+    if tiled: pairs, sub = ((nt, 2 * P, F, R), 4, True), ((nt, F, R), 4, True)
+    else: pairs, sub = ((S, P, F, 4) if c["flags"] & OUT_SPDIF else (S, P, F, 2), 4, False), ((S, F), 4, False)
+    return dict(pcm=((S, F, 6 if c["bit_depth"] == 24 else 4), 1, False), pairs=pairs, sub=sub, peaks=((S, c["n_blocks"], C), 2, False),
+                clip=((S,), 2, False))
+
+
+def check_call(c, lay):
+    sm = STATE_MAP[c["flavor"]]
+    S, R, F, flags = c["n"], sm["R"], c["n_blocks"] * c["block_len"], c["flags"]
+    n_wg = -(-S // R)
+    assert lay["frames"] == F
+    want = {}
+    for name, (shape, item, tile_cols) in host_buffers(c).items():
+        b, full = lay[name], math.prod(shape) * item
+        want[name] = full if c["passed"][name] else 0
+        assert b["bytes"] == want[name], f"{name}: {b['bytes']} bytes, process_host allocates {want[name]}"
+        assert bool(b["tile_cols"]) == tile_cols and b["per"] * (n_wg * R if tile_cols else S) == full, f"{name}: {b}"
+    # the memory path
+    if flags & MEM_DEVICE: assert lay["mem"] == DEVICE
+    else: assert lay["mem"] == (DIRECT if not c["no_direct"] and lay["direct_bytes"] <= 2 * MIB else STAGED)
+    # the direct area: 256-byte aligned regions in buffer order, each holding its buffer, nothing but alignment between them
+    offs = [lay[nm]["off"] for nm in BUFFERS]
+    assert offs[0] == 0 and all(o % 256 == 0 for o in offs + [lay["direct_bytes"]])
+    for k, nm in enumerate(BUFFERS):
+        end = offs[k + 1] if k + 1 < len(BUFFERS) else lay["direct_bytes"]
+        assert offs[k] + want[nm] <= end < offs[k] + want[nm] + 256, f"direct area: {nm} at {offs[k]}, {want[nm]} bytes, next at {end}"
+    # the staged chunks: they partition the rows, and each output's pieces of consecutive chunks are consecutive and cover it
+    moved = sum(want[nm] for nm in ("pcm", "pairs", "sub", "peaks"))
+    k, rp = lay["n_chunks"], lay["rows_per_chunk"]
+    assert 1 <= k <= 8 and (k > 1) == (moved >= 32 * MIB and n_wg >= 2), (k, moved, n_wg)
+    chunks = [(i * rp, min(n_wg, (i + 1) * rp)) for i in range(k)]
+    assert chunks[0][0] == 0 and chunks[-1][1] == n_wg and all(r0 < r1 for r0, r1 in chunks)
+    assert all(a[1] == b[0] for a, b in zip(chunks, chunks[1:]))
+    for nm in ("pcm", "pairs", "sub", "peaks"):
+        b, at = lay[nm], 0
+        for r0, r1 in chunks:
+            u0, u1 = r0 * R, r1 * R if b["tile_cols"] else min(r1 * R, S)
+            assert u0 * b["per"] == at
+            at = u1 * b["per"]
+        assert at == host_buffers(c)[nm][1] * math.prod(host_buffers(c)[nm][0])
+    # two-pass S/PDIF: only with S/PDIF, pairs and a plan that is not all on the latency layout; its scratch holds whole rows of pair words
+    assert bool(lay["two_pass"]) == (bool(flags & OUT_SPDIF) and c["passed"]["pairs"] and not c["all_latency"])
+    if lay["two_pass"]:
+        row_b = R * sm["P"] * F * 2 * 4          # the int32 pair words (R, P, F, 2) of one row
+        assert 1 <= lay["two_pass_rows"] <= n_wg and lay["two_pass_bytes"] == lay["two_pass_rows"] * row_b
+        assert lay["two_pass_bytes"] <= max(2 * GIB, row_b)
+    else:
+        assert lay["two_pass_rows"] == 0 and lay["two_pass_bytes"] == 0
+
+
+def test_call_layout(driver):
+    calls = [call(seed) for seed in range(N_CALLS)]
+    out = subprocess.run([driver], input="".join(map(render_call, calls)), capture_output=True, text=True, check=True, timeout=300).stdout
+    lays = [parse_call(line) for line in out.splitlines()]
+    assert len(lays) == len(calls)
+    reached = set()
+    for seed, (c, lay) in enumerate(zip(calls, lays)):
+        try:
+            check_call(c, lay)
+        except AssertionError as e:
+            raise AssertionError(f"call seed {seed} ({c}): {e}") from None
+        n_wg = -(-c["n"] // STATE_MAP[c["flavor"]]["R"])
+        reached |= {("mem", lay["mem"]), ("chunks", min(lay["n_chunks"], 3)), ("flavour", c["flavor"])}
+        if lay["two_pass"]: reached.add(("two_pass_rows", "some" if lay["two_pass_rows"] < n_wg else "all"))
+        if lay["mem"] == DIRECT and c["n"] % STATE_MAP[c["flavor"]]["R"]: reached.add("direct, partial last row")
+    # the calls reach every memory path, one / two / more chunks, both kinds of two-pass row counts
+    assert reached >= {("mem", DEVICE), ("mem", DIRECT), ("mem", STAGED), ("chunks", 1), ("chunks", 2), ("chunks", 3), ("flavour", 0), ("flavour", 1),
+                       ("two_pass_rows", "some"), ("two_pass_rows", "all"), "direct, partial last row"}, reached
