@@ -29,6 +29,7 @@
 #include "dspi_kernels.h"
 #include "dspi_params.h"
 #include "dspi_plan.h"
+#include "dspi_snapshot.h"
 
 using namespace dspi;
 
@@ -95,6 +96,7 @@ struct dspi_ctx {
     uint32_t *d_pdm_out = nullptr; size_t d_pdm_out_cap = 0;
     int32_t *d_spdif_in = nullptr; size_t d_spdif_in_cap = 0;
     uint32_t *d_spdif_out = nullptr; size_t d_spdif_out_cap = 0;
+    uint32_t *d_snap = nullptr; size_t d_snap_cap = 0;          // stream snapshots on host buffers: the records of one chunk of rows
     std::string err;
 };
 
@@ -469,7 +471,7 @@ void dspi_destroy(dspi_ctx *c) {
     if (c->device != DSPI_DEVICE_NONE) {
         (void)hipSetDevice(c->device);
         if (c->hs) (void)hipStreamSynchronize(c->hs);
-        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, c->d_in,
+        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_snap, c->d_in,
                         (void *)c->d_pairs, (void *)c->d_sub, (void *)c->d_peaks, (void *)c->d_clip, (void *)c->d_spdif_words})
             if (p) (void)hipFree(p);
         if (c->h_direct) (void)hipHostFree(c->h_direct);
@@ -704,6 +706,129 @@ int dspi_pdm_restart(dspi_ctx *c, int32_t stream) {
     if (rc) return rc;
     HIPCK(c, launch_pdm_reset(c->d_pdm, c->n_streams, (uint32_t)c->sm.row, c->n_wg, stream == DSPI_ALL_STREAMS ? -1 : stream, 0, c->hs));
     return DSPI_OK;
+}
+
+// ---- stream snapshots (dspi_snapshot.h: the format; dspi_snapshot.hip: the transposition kernels) ----
+static bool snap_range_ok(const dspi_ctx *c, uint32_t first, uint32_t count) { return count != 0 && (uint64_t)first + count <= c->n_streams; }
+
+// the distinct images of streams [first, first + count) in order of first use, and every stream's index into that list
+static void snap_images(const dspi_ctx *c, uint32_t first, uint32_t count, std::vector<int32_t> &used, std::vector<uint32_t> *index) {
+    std::vector<int32_t> slot(c->images.size(), -1);
+    if (index) index->resize(count);
+    for (uint32_t k = 0; k < count; k++) {
+        const int32_t im = c->stream_image[(size_t)first + k];
+        if (slot[(size_t)im] < 0) { slot[(size_t)im] = (int32_t)used.size(); used.push_back(im); }
+        if (index) (*index)[k] = (uint32_t)slot[(size_t)im];
+    }
+}
+
+// host buffers go through device memory a chunk of rows at a time: streams [s, snap_chunk_end) end on a row boundary, 25 - 40 MB of records
+static uint32_t snap_chunk_end(const dspi_ctx *c, uint32_t s, uint32_t end) {
+    const uint32_t row = (uint32_t)c->sm.row, rows = c->flavor ? 2u : 8u;
+    return (uint32_t)std::min<uint64_t>(end, ((uint64_t)s / row + rows) * row);
+}
+
+int dspi_snapshot_sizes(const dspi_ctx *c, uint32_t first, uint32_t count, size_t *head_bytes, size_t *state_bytes) {
+    if (!c || !snap_range_ok(c, first, count)) return DSPI_E_INVAL;
+    std::vector<int32_t> used;
+    snap_images(c, first, count, used, nullptr);
+    if (head_bytes) *head_bytes = snap_head_bytes(count, (uint32_t)used.size());
+    if (state_bytes) *state_bytes = snap_state_bytes(c->flavor, count);
+    return DSPI_OK;
+}
+
+int dspi_export_streams(dspi_ctx *c, uint32_t first, uint32_t count, const dspi_snapshot *snap, uint32_t flags) {
+    if (!c || !snap || !snap->head || !snap->state) return DSPI_E_INVAL;
+    if (flags & ~DSPI_MEM_DEVICE) return fail(c, DSPI_E_INVAL, "dspi_export_streams: undefined flag bits");
+    if (!snap_range_ok(c, first, count)) return fail(c, DSPI_E_INVAL, "dspi_export_streams: stream range out of bounds");
+    const bool dev = flags & DSPI_MEM_DEVICE;
+    if (dev && (reinterpret_cast<uintptr_t>(snap->state) & 15u)) return fail(c, DSPI_E_INVAL, "dspi_export_streams: device state buffer must be 16-byte aligned");
+    std::vector<int32_t> used;
+    std::vector<uint32_t> index;
+    snap_images(c, first, count, used, &index);
+    const size_t hb = snap_head_bytes(count, (uint32_t)used.size()), sb = snap_state_bytes(c->flavor, count);
+    if (snap->head_bytes < hb || snap->state_bytes < sb) return fail(c, DSPI_E_SHORT, "dspi_export_streams: buffer too small (dspi_snapshot_sizes)");
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no run-time state to export");
+    HIPCK(c, hipSetDevice(c->device));
+    int rc = pdm_state(c);      // (a context that never ran the modulator hands over its power-on words)
+    if (rc) return rc;
+    // the head: header, the range's distinct parameter objects as they are (pending state operations included), the streams' indices
+    unsigned char *const head = static_cast<unsigned char *>(snap->head);
+    memset(head, 0, hb);
+    const SnapHeader h = snap_make_header(c->flavor, c->fma, count, (uint32_t)used.size(), c->audio_started);
+    memcpy(head, &h, sizeof h);
+    for (size_t i = 0; i < used.size(); i++) memcpy(head + sizeof h + i * snap_params_stride(), c->images[(size_t)used[i]].get(), sizeof(Params));
+    memcpy(head + sizeof h + used.size() * snap_params_stride(), index.data(), (size_t)count * 4);
+    snap_seal(head);
+    if (dev) {
+        HIPCK(c, launch_snapshot(c->flavor, false, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, static_cast<uint32_t *>(snap->state), first, count, c->hs));
+        return (int)count;
+    }
+    const size_t rec = snap_state_bytes(c->flavor, 1);
+    for (uint32_t s = first, end = first + count; s < end;) {
+        const uint32_t e = snap_chunk_end(c, s, end);
+        if ((rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)(e - s) * rec))) return rc;
+        HIPCK(c, launch_snapshot(c->flavor, false, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, s, e - s, c->hs));
+        HIPCK(c, hipMemcpyAsync(static_cast<char *>(snap->state) + (size_t)(s - first) * rec, c->d_snap, (size_t)(e - s) * rec, hipMemcpyDeviceToHost, c->hs));
+        HIPCK(c, hipStreamSynchronize(c->hs));
+        s = e;
+    }
+    return (int)count;
+}
+
+int dspi_import_streams(dspi_ctx *c, uint32_t first, const dspi_snapshot *snap, uint32_t flags) {
+    if (!c || !snap || !snap->head || !snap->state) return DSPI_E_INVAL;
+    if (flags & ~DSPI_MEM_DEVICE) return fail(c, DSPI_E_INVAL, "dspi_import_streams: undefined flag bits");
+    // everything is validated before anything is written
+    if (const char *why = snap_validate_head(snap->head, snap->head_bytes, c->flavor, c->fma)) return fail(c, DSPI_E_INVAL, why);
+    SnapHeader h;
+    memcpy(&h, snap->head, sizeof h);
+    const uint32_t count = h.count;
+    if (!snap_range_ok(c, first, count)) return fail(c, DSPI_E_INVAL, "dspi_import_streams: stream range out of bounds");
+    if (snap->state_bytes < snap_state_bytes(c->flavor, count)) return fail(c, DSPI_E_SHORT, "dspi_import_streams: state buffer shorter than the head's stream count");
+    const bool dev = flags & DSPI_MEM_DEVICE;
+    if (dev && (reinterpret_cast<uintptr_t>(snap->state) & 15u)) return fail(c, DSPI_E_INVAL, "dspi_import_streams: device state buffer must be 16-byte aligned");
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no run-time state to import into");
+    HIPCK(c, hipSetDevice(c->device));
+    int rc = pdm_state(c);
+    if (rc) return rc;
+    const size_t rec = snap_state_bytes(c->flavor, 1);
+    if (!dev && (rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)(snap_chunk_end(c, first, first + count) - first) * rec))) return rc;
+    // parameters: the streams leave their images, the imported objects are appended dirty, and the fold-back pass (merge_images, at the
+    // next commit) drops what nobody uses any more and folds equal objects — the imported ones among themselves and into images already
+    // here.  Tiles, launch plan, alpha list and pending state operations follow from the ordinary commit.
+    const size_t base = c->images.size();
+    for (uint32_t i = 0; i < h.n_images; i++) {
+        auto p = std::make_unique<Params>(*c->images[0]);
+        memcpy(static_cast<void *>(p.get()), snap_params(snap->head, i), sizeof(Params));
+        p->dirty = true;
+        c->images.push_back(std::move(p)); c->image_refs.push_back(0);
+    }
+    const unsigned char *idx = snap_params(snap->head, h.n_images);
+    for (uint32_t k = 0; k < count; k++) {
+        uint32_t im;
+        memcpy(&im, idx + (size_t)k * 4, 4);
+        int32_t &si = c->stream_image[(size_t)first + k];
+        c->image_refs[(size_t)si]--;
+        si = (int32_t)(base + im);
+        c->image_refs[(size_t)si]++;
+    }
+    c->assignment_dirty = true; c->merge_hint = true;
+    if (h.flags & kSnapAudioStarted) c->audio_started = true;      // running devices arrived: dspi_load_flash_dump is no boot any more
+    // run-time state, behind whatever the context's stream still has to do
+    if (dev) {
+        HIPCK(c, launch_snapshot(c->flavor, true, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, static_cast<uint32_t *>(snap->state), first, count, c->hs));
+        return (int)count;
+    }
+    for (uint32_t s = first, end = first + count; s < end;) {
+        const uint32_t e = snap_chunk_end(c, s, end);
+        if ((rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)(e - s) * rec))) return rc;
+        HIPCK(c, hipMemcpyAsync(c->d_snap, static_cast<const char *>(snap->state) + (size_t)(s - first) * rec, (size_t)(e - s) * rec, hipMemcpyHostToDevice, c->hs));
+        HIPCK(c, launch_snapshot(c->flavor, true, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, s, e - s, c->hs));
+        HIPCK(c, hipStreamSynchronize(c->hs));
+        s = e;
+    }
+    return (int)count;
 }
 
 // ---- S/PDIF subframes: pico_audio_spdif_multi sample_encoding.h:27-47 + audio_spdif.c:76-116 (dspi_spdif.hip) ----

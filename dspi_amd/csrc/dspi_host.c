@@ -7,7 +7,12 @@
  * and the status block of stream 0.  Everything DSP happens behind the C-ABI (include/dspi.h).
  *
  *   dspi_host [-f q28|f32|f32fma] [-s streams] [-r rate] [-b block_len] [-n blocks] [-c calls]
- *             [-B bulk.bin | -P slot.bin] [-i pcm16le.raw] [-o pairs.raw] [-v volume_db]
+ *             [-B bulk.bin | -P slot.bin] [-i pcm16le.raw] [-o pairs.raw] [-v volume_db] [--load-state FILE] [--save-state FILE]
+ *             --save-state writes every stream's snapshot (dspi_export_streams: parameters and run-time state) after the last call,
+ *             --load-state imports such a file before the first: a second process goes on where the first one stopped, bit-exactly.
+ *             The file is a sequence of chunks of whole rows — {uint64 head bytes, uint64 state bytes, uint32 first stream, uint32 count},
+ *             the chunk's head, its records — so that it is written and read through a bounded buffer at any stream count.  This mode
+ *             only: not with -rt, not with -g.
  *   dspi_host -rt ...   the drop-in call as INTEGRATION.md section 3 writes it (the body of usb_audio_drain_ring, usb_audio.c:1326-1332):
  *             ONE packet of block_len frames per dspi_process(), host buffers, `calls` calls back to back, the input advancing through
  *             the PCM file (wrapping); prints the latency per call (p50 / p99 / max) and the sustained rate against real time.
@@ -59,6 +64,62 @@ static void *slurp(const char *path, size_t *len) {
 
 static double now(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + 1e-9 * t.tv_nsec; }
 static int cmp_d(const void *a, const void *b) { double x = *(const double *)a, y = *(const double *)b; return x < y ? -1 : x > y; }
+
+/* ---- --save-state / --load-state: every stream's snapshot, in chunks of whole rows of at most ~64 MB of records ---- */
+typedef struct { uint64_t head_bytes, state_bytes; uint32_t first, count; } StateChunk;
+
+static uint32_t state_chunk_streams(dspi_ctx *ctx) {
+    size_t rec = 0;
+    if (dspi_snapshot_sizes(ctx, 0, 1, NULL, &rec) || !rec) return 0;
+    const uint32_t row = dspi_tile_streams(ctx);
+    const size_t rows = ((size_t)64 << 20) / (rec * row);
+    return row * (uint32_t)(rows ? rows : 1);
+}
+
+static int save_state(dspi_ctx *ctx, const char *path) {
+    const uint32_t S = dspi_num_streams(ctx), step = state_chunk_streams(ctx);
+    FILE *f = fopen(path, "wb");
+    if (!f) { perror(path); return 2; }
+    int rc = step ? 0 : 1;
+    for (uint32_t first = 0; first < S && !rc; first += step) {
+        StateChunk c;
+        dspi_snapshot snap;
+        size_t hb = 0, sb = 0;
+        memset(&c, 0, sizeof c);
+        c.first = first; c.count = S - first < step ? S - first : step;
+        if (dspi_snapshot_sizes(ctx, c.first, c.count, &hb, &sb)) { rc = 1; break; }
+        snap.head = malloc(hb); snap.head_bytes = hb; snap.state = malloc(sb); snap.state_bytes = sb;
+        c.head_bytes = hb; c.state_bytes = sb;
+        if (!snap.head || !snap.state) { fprintf(stderr, "--save-state: out of memory\n"); rc = 2; }
+        else if (dspi_export_streams(ctx, c.first, c.count, &snap, 0) != (int)c.count) { fprintf(stderr, "dspi_export_streams: %s\n", dspi_last_error(ctx)); rc = 1; }
+        else if (fwrite(&c, sizeof c, 1, f) != 1 || fwrite(snap.head, 1, hb, f) != hb || fwrite(snap.state, 1, sb, f) != sb) { perror(path); rc = 2; }
+        free(snap.head); free(snap.state);
+    }
+    if (fclose(f) && !rc) { perror(path); rc = 2; }
+    if (!rc) printf("state of %u streams saved to %s\n", S, path);
+    return rc;
+}
+
+static int load_state(dspi_ctx *ctx, const char *path) {
+    FILE *f = fopen(path, "rb");
+    if (!f) { perror(path); return 2; }
+    int rc = 0;
+    uint32_t total = 0;
+    StateChunk c;
+    while (!rc && fread(&c, sizeof c, 1, f) == 1) {
+        dspi_snapshot snap;
+        if (c.head_bytes > ((uint64_t)1 << 32) || c.state_bytes > ((uint64_t)1 << 32)) { fprintf(stderr, "%s: not a state file\n", path); rc = 2; break; }
+        snap.head = malloc((size_t)c.head_bytes); snap.head_bytes = (size_t)c.head_bytes; snap.state = malloc((size_t)c.state_bytes); snap.state_bytes = (size_t)c.state_bytes;
+        if (!snap.head || !snap.state) { fprintf(stderr, "--load-state: out of memory\n"); rc = 2; }
+        else if (fread(snap.head, 1, snap.head_bytes, f) != snap.head_bytes || fread(snap.state, 1, snap.state_bytes, f) != snap.state_bytes) { fprintf(stderr, "%s: truncated\n", path); rc = 2; }
+        else if (dspi_import_streams(ctx, c.first, &snap, 0) != (int)c.count) { fprintf(stderr, "dspi_import_streams at stream %u: %s\n", c.first, dspi_last_error(ctx)); rc = 1; }
+        else total += c.count;
+        free(snap.head); free(snap.state);
+    }
+    fclose(f);
+    if (!rc) printf("state of %u streams loaded from %s\n", total, path);
+    return rc;
+}
 
 /* -rt: one packet per call (the firmware's own rhythm: a 1 ms USB packet, usb_audio.c:1326-1332), latency per call */
 static int realtime(dspi_ctx *ctx, uint32_t streams, uint32_t rate, uint32_t block_len, uint32_t calls, const int16_t *one, size_t have_frames,
@@ -459,7 +520,7 @@ static int node_run(int n_gpus, int strong, int dry, int flavor, uint32_t stream
 int main(int argc, char **argv) {
     int flavor = DSPI_FLAVOR_RP2350_F32;
     uint32_t streams = 4096, rate = 48000, block_len = 48, blocks = 100, calls = 10;
-    const char *bulk = NULL, *slot = NULL, *in = NULL, *outp = NULL, *allp = NULL, *latp = NULL;
+    const char *bulk = NULL, *slot = NULL, *in = NULL, *outp = NULL, *allp = NULL, *latp = NULL, *savep = NULL, *loadp = NULL;
     double vol_db = 0.0;
     int rt = 0, n_gpus = 0, strong = 0, dry = 0;
     uint32_t warmup = 2;
@@ -485,8 +546,12 @@ int main(int argc, char **argv) {
         else if (!strcmp(a, "-D") && v) { dry = !strcmp(v, "none"); i++; }
         else if (!strcmp(a, "-O") && v) { allp = v; i++; }
         else if (!strcmp(a, "-L") && v) { latp = v; i++; }
-        else { fprintf(stderr, "usage: %s [-f q28|f32|f32fma] [-s streams] [-r rate] [-b block_len] [-n blocks] [-c calls] [-B bulk.bin|-P slot.bin] [-i pcm.raw] [-o pairs.raw] [-v vol_db] [-rt] [-g gpus [-S weak|strong] [-w warmup] [-D none]]\n", argv[0]); return 2; }
+        else if (!strcmp(a, "--save-state") && v) { savep = v; i++; }
+        else if (!strcmp(a, "--load-state") && v) { loadp = v; i++; }
+        else { fprintf(stderr, "usage: %s [-f q28|f32|f32fma] [-s streams] [-r rate] [-b block_len] [-n blocks] [-c calls] [-B bulk.bin|-P slot.bin] [-i pcm.raw] [-o pairs.raw] [-v vol_db] [--load-state FILE] [--save-state FILE] [-rt] [-g gpus [-S weak|strong] [-w warmup] [-D none]]\n"
+                               "  --load-state / --save-state: every stream's snapshot, imported before the first call / exported after the last; not with -rt, not in -g node mode\n", argv[0]); return 2; }
     }
+    if ((savep || loadp) && (n_gpus > 0 || rt)) { fprintf(stderr, "--save-state / --load-state: not with -rt, not in -g node mode\n"); return 2; }
     if (n_gpus > 0) return node_run(n_gpus, strong, dry, flavor, streams, rate, block_len, blocks, calls, warmup, vol_db, bulk, slot, outp);
     if (dry) { fprintf(stderr, "-D none goes with -g\n"); return 2; }
     dspi_ctx *ctx = NULL;
@@ -497,6 +562,7 @@ int main(int argc, char **argv) {
     size_t len;
     if (bulk) { void *b = slurp(bulk, &len); rc = dspi_load_bulk(ctx, DSPI_ALL_STREAMS, b, len); printf("bulk_params_apply -> %d\n", rc); free(b); }
     if (slot) { void *b = slurp(slot, &len); rc = dspi_load_preset_slot(ctx, DSPI_ALL_STREAMS, b, len, -1); printf("preset_load -> %d\n", rc); free(b); }
+    if (loadp && (rc = load_state(ctx, loadp))) return rc;      /* (the streams' parameters come with their state: they replace what -r, -v, -B, -P set) */
 
     if (rt) {
         size_t n = 0;
@@ -554,6 +620,7 @@ int main(int argc, char **argv) {
         if (!f) { perror(outp); return 2; }
         fwrite(out.pairs, 8, (size_t)pairs_n * frames, f); fclose(f);
     }
+    if (savep && (rc = save_state(ctx, savep))) return rc;
     dspi_destroy(ctx);
     return 0;
 }

@@ -68,4 +68,9 @@ hipError_t launch_i2s(bool tiled, const int32_t *pairs, uint32_t *out, uint32_t 
 hipError_t launch_detmath(int which, const float *a, const float *b, uint32_t n, float *out, hipStream_t stream);      // dspi_status.hip
 hipError_t launch_clip_gather(const uint32_t *state, uint32_t n_streams, uint32_t row, uint32_t n_slots, uint32_t clip_slot, uint16_t *out, hipStream_t stream);
 
+// ---- stream snapshots (dspi_snapshot.hip): streams [first, first + count) of the four stream-minor arrays <-> stream-major records
+// (dspi_snapshot.h), `records` = the record of stream `first`, 16-byte aligned.  import: records -> arrays, else arrays -> records.
+hipError_t launch_snapshot(int flavor, bool import, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first,
+                           uint32_t count, hipStream_t stream);
+
 }  // namespace dspi

@@ -1,0 +1,87 @@
+// dspi_snapshot.h — the hand-over format of dspi_export_streams / dspi_import_streams (include/dspi.h): what a snapshot's head holds,
+// how one stream's run-time record is laid out, how both are sized, built and validated.  Plain C++ (no HIP): dspi_capi.cpp and
+// dspi_snapshot.hip include it, tests/snapshot_driver.cpp exercises it without a GPU.
+//
+//   head   (host memory)   SnapHeader | n_images parameter objects (Params, as bytes, each padded to 8) | count x uint32 image index
+//   state  (host / device) count records of record_words(flavor) 32-bit words, stream-major: record i is stream first + i
+//
+// One record is the stream's column of the context's four stream-minor arrays ([W][position][R]), section after
+// section in the arrays' own position order; every section starts on a 16-byte boundary (its span is its length rounded up to four
+// words, the pad words are zero), so that both sides of the transposition kernels move 16 bytes per lane:
+//   SEC_STATE   StateMap::n_slots words            every state slot (filters, crossfeed, leveller, ring position, delay write index,
+//                                                  mute envelope, last peaks, the four clip slots)
+//   SEC_LINES   n_out * max_delay words            every delay line at full length, [output][position]
+//   SEC_RING    2 * kRingLen words                 the leveller's two rings, [channel][position]
+//   SEC_PDM     kPdmStateWords words               the PDM modulator (power-on values when the source never ran it)
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include "dspi_image.h"
+
+namespace dspi {
+
+constexpr int kPdmWords = 9;            // == kPdmStateWords (dspi_kernels.h; static_assert in dspi_snapshot.hip)
+constexpr uint32_t kSnapMagic = 0x53505344u;      // "DSPS"
+constexpr uint32_t kSnapVersion = 1;
+
+enum SnapSection : int { SEC_STATE = 0, SEC_LINES, SEC_RING, SEC_PDM, SEC_COUNT };
+
+struct SnapSectionInfo {
+    uint32_t offset;      // first word of the section inside a record
+    uint32_t len;         // words that carry state = positions per row of the section's device array
+    uint32_t span;        // len rounded up to 4: the words the section occupies
+};
+struct SnapLayout {
+    SnapSectionInfo sec[SEC_COUNT];
+    uint32_t record_words;
+    uint32_t row;         // StateMap::row
+};
+
+constexpr uint32_t snap_round4(uint32_t n) { return (n + 3u) & ~3u; }
+constexpr SnapLayout make_snap_layout(int flavor) {
+    const StateMap m = make_state_map(flavor);
+    SnapLayout l{};
+    const uint32_t lens[SEC_COUNT] = {(uint32_t)m.n_slots, (uint32_t)m.n_out * (uint32_t)m.max_delay, 2u * (uint32_t)kRingLen, (uint32_t)kPdmWords};
+    uint32_t at = 0;
+    for (int s = 0; s < SEC_COUNT; s++) {
+        l.sec[s].offset = at; l.sec[s].len = lens[s]; l.sec[s].span = snap_round4(lens[s]);
+        at += l.sec[s].span;
+    }
+    l.record_words = at;
+    l.row = (uint32_t)m.row;
+    return l;
+}
+
+// 64 bytes, little-endian like everything else the library exchanges
+struct SnapHeader {
+    uint32_t magic, version;
+    uint32_t flavor;            // DSPI_FLAVOR_*
+    uint32_t contract;          // 1: DSPI_FLOAT_CONTRACT_FMA
+    uint32_t record_words;      // of one stream's record in `state`
+    uint32_t count;             // streams
+    uint32_t n_images;          // parameter objects that follow the header
+    uint32_t fingerprint;       // snap_fingerprint(flavor): the internal layout both sides must share
+    uint32_t params_bytes;      // sizeof(Params)
+    uint32_t flags;             // kSnapAudioStarted
+    uint64_t head_bytes;        // of the whole head
+    uint32_t reserved[3];
+    uint32_t crc;               // CRC-32 (the preset slots' polynomial) of the head with this field zero
+};
+static_assert(sizeof(SnapHeader) == 64, "SnapHeader is 64 bytes");
+constexpr uint32_t kSnapAudioStarted = 1u;
+
+size_t snap_params_bytes();                       // sizeof(Params)
+size_t snap_params_stride();                      // ... padded to 8
+uint32_t snap_fingerprint(int flavor);
+uint32_t snap_crc32(const void *data, size_t n, uint32_t crc = 0);      // chainable: pass the previous result
+size_t snap_head_bytes(uint32_t count, uint32_t n_images);
+size_t snap_state_bytes(int flavor, uint32_t count);
+// fills everything but the CRC; snap_seal computes it over the finished head
+SnapHeader snap_make_header(int flavor, bool fma, uint32_t count, uint32_t n_images, bool audio_started);
+void snap_seal(void *head);
+const unsigned char *snap_params(const void *head, uint32_t image);      // object `image`; image = n_images: the stream index (uint32 per stream)
+
+// nullptr = well formed for a context of (flavor, fma); else which check refused it.  Reads at most head_bytes bytes.
+const char *snap_validate_head(const void *head, size_t head_bytes, int flavor, bool fma);
+
+}  // namespace dspi

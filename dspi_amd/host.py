@@ -21,14 +21,20 @@ OUT_ENABLED_ONLY = 0x4
 OUT_I2S_SLOTS = 0x8
 OUT_SPDIF = 0x10
 OUT_CLIP_FLAGS = 0x20
+E_INVAL = -10
 E_NODEVICE = -11
 E_UNSUPPORTED = -14
+E_SHORT = -15
 
 
 class DspiError(RuntimeError):
     def __init__(self, code: int, msg: str = ""):
         super().__init__(f"dspi error {code}: {msg}")
         self.code = code
+
+
+class _Snapshot(C.Structure):
+    _fields_ = [("head", C.c_void_p), ("head_bytes", C.c_size_t), ("state", C.c_void_p), ("state_bytes", C.c_size_t)]      # dspi_snapshot
 
 
 class _Out(C.Structure):
@@ -94,6 +100,10 @@ def lib() -> C.CDLL:
     L.dspi_debug_image.argtypes = [vp, i32, vp, C.c_size_t]
     L.dspi_debug_launch_plan.argtypes = [vp, vp, C.c_size_t]
     if hasattr(L, "dspi_debug_direct_stats"): L.dspi_debug_direct_stats.argtypes = [vp, vp, C.c_size_t]      # (ABI 8; bench.py's same-box A/B loads the previous round's library through this module)
+    if hasattr(L, "dspi_snapshot_sizes"):      # (ABI 8 + snapshots: detected by symbol, as above)
+        L.dspi_snapshot_sizes.argtypes = [vp, u32, u32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.dspi_export_streams.argtypes = [vp, u32, u32, C.POINTER(_Snapshot), u32]
+        L.dspi_import_streams.argtypes = [vp, u32, C.POINTER(_Snapshot), u32]
     _lib = L
     return L
 
@@ -316,6 +326,45 @@ class Dspi:
 
     def pdm_restart(self, stream: int = ALL):
         self._ck(self.L.dspi_pdm_restart(self.h, stream), "pdm_restart")
+
+    # ---- stream snapshots (include/dspi.h: dspi_export_streams / dspi_import_streams) ----
+    def snapshot_sizes(self, first: int, count: int):
+        """(head_bytes, state_bytes) an export of streams [first, first + count) needs.  Works on host-only contexts."""
+        hb, sb = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self.L.dspi_snapshot_sizes(self.h, first, count, C.byref(hb), C.byref(sb)), "snapshot_sizes")
+        return hb.value, sb.value
+
+    def export_streams(self, first: int, count: int):
+        """The complete state of streams [first, first + count): (head: bytes, state: uint32 [count][record words]).  The context is unchanged."""
+        hb, sb = self.snapshot_sizes(first, count)
+        head = C.create_string_buffer(hb)
+        state = np.zeros((count, sb // (4 * count)), dtype=np.uint32)
+        snap = _Snapshot(C.addressof(head), hb, state.ctypes.data, sb)
+        self._ck(self.L.dspi_export_streams(self.h, first, count, C.byref(snap), 0), "export_streams")
+        return head.raw, state
+
+    def import_streams(self, first: int, head: bytes, state: np.ndarray) -> int:
+        """Overwrites streams [first, first + n) with a snapshot's n streams (n from the head); returns n.  A refused snapshot
+        (DspiError) leaves the context as it was."""
+        state = np.ascontiguousarray(state, dtype=np.uint32)
+        hbuf = C.create_string_buffer(bytes(head), len(head))
+        snap = _Snapshot(C.addressof(hbuf), len(head), state.ctypes.data, state.nbytes)
+        return self._ck(self.L.dspi_import_streams(self.h, first, C.byref(snap), 0), "import_streams")
+
+    def export_streams_device(self, first: int, count: int, state_ptr: int, state_bytes: int) -> bytes:
+        """export_streams with the records in device memory (16-byte aligned, e.g. torch.Tensor.data_ptr()); asynchronous on the
+        context's stream: sync() before another context imports them.  Returns the head."""
+        hb, _ = self.snapshot_sizes(first, count)
+        head = C.create_string_buffer(hb)
+        snap = _Snapshot(C.addressof(head), hb, state_ptr, state_bytes)
+        self._ck(self.L.dspi_export_streams(self.h, first, count, C.byref(snap), MEM_DEVICE), "export_streams")
+        return head.raw
+
+    def import_streams_device(self, first: int, head: bytes, state_ptr: int, state_bytes: int) -> int:
+        """import_streams from records in device memory; asynchronous on the context's stream."""
+        hbuf = C.create_string_buffer(bytes(head), len(head))
+        snap = _Snapshot(C.addressof(hbuf), len(head), state_ptr, state_bytes)
+        return self._ck(self.L.dspi_import_streams(self.h, first, C.byref(snap), MEM_DEVICE), "import_streams")
 
     def sync(self):
         self._ck(self.L.dspi_sync(self.h), "sync")

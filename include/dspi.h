@@ -66,7 +66,8 @@ extern "C" {
                               * dspi_debug_launch_plan, dspi_debug_image_count; 5: DSPI_OUT_ENABLED_ONLY, DSPI_OUT_I2S_SLOTS, DSPI_BOOT_POPULATED_FLASH, dspi_debug_launch_plan counts[5];
                               * 6: DSPI_OUT_SPDIF, dspi_spdif_block_pos; 7: dspi_out.clip_flags behind DSPI_OUT_CLIP_FLAGS, DSPI_OUT_SPDIF on every
                               * context, (additions only: a v6 caller's three-member dspi_out is never read past `peaks`);
-                              * 8: dspi_debug_direct_stats, dspi_debug_detmath, the direct path polls a completion word for the call's own audio time (DSPI_DIRECT_SPIN_US, DSPI_DIRECT_POLL) */
+                              * 8: dspi_debug_direct_stats, dspi_debug_detmath, the direct path polls a completion word for the call's own audio time (DSPI_DIRECT_SPIN_US, DSPI_DIRECT_POLL);
+                              * 8 + snapshots: detect by symbol (dspi_snapshot_sizes, dspi_export_streams, dspi_import_streams; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -237,6 +238,46 @@ int dspi_set_sample_rate(dspi_ctx *ctx, int32_t stream, uint32_t hz);           
 int dspi_process(dspi_ctx *ctx, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len,
                  const dspi_out *out, uint32_t flags);
 int dspi_sync(dspi_ctx *ctx);
+
+/* ---- stream snapshots: a stream's complete state, out of one context and into another ------------------------------------ */
+/* Everything a stream is — its parameters with whatever state operations are still pending on them, every state slot (filters,
+ * loudness, crossfeed, leveller, ring position, delay write index, mute envelope, last peaks, clip slots), every delay line at full
+ * length, both leveller rings, the PDM modulator's words (power-on values when the source never ran dspi_pdm_modulate) — exported
+ * after packet k and imported anywhere else continues from packet k + 1 with exactly the words an uninterrupted run produces: on
+ * another context, another GPU, another process, at another stream index (a float stream may change its row and its side of a packed
+ * lane).  Write positions travel as they are; rows whose streams carry different positions are served by the kernels' per-stream
+ * addressing.
+ *   head    host memory, always: a 64-byte header (magic, format version, flavour, float contract, record size, count, number of
+ *           parameter objects, fingerprint of the internal layout, CRC-32 of the head), one parameter object per DISTINCT parameter
+ *           set in the range, one uint32 index per stream
+ *   state   one fixed-size record per stream, stream-major, in range order: state_bytes / count bytes each (a multiple of 16);
+ *           host memory, or with DSPI_MEM_DEVICE device memory aligned to 16 bytes.  Records are independent of each other, so a
+ *           long range can be moved in chunks: export / import sub-ranges, each with its own head.
+ * A snapshot is a HAND-OVER format, not an archive: only a library of the same build (same fingerprint) takes it.
+ * What does NOT travel (per context, not per stream): the S/PDIF block position (dspi_spdif_block_pos), the direct path's polling
+ * statistics.  "Has processed audio" does: after an import of running devices the context no longer treats dspi_load_flash_dump as a boot.
+ * With DSPI_MEM_DEVICE the calls are asynchronous on the context's stream like dspi_process: between two contexts, dspi_sync the
+ * source after the export and before the import reads `state` (the import's own stream does not wait for the source's).  Without
+ * the flag the calls stage through device memory in chunks and return when the bytes are in place.  Flags other than
+ * DSPI_MEM_DEVICE are refused (DSPI_E_INVAL).  Host-only contexts: dspi_snapshot_sizes works, the other two return DSPI_E_NODEVICE
+ * after validating their arguments. */
+typedef struct dspi_snapshot {
+    void *head;   size_t head_bytes;     /* host memory, always */
+    void *state;  size_t state_bytes;    /* per-stream records; device memory with DSPI_MEM_DEVICE */
+} dspi_snapshot;
+/* Bytes an export of streams [first, first + count) needs (either pointer may be NULL).  Returns 0 or a negative DSPI_E_*. */
+int dspi_snapshot_sizes(const dspi_ctx *ctx, uint32_t first, uint32_t count, size_t *head_bytes, size_t *state_bytes);
+/* Writes streams [first, first + count) into snap (its *_bytes: the capacities).  The context is not changed: it goes on processing
+ * bit-exactly.  Returns count, DSPI_E_SHORT when a buffer is too small, or another negative DSPI_E_*. */
+int dspi_export_streams(dspi_ctx *ctx, uint32_t first, uint32_t count, const dspi_snapshot *snap, uint32_t flags);
+/* Overwrites streams [first, first + n) with the snapshot's n streams (n from the head), in order; `first` and the context's size
+ * need not be the source's.  Streams outside the range keep their state and parameters.  The imported parameter objects become images
+ * of this context; equal ones (among themselves or to images already present) fold into one at the next commit, so streams on a
+ * preset the context already holds return to the shared-parameter kernels.  EVERYTHING is validated before ANYTHING is written:
+ * a wrong magic, version, flavour, contract or fingerprint, a CRC mismatch, sizes that do not add up, an image index out of range, a
+ * short state buffer (DSPI_E_SHORT) or a range past dspi_num_streams return an error and leave the context exactly as it was.
+ * Returns n or a negative DSPI_E_*. */
+int dspi_import_streams(dspi_ctx *ctx, uint32_t first, const dspi_snapshot *snap, uint32_t flags);
 
 /* ---- PDM sub output ---------------------------------------------------- */
 /* The consumer of dspi_out.sub: the firmware's 256x oversampled 2nd-order sigma-delta modulator with noise-shaped
