@@ -97,6 +97,7 @@ struct dspi_ctx {
     int32_t *d_spdif_in = nullptr; size_t d_spdif_in_cap = 0;
     uint32_t *d_spdif_out = nullptr; size_t d_spdif_out_cap = 0;
     uint32_t *d_snap = nullptr; size_t d_snap_cap = 0;          // stream snapshots on host buffers: the records of one chunk of rows
+    uint32_t *d_snap_shift = nullptr; size_t d_snap_shift_cap = 0;      // realigning imports: two rotations per stream of a launch (dspi_snapshot.hip)
     std::string err;
 };
 
@@ -471,7 +472,7 @@ void dspi_destroy(dspi_ctx *c) {
     if (c->device != DSPI_DEVICE_NONE) {
         (void)hipSetDevice(c->device);
         if (c->hs) (void)hipStreamSynchronize(c->hs);
-        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_snap, c->d_in,
+        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_snap, (void *)c->d_snap_shift, c->d_in,
                         (void *)c->d_pairs, (void *)c->d_sub, (void *)c->d_peaks, (void *)c->d_clip, (void *)c->d_spdif_words})
             if (p) (void)hipFree(p);
         if (c->h_direct) (void)hipHostFree(c->h_direct);
@@ -722,10 +723,17 @@ static void snap_images(const dspi_ctx *c, uint32_t first, uint32_t count, std::
     }
 }
 
+static uint32_t snap_chunk_rows(const dspi_ctx *c) { return c->flavor ? 2u : 8u; }
 // host buffers go through device memory a chunk of rows at a time: streams [s, snap_chunk_end) end on a row boundary, 25 - 40 MB of records
 static uint32_t snap_chunk_end(const dspi_ctx *c, uint32_t s, uint32_t end) {
-    const uint32_t row = (uint32_t)c->sm.row, rows = c->flavor ? 2u : 8u;
+    const uint32_t row = (uint32_t)c->sm.row, rows = snap_chunk_rows(c);
     return (uint32_t)std::min<uint64_t>(end, ((uint64_t)s / row + rows) * row);
+}
+
+// records -> the context's arrays on its stream, as they are or realigned to their rows (dspi_snapshot.h snap_row_target)
+static hipError_t snap_scatter(dspi_ctx *c, bool realign, uint32_t *records, uint32_t first, uint32_t count) {
+    if (realign) return launch_snapshot_realign(c->flavor, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, records, first, count, c->n_streams, c->d_snap_shift, c->hs);
+    return launch_snapshot(c->flavor, true, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, records, first, count, c->hs);
 }
 
 int dspi_snapshot_sizes(const dspi_ctx *c, uint32_t first, uint32_t count, size_t *head_bytes, size_t *state_bytes) {
@@ -778,7 +786,7 @@ int dspi_export_streams(dspi_ctx *c, uint32_t first, uint32_t count, const dspi_
 
 int dspi_import_streams(dspi_ctx *c, uint32_t first, const dspi_snapshot *snap, uint32_t flags) {
     if (!c || !snap || !snap->head || !snap->state) return DSPI_E_INVAL;
-    if (flags & ~DSPI_MEM_DEVICE) return fail(c, DSPI_E_INVAL, "dspi_import_streams: undefined flag bits");
+    if (flags & ~(DSPI_MEM_DEVICE | DSPI_SNAP_REALIGN)) return fail(c, DSPI_E_INVAL, "dspi_import_streams: undefined flag bits");
     // everything is validated before anything is written
     if (const char *why = snap_validate_head(snap->head, snap->head_bytes, c->flavor, c->fma)) return fail(c, DSPI_E_INVAL, why);
     SnapHeader h;
@@ -786,7 +794,7 @@ int dspi_import_streams(dspi_ctx *c, uint32_t first, const dspi_snapshot *snap, 
     const uint32_t count = h.count;
     if (!snap_range_ok(c, first, count)) return fail(c, DSPI_E_INVAL, "dspi_import_streams: stream range out of bounds");
     if (snap->state_bytes < snap_state_bytes(c->flavor, count)) return fail(c, DSPI_E_SHORT, "dspi_import_streams: state buffer shorter than the head's stream count");
-    const bool dev = flags & DSPI_MEM_DEVICE;
+    const bool dev = flags & DSPI_MEM_DEVICE, realign = flags & DSPI_SNAP_REALIGN;
     if (dev && (reinterpret_cast<uintptr_t>(snap->state) & 15u)) return fail(c, DSPI_E_INVAL, "dspi_import_streams: device state buffer must be 16-byte aligned");
     if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no run-time state to import into");
     HIPCK(c, hipSetDevice(c->device));
@@ -794,6 +802,8 @@ int dspi_import_streams(dspi_ctx *c, uint32_t first, const dspi_snapshot *snap, 
     if (rc) return rc;
     const size_t rec = snap_state_bytes(c->flavor, 1);
     if (!dev && (rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)(snap_chunk_end(c, first, first + count) - first) * rec))) return rc;
+    // (the shift table is sized for the whole context once: a later, larger import never reallocates it under work still in flight)
+    if (realign && (rc = ensure(c, c->d_snap_shift, c->d_snap_shift_cap, (size_t)c->n_streams * 8))) return rc;
     // parameters: the streams leave their images, the imported objects are appended dirty, and the fold-back pass (merge_images, at the
     // next commit) drops what nobody uses any more and folds equal objects — the imported ones among themselves and into images already
     // here.  Tiles, launch plan, alpha list and pending state operations follow from the ordinary commit.
@@ -815,18 +825,62 @@ int dspi_import_streams(dspi_ctx *c, uint32_t first, const dspi_snapshot *snap, 
     }
     c->assignment_dirty = true; c->merge_hint = true;
     if (h.flags & kSnapAudioStarted) c->audio_started = true;      // running devices arrived: dspi_load_flash_dump is no boot any more
-    // run-time state, behind whatever the context's stream still has to do
+    // run-time state, behind whatever the context's stream still has to do (a realigning import reads its rows' resident neighbours
+    // there, on the device: their positions are what that work leaves)
     if (dev) {
-        HIPCK(c, launch_snapshot(c->flavor, true, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, static_cast<uint32_t *>(snap->state), first, count, c->hs));
+        HIPCK(c, snap_scatter(c, realign, static_cast<uint32_t *>(snap->state), first, count));
         return (int)count;
     }
     for (uint32_t s = first, end = first + count; s < end;) {
         const uint32_t e = snap_chunk_end(c, s, end);
         if ((rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)(e - s) * rec))) return rc;
         HIPCK(c, hipMemcpyAsync(c->d_snap, static_cast<const char *>(snap->state) + (size_t)(s - first) * rec, (size_t)(e - s) * rec, hipMemcpyHostToDevice, c->hs));
-        HIPCK(c, launch_snapshot(c->flavor, true, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, s, e - s, c->hs));
+        HIPCK(c, snap_scatter(c, realign, c->d_snap, s, e - s));      // (chunks end on row boundaries: a row's target is the same in whichever chunk)
         HIPCK(c, hipStreamSynchronize(c->hs));
         s = e;
+    }
+    return (int)count;
+}
+
+int dspi_realign_streams(dspi_ctx *c, uint32_t first, uint32_t count) {
+    if (!c) return DSPI_E_INVAL;
+    if (!snap_range_ok(c, first, count)) return fail(c, DSPI_E_INVAL, "dspi_realign_streams: stream range out of bounds");
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no run-time state to realign");
+    HIPCK(c, hipSetDevice(c->device));
+    int rc = pdm_state(c);      // (the records carry the modulators' words out and back in)
+    if (rc) return rc;
+    const size_t rec = snap_state_bytes(c->flavor, 1);
+    // scratch for a full chunk and the whole context's shifts, once, before anything is enqueued: the loop below never reallocates (a
+    // hipFree would wait for the device) and the call stays asynchronous
+    if ((rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)snap_chunk_rows(c) * (uint32_t)c->sm.row * rec))) return rc;
+    if ((rc = ensure(c, c->d_snap_shift, c->d_snap_shift_cap, (size_t)c->n_streams * 8))) return rc;
+    // run-time state only, chunk by chunk through the records' scratch, all on the context's stream: out as it is, back in rotated.  A
+    // chunk holds whole rows of the range, so its rows' targets are those of the whole range.
+    for (uint32_t s = first, end = first + count; s < end;) {
+        const uint32_t e = snap_chunk_end(c, s, end);
+        HIPCK(c, launch_snapshot(c->flavor, false, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, s, e - s, c->hs));
+        HIPCK(c, snap_scatter(c, true, c->d_snap, s, e - s));
+        s = e;
+    }
+    return (int)count;
+}
+
+int dspi_debug_stream_positions(dspi_ctx *c, uint32_t first, uint32_t count, uint32_t *widx, uint32_t *ring_pos) {
+    if (!c || !widx || !ring_pos) return DSPI_E_INVAL;
+    if (!snap_range_ok(c, first, count)) return fail(c, DSPI_E_INVAL, "dspi_debug_stream_positions: stream range out of bounds");
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no run-time state");
+    HIPCK(c, hipSetDevice(c->device));
+    HIPCK(c, hipStreamSynchronize(c->hs));
+    // the two slots' rows of every touched row of the state array ([row][slot][lane])
+    const uint32_t row = (uint32_t)c->sm.row, r0 = first / row, rows = (first + count - 1) / row - r0 + 1;
+    std::vector<uint32_t> w((size_t)rows * row), r((size_t)rows * row);
+    const size_t pitch = (size_t)c->sm.n_slots * row * 4;
+    HIPCK(c, hipMemcpy2D(w.data(), (size_t)row * 4, c->d_state + ((size_t)r0 * c->sm.n_slots + c->sm.widx) * row, pitch, (size_t)row * 4, rows, hipMemcpyDeviceToHost));
+    HIPCK(c, hipMemcpy2D(r.data(), (size_t)row * 4, c->d_state + ((size_t)r0 * c->sm.n_slots + c->sm.ring_pos) * row, pitch, (size_t)row * 4, rows, hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < count; k++) {
+        const size_t at = (size_t)first + k - (size_t)r0 * row;
+        widx[k] = w[at] & ((uint32_t)c->sm.max_delay - 1u);
+        ring_pos[k] = r[at] & ((uint32_t)kRingLen - 1u);
     }
     return (int)count;
 }

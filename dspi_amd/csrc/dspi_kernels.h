@@ -72,5 +72,9 @@ hipError_t launch_clip_gather(const uint32_t *state, uint32_t n_streams, uint32_
 // (dspi_snapshot.h), `records` = the record of stream `first`, 16-byte aligned.  import: records -> arrays, else arrays -> records.
 hipError_t launch_snapshot(int flavor, bool import, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first,
                            uint32_t count, hipStream_t stream);
+// The realigning import (dspi_snapshot.h snap_row_target): two launches, the per-stream shifts into `shift` (2 words per stream of the range,
+// 8-byte aligned device scratch), then the import rotated by them.  n_streams: the context's, for the rows' resident neighbours.
+hipError_t launch_snapshot_realign(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count,
+                                   uint32_t n_streams, uint32_t *shift, hipStream_t stream);
 
 }  // namespace dspi

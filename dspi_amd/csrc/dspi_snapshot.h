@@ -52,6 +52,30 @@ constexpr SnapLayout make_snap_layout(int flavor) {
     return l;
 }
 
+// ---- realignment (DSPI_SNAP_REALIGN, dspi_realign_streams) ----
+// A delay line and a leveller ring are circular and addressed only relative to the stream's one position slot (StateMap::widx,
+// StateMap::ring_pos): a stream whose lines are rotated by d and whose position is advanced by d is the same stream.  A realigning
+// write gives every stream it writes the positions of its destination row, so that the row's streams share one position again.
+//
+// The target rule: whose (widx, ring_pos) the streams written into row `row` take, for a call that writes streams [first, first +
+// count) of a context of n_streams: the lowest-numbered stream of the row that is below n_streams and OUTSIDE the range — a resident
+// neighbour, its positions read from the context's state array —, or, where the row has none, the first stream of the range that
+// lands in the row, its positions read from its record.  (A range of whole rows therefore moves its rows' first streams by 0.)
+struct SnapTarget {
+    uint32_t stream;      // of the destination context
+    bool resident;        // outside the range: read the state array; else read record `stream - first`
+};
+constexpr SnapTarget snap_row_target(uint32_t row, uint32_t row_streams, uint32_t n_streams, uint32_t first, uint32_t count) {
+    const uint64_t r0 = (uint64_t)row * row_streams, r1 = r0 + row_streams < n_streams ? r0 + row_streams : n_streams, end = (uint64_t)first + count;
+    if (r0 < first) return SnapTarget{(uint32_t)r0, true};            // the row begins below the range
+    if (end < r1) return SnapTarget{(uint32_t)end, true};             // the range ends inside the row
+    return SnapTarget{(uint32_t)r0, false};                           // the range covers what the context has of the row
+}
+// how far a stream at position `from` is rotated to stand at `to` (both masked; len a power of two)
+constexpr uint32_t snap_shift(uint32_t from, uint32_t to, uint32_t len) { return (to - from) & (len - 1u); }
+// the record position whose word lands at position p of a line or ring of `len` words rotated by d: line[(q + d) mod len] = record[q]
+constexpr uint32_t snap_rot_source(uint32_t p, uint32_t d, uint32_t len) { return (p - d) & (len - 1u); }
+
 // 64 bytes, little-endian like everything else the library exchanges
 struct SnapHeader {
     uint32_t magic, version;

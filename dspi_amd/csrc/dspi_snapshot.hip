@@ -23,6 +23,19 @@
 // array side stores whole 16-byte groups where all four columns are covered and single words elsewhere, so foreign streams' words are
 // never written.  Positions past a section's length (the tile grid rounds up) are never read from or written to the arrays; a
 // section's pad words (dspi_snapshot.h) are exported as zeros and ignored by the import.
+//
+// The REALIGNING import (DSPI_SNAP_REALIGN, dspi_realign_streams; the rule and the index arithmetic are in dspi_snapshot.h) rotates every
+// delay line and ring on this pass: position p of a line of column c takes the record's position (p - d_c) mod length, d_c from a
+// per-stream shift table that snapshot_targets_kernel wrote just before (one workgroup per touched row, one thread per stream: the row's
+// target positions minus the record's own), and the two position slots of the state section are advanced by the same d_c.  The array
+// side is the plain import's.  The record side can no longer move 16 bytes per lane — the run that maps onto the tile starts at
+// (p0 - d_c) mod length, aligned to 4 bytes only, and wraps once per line — so it reads single words, and with single words a wave is
+// free to read them in run order:
+//   record side   load j (of 4) of lane (k, h) of wave w reads position 32 j + k of column c = w + 4 i + 32 h in pass i (of 8): a half
+//                 wave reads 128 consecutive bytes of one record (two pieces at the wrap), a workgroup's four loads 512 bytes per column
+//   LDS           the word goes to tile[32 j + k][c]: bank (32 j + k) P + c = 32 j + k + w + 4 i + 32 h (mod 64; P = 65): for one
+//                 instruction j, i and w are fixed and k + 32 h runs over all 64 banks: conflict-free.  (Two ADJACENT columns per wave,
+//                 as on the plain path, would put lanes (k + 1, c) and (k, c + 1) into one bank: hence the half waves 32 columns apart.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -47,11 +60,18 @@ struct SnapKArgs {
     uint32_t record_words, first, count, row0;
 };
 
+struct SnapRealignArgs : SnapKArgs {
+    const uint2 *shift;                // per stream of [first, first + count): {delay lines' rotation, rings' rotation}
+};
+template <bool REALIGN> struct SnapArgsOf { typedef SnapKArgs type; };
+template <> struct SnapArgsOf<true> { typedef SnapRealignArgs type; };
+
 // word i of four, i known at run time only: selects, so that the four stay in registers
 __device__ __forceinline__ uint32_t pick(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t i) { return i == 0 ? w0 : i == 1 ? w1 : i == 2 ? w2 : w3; }
 
-template <uint32_t ROW, bool IMPORT>
-__global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const SnapKArgs a) {
+template <uint32_t ROW, bool IMPORT, bool REALIGN = false>
+__global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const typename SnapArgsOf<REALIGN>::type a) {
+    static_assert(IMPORT || !REALIGN, "only the import realigns");
     constexpr uint32_t kTilePos = IMPORT ? kImportPos : kExportPos, kCols = IMPORT ? kImportCols : kExportCols;
     static_assert(ROW % kCols == 0 && kCols % 4 == 0 && kTilePos % 4 == 0 && kSnapThreads % (kCols / 4) == 0 && kSnapThreads % (kTilePos / 4) == 0, "tile shape");
     constexpr uint32_t kPitch = kCols + 1, kRowLanes = kCols / 4, kRowsPerPass = kSnapThreads / kRowLanes, kRunLanes = kTilePos / 4, kColsPerPass = kSnapThreads / kRunLanes;
@@ -59,9 +79,10 @@ __global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const SnapKArgs 
     // the tile's section (constant indices only: a run-time index into the argument block would put it in scratch)
     uint32_t *base = a.arr[0];
     uint32_t len = a.len[0], span = a.span[0], off = a.off[0], t0 = 0;
+    [[maybe_unused]] int sec = 0;
 #pragma unroll
     for (int i = 1; i < SEC_COUNT; i++)
-        if (blockIdx.x >= a.tile0[i]) { base = a.arr[i]; len = a.len[i]; span = a.span[i]; off = a.off[i]; t0 = a.tile0[i]; }
+        if (blockIdx.x >= a.tile0[i]) { base = a.arr[i]; len = a.len[i]; span = a.span[i]; off = a.off[i]; t0 = a.tile0[i]; sec = i; }
     const uint32_t wg = a.row0 + blockIdx.y, p0 = (blockIdx.x - t0) * kTilePos, col0 = blockIdx.z * kCols;
     // the tile's columns inside [first, first + count)
     const uint64_t s0 = (uint64_t)wg * ROW, b0 = s0 + col0, lo = a.first > b0 ? a.first : b0, end = (uint64_t)a.first + a.count, hi = end < b0 + kCols ? end : b0 + kCols;
@@ -93,7 +114,40 @@ __global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const SnapKArgs 
                 *reinterpret_cast<u4 *>(rec + (size_t)(c - c_lo) * a.record_words + 4 * k) = v;
             }
     } else {
-        if (p0 + 4 * k < span)
+        if constexpr (REALIGN) {
+            static_assert(kTilePos == 128 && kCols == 64 && kSnapThreads == 256, "the realigning record side's lane mapping");
+            constexpr StateMap sm = make_state_map(ROW == 128 ? 1 : 0);
+            constexpr uint32_t kLine = (uint32_t)sm.max_delay, kRing = (uint32_t)kRingLen;
+            static_assert((kLine & (kLine - 1)) == 0 && kLine % kTilePos == 0 && kRing % kTilePos == 0, "a tile lies inside one line / ring");
+            // the tile's plane: a line, a ring — or the whole section (state, PDM: d = 0, and a mask of all ones, "length 2^32", keeps p)
+            const uint32_t pmask = sec == SEC_LINES ? kLine - 1u : sec == SEC_RING ? kRing - 1u : ~0u;
+            const uint32_t kk = tid & 31u, c_lane = (tid >> 6) + 32u * ((tid >> 5) & 1u);
+            for (uint32_t i = 0; i < kCols / 8; i++) {
+                const uint32_t c = c_lane + 4u * i;
+                if (c < c_lo || c >= c_hi) continue;
+                const size_t k_str = (size_t)(b0 + c - a.first);
+                const uint2 sh = a.shift[k_str];
+                const uint32_t d = sec == SEC_LINES ? sh.x : sec == SEC_RING ? sh.y : 0u;
+                const uint32_t *rc = a.rec + k_str * a.record_words + off;      // column c's section
+                // (four loads in flight, then four LDS writes: a position past the section's span — the tile grid rounds up — reads the
+                // section's word 0 instead, and the array side never looks at it)
+                uint32_t v[4];
+#pragma unroll
+                for (uint32_t j = 0; j < 4; j++) {
+                    const uint32_t p = p0 + 32u * j + kk;
+                    v[j] = rc[p < span ? (p & ~pmask) | snap_rot_source(p, d, pmask + 1u) : 0u];
+                }
+#pragma unroll
+                for (uint32_t j = 0; j < 4; j++) {
+                    const uint32_t pos = 32u * j + kk, p = p0 + pos;
+                    if (sec == SEC_STATE) {      // the two position slots move with their lines
+                        if (p == (uint32_t)sm.widx) v[j] = (v[j] + sh.x) & (kLine - 1u);
+                        if (p == (uint32_t)sm.ring_pos) v[j] = (v[j] + sh.y) & (kRing - 1u);
+                    }
+                    tile[pos * kPitch + c] = v[j];
+                }
+            }
+        } else if (p0 + 4 * k < span)
             for (uint32_t c = c_lo + cc0; c < c_hi; c += kColsPerPass) {
                 const u4 v = *reinterpret_cast<const u4 *>(rec + (size_t)(c - c_lo) * a.record_words + 4 * k);
                 uint32_t *t = tile + 4 * k * kPitch + c;
@@ -115,13 +169,27 @@ __global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const SnapKArgs 
     }
 }
 
-}  // namespace
+// One thread per stream of a touched row: the row's target positions (dspi_snapshot.h snap_row_target: a resident neighbour's, from the
+// state array as the stream's earlier work left it, or the range's first stream's, from its record) minus the record's own.
+template <uint32_t ROW>
+__global__ __launch_bounds__(ROW) void snapshot_targets_kernel(const uint32_t *state, const uint32_t *rec, uint32_t record_words, uint32_t state_off, uint32_t first,
+                                                               uint32_t count, uint32_t n_streams, uint32_t row0, uint2 *shift) {
+    constexpr StateMap sm = make_state_map(ROW == 128 ? 1 : 0);
+    constexpr uint32_t kLine = (uint32_t)sm.max_delay, kRing = (uint32_t)kRingLen;
+    const uint32_t row = row0 + blockIdx.x;
+    const SnapTarget t = snap_row_target(row, ROW, n_streams, first, count);
+    const uint32_t *tp = t.resident ? state + (size_t)row * sm.n_slots * ROW + (t.stream - row * ROW) : rec + (size_t)(t.stream - first) * record_words + state_off;
+    const size_t ts = t.resident ? ROW : 1;
+    const uint32_t w_t = tp[(size_t)sm.widx * ts] & (kLine - 1u), r_t = tp[(size_t)sm.ring_pos * ts] & (kRing - 1u);
+    const uint64_t s = (uint64_t)row * ROW + threadIdx.x;
+    if (s < first || s >= (uint64_t)first + count) return;
+    const uint32_t *r = rec + (size_t)(s - first) * record_words + state_off;
+    shift[s - first] = make_uint2(snap_shift(r[sm.widx] & (kLine - 1u), w_t, kLine), snap_shift(r[sm.ring_pos] & (kRing - 1u), r_t, kRing));
+}
 
-hipError_t launch_snapshot(int flavor, bool import, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first,
-                           uint32_t count, hipStream_t stream) {
-    if (count == 0) return hipSuccess;
+struct SnapGrid { dim3 grid; uint32_t rows; };
+SnapGrid snap_kargs(SnapKArgs &a, int flavor, bool import, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count) {
     const SnapLayout l = make_snap_layout(flavor);
-    SnapKArgs a{};
     uint32_t *const arrs[SEC_COUNT] = {state, dlines, ring, pdm};
     const uint32_t pos = import ? kImportPos : kExportPos, cols = import ? kImportCols : kExportCols;
     uint32_t tiles = 0;
@@ -133,13 +201,39 @@ hipError_t launch_snapshot(int flavor, bool import, uint32_t *state, uint32_t *d
     a.rec = records; a.record_words = l.record_words; a.first = first; a.count = count;
     a.row0 = first / l.row;
     const uint32_t rows = (uint32_t)(((uint64_t)first + count - 1) / l.row) - a.row0 + 1;
-    const dim3 grid(tiles, rows, l.row / cols);
+    return SnapGrid{dim3(tiles, rows, l.row / cols), rows};
+}
+
+}  // namespace
+
+hipError_t launch_snapshot(int flavor, bool import, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first,
+                           uint32_t count, hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    SnapKArgs a{};
+    const dim3 grid = snap_kargs(a, flavor, import, state, dlines, ring, pdm, records, first, count).grid;
     if (flavor) {
         if (import) hipLaunchKernelGGL((snapshot_kernel<128, true>), grid, dim3(kSnapThreads), 0, stream, a);
         else hipLaunchKernelGGL((snapshot_kernel<128, false>), grid, dim3(kSnapThreads), 0, stream, a);
     } else {
         if (import) hipLaunchKernelGGL((snapshot_kernel<64, true>), grid, dim3(kSnapThreads), 0, stream, a);
         else hipLaunchKernelGGL((snapshot_kernel<64, false>), grid, dim3(kSnapThreads), 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_snapshot_realign(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count,
+                                   uint32_t n_streams, uint32_t *shift, hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    SnapRealignArgs a{};
+    const SnapGrid g = snap_kargs(a, flavor, true, state, dlines, ring, pdm, records, first, count);
+    a.shift = reinterpret_cast<const uint2 *>(shift);
+    uint2 *const sh = reinterpret_cast<uint2 *>(shift);
+    if (flavor) {
+        hipLaunchKernelGGL((snapshot_targets_kernel<128>), dim3(g.rows), dim3(128), 0, stream, state, records, a.record_words, a.off[SEC_STATE], first, count, n_streams, a.row0, sh);
+        hipLaunchKernelGGL((snapshot_kernel<128, true, true>), g.grid, dim3(kSnapThreads), 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((snapshot_targets_kernel<64>), dim3(g.rows), dim3(64), 0, stream, state, records, a.record_words, a.off[SEC_STATE], first, count, n_streams, a.row0, sh);
+        hipLaunchKernelGGL((snapshot_kernel<64, true, true>), g.grid, dim3(kSnapThreads), 0, stream, a);
     }
     return hipGetLastError();
 }

@@ -16,6 +16,7 @@ LIB_PATH = Path(os.environ.get("DSPI_LIB") or (Path(__file__).resolve().parent /
 
 ALL = -1
 MEM_DEVICE = 0x1
+SNAP_REALIGN = 0x100
 OUT_TILED = 0x2
 OUT_ENABLED_ONLY = 0x4
 OUT_I2S_SLOTS = 0x8
@@ -104,6 +105,9 @@ def lib() -> C.CDLL:
         L.dspi_snapshot_sizes.argtypes = [vp, u32, u32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.dspi_export_streams.argtypes = [vp, u32, u32, C.POINTER(_Snapshot), u32]
         L.dspi_import_streams.argtypes = [vp, u32, C.POINTER(_Snapshot), u32]
+    if hasattr(L, "dspi_realign_streams"):      # (ABI 8 + realignment: detected by symbol; with it DSPI_SNAP_REALIGN)
+        L.dspi_realign_streams.argtypes = [vp, u32, u32]
+        L.dspi_debug_stream_positions.argtypes = [vp, u32, u32, vp, vp]
     _lib = L
     return L
 
@@ -343,13 +347,13 @@ class Dspi:
         self._ck(self.L.dspi_export_streams(self.h, first, count, C.byref(snap), 0), "export_streams")
         return head.raw, state
 
-    def import_streams(self, first: int, head: bytes, state: np.ndarray) -> int:
+    def import_streams(self, first: int, head: bytes, state: np.ndarray, realign: bool = False) -> int:
         """Overwrites streams [first, first + n) with a snapshot's n streams (n from the head); returns n.  A refused snapshot
-        (DspiError) leaves the context as it was."""
+        (DspiError) leaves the context as it was.  realign: DSPI_SNAP_REALIGN, every stream takes its destination row's write positions."""
         state = np.ascontiguousarray(state, dtype=np.uint32)
         hbuf = C.create_string_buffer(bytes(head), len(head))
         snap = _Snapshot(C.addressof(hbuf), len(head), state.ctypes.data, state.nbytes)
-        return self._ck(self.L.dspi_import_streams(self.h, first, C.byref(snap), 0), "import_streams")
+        return self._ck(self.L.dspi_import_streams(self.h, first, C.byref(snap), SNAP_REALIGN if realign else 0), "import_streams")
 
     def export_streams_device(self, first: int, count: int, state_ptr: int, state_bytes: int) -> bytes:
         """export_streams with the records in device memory (16-byte aligned, e.g. torch.Tensor.data_ptr()); asynchronous on the
@@ -360,11 +364,21 @@ class Dspi:
         self._ck(self.L.dspi_export_streams(self.h, first, count, C.byref(snap), MEM_DEVICE), "export_streams")
         return head.raw
 
-    def import_streams_device(self, first: int, head: bytes, state_ptr: int, state_bytes: int) -> int:
-        """import_streams from records in device memory; asynchronous on the context's stream."""
+    def import_streams_device(self, first: int, head: bytes, state_ptr: int, state_bytes: int, realign: bool = False) -> int:
+        """import_streams from records in device memory; asynchronous on the context's stream (also with realign)."""
         hbuf = C.create_string_buffer(bytes(head), len(head))
         snap = _Snapshot(C.addressof(hbuf), len(head), state_ptr, state_bytes)
-        return self._ck(self.L.dspi_import_streams(self.h, first, C.byref(snap), MEM_DEVICE), "import_streams")
+        return self._ck(self.L.dspi_import_streams(self.h, first, C.byref(snap), MEM_DEVICE | (SNAP_REALIGN if realign else 0)), "import_streams")
+
+    def realign_streams(self, first: int, count: int) -> int:
+        """dspi_realign_streams: streams [first, first + count) take their rows' write positions, in place; asynchronous on the context's stream."""
+        return self._ck(self.L.dspi_realign_streams(self.h, first, count), "realign_streams")
+
+    def stream_positions(self, first: int, count: int):
+        """dspi_debug_stream_positions: (delay write index, leveller ring position) of streams [first, first + count), uint32 [count] each, masked."""
+        w, r = np.zeros(count, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
+        self._ck(self.L.dspi_debug_stream_positions(self.h, first, count, w.ctypes.data, r.ctypes.data), "debug_stream_positions")
+        return w, r
 
     def sync(self):
         self._ck(self.L.dspi_sync(self.h), "sync")

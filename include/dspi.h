@@ -67,7 +67,8 @@ extern "C" {
                               * 6: DSPI_OUT_SPDIF, dspi_spdif_block_pos; 7: dspi_out.clip_flags behind DSPI_OUT_CLIP_FLAGS, DSPI_OUT_SPDIF on every
                               * context, (additions only: a v6 caller's three-member dspi_out is never read past `peaks`);
                               * 8: dspi_debug_direct_stats, dspi_debug_detmath, the direct path polls a completion word for the call's own audio time (DSPI_DIRECT_SPIN_US, DSPI_DIRECT_POLL);
-                              * 8 + snapshots: detect by symbol (dspi_snapshot_sizes, dspi_export_streams, dspi_import_streams; additions only) */
+                              * 8 + snapshots: detect by symbol (dspi_snapshot_sizes, dspi_export_streams, dspi_import_streams; additions only);
+                              * 8 + realignment: detect by symbol (dspi_realign_streams; with it DSPI_SNAP_REALIGN and dspi_debug_stream_positions; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -245,8 +246,9 @@ int dspi_sync(dspi_ctx *ctx);
  * length, both leveller rings, the PDM modulator's words (power-on values when the source never ran dspi_pdm_modulate) — exported
  * after packet k and imported anywhere else continues from packet k + 1 with exactly the words an uninterrupted run produces: on
  * another context, another GPU, another process, at another stream index (a float stream may change its row and its side of a packed
- * lane).  Write positions travel as they are; rows whose streams carry different positions are served by the kernels' per-stream
- * addressing.
+ * lane).  Write positions (delay write index, leveller ring position) travel as they are unless the import is asked to realign them
+ * (DSPI_SNAP_REALIGN below); rows whose streams carry different positions are served by the kernels' per-stream addressing, which
+ * is correct and slower than a row that shares one position.
  *   head    host memory, always: a 64-byte header (magic, format version, flavour, float contract, record size, count, number of
  *           parameter objects, fingerprint of the internal layout, CRC-32 of the head), one parameter object per DISTINCT parameter
  *           set in the range, one uint32 index per stream
@@ -259,8 +261,9 @@ int dspi_sync(dspi_ctx *ctx);
  * With DSPI_MEM_DEVICE the calls are asynchronous on the context's stream like dspi_process: between two contexts, dspi_sync the
  * source after the export and before the import reads `state` (the import's own stream does not wait for the source's).  Without
  * the flag the calls stage through device memory in chunks and return when the bytes are in place.  Flags other than
- * DSPI_MEM_DEVICE are refused (DSPI_E_INVAL).  Host-only contexts: dspi_snapshot_sizes works, the other two return DSPI_E_NODEVICE
- * after validating their arguments. */
+ * DSPI_MEM_DEVICE (both calls) and DSPI_SNAP_REALIGN (import only) are refused (DSPI_E_INVAL).  Host-only contexts:
+ * dspi_snapshot_sizes works, the other two return DSPI_E_NODEVICE after validating their arguments. */
+#define DSPI_SNAP_REALIGN 0x100u   /* dspi_import_streams: every imported stream takes the write positions of its destination row */
 typedef struct dspi_snapshot {
     void *head;   size_t head_bytes;     /* host memory, always */
     void *state;  size_t state_bytes;    /* per-stream records; device memory with DSPI_MEM_DEVICE */
@@ -278,6 +281,26 @@ int dspi_export_streams(dspi_ctx *ctx, uint32_t first, uint32_t count, const dsp
  * short state buffer (DSPI_E_SHORT) or a range past dspi_num_streams return an error and leave the context exactly as it was.
  * Returns n or a negative DSPI_E_*. */
 int dspi_import_streams(dspi_ctx *ctx, uint32_t first, const dspi_snapshot *snap, uint32_t flags);
+/* ---- realignment: a row's streams back onto one write position ------------------------------------------------------------- */
+/* A delay line and a leveller ring are circular and addressed only relative to the stream's position slot, so a stream whose nine (five)
+ * lines are rotated by d and whose delay write index is advanced by d — likewise the two rings and the ring position — is the same
+ * stream: its output does not change by a bit.  The chain kernels serve a row (128 float / 64 Q28 streams) whose streams share their
+ * positions with one row access per wave; streams that arrived from a context of another age do not share them.
+ * With DSPI_SNAP_REALIGN, dspi_import_streams writes stream k rotated: with L the line length (4096 / 2048), N = 1024 the ring length,
+ * (w_s, r_s) the positions in k's record (masked to L, N) and (w_t, r_t) the target of k's destination row,
+ *   line[o][(p + w_t - w_s) mod L] = record.line[o][p]    ring[ch][(p + r_t - r_s) mod N] = record.ring[ch][p]    widx := w_t   ring_pos := r_t
+ * and everything else (other state slots, PDM words, parameters, images, pending operations) exactly as without the flag.
+ * The target of a row is the (widx, ring_pos) of its lowest-numbered stream that is below dspi_num_streams and OUTSIDE the range being
+ * written — a resident neighbour, read on the device behind whatever the context's stream still has to do —; a row without one takes the
+ * pair of the first stream of the range that lands in it.  So a range of whole rows moves its rows' first streams by 0, and into a fresh
+ * context it is word for word the plain import.  DSPI_MEM_DEVICE imports stay asynchronous.  dspi_export_streams refuses the flag.
+ *
+ * dspi_realign_streams does the same in place for streams [first, first + count) of a context (rows mixed by earlier plain imports, or
+ * streams that drifted apart with no snapshot at all: different histories of delays active / leveller on): run-time state only, through
+ * the context's own device scratch, asynchronous on the context's stream like dspi_process with device buffers.  No parameter object,
+ * image or pending operation is touched; a second call on an aligned range changes nothing.  Arguments are validated before anything is
+ * written; host-only contexts return DSPI_E_NODEVICE after that.  Returns count or a negative DSPI_E_*. */
+int dspi_realign_streams(dspi_ctx *ctx, uint32_t first, uint32_t count);
 
 /* ---- PDM sub output ---------------------------------------------------- */
 /* The consumer of dspi_out.sub: the firmware's 256x oversampled 2nd-order sigma-delta modulator with noise-shaped
@@ -336,6 +359,10 @@ int dspi_debug_image(dspi_ctx *ctx, int32_t stream, void *buf, size_t cap);
  * presets of one structure at once (a workgroup's stream slots each read their own image).  Returns the number of counts written
  * (5, 6 or 7) or a negative DSPI_E_*. */
 int dspi_debug_launch_plan(dspi_ctx *ctx, uint32_t *counts, size_t n_counts);
+/* The delay write index and the leveller ring position of streams [first, first + count), masked to the line / ring length, into host
+ * buffers of count words each.  Synchronises the context's stream.  Tests use it to prove that a scenario really was misaligned before
+ * a realignment and is uniform per row after it.  Returns count or a negative DSPI_E_*. */
+int dspi_debug_stream_positions(dspi_ctx *ctx, uint32_t first, uint32_t count, uint32_t *widx, uint32_t *ring_pos);
 /* include/dspi_detmath.h evaluated on the DEVICE, host buffers, n <= 2^24: which = 0: out[i] = log10f(a[i]) and 1: powf(a[i], b[i]) in the two-step
  * forms; 2: log10f, 3: 10^a[i], 4: a[i]^b[i] in the forms the chain kernels use (step 1 + exception tables).  Tests compare all of them bit for
  * bit with the host build of the same header and with binary128. */
