@@ -98,6 +98,13 @@ struct dspi_ctx {
     uint32_t *d_spdif_out = nullptr; size_t d_spdif_out_cap = 0;
     uint32_t *d_snap = nullptr; size_t d_snap_cap = 0;          // stream snapshots on host buffers: the records of one chunk of rows
     uint32_t *d_snap_shift = nullptr; size_t d_snap_shift_cap = 0;      // realigning imports: two rotations per stream of a launch (dspi_snapshot.hip)
+    // paused streams (dspi_pause_streams): a property of the SLOT.  `active` is the truth (one byte per stream, 1 = takes part in dspi_process;
+    // empty until the first pause); the launch plan is built from it (PlanInput::active) and the kernels that walk every stream whatever the
+    // plan says (PDM modulator, two-pass S/PDIF encoder, value-tile builder, the resume's target rule) read one bit per stream on the device,
+    // uploaded when it has changed and something needs it (upload_activity)
+    std::vector<uint8_t> active; uint32_t n_paused = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> paused_runs; bool paused_runs_dirty = false;      // [first, end) of consecutive paused streams: what the host-buffer paths zero
+    uint32_t *d_active = nullptr; size_t d_active_cap = 0; bool active_dirty = false;
     std::string err;
 };
 
@@ -220,6 +227,55 @@ int ensure(dspi_ctx *c, P *&ptr, size_t &cap, size_t bytes) {
     return 0;
 }
 
+// the device's activity bitmap as the host has it.  Behind a synchronisation (no kernel may still be reading the words): pauses are rare.
+int upload_activity(dspi_ctx *c) {
+    if (!c->active_dirty) return 0;
+    std::vector<uint32_t> bits(((size_t)c->n_streams + 31) / 32, 0u);
+    for (uint32_t s = 0; s < c->n_streams; s++) if (c->active[s]) bits[s >> 5] |= 1u << (s & 31u);
+    int rc = ensure(c, c->d_active, c->d_active_cap, bits.size() * 4);
+    if (rc) return rc;
+    HIPCK(c, hipStreamSynchronize(c->hs));
+    HIPCK(c, hipMemcpy(c->d_active, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
+    c->active_dirty = false;
+    return 0;
+}
+// The host-buffer paths hand back zeros in the paused streams' regions, which no kernel writes: the regions to clear, as runs of paused
+// streams.  Empty = "clear the whole buffers" (more than kMaxPausedRuns runs: one large clear beats thousands of small ones).
+constexpr size_t kMaxPausedRuns = 64;
+const std::vector<std::pair<uint32_t, uint32_t>> &paused_runs(dspi_ctx *c) {
+    if (c->paused_runs_dirty) {
+        c->paused_runs.clear();
+        for (uint32_t s = 0; s < c->n_streams && c->paused_runs.size() <= kMaxPausedRuns;) {
+            if (c->active[s]) { s++; continue; }
+            uint32_t e = s;
+            while (e < c->n_streams && !c->active[e]) e++;
+            c->paused_runs.emplace_back(s, e);
+            s = e;
+        }
+        if (c->paused_runs.size() > kMaxPausedRuns) c->paused_runs.clear();
+        c->paused_runs_dirty = false;
+    }
+    return c->paused_runs;
+}
+// the pieces of one buffer of a call that hold paused streams: f(offset, bytes).  Tiled words: the whole tiles that hold one.
+template <class F>
+void for_paused_regions(dspi_ctx *c, const CallBuffer &b, F f) {
+    if (!b.bytes) return;
+    const auto &runs = paused_runs(c);
+    if (runs.empty()) { f((size_t)0, b.bytes); return; }
+    const size_t row = (size_t)c->sm.row;
+    size_t done = 0;      // (tiles: runs in one tile are cleared once)
+    for (const auto &r : runs) {
+        size_t lo = r.first, hi = r.second;
+        if (b.tile_cols) { lo = lo / row * row; hi = (hi + row - 1) / row * row; }
+        lo = std::max(lo, done);
+        if (hi > lo) f(lo * b.per, (hi - lo) * b.per);
+        done = std::max(done, hi);
+    }
+}
+// what the kernels get: null while nothing is paused (they then do what they always did)
+const uint32_t *activity(const dspi_ctx *c) { return c->n_paused ? c->d_active : nullptr; }
+
 int rebuild_assignment(dspi_ctx *c) {
     const size_t ni = c->images.size();
     c->image_rows = image_rows(c->flavor, (uint32_t)c->sm.row, c->stream_image.data(), c->n_streams, ni);
@@ -244,6 +300,7 @@ int rebuild_launch_lists(dspi_ctx *c) {
     PlanInput &in = c->plan_in;
     in.flavor = c->flavor; in.n_streams = c->n_streams; in.row = (uint32_t)c->sm.row;
     in.stream_image = c->stream_image; in.refs = c->image_refs;
+    if (c->n_paused) in.active = c->active; else in.active.clear();      // (nothing paused: the plan of a context that never paused, item for item)
     int cus = 0;
     if (c->device < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0) cus = 256;
     in.cus = (uint32_t)cus;
@@ -360,6 +417,7 @@ int commit_params(dspi_ctx *c) {
         for (size_t k = i; k < j; k++) c->images[k]->ops = StateOps{};
         i = j;
     }
+    if (c->n_paused) { int rc = upload_activity(c); if (rc) return rc; }
     if (c->launch_dirty) { int rc = rebuild_launch_lists(c); if (rc) return rc; }
     if (c->flavor) {       // value tiles of the per-lane-value rows that hold an image uploaded above
         std::vector<uint32_t> rows;
@@ -377,7 +435,7 @@ int commit_params(dspi_ctx *c) {
             HIPCK(c, hipStreamSynchronize(c->hs));      // no launch may still be reading the tiles or the row list
             HIPCK(c, hipMemcpy(c->d_pv_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
             static const bool all_differ = getenv("DSPI_DEBUG") && (strtoul(getenv("DSPI_DEBUG"), nullptr, 0) & 1u);      // development switch (timing of the worst case)
-            HIPCK(c, launch_pv_build(c->d_images, c->d_stream_image, c->d_pv_rows, (uint32_t)rows.size(), c->d_vals, c->n_streams, all_differ, c->hs));
+            HIPCK(c, launch_pv_build(c->d_images, c->d_stream_image, c->d_pv_rows, (uint32_t)rows.size(), c->d_vals, c->n_streams, all_differ, activity(c), c->hs));
         }
     }
     return 0;
@@ -472,7 +530,7 @@ void dspi_destroy(dspi_ctx *c) {
     if (c->device != DSPI_DEVICE_NONE) {
         (void)hipSetDevice(c->device);
         if (c->hs) (void)hipStreamSynchronize(c->hs);
-        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_snap, (void *)c->d_snap_shift, c->d_in,
+        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, c->d_in,
                         (void *)c->d_pairs, (void *)c->d_sub, (void *)c->d_peaks, (void *)c->d_clip, (void *)c->d_spdif_words})
             if (p) (void)hipFree(p);
         if (c->h_direct) (void)hipHostFree(c->h_direct);
@@ -681,6 +739,7 @@ int dspi_pdm_modulate(dspi_ctx *c, const int32_t *sub, uint32_t n_frames, uint32
     HIPCK(c, hipSetDevice(c->device));
     int rc = pdm_state(c);
     if (rc) return rc;
+    if (c->n_paused && (rc = upload_activity(c))) return rc;
     const bool tiled = flags & DSPI_OUT_TILED, dev = flags & DSPI_MEM_DEVICE;
     const size_t cols = tiled ? (size_t)c->n_wg * c->sm.row : (size_t)c->n_streams;
     const size_t in_b = cols * n_frames * 4, out_b = in_b * 8;
@@ -690,8 +749,9 @@ int dspi_pdm_modulate(dspi_ctx *c, const int32_t *sub, uint32_t n_frames, uint32
         if ((rc = ensure(c, c->d_pdm_in, c->d_pdm_in_cap, in_b)) || (rc = ensure(c, c->d_pdm_out, c->d_pdm_out_cap, out_b))) return rc;
         HIPCK(c, hipMemcpyAsync(c->d_pdm_in, sub, in_b, hipMemcpyHostToDevice, c->hs));
         d_in = c->d_pdm_in; d_out = c->d_pdm_out;
+        if (c->n_paused) HIPCK(c, hipMemsetAsync(c->d_pdm_out, 0, out_b, c->hs));      // paused streams' words stay unwritten: the staging buffer goes back whole, with zeros there
     }
-    HIPCK(c, launch_pdm(tiled, c->d_pdm, d_in, d_out, c->n_streams, n_frames, (uint32_t)c->sm.row, c->n_wg, c->hs));
+    HIPCK(c, launch_pdm(tiled, c->d_pdm, d_in, d_out, c->n_streams, n_frames, (uint32_t)c->sm.row, c->n_wg, activity(c), c->hs));
     if (!dev) {
         HIPCK(c, hipMemcpyAsync(words, c->d_pdm_out, out_b, hipMemcpyDeviceToHost, c->hs));
         HIPCK(c, hipStreamSynchronize(c->hs));
@@ -865,6 +925,72 @@ int dspi_realign_streams(dspi_ctx *c, uint32_t first, uint32_t count) {
     return (int)count;
 }
 
+// ---- paused streams: devices that receive no packet in a call (include/dspi.h) ----
+int dspi_pause_streams(dspi_ctx *c, uint32_t first, uint32_t count) {
+    if (!c) return DSPI_E_INVAL;
+    if (!snap_range_ok(c, first, count)) return fail(c, DSPI_E_INVAL, "dspi_pause_streams: stream range out of bounds");
+    if (c->active.empty()) c->active.assign(c->n_streams, 1);
+    bool changed = false;
+    for (uint32_t s = first; s < first + count; s++)
+        if (c->active[s]) { c->active[s] = 0; c->n_paused++; changed = true; }
+    if (changed) { c->launch_dirty = true; c->active_dirty = true; c->paused_runs_dirty = true; }      // the lists are rebuilt and the bitmap goes up at the next commit
+    return (int)count;
+}
+
+int dspi_resume_streams(dspi_ctx *c, uint32_t first, uint32_t count, uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    if (flags & ~DSPI_RESUME_AS_IS) return fail(c, DSPI_E_INVAL, "dspi_resume_streams: undefined flag bits");
+    if (!snap_range_ok(c, first, count)) return fail(c, DSPI_E_INVAL, "dspi_resume_streams: stream range out of bounds");
+    // the streams this call resumes lie in [lo, hi]; the others of the range are residents
+    uint32_t lo = 0, hi = 0, n = 0;
+    if (c->n_paused)
+        for (uint32_t s = first; s < first + count; s++)
+            if (!c->active[s]) { if (!n++) lo = s; hi = s; }
+    if (!n) return (int)count;
+    if (c->device != DSPI_DEVICE_NONE && !(flags & DSPI_RESUME_AS_IS)) {
+        // Their rows went on while they stood still: rotate them onto their rows' positions (dspi_snapshot.h snap_row_target_active), run-time
+        // state only, through the records' scratch like dspi_realign_streams — out as it is, back in rotated —, on the context's stream.  The
+        // rule reads the bitmap as it stood BEFORE this call: when pauses or resumes were made since the last dspi_process the device's copy
+        // is brought up to date first (that upload synchronises; otherwise the call only enqueues).
+        HIPCK(c, hipSetDevice(c->device));
+        int rc = pdm_state(c);
+        if (rc) return rc;
+        const size_t rec = snap_state_bytes(c->flavor, 1);
+        if ((rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)snap_chunk_rows(c) * (uint32_t)c->sm.row * rec))) return rc;
+        if ((rc = ensure(c, c->d_snap_shift, c->d_snap_shift_cap, (size_t)c->n_streams * 8))) return rc;
+        if ((rc = upload_activity(c))) return rc;
+        // Only rows that hold a stream to resume go through the scratch: a piece = [s, e) inside one scratch chunk, from the first such
+        // stream to the end of the last such row of the chunk (cut at hi); rows between the pieces are not touched.
+        const uint32_t row = (uint32_t)c->sm.row;
+        for (uint32_t s = lo, end = hi + 1; s < end;) {
+            while (s < end && c->active[s]) s++;
+            if (s >= end) break;
+            const uint32_t ce = snap_chunk_end(c, s, end);
+            uint32_t e = s + 1;
+            for (uint32_t t = s; t < ce; t++) if (!c->active[t]) e = std::min(ce, (t / row + 1) * row);
+            HIPCK(c, launch_snapshot(c->flavor, false, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, s, e - s, c->hs));
+            HIPCK(c, launch_snapshot_resume(c->flavor, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, s, e - s, c->n_streams, c->d_active, lo, hi - lo + 1,
+                                            c->d_snap_shift, c->hs));
+            s = e;
+        }
+    }
+    for (uint32_t s = lo; s <= hi; s++)
+        if (!c->active[s]) { c->active[s] = 1; c->n_paused--; }
+    c->launch_dirty = true; c->active_dirty = true; c->paused_runs_dirty = true;
+    return (int)count;
+}
+
+int dspi_streams_paused(const dspi_ctx *c, uint32_t first, uint32_t count, uint8_t *paused) {
+    if (!c || !snap_range_ok(c, first, count)) return DSPI_E_INVAL;
+    int n = 0;
+    for (uint32_t k = 0; k < count; k++) {
+        const bool p = c->n_paused && !c->active[(size_t)first + k];
+        if (paused) paused[k] = p ? 1 : 0;
+        n += p ? 1 : 0;
+    }
+    return n;
+}
+
 int dspi_debug_stream_positions(dspi_ctx *c, uint32_t first, uint32_t count, uint32_t *widx, uint32_t *ring_pos) {
     if (!c || !widx || !ring_pos) return DSPI_E_INVAL;
     if (!snap_range_ok(c, first, count)) return fail(c, DSPI_E_INVAL, "dspi_debug_stream_positions: stream range out of bounds");
@@ -997,7 +1123,8 @@ static int launch_paths(dspi_ctx *c, KArgs &a, uint32_t r0, uint32_t r1) {
 }
 
 // ... of a call (a: its arguments, a.pairs the caller's words).  Two-pass S/PDIF: L.two_pass_rows rows at a time into the scratch of pair
-// words, then the subframe encoder from there into a.pairs
+// words, then the subframe encoder from there into a.pairs.  Paused streams: the chain leaves their words in the scratch stale, and the
+// ENCODER SKIPS them (SpdifRates::active) — the scratch is not zeroed —, so that in the caller's device buffer their subframes stay unwritten
 static int launch_rows(dspi_ctx *c, KArgs a, const CallLayout &L, uint32_t r0, uint32_t r1) {
     if (!L.spdif_two_pass) return launch_paths(c, a, r0, r1);
     char *const subframes = reinterpret_cast<char *>(a.pairs);
@@ -1009,7 +1136,7 @@ static int launch_rows(dspi_ctx *c, KArgs a, const CallLayout &L, uint32_t r0, u
         int rc = launch_paths(c, a, q0, q1);
         if (rc) return rc;
         hipError_t e = launch_spdif(false, c->d_spdif_words, reinterpret_cast<uint32_t *>(subframes + s0 * L.pairs.per), (uint32_t)(s1 - s0), (uint32_t)c->sm.n_pairs,
-                                    (uint32_t)L.frames, row, q1 - q0, c->spdif_pos, 0u, SpdifRates{c->d_images, c->d_stream_image, (uint32_t)s0}, c->hs);
+                                    (uint32_t)L.frames, row, q1 - q0, c->spdif_pos, 0u, SpdifRates{c->d_images, c->d_stream_image, (uint32_t)s0, activity(c)}, c->hs);
         if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string("spdif encoder launch: ") + hipGetErrorString(e));
     }
     return 0;
@@ -1070,6 +1197,11 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     if (flags & DSPI_OUT_ENABLED_ONLY) {      // (silent parts stay unwritten by the kernels: the caller finds zeros, the firmware's own fill)
         if (out->pairs) memset(h + L.pairs.off, 0, L.pairs.bytes);
         if (out->sub) memset(h + L.sub.off, 0, L.sub.bytes);
+    }
+    if (c->n_paused) {      // (paused streams' regions stay unwritten likewise: zeros, there only)
+        if (out->pairs && !(flags & DSPI_OUT_ENABLED_ONLY)) for_paused_regions(c, L.pairs, [&](size_t at, size_t n) { memset(h + L.pairs.off + at, 0, n); });
+        if (out->sub && !(flags & DSPI_OUT_ENABLED_ONLY)) for_paused_regions(c, L.sub, [&](size_t at, size_t n) { memset(h + L.sub.off + at, 0, n); });
+        if (out->peaks) for_paused_regions(c, L.peaks, [&](size_t at, size_t n) { memset(h + L.peaks.off + at, 0, n); });
     }
     if ((L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) || (rc = launch_rows(c, a, L, 0, c->n_wg)) ||
         (clip_out && (rc = gather_clip(c, reinterpret_cast<uint16_t *>(d + L.clip.off))))) return rc;
@@ -1142,6 +1274,15 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     if (flags & DSPI_OUT_ENABLED_ONLY) {
         if (a.pairs) HIPCK(c, hipMemsetAsync(a.pairs, 0, L.pairs.bytes, c->hs));
         if (a.sub) HIPCK(c, hipMemsetAsync(a.sub, 0, L.sub.bytes, c->hs));
+    }
+    // ... and the same for the regions of paused streams, which no kernel writes (peaks too): those regions only
+    if (c->n_paused) {
+        hipError_t me = hipSuccess;
+        auto clear = [&](void *base) { return [&, base](size_t at, size_t n) { if (me == hipSuccess) me = hipMemsetAsync(static_cast<char *>(base) + at, 0, n, c->hs); }; };
+        if (a.pairs && !(flags & DSPI_OUT_ENABLED_ONLY)) for_paused_regions(c, L.pairs, clear(a.pairs));
+        if (a.sub && !(flags & DSPI_OUT_ENABLED_ONLY)) for_paused_regions(c, L.sub, clear(a.sub));
+        if (a.peaks) for_paused_regions(c, L.peaks, clear(a.peaks));
+        HIPCK(c, me);
     }
     if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) return rc;
     const uint32_t n_chunks = L.n_chunks, row = (uint32_t)c->sm.row;

@@ -41,8 +41,9 @@ hipError_t launch_state_ops(int flavor, const WgItem *items, uint32_t n_items, c
                             uint32_t *ring, uint32_t n_streams, hipStream_t stream);
 // (re)build the value tiles of the listed rows from the images of their streams
 // all_differ: development switch, every band is treated as different between the row's streams (the worst case, for timing)
+// active: the context's activity bitmap or null = every stream: "which bands differ" is decided among the row's active streams
 hipError_t launch_pv_build(const DevImage *img, const uint32_t *stream_image, const uint32_t *rows, uint32_t n_rows, float *vals, uint32_t n_streams, bool all_differ,
-                           hipStream_t stream);
+                           const uint32_t *active, hipStream_t stream);
 hipError_t launch_state_init(int flavor, uint32_t *state, uint32_t n_wg, hipStream_t stream);
 // debug: taps [kBands+1][n] after every band of EQ channel `ch` of *img (float flavour), other [kBands][n] = the other
 // contract's one-step result from the same input and state
@@ -50,14 +51,17 @@ hipError_t launch_eq_taps(bool fma, const DevImage *img, int ch, const float *x,
 
 // ---- PDM sub output (dspi_pdm.hip): per-stream state [n_wg][kPdmStateWords][row]: err err2 x1 x2 y1 y2 err_acc rng fade_in_pos
 constexpr int kPdmStateWords = 9;
+// active: the context's activity bitmap (one bit per stream) or null = every stream; a paused stream's state and words are not touched
 hipError_t launch_pdm(bool tiled, uint32_t *state, const int32_t *sub, uint32_t *words, uint32_t n_streams, uint32_t n_frames, uint32_t row,
-                      uint32_t n_wg, hipStream_t stream);
+                      uint32_t n_wg, const uint32_t *active, hipStream_t stream);
 hipError_t launch_pdm_reset(uint32_t *state, uint32_t n_streams, uint32_t row, uint32_t n_wg, int32_t only_stream, int init, hipStream_t stream);
 
 // ---- S/PDIF subframe encoder (dspi_spdif.hip)
 // The sample-rate byte of the channel status (audio_spdif.c:250-256) is a property of the DEVICE: streams of one context may run at
 // different rates.  stream_image == nullptr: every stream at `fs`; else stream s reads img[stream_image[stream0 + s]].fs_hz.
-struct SpdifRates { const DevImage *img; const uint32_t *stream_image; uint32_t stream0; };
+// active (dspi_process's two-pass S/PDIF only, stream-major): the context's activity bitmap, indexed like stream_image; streams whose bit is
+// clear are skipped — nothing of theirs is read or written.  null: every stream (dspi_spdif_encode is stateless per stream and knows no pauses).
+struct SpdifRates { const DevImage *img; const uint32_t *stream_image; uint32_t stream0; const uint32_t *active = nullptr; };
 hipError_t launch_spdif(bool tiled, const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames, uint32_t row,
                         uint32_t n_wg, uint32_t block_pos, uint32_t fs, const SpdifRates &rates, hipStream_t stream);
 // I2S slots (audio_i2s_multi.c:217-226): words << 8 for the pairs in pair_mask; same layouts as the pair words themselves
@@ -76,5 +80,10 @@ hipError_t launch_snapshot(int flavor, bool import, uint32_t *state, uint32_t *d
 // 8-byte aligned device scratch), then the import rotated by them.  n_streams: the context's, for the rows' resident neighbours.
 hipError_t launch_snapshot_realign(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count,
                                    uint32_t n_streams, uint32_t *shift, hipStream_t stream);
+// dspi_resume_streams: the same two launches under the activity-aware rule (dspi_snapshot.h snap_row_target_active).  `active`: the bitmap
+// before the call, one bit per stream; [r_first, r_first + r_count): the call's range, of which `records` hold the rows' chunk [first,
+// first + count); streams the call does not resume are written back unrotated.
+hipError_t launch_snapshot_resume(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count,
+                                  uint32_t n_streams, const uint32_t *active, uint32_t r_first, uint32_t r_count, uint32_t *shift, hipStream_t stream);
 
 }  // namespace dspi

@@ -1708,7 +1708,11 @@ __global__ void pv_clear_kernel(const uint32_t *rows, float *vals, uint32_t all_
     uint32_t *mask = reinterpret_cast<uint32_t *>(vals + (size_t)rows[blockIdx.x] * kPvTileFloats + kPvMaskWord);
     if (threadIdx.x < 4) mask[threadIdx.x] = all_differ ? 0xffffffffu : 0u;
 }
-__global__ __launch_bounds__(256) void pv_build_kernel(const DevImage *img, const uint32_t *stream_image, const uint32_t *rows, float *vals, uint32_t n_streams) {
+// active (or null = every stream): the context's activity bitmap.  A band's mask bit says that its words differ among the row's ACTIVE
+// streams: the reference is the row's first active stream, and a paused column (whose image may be of another structure altogether: the
+// plan made the row from its active streams) never sets a bit.  Its values are stored all the same; no launch reads them.
+__global__ __launch_bounds__(256) void pv_build_kernel(const DevImage *img, const uint32_t *stream_image, const uint32_t *rows, float *vals, uint32_t n_streams,
+                                                       const uint32_t *active) {
     constexpr int kWords = kPvBandSlots * 6 + PV_COUNT;
     const uint32_t wg = rows[blockIdx.y];
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;             // word * 128 + column: a wave writes columns of one word
@@ -1726,7 +1730,14 @@ __global__ __launch_bounds__(256) void pv_build_kernel(const DevImage *img, cons
             const uint32_t bits = coef(im);
             v = __builtin_bit_cast(float, bits);
             // a band whose coefficient words are the same in every stream of the row can run on the image's scalars (value-tile mask)
-            if (bits != coef(img + stream_image[wg * 128u])) atomicOr(reinterpret_cast<uint32_t *>(tile + kPvMaskWord) + (slot >> 5), 1u << (slot & 31u));
+            uint32_t ref = wg * 128u;      // the row's first stream that takes part (a per-lane-value row has one)
+            bool mine = true;
+            if (active) {
+                const uint32_t end = min(wg * 128u + 128u, n_streams);
+                while (ref < end && !((active[ref >> 5] >> (ref & 31u)) & 1u)) ref++;
+                mine = ref < end && ((active[stream >> 5] >> (stream & 31u)) & 1u);
+            }
+            if (mine && bits != coef(img + stream_image[ref])) atomicOr(reinterpret_cast<uint32_t *>(tile + kPvMaskWord) + (slot >> 5), 1u << (slot & 31u));
         }
         dst = ((size_t)(slot * 3u + (k >> 1)) * kLanes + (col >> 1)) * 4u + (k & 1u) * 2u + (col & 1u);
     } else {
@@ -1748,11 +1759,11 @@ __global__ __launch_bounds__(256) void pv_build_kernel(const DevImage *img, cons
 }
 
 hipError_t launch_pv_build(const DevImage *img, const uint32_t *stream_image, const uint32_t *rows, uint32_t n_rows, float *vals, uint32_t n_streams, bool all_differ,
-                           hipStream_t stream) {
+                           const uint32_t *active, hipStream_t stream) {
     constexpr int kWords = kPvBandSlots * 6 + PV_COUNT;
     if (n_rows == 0) return hipSuccess;
     hipLaunchKernelGGL(pv_clear_kernel, dim3(n_rows), dim3(64), 0, stream, rows, vals, all_differ ? 1u : 0u);
-    hipLaunchKernelGGL(pv_build_kernel, dim3((kWords * 128 + 255) / 256, n_rows), dim3(256), 0, stream, img, stream_image, rows, vals, n_streams);
+    hipLaunchKernelGGL(pv_build_kernel, dim3((kWords * 128 + 255) / 256, n_rows), dim3(256), 0, stream, img, stream_image, rows, vals, n_streams, active);
     return hipGetLastError();
 }
 

@@ -11,6 +11,9 @@
 // streams).  A workgroup is one tile row of the context (128 float / 64 Q28 streams): with the tiled layouts every
 // access is one coalesced row ([tile][frame][R] in, [tile][frame][8][R] out).  VALU-issue bound: ~2 800 integer
 // instructions per sample; 32 bytes out per 4 bytes in.
+//
+// Paused streams (dspi_pause_streams): a lane whose stream's bit in the activity bitmap is clear returns before it reads anything — its
+// modulator state stays frozen, its `sub` is not read and its `words` are not written (both layouts).  No bitmap (null): every stream runs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -35,10 +38,11 @@ constexpr int kPdmThreads = 256;
 
 template <bool TILED>
 __global__ __launch_bounds__(kPdmThreads) void pdm_kernel(uint32_t *state, const int32_t *sub, uint32_t *words, uint32_t n_streams, uint32_t n_frames,
-                                                           uint32_t row) {
+                                                           uint32_t row, const uint32_t *active) {
     const uint32_t wg = blockIdx.x * (kPdmThreads / row) + threadIdx.x / row, col = threadIdx.x % row;
     const uint32_t stream = wg * row + col;
     if (stream >= n_streams) return;
+    if (active && !((active[stream >> 5] >> (stream & 31u)) & 1u)) return;
     uint32_t *gs = state + (size_t)wg * kPdmStateWords * row + col;
     int32_t err = (int32_t)gs[0 * row], err2 = (int32_t)gs[1 * row];
     int32_t x1 = (int32_t)gs[2 * row], x2 = (int32_t)gs[3 * row], y1 = (int32_t)gs[4 * row], y2 = (int32_t)gs[5 * row], err_acc = (int32_t)gs[6 * row];
@@ -123,10 +127,10 @@ __global__ void pdm_reset_kernel(uint32_t *state, uint32_t n_streams, uint32_t r
 }  // namespace
 
 hipError_t launch_pdm(bool tiled, uint32_t *state, const int32_t *sub, uint32_t *words, uint32_t n_streams, uint32_t n_frames, uint32_t row,
-                      uint32_t n_wg, hipStream_t stream) {
+                      uint32_t n_wg, const uint32_t *active, hipStream_t stream) {
     const uint32_t per = kPdmThreads / row, blocks = (n_wg + per - 1) / per;
-    if (tiled) hipLaunchKernelGGL(pdm_kernel<true>, dim3(blocks), dim3(kPdmThreads), 0, stream, state, sub, words, n_streams, n_frames, row);
-    else hipLaunchKernelGGL(pdm_kernel<false>, dim3(blocks), dim3(kPdmThreads), 0, stream, state, sub, words, n_streams, n_frames, row);
+    if (tiled) hipLaunchKernelGGL(pdm_kernel<true>, dim3(blocks), dim3(kPdmThreads), 0, stream, state, sub, words, n_streams, n_frames, row, active);
+    else hipLaunchKernelGGL(pdm_kernel<false>, dim3(blocks), dim3(kPdmThreads), 0, stream, state, sub, words, n_streams, n_frames, row, active);
     return hipGetLastError();
 }
 

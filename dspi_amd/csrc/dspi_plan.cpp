@@ -58,10 +58,12 @@ uint32_t skew_pair_limit(int cls, uint32_t cus, F32Layout layout) {
     return (cls == 1 ? 8u : 4u) * cus;
 }
 
-std::vector<std::vector<WgItem>> image_rows(int flavor, uint32_t row, const int32_t *stream_image, uint32_t n_streams, size_t n_images) {
+std::vector<std::vector<WgItem>> image_rows(int flavor, uint32_t row, const int32_t *stream_image, uint32_t n_streams, size_t n_images,
+                                            const uint8_t *active) {
     const bool two = flavor != 0;                 // float flavour: two streams per lane
     std::vector<std::vector<WgItem>> v(n_images);
     for (uint32_t s = 0; s < n_streams; s++) {
+        if (active && !active[s]) continue;
         auto &l = v[(size_t)stream_image[s]];
         const uint32_t wg = s / row, col = s % row;
         if (l.empty() || l.back().wg != wg) l.push_back(WgItem{wg, 0u, 0ull, 0ull});
@@ -95,14 +97,14 @@ std::vector<WgItem> &list(LaunchPlan &p, Path path) { return p.items[(int)path];
 uint32_t tag(uint32_t image, uint32_t part) { return image | (part << kSkPartShift); }
 
 // Q28: rows with one image keep the workgroup-uniform path; rows with several run every lane on its own image, one item per row
-void q28_lists(const PlanInput &in, const ImageRows &rows_of, LaunchPlan &plan) {
+void q28_lists(const std::vector<uint32_t> &refs, const ImageRows &rows_of, LaunchPlan &plan) {
     std::map<uint32_t, std::pair<uint64_t, int>> rows;      // row -> (lanes, images)
     for (size_t i = 0; i < rows_of.size(); i++)
-        if (in.refs[i] > 0)
+        if (refs[i] > 0)
             for (const WgItem &it : rows_of[i]) { auto &r = rows[it.wg]; r.first |= it.mask; r.second++; }
     auto &uniform = list(plan, Path::Q28Uniform);
     for (size_t i = 0; i < rows_of.size(); i++)
-        if (in.refs[i] > 0)
+        if (refs[i] > 0)
             for (WgItem it : rows_of[i])
                 if (rows[it.wg].second == 1) { it.image = (uint32_t)i; uniform.push_back(it); }
     sort_by_row(uniform);
@@ -139,9 +141,9 @@ Rows per_lane_value_rows(const PlanInput &in, const ImageRows &rows_of, std::vec
 // Step 2 (float): lanes whose two streams share an image -> the packed kernel, one item per (row, image); per-lane-value rows -> one
 // item per row, WgItem::image = the row's first image (read for the structure); every other lane -> the one-stream kernel, both lane
 // components in one launch (WgItem::image = component), all images of a row in one item.  Leveller on / off: separate paths.
-void shared_lists(const PlanInput &in, const ImageRows &rows_of, const Rows &rows, LaunchPlan &plan) {
+void shared_lists(const PlanInput &in, const std::vector<uint32_t> &refs, const ImageRows &rows_of, const Rows &rows, LaunchPlan &plan) {
     for (size_t i = 0; i < rows_of.size(); i++) {
-        if (in.refs[i] == 0) continue;
+        if (refs[i] == 0) continue;
         auto &dst = list(plan, leveller(in, i) ? Path::F32PackedLev : Path::F32Packed);
         for (const WgItem &it : rows_of[i]) {
             const uint64_t both = it.mask & it.mask1;
@@ -162,7 +164,7 @@ void shared_lists(const PlanInput &in, const ImageRows &rows_of, const Rows &row
         std::map<uint32_t, uint64_t> lanes;      // row -> lanes whose stream `comp` alone is on an image
         auto only = [&](uint64_t m0, uint64_t m1) { return comp ? (m1 & ~m0) : (m0 & ~m1); };
         for (size_t i = 0; i < rows_of.size(); i++)
-            if (in.refs[i] > 0)
+            if (refs[i] > 0)
                 for (const WgItem &it : rows_of[i])      // (a per-lane-value row: only its half-filled lanes come here, below)
                     if (!plan.row_pv[it.wg] && only(it.mask, it.mask1)) lanes[it.wg] |= only(it.mask, it.mask1);
         for (const auto &r : rows)
@@ -173,9 +175,10 @@ void shared_lists(const PlanInput &in, const ImageRows &rows_of, const Rows &row
 }
 
 // The packed kernel leaves the last stream of an odd stream count to the one-stream kernel; the latency layout serves such a lane
-// itself (its stores check the second stream) — a context of ONE stream is this case
+// itself (its stores check the second stream) — a context of ONE stream is this case.  A paused last stream is in no list: no odd lane
+// (and its image, which may be one that no active stream uses, is not read).
 OddLane odd_lane(const PlanInput &in, const std::vector<uint8_t> &row_pv) {
-    if (!(in.n_streams & 1u)) return OddLane{0, 0, 0, 0};
+    if (!(in.n_streams & 1u) || (!in.active.empty() && !in.active[in.n_streams - 1u])) return OddLane{0, 0, 0, 0};
     const uint32_t last = in.n_streams - 1u, row = last / in.row, image = (uint32_t)in.stream_image[last];
     return OddLane{row, (last % in.row) / 2u, image, row_pv[row] ? 0 : skew_class(in.sig[image])};
 }
@@ -187,13 +190,13 @@ OddLane odd_lane(const PlanInput &in, const std::vector<uint8_t> &row_pv) {
 // image, for the structure); several structures -> one item per image, the other images' slots inactive (the kernels store per half).
 // The limit counts lanes, a lane of the last kind once per image.  DSPI_SKEW_PAIRED=0 keeps to the last form (development, tests).
 // Returns whether it placed the lanes.
-bool all_small_rule(const PlanInput &in, const ImageRows &rows_of, LaunchPlan &plan) {
+bool all_small_rule(const PlanInput &in, const std::vector<uint32_t> &refs, const ImageRows &rows_of, LaunchPlan &plan) {
     auto limit = [&](int cls) { return (uint64_t)skew_pair_limit(cls, in.cus, in.layout); };
     uint64_t slots[4] = {0, 0, 0, 0};
     {   // a first bound: the lanes in use, whatever their images
         std::map<uint32_t, uint64_t> used[4];
         for (size_t i = 0; i < rows_of.size(); i++)
-            if (in.refs[i] > 0)
+            if (refs[i] > 0)
                 for (const WgItem &it : rows_of[i]) used[skew_class(in.sig[i])][it.wg] |= it.mask | it.mask1;
         for (int cls = 1; cls <= 3; cls++) for (const auto &u : used[cls]) slots[cls] += (uint64_t)__builtin_popcountll(u.second);
     }
@@ -203,7 +206,7 @@ bool all_small_rule(const PlanInput &in, const ImageRows &rows_of, LaunchPlan &p
     struct Cell { std::vector<Slot> v; bool same = false; };
     std::map<std::pair<uint32_t, uint32_t>, Cell> cells[4];      // [class]: (row, part) -> images
     for (size_t i = 0; i < rows_of.size(); i++) {
-        if (in.refs[i] == 0) continue;
+        if (refs[i] == 0) continue;
         const int cls = skew_class(in.sig[i]);
         const uint32_t ppw = pairs_per_wg(cls);
         for (const WgItem &it : rows_of[i])
@@ -285,11 +288,20 @@ void odd_last_stream(const OddLane &odd, LaunchPlan &plan) {
 LaunchPlan plan_launches(const PlanInput &in) {
     LaunchPlan plan;
     plan.row_pv.assign((in.n_streams + in.row - 1) / in.row, 0);
-    const ImageRows rows_of = image_rows(in.flavor, in.row, in.stream_image.data(), in.n_streams, in.refs.size());
-    if (!in.flavor) q28_lists(in, rows_of, plan);
+    // paused streams (PlanInput::active) are left out here, once: every list, rule and lane count below sees the active streams alone,
+    // and an image counts the active streams on it
+    const bool some_paused = !in.active.empty();
+    const ImageRows rows_of = image_rows(in.flavor, in.row, in.stream_image.data(), in.n_streams, in.refs.size(), some_paused ? in.active.data() : nullptr);
+    std::vector<uint32_t> active_refs;
+    if (some_paused) {
+        active_refs.assign(in.refs.size(), 0u);
+        for (uint32_t s = 0; s < in.n_streams; s++) if (in.active[s]) active_refs[(size_t)in.stream_image[s]]++;
+    }
+    const std::vector<uint32_t> &refs = some_paused ? active_refs : in.refs;
+    if (!in.flavor) q28_lists(refs, rows_of, plan);
     else {
         const Rows rows = per_lane_value_rows(in, rows_of, plan.row_pv);
-        shared_lists(in, rows_of, rows, plan);
+        shared_lists(in, refs, rows_of, rows, plan);
         // the size rule's lanes per class: the shared-preset lanes, and the odd last stream
         const OddLane odd = odd_lane(in, plan.row_pv);
         uint64_t pairs[4] = {0, 0, 0, 0};
@@ -297,7 +309,7 @@ LaunchPlan plan_launches(const PlanInput &in) {
             for (const WgItem &it : list(plan, p)) pairs[skew_class(in.sig[it.image])] += (uint64_t)__builtin_popcountll(it.mask);
         if (odd.cls) pairs[odd.cls]++;
         bool take[4] = {false, false, false, false};
-        if (!all_small_rule(in, rows_of, plan))
+        if (!all_small_rule(in, refs, rows_of, plan))
             for (int cls = 1; cls <= 3; cls++) take[cls] = pairs[cls] > 0 && pairs[cls] <= skew_pair_limit(cls, in.cus, in.layout);
         size_rule(in, plan, take);
         if (odd.cls && take[odd.cls]) odd_last_stream(odd, plan);

@@ -78,14 +78,18 @@ enum class F32Layout : uint8_t { Auto, Skew, Packed };      // DSPI_F32_LAYOUT: 
 uint32_t skew_pair_limit(int cls, uint32_t cus, F32Layout layout);
 
 // per image, the rows that hold its streams in row order: WgItem{row, 0, lanes of the first stream, lanes of the second} (Q28:
-// one stream per lane, mask1 = 0).  The state mutations run on these (dspi_capi.cpp commit_params).
-std::vector<std::vector<WgItem>> image_rows(int flavor, uint32_t row, const int32_t *stream_image, uint32_t n_streams, size_t n_images);
+// one stream per lane, mask1 = 0).  The state mutations run on these (dspi_capi.cpp commit_params).  `active` (one byte per stream, or
+// null: every stream) leaves the streams out whose byte is 0: the launch plan's own rows (plan_launches), never the state mutations'.
+std::vector<std::vector<WgItem>> image_rows(int flavor, uint32_t row, const int32_t *stream_image, uint32_t n_streams, size_t n_images,
+                                            const uint8_t *active = nullptr);
 
 struct PlanInput {
     int flavor = 1;                          // 0 = Q28, else float
     uint32_t n_streams = 0, row = 128;       // row: streams per workgroup (StateMap::row)
     std::vector<int32_t> stream_image;       // [n_streams]
     std::vector<uint32_t> refs;              // [image] streams that use it
+    std::vector<uint8_t> active;             // [n_streams] 0: the stream is paused (dspi_pause_streams) and takes no part in a launch; empty: none is.
+                                             // The plan is built from the active streams alone — rows, refs, every rule's lane counts
     std::vector<ImageSig> sig;               // [image] float only (ImageSig::flags: IF_LEVELLER_ON picks the leveller-on paths)
     std::vector<BandHash> bands;             // [image] float only
     uint32_t cus = 256;                      // compute units of the device

@@ -71,6 +71,20 @@ constexpr SnapTarget snap_row_target(uint32_t row, uint32_t row_streams, uint32_
     if (end < r1) return SnapTarget{(uint32_t)end, true};             // the range ends inside the row
     return SnapTarget{(uint32_t)r0, false};                           // the range covers what the context has of the row
 }
+// ... for dspi_resume_streams (include/dspi.h), which realigns in place the streams of [first, first + count) that were paused: `active` is
+// the context's activity bitmap BEFORE the call (bit s % 32 of word s / 32: stream s takes part in dspi_process).  The row's target is its
+// lowest-numbered stream below n_streams that is active — in the range or not: a stream of the range that was active is a resident and is
+// not moved —, its positions read from the state array; a row without one takes the first stream of the range that lies in it (every
+// stream of the range there is then one this call resumes), from its record.  With every stream outside the range active and every
+// stream inside paused this is snap_row_target.
+constexpr bool snap_stream_active(const uint32_t *active, uint64_t s) { return (active[s >> 5] >> (s & 31u)) & 1u; }
+constexpr SnapTarget snap_row_target_active(uint32_t row, uint32_t row_streams, uint32_t n_streams, uint32_t first, uint32_t count, const uint32_t *active) {
+    const uint64_t r0 = (uint64_t)row * row_streams, r1 = r0 + row_streams < n_streams ? r0 + row_streams : n_streams;
+    for (uint64_t s = r0; s < r1; s++) if (snap_stream_active(active, s)) return SnapTarget{(uint32_t)s, true};
+    const uint64_t lo = r0 > first ? r0 : first, end = (uint64_t)first + count, hi = end < r1 ? end : r1;
+    for (uint64_t s = lo; s < hi; s++) if (!snap_stream_active(active, s)) return SnapTarget{(uint32_t)s, false};
+    return SnapTarget{(uint32_t)lo, false};      // (the call resumes nobody in this row: never read)
+}
 // how far a stream at position `from` is rotated to stand at `to` (both masked; len a power of two)
 constexpr uint32_t snap_shift(uint32_t from, uint32_t to, uint32_t len) { return (to - from) & (len - 1u); }
 // the record position whose word lands at position p of a line or ring of `len` words rotated by d: line[(q + d) mod len] = record[q]

@@ -187,6 +187,31 @@ __global__ __launch_bounds__(ROW) void snapshot_targets_kernel(const uint32_t *s
     shift[s - first] = make_uint2(snap_shift(r[sm.widx] & (kLine - 1u), w_t, kLine), snap_shift(r[sm.ring_pos] & (kRing - 1u), r_t, kRing));
 }
 
+// ... for dspi_resume_streams: the activity-aware rule (dspi_snapshot.h snap_row_target_active) on the bitmap as it stood before the call.
+// Only the streams the call resumes — in the call's range [r_first, r_first + r_count) and paused — move; every other stream of the
+// records [first, first + count) (a chunk of the range's rows) gets the shift (0, 0) and is written back as it is.
+template <uint32_t ROW>
+__global__ __launch_bounds__(ROW) void snapshot_targets_active_kernel(const uint32_t *state, const uint32_t *rec, uint32_t record_words, uint32_t state_off, uint32_t first,
+                                                                      uint32_t count, uint32_t n_streams, uint32_t row0, const uint32_t *active, uint32_t r_first,
+                                                                      uint32_t r_count, uint2 *shift) {
+    constexpr StateMap sm = make_state_map(ROW == 128 ? 1 : 0);
+    constexpr uint32_t kLine = (uint32_t)sm.max_delay, kRing = (uint32_t)kRingLen;
+    const uint32_t row = row0 + blockIdx.x;
+    const uint64_t s = (uint64_t)row * ROW + threadIdx.x;
+    if (s < first || s >= (uint64_t)first + count) return;
+    uint2 d = make_uint2(0u, 0u);
+    if (s >= r_first && s < (uint64_t)r_first + r_count && !snap_stream_active(active, s)) {
+        const SnapTarget t = snap_row_target_active(row, ROW, n_streams, r_first, r_count, active);
+        // (a target from the records lies in this chunk: chunks hold the range's rows whole)
+        const uint32_t *tp = t.resident ? state + (size_t)row * sm.n_slots * ROW + (t.stream - row * ROW) : rec + (size_t)(t.stream - first) * record_words + state_off;
+        const size_t ts = t.resident ? ROW : 1;
+        const uint32_t w_t = tp[(size_t)sm.widx * ts] & (kLine - 1u), r_t = tp[(size_t)sm.ring_pos * ts] & (kRing - 1u);
+        const uint32_t *r = rec + (size_t)(s - first) * record_words + state_off;
+        d = make_uint2(snap_shift(r[sm.widx] & (kLine - 1u), w_t, kLine), snap_shift(r[sm.ring_pos] & (kRing - 1u), r_t, kRing));
+    }
+    shift[s - first] = d;
+}
+
 struct SnapGrid { dim3 grid; uint32_t rows; };
 SnapGrid snap_kargs(SnapKArgs &a, int flavor, bool import, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count) {
     const SnapLayout l = make_snap_layout(flavor);
@@ -233,6 +258,25 @@ hipError_t launch_snapshot_realign(int flavor, uint32_t *state, uint32_t *dlines
         hipLaunchKernelGGL((snapshot_kernel<128, true, true>), g.grid, dim3(kSnapThreads), 0, stream, a);
     } else {
         hipLaunchKernelGGL((snapshot_targets_kernel<64>), dim3(g.rows), dim3(64), 0, stream, state, records, a.record_words, a.off[SEC_STATE], first, count, n_streams, a.row0, sh);
+        hipLaunchKernelGGL((snapshot_kernel<64, true, true>), g.grid, dim3(kSnapThreads), 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_snapshot_resume(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count,
+                                  uint32_t n_streams, const uint32_t *active, uint32_t r_first, uint32_t r_count, uint32_t *shift, hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    SnapRealignArgs a{};
+    const SnapGrid g = snap_kargs(a, flavor, true, state, dlines, ring, pdm, records, first, count);
+    a.shift = reinterpret_cast<const uint2 *>(shift);
+    uint2 *const sh = reinterpret_cast<uint2 *>(shift);
+    if (flavor) {
+        hipLaunchKernelGGL((snapshot_targets_active_kernel<128>), dim3(g.rows), dim3(128), 0, stream, state, records, a.record_words, a.off[SEC_STATE], first, count, n_streams, a.row0,
+                           active, r_first, r_count, sh);
+        hipLaunchKernelGGL((snapshot_kernel<128, true, true>), g.grid, dim3(kSnapThreads), 0, stream, a);
+    } else {
+        hipLaunchKernelGGL((snapshot_targets_active_kernel<64>), dim3(g.rows), dim3(64), 0, stream, state, records, a.record_words, a.off[SEC_STATE], first, count, n_streams, a.row0,
+                           active, r_first, r_count, sh);
         hipLaunchKernelGGL((snapshot_kernel<64, true, true>), g.grid, dim3(kSnapThreads), 0, stream, a);
     }
     return hipGetLastError();

@@ -64,6 +64,10 @@ __global__ __launch_bounds__(256) void spdif_kernel_frames(const int32_t *pairs,
                                                           uint32_t status_lo, uint32_t status_hi, SpdifRates rates, uint32_t n_pairs) {
     const uint64_t idx = (uint64_t)blockIdx.x * 256u + threadIdx.x;      // (stream * n_pairs + pair) * n_frames + frame
     if (idx >= total) return;
+    if (rates.active) {      // dspi_process in two passes: a paused stream's words in the scratch are stale, and its subframes are not the call's to write
+        const uint32_t s = rates.stream0 + (uint32_t)(idx / ((uint64_t)n_pairs * n_frames));
+        if (!((rates.active[s >> 5] >> (s & 31u)) & 1u)) return;
+    }
     if (rates.stream_image) status_lo = spdif_status_lo(rates.img[rates.stream_image[rates.stream0 + (uint32_t)(idx / ((uint64_t)n_pairs * n_frames))]].fs_hz);
     const uint32_t f = (uint32_t)(idx % n_frames);
     const uint32_t pos = (block_pos + f) % 192u;
@@ -81,6 +85,10 @@ __global__ __launch_bounds__(256) void spdif_kernel_frames2(const int32_t *pairs
                                                            uint32_t status_lo, uint32_t status_hi, SpdifRates rates, uint32_t n_pairs) {
     const uint64_t idx = (uint64_t)blockIdx.x * 256u + threadIdx.x;      // (stream * n_pairs + pair) * (n_frames / 2) + frame pair
     if (idx >= total2) return;
+    if (rates.active) {      // dspi_process in two passes: a paused stream's words in the scratch are stale, and its subframes are not the call's to write
+        const uint32_t s = rates.stream0 + (uint32_t)(idx / ((uint64_t)n_pairs * half_frames));
+        if (!((rates.active[s >> 5] >> (s & 31u)) & 1u)) return;
+    }
     if (rates.stream_image) status_lo = spdif_status_lo(rates.img[rates.stream_image[rates.stream0 + (uint32_t)(idx / ((uint64_t)n_pairs * half_frames))]].fs_hz);
     const uint32_t f = (uint32_t)(idx % half_frames) * 2u;
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));

@@ -17,6 +17,7 @@ LIB_PATH = Path(os.environ.get("DSPI_LIB") or (Path(__file__).resolve().parent /
 ALL = -1
 MEM_DEVICE = 0x1
 SNAP_REALIGN = 0x100
+RESUME_AS_IS = 0x1
 OUT_TILED = 0x2
 OUT_ENABLED_ONLY = 0x4
 OUT_I2S_SLOTS = 0x8
@@ -108,6 +109,10 @@ def lib() -> C.CDLL:
     if hasattr(L, "dspi_realign_streams"):      # (ABI 8 + realignment: detected by symbol; with it DSPI_SNAP_REALIGN)
         L.dspi_realign_streams.argtypes = [vp, u32, u32]
         L.dspi_debug_stream_positions.argtypes = [vp, u32, u32, vp, vp]
+    if hasattr(L, "dspi_pause_streams"):      # (ABI 8 + paused streams: detected by symbol; with it DSPI_RESUME_AS_IS)
+        L.dspi_pause_streams.argtypes = [vp, u32, u32]
+        L.dspi_resume_streams.argtypes = [vp, u32, u32, u32]
+        L.dspi_streams_paused.argtypes = [vp, u32, u32, vp]
     _lib = L
     return L
 
@@ -379,6 +384,23 @@ class Dspi:
         w, r = np.zeros(count, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
         self._ck(self.L.dspi_debug_stream_positions(self.h, first, count, w.ctypes.data, r.ctypes.data), "debug_stream_positions")
         return w, r
+
+    # ---- paused streams (include/dspi.h: devices that receive no packet in a call) ----
+    def pause_streams(self, first: int, count: int) -> int:
+        """dspi_pause_streams: streams [first, first + count) sit out every dspi_process from the next one on, their state frozen."""
+        return self._ck(self.L.dspi_pause_streams(self.h, first, count), "pause_streams")
+
+    def resume_streams(self, first: int, count: int, as_is: bool = False) -> int:
+        """dspi_resume_streams: the paused streams of the range take part again, realigned to their rows' write positions (as_is:
+        DSPI_RESUME_AS_IS, they keep their own)."""
+        return self._ck(self.L.dspi_resume_streams(self.h, first, count, RESUME_AS_IS if as_is else 0), "resume_streams")
+
+    def streams_paused(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """dspi_streams_paused: uint8 [count], 1 = paused (default: the whole context)."""
+        count = self.n_streams - first if count is None else count
+        p = np.zeros(count, dtype=np.uint8)
+        self._ck(self.L.dspi_streams_paused(self.h, first, count, p.ctypes.data), "streams_paused")
+        return p
 
     def sync(self):
         self._ck(self.L.dspi_sync(self.h), "sync")

@@ -68,7 +68,8 @@ extern "C" {
                               * context, (additions only: a v6 caller's three-member dspi_out is never read past `peaks`);
                               * 8: dspi_debug_direct_stats, dspi_debug_detmath, the direct path polls a completion word for the call's own audio time (DSPI_DIRECT_SPIN_US, DSPI_DIRECT_POLL);
                               * 8 + snapshots: detect by symbol (dspi_snapshot_sizes, dspi_export_streams, dspi_import_streams; additions only);
-                              * 8 + realignment: detect by symbol (dspi_realign_streams; with it DSPI_SNAP_REALIGN and dspi_debug_stream_positions; additions only) */
+                              * 8 + realignment: detect by symbol (dspi_realign_streams; with it DSPI_SNAP_REALIGN and dspi_debug_stream_positions; additions only);
+                              * 8 + paused streams: detect by symbol (dspi_pause_streams; with it dspi_resume_streams, dspi_streams_paused, DSPI_RESUME_AS_IS; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -301,6 +302,48 @@ int dspi_import_streams(dspi_ctx *ctx, uint32_t first, const dspi_snapshot *snap
  * image or pending operation is touched; a second call on an aligned range changes nothing.  Arguments are validated before anything is
  * written; host-only contexts return DSPI_E_NODEVICE after that.  Returns count or a negative DSPI_E_*. */
 int dspi_realign_streams(dspi_ctx *ctx, uint32_t first, uint32_t count);
+
+/* ---- paused streams: devices that receive no packet in a call ---------------------------------------------------------------- */
+/* The firmware's chain runs only when a USB packet arrives (usb_audio_drain_ring, usb_audio.c:1326-1332); between packets nothing moves
+ * ("clamp during USB gaps", :1304-1305): filters, leveller envelope, delay lines, mute countdown and peak words stay where the last packet
+ * left them, and the next packet continues from there.  Vendor requests still land while no audio flows, and their side effects on audio
+ * state (path resets, line zeroing on a preset load) happen in the main loop, not in the packet.  A paused stream is such a device: it sits
+ * out whole dspi_process calls (feeding it zeros would be wrong: the filters ring down, the leveller adapts, the lines fill with silence,
+ * the mute envelope runs).  A stream takes part in a whole call or in none of it; packet lengths stay one per call.
+ *   effect and timing   pause and resume take effect at the next dspi_process, like every parameter call.  Pausing a paused stream or
+ *                       resuming an active one is a no-op for that stream.  Both calls return count.  A range past dspi_num_streams, a
+ *                       count of 0 or (resume) an undefined flag bit is DSPI_E_INVAL and changes nothing.  Both calls and the query work
+ *                       on host-only contexts, where they are bookkeeping.
+ *   in dspi_process     a paused stream takes no part: none of its state slots, delay lines, rings, peak slots, clip slots or mute
+ *                       countdown is read for audio or written, and its part of pcm_in is never read (the buffer still spans all streams).
+ *   what the caller finds   with DSPI_MEM_DEVICE no byte of its region of pairs, sub or peaks is written (with DSPI_OUT_TILED the region is
+ *                       its column); with host buffers those regions come back as zeros.  With DSPI_OUT_SPDIF on host buffers the regions
+ *                       hold zero words, which are not valid subframes — do not shift them out (a later build may deliver the subframes of
+ *                       silence there instead, as the two-pass path does for DSPI_OUT_ENABLED_ONLY's silent pairs: rely on neither).
+ *                       clip_flags[stream] is still written and dspi_get_status still answers: both report the frozen state.
+ *   parameter calls     addressed to a paused stream, single or broadcast, work as before, and their state operations (filter path
+ *                       resets, the preset mute, zeroed lines) are applied at the next dspi_process commit whether the stream is paused or
+ *                       not: the firmware's main loop does not wait for audio.
+ *   every stream paused dspi_process launches no chain kernel and returns DSPI_OK; the S/PDIF block position (per context) still
+ *                       advances; such a call does not make a DSPI_BOOT_POPULATED_FLASH context "running" (dspi_load_flash_dump stays a boot).
+ *   dspi_pdm_modulate   skips paused streams: their modulator state stays frozen, their `words` are unwritten in device buffers and zero
+ *                       in host buffers.  dspi_spdif_encode and dspi_i2s_encode are stateless per stream and know no pauses.
+ *   snapshots           activity is a property of the SLOT, not of the stream: it does not travel.  Exporting a paused stream works and
+ *                       gives the frozen state; importing into a paused slot leaves the slot paused.
+ *   resume              while a stream stands still its row's write positions go on.  By default a resumed stream takes the delay write
+ *                       index and ring position of its row, its lines and rings rotated as DSPI_SNAP_REALIGN does (above): the same stream,
+ *                       bit for bit, back on the kernels' one-access-per-row path.  The target of a row is the (widx, ring_pos) of the
+ *                       row's lowest-numbered stream that is below dspi_num_streams and was ACTIVE before the call; a row without one takes
+ *                       the pair of the first stream of the range that this call actually resumes and that lies in the row.  Streams of the
+ *                       range that were already active are residents and are not moved.  DSPI_RESUME_AS_IS skips the rotation: the stream
+ *                       keeps its stale positions, which is correct and runs on the kernels' per-stream addressing (slower).  The call is
+ *                       asynchronous on the context's stream like dspi_realign_streams; it synchronises once when pauses or resumes were
+ *                       made since the last dspi_process (the rule reads the activity as it stood before the call, on the device). */
+#define DSPI_RESUME_AS_IS 0x1u   /* dspi_resume_streams: keep the streams' own write positions (no realignment) */
+int dspi_pause_streams (dspi_ctx *ctx, uint32_t first, uint32_t count);
+int dspi_resume_streams(dspi_ctx *ctx, uint32_t first, uint32_t count, uint32_t flags);
+/* paused[i] = 1 if stream first + i is paused (paused may be NULL); returns how many of the range are paused */
+int dspi_streams_paused(const dspi_ctx *ctx, uint32_t first, uint32_t count, uint8_t *paused);
 
 /* ---- PDM sub output ---------------------------------------------------- */
 /* The consumer of dspi_out.sub: the firmware's 256x oversampled 2nd-order sigma-delta modulator with noise-shaped
