@@ -28,6 +28,7 @@
 #include "dspi_image.h"
 #include "dspi_kernels.h"
 #include "dspi_params.h"
+#include "dspi_move.h"
 #include "dspi_plan.h"
 #include "dspi_snapshot.h"
 
@@ -105,6 +106,11 @@ struct dspi_ctx {
     std::vector<uint8_t> active; uint32_t n_paused = 0;
     std::vector<std::pair<uint32_t, uint32_t>> paused_runs; bool paused_runs_dirty = false;      // [first, end) of consecutive paused streams: what the host-buffer paths zero
     uint32_t *d_active = nullptr; size_t d_active_cap = 0; bool active_dirty = false;
+    // dspi_move_streams: records per batch (DSPI_MOVE_BATCH, read once at dspi_create; 0 = the snapshot chunk), and one call's work lists —
+    // built in a pinned host area, copied up on the context's stream; the event says when the area may be rewritten
+    uint32_t move_batch = 0;
+    uint32_t *d_move = nullptr; size_t d_move_cap = 0;
+    uint32_t *h_move = nullptr; size_t h_move_cap = 0; hipEvent_t ev_move = nullptr;
     std::string err;
 };
 
@@ -500,6 +506,7 @@ int dspi_create(dspi_ctx **out, int flavor, uint32_t n_streams, int hip_device) 
     c->populated = populated;
     c->no_direct = getenv("DSPI_NO_DIRECT") != nullptr;
     if (const char *e = getenv("DSPI_DIRECT_SPIN_US")) { const long v = atol(e); if (v > 0) c->direct_spin_us = (uint32_t)std::min<long>(v, 1000000L); }
+    if (const char *e = getenv("DSPI_MOVE_BATCH")) { const long v = atol(e); if (v > 0) c->move_batch = (uint32_t)std::min<long>(std::max<long>(v, 2L), 65535L); }
     c->images.push_back(std::make_unique<Params>(flavor, fma, !populated));
     c->image_refs.push_back(n_streams);
     c->stream_image.assign(n_streams, 0);
@@ -530,11 +537,13 @@ void dspi_destroy(dspi_ctx *c) {
     if (c->device != DSPI_DEVICE_NONE) {
         (void)hipSetDevice(c->device);
         if (c->hs) (void)hipStreamSynchronize(c->hs);
-        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, c->d_in,
+        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, (void *)c->d_move, c->d_in,
                         (void *)c->d_pairs, (void *)c->d_sub, (void *)c->d_peaks, (void *)c->d_clip, (void *)c->d_spdif_words})
             if (p) (void)hipFree(p);
         if (c->h_direct) (void)hipHostFree(c->h_direct);
         if (c->h_done) (void)hipHostFree(c->h_done);
+        if (c->h_move) (void)hipHostFree(c->h_move);
+        if (c->ev_move) (void)hipEventDestroy(c->ev_move);
         for (hipEvent_t e : c->pipe_events) (void)hipEventDestroy(e);
         if (c->hs_in) (void)hipStreamDestroy(c->hs_in);
         if (c->hs_out) (void)hipStreamDestroy(c->hs_out);
@@ -989,6 +998,111 @@ int dspi_streams_paused(const dspi_ctx *c, uint32_t first, uint32_t count, uint8
         n += p ? 1 : 0;
     }
     return n;
+}
+
+// ---- stream moves (dspi_move.h: validation, compaction rule, targets, batch schedule; dspi_snapshot.hip: the list-addressed kernels) ----
+static_assert(sizeof(dspi_stream_move) == sizeof(StreamMove) && offsetof(dspi_stream_move, dst) == offsetof(StreamMove, dst), "dspi_stream_move is StreamMove");
+static const uint8_t *move_activity(const dspi_ctx *c) { return c->n_paused ? c->active.data() : nullptr; }      // (null: every slot is active)
+
+// one call's work lists into device memory, behind the context's earlier work
+static int move_upload(dspi_ctx *c, const std::vector<uint32_t> &words) {
+    const size_t bytes = words.size() * 4;
+    if (!c->ev_move) HIPCK(c, hipEventCreateWithFlags(&c->ev_move, hipEventDisableTiming));
+    HIPCK(c, hipEventSynchronize(c->ev_move));      // the previous call's copy has left the area (long since, as a rule)
+    if (bytes > c->h_move_cap) {
+        if (c->h_move) HIPCK(c, hipHostFree(c->h_move));
+        c->h_move = nullptr; c->h_move_cap = 0;
+        void *p = nullptr;
+        if (hipHostMalloc(&p, bytes * 2, hipHostMallocDefault) != hipSuccess) return fail(c, DSPI_E_NOMEM, "hipHostMalloc failed (move lists)");
+        c->h_move = (uint32_t *)p; c->h_move_cap = bytes * 2;
+    }
+    int rc = ensure(c, c->d_move, c->d_move_cap, bytes);
+    if (rc) return rc;
+    memcpy(c->h_move, words.data(), bytes);
+    HIPCK(c, hipMemcpyAsync(c->d_move, c->h_move, bytes, hipMemcpyHostToDevice, c->hs));
+    HIPCK(c, hipEventRecord(c->ev_move, c->hs));
+    return 0;
+}
+
+int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    if (flags & ~DSPI_MOVE_AS_IS) return fail(c, DSPI_E_INVAL, "dspi_move_streams: undefined flag bits");
+    // everything is validated before anything is written
+    const StreamMove *list = reinterpret_cast<const StreamMove *>(moves);
+    if (const char *why = move_validate(list, n, c->n_streams, move_activity(c))) return fail(c, DSPI_E_INVAL, std::string("dspi_move_streams: ") + why);
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no run-time state to move");
+    std::vector<StreamMove> mv;
+    for (uint32_t i = 0; i < n; i++) if (list[i].src != list[i].dst) mv.push_back(list[i]);
+    if (mv.empty()) return 0;
+    const uint32_t nm = (uint32_t)mv.size(), row = (uint32_t)c->sm.row;
+    HIPCK(c, hipSetDevice(c->device));
+    int rc = pdm_state(c);      // (the records carry the modulators' words along)
+    if (rc) return rc;
+    const uint32_t cap = c->move_batch ? c->move_batch : snap_chunk_rows(c) * row;
+    if ((rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)cap * snap_state_bytes(c->flavor, 1)))) return rc;
+    const bool realign = !(flags & DSPI_MOVE_AS_IS);
+    if (realign && (rc = ensure(c, c->d_snap_shift, c->d_snap_shift_cap, (size_t)c->n_streams * 8))) return rc;
+    // the call's work lists, one upload: the targets (every shift is computed once, by one launch, before anything is written: batches
+    // cannot disagree), then per batch the gather's and the scatter's row items and their columns' record indices
+    const std::vector<MoveBatch> batches = move_schedule(mv.data(), nm, cap);
+    std::vector<uint32_t> words;
+    if (realign) {
+        const std::vector<MoveTarget> t = move_targets(mv.data(), nm, c->n_streams, row, move_activity(c));
+        words.resize((t.size() * 3 + 3) & ~(size_t)3);
+        memcpy(words.data(), t.data(), t.size() * sizeof(MoveTarget));
+    }
+    std::vector<MoveRowItem> items;
+    std::vector<uint32_t> colrec;
+    struct Span { size_t g0, g1, s1; };      // items [g0, g1): the batch's gather, [g1, s1): its scatter
+    std::vector<Span> spans;
+    for (const MoveBatch &b : batches) {
+        Span sp{items.size(), 0, 0};
+        move_row_items(b.gather, row, items, colrec); sp.g1 = items.size();
+        move_row_items(b.scatter, row, items, colrec); sp.s1 = items.size();
+        spans.push_back(sp);
+    }
+    const size_t items_at = words.size(), colrec_at = items_at + items.size() * 4;
+    words.resize(colrec_at + colrec.size());
+    memcpy(words.data() + items_at, items.data(), items.size() * sizeof(MoveRowItem));
+    memcpy(words.data() + colrec_at, colrec.data(), colrec.size() * 4);
+    if ((rc = move_upload(c, words))) return rc;
+    // run-time state, on the context's stream, behind whatever it still has to do
+    if (realign) HIPCK(c, launch_move_targets(c->flavor, c->d_state, c->d_move, nm, c->d_snap_shift, c->hs));
+    for (const Span &sp : spans) {
+        HIPCK(c, launch_move_gather(c->flavor, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, c->d_move + items_at + sp.g0 * 4, c->d_move + colrec_at + sp.g0 * row,
+                                    (uint32_t)(sp.g1 - sp.g0), c->hs));
+        HIPCK(c, launch_move_scatter(c->flavor, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, c->d_move + items_at + sp.g1 * 4, c->d_move + colrec_at + sp.g1 * row,
+                                     (uint32_t)(sp.s1 - sp.g1), realign ? c->d_snap_shift : nullptr, c->hs));
+    }
+    // parameters travel by reference, activity travels with the stream: all sources are read before any destination is written.  A
+    // destination that is no source loses its occupant (one reference less); a source that is no destination keeps its own and becomes
+    // a paused, frozen copy.  (Such entries exist only where something is paused: `active` is allocated then.)
+    const bool have_active = !c->active.empty();
+    std::vector<int32_t> img(nm);
+    std::vector<uint8_t> act(nm, 1), is_dst(c->n_streams, 0);
+    for (uint32_t i = 0; i < nm; i++) { img[i] = c->stream_image[mv[i].src]; if (have_active) act[i] = c->active[mv[i].src]; is_dst[mv[i].dst] = 1; }
+    bool one_way = false;
+    for (uint32_t i = 0; i < nm; i++) {
+        int32_t &si = c->stream_image[mv[i].dst];
+        c->image_refs[(size_t)si]--; si = img[i]; c->image_refs[(size_t)si]++;
+        if (have_active) c->active[mv[i].dst] = act[i];
+    }
+    for (uint32_t i = 0; i < nm; i++)
+        if (!is_dst[mv[i].src]) { c->active[mv[i].src] = 0; one_way = true; }
+    if (have_active) { c->n_paused = 0; for (uint32_t s = 0; s < c->n_streams; s++) c->n_paused += c->active[s] ? 0u : 1u; }
+    c->assignment_dirty = true; c->launch_dirty = true;
+    if (have_active) { c->active_dirty = true; c->paused_runs_dirty = true; }
+    if (one_way) c->merge_hint = true;      // an image may have lost its last stream: the fold-back pass drops it
+    return (int)nm;
+}
+
+int dspi_plan_compaction(const dspi_ctx *c, dspi_stream_move *moves, uint32_t cap, uint32_t flags) {
+    if (!c || (flags & ~DSPI_COMPACT_ONE_WAY)) return DSPI_E_INVAL;
+    const std::vector<StreamMove> plan = move_compaction(move_activity(c), c->n_streams, flags & DSPI_COMPACT_ONE_WAY);
+    if (!moves) return (int)plan.size();
+    if (plan.size() > cap) return DSPI_E_SHORT;
+    if (!plan.empty()) memcpy(moves, plan.data(), plan.size() * sizeof(StreamMove));
+    return (int)plan.size();
 }
 
 int dspi_debug_stream_positions(dspi_ctx *c, uint32_t first, uint32_t count, uint32_t *widx, uint32_t *ring_pos) {

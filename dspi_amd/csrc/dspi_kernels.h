@@ -86,4 +86,15 @@ hipError_t launch_snapshot_realign(int flavor, uint32_t *state, uint32_t *dlines
 hipError_t launch_snapshot_resume(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count,
                                   uint32_t n_streams, const uint32_t *active, uint32_t r_first, uint32_t r_count, uint32_t *shift, hipStream_t stream);
 
+// ---- stream moves (dspi_move_streams; dspi_move.h: the lists; dspi_snapshot.hip: the kernels) ----
+// The same transposition addressed by list: `items` = n_items MoveRowItem (one per touched row), `colrec` = per item one record index per
+// column of the row (kMoveNone: the column is not listed and is neither read into a record nor written), both in device memory; `records`
+// = record 0 of the scratch.  The gather reads listed columns into their records; the scatter writes records into listed columns, rotated
+// by shift[destination stream] (two words per stream of the context, from launch_move_targets) or, shift == nullptr, as they are.
+hipError_t launch_move_targets(int flavor, const uint32_t *state, const uint32_t *targets, uint32_t n, uint32_t *shift, hipStream_t stream);      // targets: n MoveTarget
+hipError_t launch_move_gather(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, const uint32_t *items, const uint32_t *colrec,
+                              uint32_t n_items, hipStream_t stream);
+hipError_t launch_move_scatter(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, const uint32_t *items, const uint32_t *colrec,
+                               uint32_t n_items, const uint32_t *shift, hipStream_t stream);
+
 }  // namespace dspi

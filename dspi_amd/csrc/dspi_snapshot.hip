@@ -36,15 +36,25 @@
 //   LDS           the word goes to tile[32 j + k][c]: bank (32 j + k) P + c = 32 j + k + w + 4 i + 32 h (mod 64; P = 65): for one
 //                 instruction j, i and w are fixed and k + 32 h runs over all 64 banks: conflict-free.  (Two ADJACENT columns per wave,
 //                 as on the plain path, would put lanes (k + 1, c) and (k, c + 1) into one bank: hence the half waves 32 columns apart.)
+//
+// The LIST-ADDRESSED kernels (dspi_move_streams; the lists: dspi_move.h) are the same three code paths with another answer to "which columns
+// of which row": blockIdx.y is a work item — a touched row, a record index per column (kMoveNone: not listed) and two masks over the row's
+// groups of four columns, "any listed" and "all listed" — instead of a row of a range.  Tiles, LDS pitch, lane mappings and bank arithmetic
+// are unchanged.  A tile without a listed column returns at once; the record side skips unlisted columns (their LDS words are never
+// filled on the gather and never read on the scatter); the scatter's array side stores 16 bytes where all four columns are listed and
+// single words elsewhere, so a touched row's unlisted columns are never written.  The realigning scatter looks its shifts up by destination
+// stream; move_targets_kernel wrote them, once per call, before the first scatter.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "dspi_kernels.h"
+#include "dspi_move.h"
 #include "dspi_snapshot.h"
 
 namespace dspi {
 
 static_assert(kPdmWords == kPdmStateWords, "the snapshot's PDM section is the modulator's state");
+static_assert(sizeof(MoveRowItem) == 16 && sizeof(MoveTarget) == 12, "the move list's work items go up as 32-bit words");
 
 namespace {
 
@@ -63,14 +73,21 @@ struct SnapKArgs {
 struct SnapRealignArgs : SnapKArgs {
     const uint2 *shift;                // per stream of [first, first + count): {delay lines' rotation, rings' rotation}
 };
-template <bool REALIGN> struct SnapArgsOf { typedef SnapKArgs type; };
-template <> struct SnapArgsOf<true> { typedef SnapRealignArgs type; };
+// the list-addressed kernels (dspi_move_streams): blockIdx.y is a work item, a touched row with a record index per column
+struct SnapListArgs : SnapKArgs {
+    const MoveRowItem *items;
+    const uint32_t *colrec;            // [item][ROW]: the record of each column, kMoveNone = not listed
+    const uint2 *shift;                // realigning scatter: per stream of the CONTEXT, indexed by the destination slot
+};
+template <bool REALIGN, bool LIST> struct SnapArgsOf { typedef SnapKArgs type; };
+template <> struct SnapArgsOf<true, false> { typedef SnapRealignArgs type; };
+template <bool REALIGN> struct SnapArgsOf<REALIGN, true> { typedef SnapListArgs type; };
 
 // word i of four, i known at run time only: selects, so that the four stay in registers
 __device__ __forceinline__ uint32_t pick(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t i) { return i == 0 ? w0 : i == 1 ? w1 : i == 2 ? w2 : w3; }
 
-template <uint32_t ROW, bool IMPORT, bool REALIGN = false>
-__global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const typename SnapArgsOf<REALIGN>::type a) {
+template <uint32_t ROW, bool IMPORT, bool REALIGN = false, bool LIST = false>
+__global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const typename SnapArgsOf<REALIGN, LIST>::type a) {
     static_assert(IMPORT || !REALIGN, "only the import realigns");
     constexpr uint32_t kTilePos = IMPORT ? kImportPos : kExportPos, kCols = IMPORT ? kImportCols : kExportCols;
     static_assert(ROW % kCols == 0 && kCols % 4 == 0 && kTilePos % 4 == 0 && kSnapThreads % (kCols / 4) == 0 && kSnapThreads % (kTilePos / 4) == 0, "tile shape");
@@ -83,17 +100,38 @@ __global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const typename S
 #pragma unroll
     for (int i = 1; i < SEC_COUNT; i++)
         if (blockIdx.x >= a.tile0[i]) { base = a.arr[i]; len = a.len[i]; span = a.span[i]; off = a.off[i]; t0 = a.tile0[i]; sec = i; }
-    const uint32_t wg = a.row0 + blockIdx.y, p0 = (blockIdx.x - t0) * kTilePos, col0 = blockIdx.z * kCols;
-    // the tile's columns inside [first, first + count)
-    const uint64_t s0 = (uint64_t)wg * ROW, b0 = s0 + col0, lo = a.first > b0 ? a.first : b0, end = (uint64_t)a.first + a.count, hi = end < b0 + kCols ? end : b0 + kCols;
-    if (hi <= lo) return;
-    const uint32_t c_lo = (uint32_t)(lo - b0), c_hi = (uint32_t)(hi - b0);      // relative to col0
-    uint32_t *const arr = base + ((size_t)wg * len + p0) * ROW + col0;
-    uint32_t *const rec = a.rec + (size_t)(b0 + c_lo - a.first) * a.record_words + off + p0;      // column c_lo's run
+    const uint32_t p0 = (blockIdx.x - t0) * kTilePos, col0 = blockIdx.z * kCols;
     const uint32_t tid = threadIdx.x;
     const uint32_t q = tid % kRowLanes, r0 = tid / kRowLanes;       // array side: columns 4q .. 4q + 3 of position p0 + r
     const uint32_t k = tid % kRunLanes, cc0 = tid / kRunLanes;      // record side: positions p0 + 4k .. + 3 of column c
-    const bool q_any = 4 * q + 4 > c_lo && 4 * q < c_hi, q_all = 4 * q >= c_lo && 4 * q + 4 <= c_hi;
+    // the tile's columns: those inside [first, first + count) — or, LIST, those of the work item's row that carry a record index
+    uint32_t wg, c_lo = 0, c_hi = kCols;      // relative to col0
+    bool q_any, q_all;
+    [[maybe_unused]] uint64_t b0 = 0;
+    [[maybe_unused]] uint32_t *rec = nullptr;          // column c_lo's run
+    [[maybe_unused]] const uint32_t *cr = nullptr;     // LIST: the tile's columns' record indices
+    if constexpr (LIST) {
+        const MoveRowItem it = a.items[blockIdx.y];
+        const uint32_t any = it.q_any >> (col0 / 4), all = it.q_all >> (col0 / 4);
+        if (!(any & ((1u << kRowLanes) - 1u))) return;
+        wg = it.row;
+        cr = a.colrec + (size_t)blockIdx.y * ROW + col0;
+        q_any = (any >> q) & 1u; q_all = (all >> q) & 1u;
+    } else {
+        wg = a.row0 + blockIdx.y;
+        const uint64_t s0 = (uint64_t)wg * ROW, lo = a.first > s0 + col0 ? a.first : s0 + col0, end = (uint64_t)a.first + a.count, hi = end < s0 + col0 + kCols ? end : s0 + col0 + kCols;
+        b0 = s0 + col0;
+        if (hi <= lo) return;
+        c_lo = (uint32_t)(lo - b0); c_hi = (uint32_t)(hi - b0);
+        rec = a.rec + (size_t)(b0 + c_lo - a.first) * a.record_words + off + p0;
+        q_any = 4 * q + 4 > c_lo && 4 * q < c_hi; q_all = 4 * q >= c_lo && 4 * q + 4 <= c_hi;
+    }
+    uint32_t *const arr = base + ((size_t)wg * len + p0) * ROW + col0;
+    // column c's run of the tile on the record side (LIST: null where the column is not listed)
+    auto run_of = [&](uint32_t c) -> uint32_t * {
+        if constexpr (LIST) { const uint32_t ri = cr[c]; return ri == kMoveNone ? nullptr : a.rec + (size_t)ri * a.record_words + off + p0; }
+        else return rec + (size_t)(c - c_lo) * a.record_words;
+    };
     // record side: a lane touches its four positions in the order rot, rot + 1, ... (mod 4), see the bank arithmetic at the top
     const uint32_t rot = ((k >> 4) * (64u / kRunLanes)) & 3u;
 
@@ -111,7 +149,9 @@ __global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const typename S
                 const uint32_t *t = tile + 4 * k * kPitch + c;
                 const uint32_t w0 = t[rot * kPitch], w1 = t[((rot + 1) & 3u) * kPitch], w2 = t[((rot + 2) & 3u) * kPitch], w3 = t[((rot + 3) & 3u) * kPitch];
                 const u4 v = u4{pick(w0, w1, w2, w3, (0u - rot) & 3u), pick(w0, w1, w2, w3, (1u - rot) & 3u), pick(w0, w1, w2, w3, (2u - rot) & 3u), pick(w0, w1, w2, w3, (3u - rot) & 3u)};
-                *reinterpret_cast<u4 *>(rec + (size_t)(c - c_lo) * a.record_words + 4 * k) = v;
+                uint32_t *const run = run_of(c);
+                if (LIST && !run) continue;
+                *reinterpret_cast<u4 *>(run + 4 * k) = v;
             }
     } else {
         if constexpr (REALIGN) {
@@ -125,8 +165,10 @@ __global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const typename S
             for (uint32_t i = 0; i < kCols / 8; i++) {
                 const uint32_t c = c_lane + 4u * i;
                 if (c < c_lo || c >= c_hi) continue;
-                const size_t k_str = (size_t)(b0 + c - a.first);
-                const uint2 sh = a.shift[k_str];
+                size_t k_str, k_shift;      // column c's record, and its entry of the shift table
+                if constexpr (LIST) { if (cr[c] == kMoveNone) continue; k_str = cr[c]; k_shift = (size_t)wg * ROW + col0 + c; }
+                else k_str = k_shift = (size_t)(b0 + c - a.first);
+                const uint2 sh = a.shift[k_shift];
                 const uint32_t d = sec == SEC_LINES ? sh.x : sec == SEC_RING ? sh.y : 0u;
                 const uint32_t *rc = a.rec + k_str * a.record_words + off;      // column c's section
                 // (four loads in flight, then four LDS writes: a position past the section's span — the tile grid rounds up — reads the
@@ -149,7 +191,9 @@ __global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const typename S
             }
         } else if (p0 + 4 * k < span)
             for (uint32_t c = c_lo + cc0; c < c_hi; c += kColsPerPass) {
-                const u4 v = *reinterpret_cast<const u4 *>(rec + (size_t)(c - c_lo) * a.record_words + 4 * k);
+                const uint32_t *const run = run_of(c);
+                if (LIST && !run) continue;
+                const u4 v = *reinterpret_cast<const u4 *>(run + 4 * k);
                 uint32_t *t = tile + 4 * k * kPitch + c;
 #pragma unroll
                 for (uint32_t j = 0; j < 4; j++) { const uint32_t i = (j + rot) & 3u; t[i * kPitch] = pick(v.x, v.y, v.z, v.w, i); }
@@ -163,7 +207,7 @@ __global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const typename S
                 if (q_all) *reinterpret_cast<u4 *>(g) = u4{t[0], t[1], t[2], t[3]};
                 else {
 #pragma unroll
-                    for (uint32_t j = 0; j < 4; j++) if (4 * q + j >= c_lo && 4 * q + j < c_hi) g[j] = t[j];
+                    for (uint32_t j = 0; j < 4; j++) if (LIST ? cr[4 * q + j] != kMoveNone : 4 * q + j >= c_lo && 4 * q + j < c_hi) g[j] = t[j];
                 }
             }
     }
@@ -229,7 +273,66 @@ SnapGrid snap_kargs(SnapKArgs &a, int flavor, bool import, uint32_t *state, uint
     return SnapGrid{dim3(tiles, rows, l.row / cols), rows};
 }
 
+// One thread per entry of a move list: how far the stream arriving at `dst` is rotated to stand at its row's target positions
+// (dspi_move.h move_targets: `target` names the slot whose positions those are), all three read from the state array as the context's
+// earlier work left it and before any scatter of the call writes.
+template <uint32_t ROW>
+__global__ __launch_bounds__(kSnapThreads) void move_targets_kernel(const uint32_t *state, const MoveTarget *t, uint32_t n, uint2 *shift) {
+    constexpr StateMap sm = make_state_map(ROW == 128 ? 1 : 0);
+    constexpr uint32_t kLine = (uint32_t)sm.max_delay, kRing = (uint32_t)kRingLen;
+    const uint32_t i = blockIdx.x * kSnapThreads + threadIdx.x;
+    if (i >= n) return;
+    const MoveTarget e = t[i];
+    const uint32_t *from = state + (size_t)(e.src / ROW) * sm.n_slots * ROW + e.src % ROW, *to = state + (size_t)(e.target / ROW) * sm.n_slots * ROW + e.target % ROW;
+    shift[e.dst] = make_uint2(snap_shift(from[(size_t)sm.widx * ROW] & (kLine - 1u), to[(size_t)sm.widx * ROW] & (kLine - 1u), kLine),
+                              snap_shift(from[(size_t)sm.ring_pos * ROW] & (kRing - 1u), to[(size_t)sm.ring_pos * ROW] & (kRing - 1u), kRing));
+}
+
+dim3 snap_list_kargs(SnapListArgs &a, int flavor, bool import, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, const uint32_t *items,
+                     const uint32_t *colrec, uint32_t n_items) {
+    dim3 grid = snap_kargs(a, flavor, import, state, dlines, ring, pdm, records, 0, 1).grid;
+    a.first = 0; a.count = 0; a.row0 = 0;
+    a.items = reinterpret_cast<const MoveRowItem *>(items); a.colrec = colrec; a.shift = nullptr;
+    grid.y = n_items;
+    return grid;
+}
+
 }  // namespace
+
+hipError_t launch_move_targets(int flavor, const uint32_t *state, const uint32_t *targets, uint32_t n, uint32_t *shift, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const dim3 grid((n + kSnapThreads - 1) / kSnapThreads);
+    const MoveTarget *t = reinterpret_cast<const MoveTarget *>(targets);
+    if (flavor) hipLaunchKernelGGL((move_targets_kernel<128>), grid, dim3(kSnapThreads), 0, stream, state, t, n, reinterpret_cast<uint2 *>(shift));
+    else hipLaunchKernelGGL((move_targets_kernel<64>), grid, dim3(kSnapThreads), 0, stream, state, t, n, reinterpret_cast<uint2 *>(shift));
+    return hipGetLastError();
+}
+
+hipError_t launch_move_gather(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, const uint32_t *items, const uint32_t *colrec,
+                              uint32_t n_items, hipStream_t stream) {
+    if (n_items == 0) return hipSuccess;
+    SnapListArgs a{};
+    const dim3 grid = snap_list_kargs(a, flavor, false, state, dlines, ring, pdm, records, items, colrec, n_items);
+    if (flavor) hipLaunchKernelGGL((snapshot_kernel<128, false, false, true>), grid, dim3(kSnapThreads), 0, stream, a);
+    else hipLaunchKernelGGL((snapshot_kernel<64, false, false, true>), grid, dim3(kSnapThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_move_scatter(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, const uint32_t *items, const uint32_t *colrec,
+                               uint32_t n_items, const uint32_t *shift, hipStream_t stream) {
+    if (n_items == 0) return hipSuccess;
+    SnapListArgs a{};
+    const dim3 grid = snap_list_kargs(a, flavor, true, state, dlines, ring, pdm, records, items, colrec, n_items);
+    a.shift = reinterpret_cast<const uint2 *>(shift);
+    if (flavor) {
+        if (shift) hipLaunchKernelGGL((snapshot_kernel<128, true, true, true>), grid, dim3(kSnapThreads), 0, stream, a);
+        else hipLaunchKernelGGL((snapshot_kernel<128, true, false, true>), grid, dim3(kSnapThreads), 0, stream, a);
+    } else {
+        if (shift) hipLaunchKernelGGL((snapshot_kernel<64, true, true, true>), grid, dim3(kSnapThreads), 0, stream, a);
+        else hipLaunchKernelGGL((snapshot_kernel<64, true, false, true>), grid, dim3(kSnapThreads), 0, stream, a);
+    }
+    return hipGetLastError();
+}
 
 hipError_t launch_snapshot(int flavor, bool import, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first,
                            uint32_t count, hipStream_t stream) {

@@ -18,6 +18,8 @@ ALL = -1
 MEM_DEVICE = 0x1
 SNAP_REALIGN = 0x100
 RESUME_AS_IS = 0x1
+MOVE_AS_IS = 0x1
+COMPACT_ONE_WAY = 0x1
 OUT_TILED = 0x2
 OUT_ENABLED_ONLY = 0x4
 OUT_I2S_SLOTS = 0x8
@@ -113,6 +115,9 @@ def lib() -> C.CDLL:
         L.dspi_pause_streams.argtypes = [vp, u32, u32]
         L.dspi_resume_streams.argtypes = [vp, u32, u32, u32]
         L.dspi_streams_paused.argtypes = [vp, u32, u32, vp]
+    if hasattr(L, "dspi_move_streams"):      # (ABI 8 + stream moves: detected by symbol; with it DSPI_MOVE_AS_IS, DSPI_COMPACT_ONE_WAY)
+        L.dspi_move_streams.argtypes = [vp, vp, u32, u32]
+        L.dspi_plan_compaction.argtypes = [vp, vp, u32, u32]
     _lib = L
     return L
 
@@ -401,6 +406,22 @@ class Dspi:
         p = np.zeros(count, dtype=np.uint8)
         self._ck(self.L.dspi_streams_paused(self.h, first, count, p.ctypes.data), "streams_paused")
         return p
+
+    # ---- stream moves (include/dspi.h: a stream changes its slot inside its context) ----
+    def move_streams(self, moves, as_is: bool = False) -> int:
+        """dspi_move_streams: moves = [(src, dst), ...] (or an (n, 2) array); slot dst takes the stream slot src held, all entries at once,
+        realigned to its destination row (as_is: DSPI_MOVE_AS_IS, it keeps its own write positions).  Returns the entries applied."""
+        m = np.ascontiguousarray(np.asarray(moves, dtype=np.uint32).reshape(-1, 2))
+        return self._ck(self.L.dspi_move_streams(self.h, m.ctypes.data if len(m) else None, len(m), MOVE_AS_IS if as_is else 0), "move_streams")
+
+    def plan_compaction(self, one_way: bool = False) -> np.ndarray:
+        """dspi_plan_compaction: the (src, dst) list, uint32 [n][2], after which the active streams fill the lowest slots (one_way:
+        DSPI_COMPACT_ONE_WAY, paused slots are free and not preserved).  Works on host-only contexts."""
+        flags = COMPACT_ONE_WAY if one_way else 0
+        n = self._ck(self.L.dspi_plan_compaction(self.h, None, 0, flags), "plan_compaction")
+        m = np.zeros((n, 2), dtype=np.uint32)
+        if n: self._ck(self.L.dspi_plan_compaction(self.h, m.ctypes.data, n, flags), "plan_compaction")
+        return m
 
     def sync(self):
         self._ck(self.L.dspi_sync(self.h), "sync")

@@ -69,7 +69,8 @@ extern "C" {
                               * 8: dspi_debug_direct_stats, dspi_debug_detmath, the direct path polls a completion word for the call's own audio time (DSPI_DIRECT_SPIN_US, DSPI_DIRECT_POLL);
                               * 8 + snapshots: detect by symbol (dspi_snapshot_sizes, dspi_export_streams, dspi_import_streams; additions only);
                               * 8 + realignment: detect by symbol (dspi_realign_streams; with it DSPI_SNAP_REALIGN and dspi_debug_stream_positions; additions only);
-                              * 8 + paused streams: detect by symbol (dspi_pause_streams; with it dspi_resume_streams, dspi_streams_paused, DSPI_RESUME_AS_IS; additions only) */
+                              * 8 + paused streams: detect by symbol (dspi_pause_streams; with it dspi_resume_streams, dspi_streams_paused, DSPI_RESUME_AS_IS; additions only);
+                              * 8 + stream moves: detect by symbol (dspi_move_streams; with it dspi_plan_compaction, dspi_stream_move, DSPI_MOVE_AS_IS, DSPI_COMPACT_ONE_WAY; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -344,6 +345,51 @@ int dspi_pause_streams (dspi_ctx *ctx, uint32_t first, uint32_t count);
 int dspi_resume_streams(dspi_ctx *ctx, uint32_t first, uint32_t count, uint32_t flags);
 /* paused[i] = 1 if stream first + i is paused (paused may be NULL); returns how many of the range are paused */
 int dspi_streams_paused(const dspi_ctx *ctx, uint32_t first, uint32_t count, uint8_t *paused);
+
+/* ---- stream moves: a stream changes its slot inside its context ------------------------------------------------------------------ */
+/* A context whose devices come and go ends up with its active streams scattered: lanes whose mate is paused leave the packed kernel, and
+ * half the streams can cost more than all of them (profiles/pause.md).  dspi_move_streams moves streams between slots by list, so that the
+ * active ones can be put back into whole rows; dspi_plan_compaction writes the list that does exactly that.
+ *   what the call does  after it, slot `dst` holds the stream that slot `src` held before it, for every entry AT ONCE: all sources are
+ *                       read as they stood before the call, so swaps, cycles and chains are legal.  Entries with src == dst are dropped;
+ *                       those streams count as residents (below).  Returns the number of entries applied (identities excluded).
+ *   what travels        everything a snapshot carries — every state slot (last peaks, clip slots, mute envelope, ring position, delay write
+ *                       index among them), every delay line at full length, both leveller rings, the PDM modulator words — and the
+ *                       stream's parameter object BY REFERENCE: the slot's image reference moves, no parameter object is copied and no
+ *                       image is added; pending state operations stay on the object and reach the stream at its new slot at the next
+ *                       commit.  Whether the stream is paused travels too: here, unlike in snapshots, activity belongs to the stream.  So
+ *                       dspi_get_status, dspi_collect_bulk, dspi_vendor_get and dspi_clear_clips answer at dst as they answered at src.
+ *   open ends           a slot that is a source and not a destination keeps its bytes and its parameter reference as a frozen copy and
+ *                       becomes PAUSED.  A slot that is a destination and not a source loses its former occupant; it must be paused
+ *                       before the call: a move never overwrites an active stream that the same call does not move away.
+ *   realignment         by default every moved stream takes the (widx, ring_pos) of its destination row, its lines and rings rotated
+ *                       exactly as DSPI_SNAP_REALIGN rotates them (above).  A resident is a stream below dspi_num_streams that was active
+ *                       before the call and is neither a source nor a destination of it.  A row's target is the position pair of its
+ *                       lowest-numbered resident, read on the device behind the context's earlier work; a row without a resident takes the
+ *                       pair of the stream that arrives at the row's lowest-numbered destination, as it stands at its source.  All
+ *                       rotations are fixed once for the whole call before anything is written.  Moved paused streams are rotated too
+ *                       (harmless: a later resume realigns them again).  DSPI_MOVE_AS_IS skips the rotation.
+ *   validation          everything is validated before anything is written.  n == 0, a null list, an index at or past dspi_num_streams,
+ *                       a slot that is the source of two entries, a slot that is the destination of two entries, an active destination
+ *                       that is not a source, an undefined flag bit: DSPI_E_INVAL, and the context is bit for bit as it was.  Host-only
+ *                       contexts validate and then return DSPI_E_NODEVICE, as the import does.
+ *   timing              asynchronous on the context's stream like dspi_realign_streams (who the residents are is decided on the host, whose
+ *                       record of the pauses is the truth: the call never waits for the device's copy of it); takes effect at the next
+ *                       dspi_process.  A list of any length goes through the context's record scratch in batches (DSPI_MOVE_BATCH, read at
+ *                       dspi_create: records per batch, at least 2; default: the snapshot chunk).
+ *   not touched         the S/PDIF block position, the direct path's statistics, "has processed audio".
+ *
+ * dspi_plan_compaction is bookkeeping and works on host-only contexts: it writes the shortest list after which slots [0, A) are active and
+ * [A, dspi_num_streams) paused, A = the number of active streams.  H = the paused slots below A, T = the active slots at or above A, both
+ * ascending (always equally many); pair i is the swap {T[i] -> H[i]}, {H[i] -> T[i]} — no paused device is lost — or, with
+ * DSPI_COMPACT_ONE_WAY (the caller treats paused slots as free), {T[i] -> H[i]} alone.  Returns the number of entries; moves == NULL only
+ * counts; a cap below that number is DSPI_E_SHORT and writes nothing.  The caller relocates its own per-stream buffers by the same list.
+ * Not in scope: choosing the pairing by parameter image, so that the two streams of a lane share a preset. */
+typedef struct dspi_stream_move { uint32_t src, dst; } dspi_stream_move;
+#define DSPI_MOVE_AS_IS      0x1u   /* dspi_move_streams: keep the streams' own write positions (no realignment) */
+#define DSPI_COMPACT_ONE_WAY 0x1u   /* dspi_plan_compaction: paused slots are free, do not preserve them */
+int dspi_move_streams(dspi_ctx *ctx, const dspi_stream_move *moves, uint32_t n, uint32_t flags);
+int dspi_plan_compaction(const dspi_ctx *ctx, dspi_stream_move *moves, uint32_t cap, uint32_t flags);
 
 /* ---- PDM sub output ---------------------------------------------------- */
 /* The consumer of dspi_out.sub: the firmware's 256x oversampled 2nd-order sigma-delta modulator with noise-shaped
