@@ -28,6 +28,7 @@
 #include "dspi_image.h"
 #include "dspi_kernels.h"
 #include "dspi_params.h"
+#include "dspi_boot.h"
 #include "dspi_move.h"
 #include "dspi_plan.h"
 #include "dspi_snapshot.h"
@@ -1103,6 +1104,43 @@ int dspi_plan_compaction(const dspi_ctx *c, dspi_stream_move *moves, uint32_t ca
     if (plan.size() > cap) return DSPI_E_SHORT;
     if (!plan.empty()) memcpy(moves, plan.data(), plan.size() * sizeof(StreamMove));
     return (int)plan.size();
+}
+
+// ---- stream boots (dspi_boot.h: validation and the kernel's work items; dspi_boot.hip: the power-on kernel) ----
+int dspi_boot_streams(dspi_ctx *c, const uint32_t *streams, uint32_t n, const void *dump, size_t len, uint32_t flags, int *selection) {
+    if (!c) return DSPI_E_INVAL;
+    if (flags & ~DSPI_BOOT_STREAMS_AS_IS) return fail(c, DSPI_E_INVAL, "dspi_boot_streams: undefined flag bits");
+    // everything is validated before anything is written
+    if (const char *why = boot_validate(streams, n, c->n_streams)) return fail(c, DSPI_E_INVAL, std::string("dspi_boot_streams: ") + why);
+    if (dump && len < kFlashDumpBytes) return fail(c, DSPI_E_SHORT, "dspi_boot_streams: dump shorter than DSPI_FLASH_DUMP_BYTES");
+    // the device that has just been powered on: dspi_create's own, or one that boots from the dump's flash (first_boot = false, then
+    // boot(dump): Params::load_flash_dump's boot path; sample rate, UAC1 volume and mute stay at their power-on values)
+    auto p = std::make_unique<Params>(c->flavor, c->fma, dump ? false : !c->populated);
+    int sel = 48;
+    if (dump) sel = p->load_flash_dump(dump, len, true);
+    p->dirty = true;
+    // run-time state, on the context's stream, behind whatever it still has to do (the kernel reads the rows' residents' positions there)
+    if (c->device != DSPI_DEVICE_NONE) {
+        HIPCK(c, hipSetDevice(c->device));
+        const std::vector<BootRowItem> items = boot_row_items(streams, n, c->n_streams, (uint32_t)c->sm.row, move_activity(c), (flags & DSPI_BOOT_STREAMS_AS_IS) != 0);
+        std::vector<uint32_t> words(items.size() * (sizeof(BootRowItem) / 4));
+        memcpy(words.data(), items.data(), items.size() * sizeof(BootRowItem));
+        int rc = move_upload(c, words);
+        if (rc) return rc;
+        HIPCK(c, launch_boot(c->flavor, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_move, (uint32_t)items.size(), c->hs));
+    }
+    // parameters: the listed streams leave their objects (whose pending state operations never reach them) and share ONE new one, whose
+    // own pending operations the next commit applies over the power-on state, as after dspi_create.  An object that lost its last stream
+    // is dropped, and a new object equal to one already here folded into it, by the fold-back pass (merge_images).
+    const int32_t slot = (int32_t)c->images.size();
+    c->images.push_back(std::move(p)); c->image_refs.push_back(0);
+    for (uint32_t i = 0; i < n; i++) {
+        int32_t &si = c->stream_image[streams[i]];
+        c->image_refs[(size_t)si]--; si = slot; c->image_refs[(size_t)slot]++;
+    }
+    c->assignment_dirty = true; c->launch_dirty = true; c->merge_hint = true;
+    if (selection) *selection = sel;
+    return (int)n;
 }
 
 int dspi_debug_stream_positions(dspi_ctx *c, uint32_t first, uint32_t count, uint32_t *widx, uint32_t *ring_pos) {

@@ -453,20 +453,21 @@ __device__ __forceinline__ void sk_outputs(const KArgs &a, SkShared<EQO> &sh, Im
     const uint32_t lp = (pmask & 1u) ? 0u : 1u;
     auto pr_mine = [&](int pr) { return !split || ((pr < 2) == (ow == 0)); };
     const bool ch_mine = !split || ((lane < 6u) == (ow == 0));      // meter words: lanes 0-1 the master channels, 2 + o the outputs
-    struct OutSt { v2u widx, loading, counter, clip; v2f smooth, vmm; };
+    struct OutSt { v2u widx, loading, counter, clip, rpos; v2f smooth, vmm; };
     OutSt os[kPer];
     bool ow_live[kPer];
 #pragma unroll
     for (int h = 0; h < kPer; ++h) {
         const uint32_t opi = (split ? lp : (uint32_t)ow + (uint32_t)C::emit_waves * h), ocol = (part * kSkPairs + opi) * 2u;
         ow_live[h] = (pmask >> opi) & 1u;
-        os[h].widx = os[h].loading = os[h].counter = os[h].clip = v2u{0u, 0u};
+        os[h].widx = os[h].loading = os[h].counter = os[h].clip = os[h].rpos = v2u{0u, 0u};
         os[h].smooth = os[h].vmm = splat(0.0f);
         if (ow_live[h]) {
             os[h].widx = *reinterpret_cast<const v2u *>(gs0 + (size_t)sm.widx * ROWP + ocol);
             os[h].loading = *reinterpret_cast<const v2u *>(gs0 + (size_t)(sm.mute + 0) * ROWP + ocol);
             os[h].counter = *reinterpret_cast<const v2u *>(gs0 + (size_t)(sm.mute + 1) * ROWP + ocol);
             os[h].smooth = as_v2f(*reinterpret_cast<const v2u *>(gs0 + (size_t)(sm.mute + 2) * ROWP + ocol));
+            os[h].rpos = *reinterpret_cast<const v2u *>(gs0 + (size_t)sm.ring_pos * ROWP + ocol);
         }
     }
     typedef typename SkNum<PP>::type NT;
@@ -749,6 +750,9 @@ __device__ __forceinline__ void sk_outputs(const KArgs &a, SkShared<EQO> &sh, Im
                 sk_st2(gs + (size_t)(sm.mute + 0) * ROWP, os[h].loading, one, two);
                 sk_st2(gs + (size_t)(sm.mute + 1) * ROWP, os[h].counter, one, two);
                 sk_st2(gs + (size_t)(sm.mute + 2) * ROWP, as_v2u(os[h].smooth), one, two);
+                // the leveller is off and its rings are not touched here, but the ring position moves on by the launch's frames as in
+                // every other chain kernel: a stream without the leveller stays on the position of its row's streams that run it
+                sk_st2(gs + (size_t)sm.ring_pos * ROWP, (os[h].rpos + (uint32_t)F) & (uint32_t)(kRingLen - 1), one, two);
             }
             if (one) atomicOr(gs + (size_t)(sm.clip + 0) * ROWP, os[h].clip.x);      // sticky bits: OR-ed into the stream's word (fetch_status ORs the slots)
             if (two) atomicOr(gs + (size_t)(sm.clip + 0) * ROWP + 1, os[h].clip.y);

@@ -136,6 +136,14 @@ constexpr StateMap make_state_map(int flavor) {
     return m;
 }
 
+// Power-on word of state slot `slot`: zero everywhere except the leveller's unity gains (gain_cur, gain_prev) and the mute envelope,
+// preset_mute_smooth_gain = 1.0f (usb_audio.c:457).  The one definition: state_init_kernel (dspi_create) and the power-on kernel
+// (dspi_boot_streams, dspi_boot.hip) both write what it says.
+constexpr uint32_t state_power_on_word(int flavor, int slot) {
+    const StateMap m = make_state_map(flavor);
+    return slot == m.lev + 3 || slot == m.lev + 4 ? (flavor ? 0x3f800000u : 1u << 28) : slot == m.mute + 2 ? 0x3f800000u : 0u;
+}
+
 // pending state mutations of an image, applied to all of its streams before the next packet
 struct StateOps {
     uint32_t reset_band[kMaxCh];   // bit b: zero the state pair of (ch, band b)

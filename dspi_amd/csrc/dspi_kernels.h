@@ -51,6 +51,10 @@ hipError_t launch_eq_taps(bool fma, const DevImage *img, int ch, const float *x,
 
 // ---- PDM sub output (dspi_pdm.hip): per-stream state [n_wg][kPdmStateWords][row]: err err2 x1 x2 y1 y2 err_acc rng fade_in_pos
 constexpr int kPdmStateWords = 9;
+constexpr int kPdmRngWord = 7;
+// power-on word i of a modulator: zero except the dither RNG's seed (pdm_generator.c:63).  The one definition: the modulator's own
+// initialiser (dspi_pdm.hip) and the power-on kernel (dspi_boot_streams, dspi_boot.hip) both write what it says.
+constexpr uint32_t pdm_power_on_word(int i) { return i == kPdmRngWord ? 123456789u : 0u; }
 // active: the context's activity bitmap (one bit per stream) or null = every stream; a paused stream's state and words are not touched
 hipError_t launch_pdm(bool tiled, uint32_t *state, const int32_t *sub, uint32_t *words, uint32_t n_streams, uint32_t n_frames, uint32_t row,
                       uint32_t n_wg, const uint32_t *active, hipStream_t stream);
@@ -96,5 +100,10 @@ hipError_t launch_move_gather(int flavor, uint32_t *state, uint32_t *dlines, uin
                               uint32_t n_items, hipStream_t stream);
 hipError_t launch_move_scatter(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, const uint32_t *items, const uint32_t *colrec,
                                uint32_t n_items, const uint32_t *shift, hipStream_t stream);
+
+// ---- stream boots (dspi_boot_streams; dspi_boot.h: the list; dspi_boot.hip: the kernel) ----
+// Power-on words into the listed columns of the four arrays (pdm may be null: a context that never ran the modulator has no array yet):
+// `items` = n_items BootRowItem in device memory, one per touched row.  Reads nothing but the two position words of each item's target.
+hipError_t launch_boot(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, const uint32_t *items, uint32_t n_items, hipStream_t stream);
 
 }  // namespace dspi

@@ -1472,7 +1472,9 @@ __global__ void state_ops_kernel(const WgItem *items, StateOps ops, uint32_t *st
             const uint32_t unity = FLAVOR ? 0x3f800000u : (1u << 28);
             gs[(size_t)(sm.lev + 0) * ROW] = 0; gs[(size_t)(sm.lev + 1) * ROW] = 0; gs[(size_t)(sm.lev + 2) * ROW] = 0;
             gs[(size_t)(sm.lev + 3) * ROW] = unity; gs[(size_t)(sm.lev + 4) * ROW] = unity;
-            gs[(size_t)sm.ring_pos * ROW] = 0;
+            // (the ring position stays, as the delay write index does below: both rings are zeroed whole and addressed only relative to
+            // it, so the stream is the one the firmware has at position 0 — and a reset addressed to ONE stream, a preset loaded into a
+            // device that has just arrived, does not take its row off the shared-position path)
         }
         if (ops.mute_start) { gs[(size_t)(sm.mute + 0) * ROW] = 1; gs[(size_t)(sm.mute + 1) * ROW] = ops.mute_samples; }
         if (ops.mute_cancel) gs[(size_t)(sm.mute + 0) * ROW] = 0;
@@ -1497,10 +1499,11 @@ __global__ void state_init_kernel(uint32_t *state, uint32_t n_wg) {
     const uint32_t wg = blockIdx.x, col = threadIdx.x;
     if (wg >= n_wg || col >= ROW) return;
     uint32_t *gs = state + (size_t)wg * sm.n_slots * ROW + col;
-    const uint32_t unity = FLAVOR ? 0x3f800000u : (1u << 28);
-    gs[(size_t)(sm.lev + 3) * ROW] = unity;
-    gs[(size_t)(sm.lev + 4) * ROW] = unity;
-    gs[(size_t)(sm.mute + 2) * ROW] = 0x3f800000u;   // preset_mute_smooth_gain = 1.0f (usb_audio.c:457)
+    // (the array was zeroed just before: only the words that are not zero — dspi_image.h state_power_on_word; the slot index is a
+    // compile-time constant in every iteration, so this is the three stores it names)
+#pragma unroll
+    for (int s = 0; s < sm.n_slots; ++s)
+        if (state_power_on_word(FLAVOR, s) != 0u) gs[(size_t)s * ROW] = state_power_on_word(FLAVOR, s);
 }
 
 }  // namespace

@@ -113,15 +113,14 @@ __global__ __launch_bounds__(kPdmThreads) void pdm_kernel(uint32_t *state, const
     gs[7 * row] = rng; gs[8 * row] = fade;
 }
 
-// power-on (init != 0: rng = 123456789, pdm_generator.c:63) or the re-enable path (:241-252: everything but the RNG)
+// power-on (init != 0: pdm_power_on_word, dspi_kernels.h) or the re-enable path (pdm_generator.c:241-252: everything but the RNG)
 __global__ void pdm_reset_kernel(uint32_t *state, uint32_t n_streams, uint32_t row, int32_t only_stream, int init) {
     const uint32_t wg = blockIdx.x, col = threadIdx.x;
     const uint32_t stream = wg * row + col;
     if (col >= row || stream >= n_streams || (only_stream >= 0 && stream != (uint32_t)only_stream)) return;
     uint32_t *gs = state + (size_t)wg * kPdmStateWords * row + col;
     for (int i = 0; i < kPdmStateWords; ++i)
-        if (i != 7) gs[(size_t)i * row] = 0;
-    if (init) gs[7 * row] = 123456789u;
+        if (init || i != kPdmRngWord) gs[(size_t)i * row] = pdm_power_on_word(i);
 }
 
 }  // namespace

@@ -20,6 +20,7 @@ SNAP_REALIGN = 0x100
 RESUME_AS_IS = 0x1
 MOVE_AS_IS = 0x1
 COMPACT_ONE_WAY = 0x1
+BOOT_STREAMS_AS_IS = 0x1
 OUT_TILED = 0x2
 OUT_ENABLED_ONLY = 0x4
 OUT_I2S_SLOTS = 0x8
@@ -118,6 +119,8 @@ def lib() -> C.CDLL:
     if hasattr(L, "dspi_move_streams"):      # (ABI 8 + stream moves: detected by symbol; with it DSPI_MOVE_AS_IS, DSPI_COMPACT_ONE_WAY)
         L.dspi_move_streams.argtypes = [vp, vp, u32, u32]
         L.dspi_plan_compaction.argtypes = [vp, vp, u32, u32]
+    if hasattr(L, "dspi_boot_streams"):      # (ABI 8 + stream boots: detected by symbol; with it DSPI_BOOT_STREAMS_AS_IS)
+        L.dspi_boot_streams.argtypes = [vp, vp, u32, vp, C.c_size_t, u32, C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -422,6 +425,18 @@ class Dspi:
         m = np.zeros((n, 2), dtype=np.uint32)
         if n: self._ck(self.L.dspi_plan_compaction(self.h, m.ctypes.data, n, flags), "plan_compaction")
         return m
+
+    # ---- stream boots (include/dspi.h: a slot is power-cycled inside its running context) ----
+    def boot_streams(self, streams, dump: bytes | None = None, as_is: bool = False) -> int:
+        """dspi_boot_streams: every listed slot becomes a device that has just been powered on — dspi_create's own (dump None) or one that
+        boots from the 48 KB preset area `dump` — on its row's write positions (as_is: DSPI_BOOT_STREAMS_AS_IS, on the power-on positions).
+        Returns preset_boot_load's selection (dspi_load_flash_dump's codes; 48 without a dump).  Works on host-only contexts."""
+        s = np.ascontiguousarray(np.asarray(streams, dtype=np.uint32).reshape(-1))
+        sel = C.c_int(-1)
+        n = self._ck(self.L.dspi_boot_streams(self.h, s.ctypes.data if len(s) else None, len(s), dump, len(dump) if dump is not None else 0,
+                                              BOOT_STREAMS_AS_IS if as_is else 0, C.byref(sel)), "boot_streams")
+        assert n == len(s)
+        return sel.value
 
     def sync(self):
         self._ck(self.L.dspi_sync(self.h), "sync")

@@ -70,7 +70,8 @@ extern "C" {
                               * 8 + snapshots: detect by symbol (dspi_snapshot_sizes, dspi_export_streams, dspi_import_streams; additions only);
                               * 8 + realignment: detect by symbol (dspi_realign_streams; with it DSPI_SNAP_REALIGN and dspi_debug_stream_positions; additions only);
                               * 8 + paused streams: detect by symbol (dspi_pause_streams; with it dspi_resume_streams, dspi_streams_paused, DSPI_RESUME_AS_IS; additions only);
-                              * 8 + stream moves: detect by symbol (dspi_move_streams; with it dspi_plan_compaction, dspi_stream_move, DSPI_MOVE_AS_IS, DSPI_COMPACT_ONE_WAY; additions only) */
+                              * 8 + stream moves: detect by symbol (dspi_move_streams; with it dspi_plan_compaction, dspi_stream_move, DSPI_MOVE_AS_IS, DSPI_COMPACT_ONE_WAY; additions only);
+                              * 8 + stream boots: detect by symbol (dspi_boot_streams; with it DSPI_BOOT_STREAMS_AS_IS; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -390,6 +391,49 @@ typedef struct dspi_stream_move { uint32_t src, dst; } dspi_stream_move;
 #define DSPI_COMPACT_ONE_WAY 0x1u   /* dspi_plan_compaction: paused slots are free, do not preserve them */
 int dspi_move_streams(dspi_ctx *ctx, const dspi_stream_move *moves, uint32_t n, uint32_t flags);
 int dspi_plan_compaction(const dspi_ctx *ctx, dspi_stream_move *moves, uint32_t cap, uint32_t flags);
+
+/* ---- stream boots: a slot is power-cycled inside its running context -------------------------------------------------------------- */
+/* Devices are unplugged and plugged in again, firmware reboots, and a slot that compaction freed (dspi_plan_compaction with
+ * DSPI_COMPACT_ONE_WAY) is where a device that arrives goes.  dspi_create makes power-on state for a whole context, and
+ * dspi_load_flash_dump is a boot only before the first audio; dspi_boot_streams makes it for listed slots of a running context, without a
+ * second context and without moving a record of zeros.
+ *   what the call does  every listed slot becomes a device that has just been powered on; its former occupant is gone.  The list may
+ *                       be in any order.  Returns n.
+ *   dump == NULL        the device dspi_create makes on this context: by default a first boot on an erased flash (the 512-sample mute is
+ *                       armed, then the fade-in), on a DSPI_BOOT_POPULATED_FLASH context the populated flash without a selected preset.
+ *                       len is ignored.
+ *   dump != NULL        the device boots from that preset area (DSPI_FLASH_DUMP_BYTES, laid out as for dspi_load_flash_dump) exactly as
+ *                       a DSPI_BOOT_POPULATED_FLASH context that has processed no audio boots from it — on every context, whether it
+ *                       has processed audio or not.  A boot that writes the flash (no directory, a v1 directory) arms the mute.
+ *   selection           (may be NULL) receives preset_boot_load's code as dspi_load_flash_dump returns it (0..9, 16 + n, 32, 48); 48 for
+ *                       a NULL dump.
+ *   host settings       sample rate 44.1 kHz, UAC1 volume 0 dB and unmuted are power-on values too: the caller sets them afterwards, as
+ *                       a USB host does after enumeration.
+ *   parameters          all listed streams leave their parameter objects and share ONE new object, so a batch of arrivals stays on the
+ *                       shared-parameter kernels.  Pending state operations of the objects they left never reach them; the new
+ *                       object's own (the mute that a flash-writing boot arms) are applied at the next dspi_process commit over the
+ *                       power-on state, the order after dspi_create.  An object that lost its last stream is dropped at that commit.
+ *   run-time state      every state slot goes to its power-on word (unity leveller gains, mute envelope 1.0, zero elsewhere — last
+ *                       peaks and clip slots among them: dspi_get_status answers zeros), every delay line is zeroed at full length,
+ *                       both leveller rings are zeroed, and the PDM modulator words go to their power-on values if the context has run
+ *                       the modulator (otherwise they are power-on values already).
+ *   write positions     zero lines and rings are zero under every rotation, so nothing is rotated: by default a booted stream TAKES the
+ *                       (widx, ring_pos) of its row, and the row stays on the kernels' one-access-per-row path.  A resident is a stream
+ *                       below dspi_num_streams that is active and not in the list, as for moves.  A row's target is the pair of its
+ *                       lowest-numbered resident, read on the device behind the context's earlier work; a row without a resident gets
+ *                       (0, 0).  DSPI_BOOT_STREAMS_AS_IS writes (0, 0) always.
+ *   activity            a property of the slot, as in snapshots: a paused slot stays paused — the new device sits frozen in power-on
+ *                       state until dspi_resume_streams — and an active slot stays active.
+ *   validation          everything is validated before anything is written.  n == 0, a null list, an index at or past
+ *                       dspi_num_streams, a slot listed twice, an undefined flag bit: DSPI_E_INVAL; a non-NULL dump with len below
+ *                       DSPI_FLASH_DUMP_BYTES: DSPI_E_SHORT; the context is bit for bit as it was.
+ *   timing              asynchronous on the context's stream like dspi_move_streams; takes effect at the next dspi_process.
+ *   host-only contexts  the call works there (parameter objects, references, selection): that is what a host-only context is for.
+ *   not touched         the S/PDIF block position, the direct path's statistics, "has processed audio".
+ * Not in scope: choosing which free slot an arrival takes, and per-stream S/PDIF block positions. */
+#define DSPI_BOOT_STREAMS_AS_IS 0x1u   /* keep the power-on write positions (delay write index 0, ring position 0) */
+int dspi_boot_streams(dspi_ctx *ctx, const uint32_t *streams, uint32_t n,
+                      const void *dump, size_t len, uint32_t flags, int *selection);
 
 /* ---- PDM sub output ---------------------------------------------------- */
 /* The consumer of dspi_out.sub: the firmware's 256x oversampled 2nd-order sigma-delta modulator with noise-shaped
