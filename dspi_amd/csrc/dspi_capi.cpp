@@ -32,6 +32,7 @@
 #include "dspi_move.h"
 #include "dspi_plan.h"
 #include "dspi_snapshot.h"
+#include "dspi_spdifpos.h"
 
 using namespace dspi;
 
@@ -57,6 +58,11 @@ struct dspi_ctx {
     uint32_t *d_stream_image = nullptr; size_t d_stream_image_cap = 0;   // image index per stream (per-lane parameter kernel)
     bool launch_dirty = true;
     uint32_t spdif_pos = 0;      // DSPI_OUT_SPDIF: block position of the next call's first frame
+    // dspi_spdif_per_stream: while on, DSPI_OUT_SPDIF encodes stream s at its own position (dspi_spdifpos.h) and spdif_pos above only counts;
+    // the device's copy of the per-stream words goes up behind the context's stream when a call has changed one (upload_spdif_pos)
+    SpdifPos spdif_ps;
+    uint32_t *d_spdif_ps = nullptr; size_t d_spdif_ps_cap = 0;
+    uint32_t *d_spdif_vpos = nullptr; size_t d_spdif_vpos_cap = 0;      // dspi_spdif_encode_v on host buffers: the caller's positions
     bool populated = false;      // DSPI_BOOT_POPULATED_FLASH: the streams are devices whose flash already holds a preset directory
     bool audio_started = false;  // a dspi_process has run: the devices are no longer booting (dspi_load_flash_dump)
     bool no_direct = false;      // DSPI_NO_DIRECT (development / tests, read once at dspi_create): the staged path for small host calls too
@@ -282,6 +288,20 @@ void for_paused_regions(dspi_ctx *c, const CallBuffer &b, F f) {
 }
 // what the kernels get: null while nothing is paused (they then do what they always did)
 const uint32_t *activity(const dspi_ctx *c) { return c->n_paused ? c->d_active : nullptr; }
+// who is paused, for the modules that keep per-stream books (dspi_move.h, dspi_spdifpos.h); null: every slot is active
+const uint8_t *host_activity(const dspi_ctx *c) { return c->n_paused ? c->active.data() : nullptr; }
+
+// per-stream S/PDIF positions: the device's copy of the words as the host has them.  Like upload_activity, behind a synchronisation (no
+// encoder may still be reading the words), and only after a call that changed one: sets, pauses, resumes, moves and boots are rare.
+int upload_spdif_pos(dspi_ctx *c) {
+    if (!c->spdif_ps.dirty && c->d_spdif_ps) return 0;
+    int rc = ensure(c, c->d_spdif_ps, c->d_spdif_ps_cap, (size_t)c->n_streams * 4);
+    if (rc) return rc;
+    HIPCK(c, hipStreamSynchronize(c->hs));
+    HIPCK(c, hipMemcpy(c->d_spdif_ps, c->spdif_ps.word.data(), (size_t)c->n_streams * 4, hipMemcpyHostToDevice));
+    c->spdif_ps.dirty = false;
+    return 0;
+}
 
 int rebuild_assignment(dspi_ctx *c) {
     const size_t ni = c->images.size();
@@ -538,7 +558,7 @@ void dspi_destroy(dspi_ctx *c) {
     if (c->device != DSPI_DEVICE_NONE) {
         (void)hipSetDevice(c->device);
         if (c->hs) (void)hipStreamSynchronize(c->hs);
-        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, (void *)c->d_move, c->d_in,
+        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_spdif_ps, (void *)c->d_spdif_vpos, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, (void *)c->d_move, c->d_in,
                         (void *)c->d_pairs, (void *)c->d_sub, (void *)c->d_peaks, (void *)c->d_clip, (void *)c->d_spdif_words})
             if (p) (void)hipFree(p);
         if (c->h_direct) (void)hipHostFree(c->h_direct);
@@ -939,6 +959,7 @@ int dspi_realign_streams(dspi_ctx *c, uint32_t first, uint32_t count) {
 int dspi_pause_streams(dspi_ctx *c, uint32_t first, uint32_t count) {
     if (!c) return DSPI_E_INVAL;
     if (!snap_range_ok(c, first, count)) return fail(c, DSPI_E_INVAL, "dspi_pause_streams: stream range out of bounds");
+    if (c->spdif_ps.on) c->spdif_ps.pause(first, count, host_activity(c));      // (the S/PDIF position freezes; it is never realigned)
     if (c->active.empty()) c->active.assign(c->n_streams, 1);
     bool changed = false;
     for (uint32_t s = first; s < first + count; s++)
@@ -984,6 +1005,7 @@ int dspi_resume_streams(dspi_ctx *c, uint32_t first, uint32_t count, uint32_t fl
             s = e;
         }
     }
+    if (c->spdif_ps.on) c->spdif_ps.resume(lo, hi - lo + 1, host_activity(c));      // (... and continues from the frozen value)
     for (uint32_t s = lo; s <= hi; s++)
         if (!c->active[s]) { c->active[s] = 1; c->n_paused--; }
     c->launch_dirty = true; c->active_dirty = true; c->paused_runs_dirty = true;
@@ -1078,6 +1100,7 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
     // parameters travel by reference, activity travels with the stream: all sources are read before any destination is written.  A
     // destination that is no source loses its occupant (one reference less); a source that is no destination keeps its own and becomes
     // a paused, frozen copy.  (Such entries exist only where something is paused: `active` is allocated then.)
+    if (c->spdif_ps.on) c->spdif_ps.move(mv.data(), nm, host_activity(c));      // (the S/PDIF position is the device's own counter: it travels too)
     const bool have_active = !c->active.empty();
     std::vector<int32_t> img(nm);
     std::vector<uint8_t> act(nm, 1), is_dst(c->n_streams, 0);
@@ -1139,6 +1162,7 @@ int dspi_boot_streams(dspi_ctx *c, const uint32_t *streams, uint32_t n, const vo
         c->image_refs[(size_t)si]--; si = slot; c->image_refs[(size_t)slot]++;
     }
     c->assignment_dirty = true; c->launch_dirty = true; c->merge_hint = true;
+    if (c->spdif_ps.on) c->spdif_ps.boot(streams, n, host_activity(c));      // a device that has just been powered on sends frame 0 of a block first
     if (selection) *selection = sel;
     return (int)n;
 }
@@ -1233,6 +1257,63 @@ int dspi_spdif_block_pos(dspi_ctx *c, int32_t set) {
     return (int)c->spdif_pos;
 }
 
+// ---- per-stream block positions (dspi_spdifpos.h) ----
+int dspi_spdif_per_stream(dspi_ctx *c, int enable) {
+    if (!c) return DSPI_E_INVAL;
+    if (enable > 0) c->spdif_ps.enable(c->n_streams, c->spdif_pos);
+    else if (enable == 0) c->spdif_ps.disable();
+    return c->spdif_ps.on ? 1 : 0;
+}
+
+int dspi_spdif_stream_pos(dspi_ctx *c, uint32_t first, uint32_t count, const uint32_t *set, uint32_t *get) {
+    if (!c) return DSPI_E_INVAL;
+    if (!c->spdif_ps.on) return fail(c, DSPI_E_INVAL, "dspi_spdif_stream_pos: per-stream positions are off (dspi_spdif_per_stream)");
+    if (!snap_range_ok(c, first, count)) return fail(c, DSPI_E_INVAL, "dspi_spdif_stream_pos: stream range out of bounds");
+    // everything is validated before anything is written
+    if (set) for (uint32_t k = 0; k < count; k++) if (set[k] >= kSpdifBlock) return fail(c, DSPI_E_INVAL, "dspi_spdif_stream_pos: a position is 0..191");
+    if (set) for (uint32_t k = 0; k < count; k++) c->spdif_ps.set(first + k, set[k], host_activity(c));
+    if (get) for (uint32_t k = 0; k < count; k++) get[k] = c->spdif_ps.get(first + k, host_activity(c));
+    return (int)count;
+}
+
+int dspi_spdif_encode_v(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos, uint32_t *subframes, uint32_t flags) {
+    if (!c || !pairs || !subframes || !block_pos || n_frames == 0) return DSPI_E_INVAL;
+    if (flags & ~(DSPI_MEM_DEVICE | DSPI_OUT_TILED)) return fail(c, DSPI_E_INVAL, "dspi_spdif_encode_v: undefined flag bits");
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    const bool tiled = flags & DSPI_OUT_TILED, dev = flags & DSPI_MEM_DEVICE;
+    // host positions are validated before anything is launched; device positions are the kernels' to reduce modulo 192
+    if (!dev) for (uint32_t s = 0; s < c->n_streams; s++) if (block_pos[s] >= kSpdifBlock) return fail(c, DSPI_E_INVAL, "dspi_spdif_encode_v: a position is 0..191");
+    HIPCK(c, hipSetDevice(c->device));
+    const size_t cols = tiled ? (size_t)c->n_wg * c->sm.row : (size_t)c->n_streams;
+    const size_t in_b = cols * c->sm.n_pairs * n_frames * 8, out_b = in_b * 2, pos_b = (size_t)c->n_streams * 4;
+    const int32_t *d_in = pairs;
+    uint32_t *d_out = subframes;
+    const uint32_t *d_pos = block_pos;
+    int rc;
+    if (!dev) {
+        if ((rc = ensure(c, c->d_spdif_in, c->d_spdif_in_cap, in_b)) || (rc = ensure(c, c->d_spdif_out, c->d_spdif_out_cap, out_b)) ||
+            (rc = ensure(c, c->d_spdif_vpos, c->d_spdif_vpos_cap, pos_b))) return rc;
+        HIPCK(c, hipMemcpyAsync(c->d_spdif_in, pairs, in_b, hipMemcpyHostToDevice, c->hs));
+        HIPCK(c, hipMemcpyAsync(c->d_spdif_vpos, block_pos, pos_b, hipMemcpyHostToDevice, c->hs));
+        d_in = c->d_spdif_in; d_out = c->d_spdif_out; d_pos = c->d_spdif_vpos;
+    }
+    // the sample-rate byte: per stream, as in dspi_spdif_encode
+    const uint32_t fs = readable(c, DSPI_ALL_STREAMS).freq;
+    bool one_rate = true;
+    for (size_t i = 0; i < c->images.size(); i++) if (c->image_refs[i] > 0 && c->images[i]->freq != fs) one_rate = false;
+    SpdifRates rates{nullptr, nullptr, 0u};
+    if (!one_rate) {
+        if ((rc = commit_params(c))) return rc;
+        rates = SpdifRates{c->d_images, c->d_stream_image, 0u};
+    }
+    HIPCK(c, launch_spdif(tiled, d_in, d_out, c->n_streams, (uint32_t)c->sm.n_pairs, n_frames, (uint32_t)c->sm.row, c->n_wg, 0u, fs, rates, c->hs, d_pos));
+    if (!dev) {
+        HIPCK(c, hipMemcpyAsync(subframes, c->d_spdif_out, out_b, hipMemcpyDeviceToHost, c->hs));
+        HIPCK(c, hipStreamSynchronize(c->hs));
+    }
+    return DSPI_OK;
+}
+
 int dspi_sync(dspi_ctx *c) {
     if (!c) return DSPI_E_INVAL;
     if (c->device == DSPI_DEVICE_NONE) return DSPI_E_NODEVICE;
@@ -1288,7 +1369,8 @@ static int launch_rows(dspi_ctx *c, KArgs a, const CallLayout &L, uint32_t r0, u
         int rc = launch_paths(c, a, q0, q1);
         if (rc) return rc;
         hipError_t e = launch_spdif(false, c->d_spdif_words, reinterpret_cast<uint32_t *>(subframes + s0 * L.pairs.per), (uint32_t)(s1 - s0), (uint32_t)c->sm.n_pairs,
-                                    (uint32_t)L.frames, row, q1 - q0, c->spdif_pos, 0u, SpdifRates{c->d_images, c->d_stream_image, (uint32_t)s0, activity(c)}, c->hs);
+                                    (uint32_t)L.frames, row, q1 - q0, c->spdif_ps.on ? c->spdif_ps.clock : c->spdif_pos, 0u,
+                                    SpdifRates{c->d_images, c->d_stream_image, (uint32_t)s0, activity(c)}, c->hs, c->spdif_ps.on ? c->d_spdif_ps : nullptr);
         if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string("spdif encoder launch: ") + hipGetErrorString(e));
     }
     return 0;
@@ -1519,12 +1601,13 @@ int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_bloc
     in.n_streams = c->n_streams; in.n_wg = c->n_wg; in.row = (uint32_t)c->sm.row; in.n_ch = (uint32_t)c->sm.n_ch; in.n_out = (uint32_t)c->sm.n_out;
     in.n_pairs = (uint32_t)c->sm.n_pairs; in.n_blocks = n_blocks; in.block_len = block_len; in.bit_depth = (uint32_t)bit_depth; in.flags = flags;
     in.pairs = out->pairs; in.sub = out->sub; in.peaks = out->peaks; in.clip = clip_out; in.no_direct = c->no_direct;
-    in.all_latency = c->flavor != 0;
+    in.all_latency = c->flavor != 0; in.spdif_per_stream = c->spdif_ps.on;
     for (const PathInfo &pi : kPaths)
         if (pi.group != PathGroup::Latency && !c->plan.items[(int)pi.path].empty()) in.all_latency = false;
     const CallLayout L = plan_call(in);
     const bool tiled = flags & DSPI_OUT_TILED, spdif = flags & DSPI_OUT_SPDIF;
     if (spdif && (tiled || (flags & DSPI_OUT_I2S_SLOTS))) return fail(c, DSPI_E_INVAL, "DSPI_OUT_SPDIF goes with neither DSPI_OUT_TILED nor DSPI_OUT_I2S_SLOTS");
+    if (L.spdif_two_pass && c->spdif_ps.on && (rc = upload_spdif_pos(c))) return rc;
 
     KArgs a{};
     a.img = c->d_images; a.stream_image = c->d_stream_image; a.vals = c->d_vals;
@@ -1547,7 +1630,10 @@ int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_bloc
     case CallMem::Direct: rc = process_direct(c, L, a, pcm_in, out, clip_out, flags, call_t0); break;
     case CallMem::Staged: rc = process_staged(c, L, a, pcm_in, out, clip_out, flags); break;
     }
-    if (rc == DSPI_OK && spdif) c->spdif_pos = (uint32_t)((c->spdif_pos + L.frames) % 192u);      // a failed call leaves the block position alone
+    if (rc == DSPI_OK && spdif) {      // a failed call leaves the block positions alone
+        c->spdif_pos = (uint32_t)((c->spdif_pos + L.frames) % 192u);
+        if (c->spdif_ps.on) c->spdif_ps.advance(L.frames);      // every stream that was active in the call; the paused ones hold their own
+    }
     return rc;
 }
 

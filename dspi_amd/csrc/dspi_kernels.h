@@ -66,8 +66,11 @@ hipError_t launch_pdm_reset(uint32_t *state, uint32_t n_streams, uint32_t row, u
 // active (dspi_process's two-pass S/PDIF only, stream-major): the context's activity bitmap, indexed like stream_image; streams whose bit is
 // clear are skipped — nothing of theirs is read or written.  null: every stream (dspi_spdif_encode is stateless per stream and knows no pauses).
 struct SpdifRates { const DevImage *img; const uint32_t *stream_image; uint32_t stream0; const uint32_t *active = nullptr; };
+// stream_pos (dspi_spdif_encode_v; dspi_process while dspi_spdif_per_stream is on): null = every stream starts at block_pos, the kernels of
+// always; else one word per stream in device memory, indexed like stream_image (stream s reads stream_pos[stream0 + s]): the stream's first
+// frame stands at (block_pos + stream_pos[..] mod 192) mod 192, block_pos < 192.
 hipError_t launch_spdif(bool tiled, const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames, uint32_t row,
-                        uint32_t n_wg, uint32_t block_pos, uint32_t fs, const SpdifRates &rates, hipStream_t stream);
+                        uint32_t n_wg, uint32_t block_pos, uint32_t fs, const SpdifRates &rates, hipStream_t stream, const uint32_t *stream_pos = nullptr);
 // I2S slots (audio_i2s_multi.c:217-226): words << 8 for the pairs in pair_mask; same layouts as the pair words themselves
 hipError_t launch_i2s(bool tiled, const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames, uint32_t row,
                       uint32_t n_wg, uint32_t pair_mask, hipStream_t stream);

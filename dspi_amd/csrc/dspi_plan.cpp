@@ -335,7 +335,9 @@ CallLayout plan_call(const CallInput &in) {
     // of the output, not of the stream count) runs the chain into a scratch buffer of pair words, row chunk by row chunk, and the subframe
     // encoder from there into `pairs`: the same words, the block position carried the same way.  The scratch is capped by BYTES: ~1 GiB
     // worth of rows; one workgroup per CU (256 rows) only while that stays within 2 GiB; never less than one row.
-    L.spdif_two_pass = spdif && !in.all_latency && in.pairs;
+    // With per-stream block positions (dspi_spdif_per_stream) every flagged call goes this way, the latency layout's launches too: its
+    // kernels write plain pair words into the scratch (KArgs::pairs_stream0) and the encoder alone knows the streams' positions.
+    L.spdif_two_pass = spdif && in.pairs && (!in.all_latency || in.spdif_per_stream);
     if (L.spdif_two_pass) {
         const size_t row_b = (size_t)in.row * in.n_pairs * F * 8;
         size_t rows = std::max<size_t>(1, ((size_t)1 << 30) / row_b);

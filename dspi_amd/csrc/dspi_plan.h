@@ -116,6 +116,7 @@ struct CallInput {
     bool pairs = false, sub = false, peaks = false, clip = false;      // the outputs the caller passed (clip: with DSPI_OUT_CLIP_FLAGS)
     bool no_direct = false;                           // DSPI_NO_DIRECT
     bool all_latency = false;                         // float, and every non-empty path of the launch plan is on the latency layout
+    bool spdif_per_stream = false;                    // dspi_spdif_per_stream is on: the latency layout's fused encoder knows one position per launch
 };
 
 struct CallBuffer {
@@ -131,7 +132,7 @@ enum class CallMem : uint8_t { Device, Direct, Staged };
 struct CallLayout {
     size_t frames = 0;
     CallBuffer pcm, pairs, sub, peaks, clip;
-    bool spdif_two_pass = false;                      // DSPI_OUT_SPDIF off the latency layout: the chain's pair words, then the encoder
+    bool spdif_two_pass = false;                      // DSPI_OUT_SPDIF off the latency layout, or with per-stream positions: the chain's pair words, then the encoder
     uint32_t two_pass_rows = 0; size_t two_pass_bytes = 0;      // rows per pass, their scratch of pair words
     CallMem mem = CallMem::Staged;
     size_t direct_bytes = 0;                          // the direct area: pcm, pairs, sub, peaks, clip at their `off`

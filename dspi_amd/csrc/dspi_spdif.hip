@@ -24,13 +24,18 @@ namespace {
 
 constexpr uint32_t kFrameSlice = 32;
 
-template <bool TILED>
-__global__ __launch_bounds__(128) void spdif_kernel(const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames,
-                                                     uint32_t row, uint32_t block_pos, uint32_t status_lo, uint32_t status_hi, SpdifRates rates) {
+// Every encoder exists twice: as it always was (one block position for the whole launch), and with per-stream positions (the `_v` kernels:
+// dspi_spdif_encode_v, and dspi_process while dspi_spdif_per_stream is on): PS adds one word per stream, spos[absolute stream] — indexed like
+// SpdifRates::active, from rates.stream0 on —, taken modulo 192 and added to block_pos (the context's clock; 0 for dspi_spdif_encode_v).
+// The bodies are shared and PS is a compile-time switch, so the kernels without it are instruction for instruction what they were.
+template <bool TILED, bool PS>
+__device__ __forceinline__ void spdif_lanes(const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames,
+                                            uint32_t row, uint32_t block_pos, uint32_t status_lo, uint32_t status_hi, const SpdifRates &rates, const uint32_t *spos) {
     const uint32_t wg = blockIdx.x, pair = blockIdx.y, col = threadIdx.x;
     const uint32_t stream = wg * row + col;
     if (col >= row || stream >= n_streams) return;
     if (rates.stream_image) status_lo = spdif_status_lo(rates.img[rates.stream_image[rates.stream0 + stream]].fs_hz);
+    if (PS) block_pos += spos[rates.stream0 + stream] % 192u;      // the lane's own position, loaded once
     const size_t F = n_frames;
     // tiled: outputs 2*pair and 2*pair+1 are separate [frame][R] planes; stream-major: interleaved [frame][2]
     const int32_t *inL = TILED ? pairs + ((size_t)wg * (2 * n_pairs) + 2 * pair) * F * row + col : pairs + ((size_t)stream * n_pairs + pair) * F * 2;
@@ -57,11 +62,22 @@ __global__ __launch_bounds__(128) void spdif_kernel(const int32_t *pairs, uint32
         pos = (pos + 1 == 192u) ? 0u : pos + 1;
     }
 }
+template <bool TILED>
+__global__ __launch_bounds__(128) void spdif_kernel(const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames,
+                                                     uint32_t row, uint32_t block_pos, uint32_t status_lo, uint32_t status_hi, SpdifRates rates) {
+    spdif_lanes<TILED, false>(pairs, out, n_streams, n_pairs, n_frames, row, block_pos, status_lo, status_hi, rates, nullptr);
+}
+template <bool TILED>
+__global__ __launch_bounds__(128) void spdif_kernel_v(const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames,
+                                                       uint32_t row, uint32_t block_pos, uint32_t status_lo, uint32_t status_hi, SpdifRates rates, const uint32_t *spos) {
+    spdif_lanes<TILED, true>(pairs, out, n_streams, n_pairs, n_frames, row, block_pos, status_lo, status_hi, rates, spos);
+}
 
 // Stream-major buffers are contiguous in time per (stream, pair), and a frame's subframes depend on nothing but its own
 // words and its block position: one lane per FRAME here, so a wave reads 512 and writes 1024 contiguous bytes.
-__global__ __launch_bounds__(256) void spdif_kernel_frames(const int32_t *pairs, uint32_t *out, uint64_t total, uint32_t n_frames, uint32_t block_pos,
-                                                          uint32_t status_lo, uint32_t status_hi, SpdifRates rates, uint32_t n_pairs) {
+template <bool PS>
+__device__ __forceinline__ void spdif_frames(const int32_t *pairs, uint32_t *out, uint64_t total, uint32_t n_frames, uint32_t block_pos,
+                                             uint32_t status_lo, uint32_t status_hi, const SpdifRates &rates, uint32_t n_pairs, const uint32_t *spos) {
     const uint64_t idx = (uint64_t)blockIdx.x * 256u + threadIdx.x;      // (stream * n_pairs + pair) * n_frames + frame
     if (idx >= total) return;
     if (rates.active) {      // dspi_process in two passes: a paused stream's words in the scratch are stale, and its subframes are not the call's to write
@@ -69,6 +85,7 @@ __global__ __launch_bounds__(256) void spdif_kernel_frames(const int32_t *pairs,
         if (!((rates.active[s >> 5] >> (s & 31u)) & 1u)) return;
     }
     if (rates.stream_image) status_lo = spdif_status_lo(rates.img[rates.stream_image[rates.stream0 + (uint32_t)(idx / ((uint64_t)n_pairs * n_frames))]].fs_hz);
+    if (PS) block_pos += spos[rates.stream0 + (uint32_t)(idx / ((uint64_t)n_pairs * n_frames))] % 192u;
     const uint32_t f = (uint32_t)(idx % n_frames);
     const uint32_t pos = (block_pos + f) % 192u;
     const uint32_t wl = (uint32_t)pairs[idx * 2], wr = (uint32_t)pairs[idx * 2 + 1];
@@ -79,10 +96,19 @@ __global__ __launch_bounds__(256) void spdif_kernel_frames(const int32_t *pairs,
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
     *reinterpret_cast<u4 *>(out + idx * 4) = u4{l0, h0, l1, h1};
 }
+__global__ __launch_bounds__(256) void spdif_kernel_frames(const int32_t *pairs, uint32_t *out, uint64_t total, uint32_t n_frames, uint32_t block_pos,
+                                                          uint32_t status_lo, uint32_t status_hi, SpdifRates rates, uint32_t n_pairs) {
+    spdif_frames<false>(pairs, out, total, n_frames, block_pos, status_lo, status_hi, rates, n_pairs, nullptr);
+}
+__global__ __launch_bounds__(256) void spdif_kernel_frames_v(const int32_t *pairs, uint32_t *out, uint64_t total, uint32_t n_frames, uint32_t block_pos,
+                                                            uint32_t status_lo, uint32_t status_hi, SpdifRates rates, uint32_t n_pairs, const uint32_t *spos) {
+    spdif_frames<true>(pairs, out, total, n_frames, block_pos, status_lo, status_hi, rates, n_pairs, spos);
+}
 
 // even frame counts: two frames per lane (16 bytes in, 32 bytes out)
-__global__ __launch_bounds__(256) void spdif_kernel_frames2(const int32_t *pairs, uint32_t *out, uint64_t total2, uint32_t half_frames, uint32_t block_pos,
-                                                           uint32_t status_lo, uint32_t status_hi, SpdifRates rates, uint32_t n_pairs) {
+template <bool PS>
+__device__ __forceinline__ void spdif_frames2(const int32_t *pairs, uint32_t *out, uint64_t total2, uint32_t half_frames, uint32_t block_pos,
+                                              uint32_t status_lo, uint32_t status_hi, const SpdifRates &rates, uint32_t n_pairs, const uint32_t *spos) {
     const uint64_t idx = (uint64_t)blockIdx.x * 256u + threadIdx.x;      // (stream * n_pairs + pair) * (n_frames / 2) + frame pair
     if (idx >= total2) return;
     if (rates.active) {      // dspi_process in two passes: a paused stream's words in the scratch are stale, and its subframes are not the call's to write
@@ -90,6 +116,7 @@ __global__ __launch_bounds__(256) void spdif_kernel_frames2(const int32_t *pairs
         if (!((rates.active[s >> 5] >> (s & 31u)) & 1u)) return;
     }
     if (rates.stream_image) status_lo = spdif_status_lo(rates.img[rates.stream_image[rates.stream0 + (uint32_t)(idx / ((uint64_t)n_pairs * half_frames))]].fs_hz);
+    if (PS) block_pos += spos[rates.stream0 + (uint32_t)(idx / ((uint64_t)n_pairs * half_frames))] % 192u;
     const uint32_t f = (uint32_t)(idx % half_frames) * 2u;
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
     const u4 w = *reinterpret_cast<const u4 *>(pairs + idx * 4);
@@ -105,6 +132,14 @@ __global__ __launch_bounds__(256) void spdif_kernel_frames2(const int32_t *pairs
     }
     *reinterpret_cast<u4 *>(out + idx * 8) = o[0];
     *reinterpret_cast<u4 *>(out + idx * 8 + 4) = o[1];
+}
+__global__ __launch_bounds__(256) void spdif_kernel_frames2(const int32_t *pairs, uint32_t *out, uint64_t total2, uint32_t half_frames, uint32_t block_pos,
+                                                           uint32_t status_lo, uint32_t status_hi, SpdifRates rates, uint32_t n_pairs) {
+    spdif_frames2<false>(pairs, out, total2, half_frames, block_pos, status_lo, status_hi, rates, n_pairs, nullptr);
+}
+__global__ __launch_bounds__(256) void spdif_kernel_frames2_v(const int32_t *pairs, uint32_t *out, uint64_t total2, uint32_t half_frames, uint32_t block_pos,
+                                                             uint32_t status_lo, uint32_t status_hi, SpdifRates rates, uint32_t n_pairs, const uint32_t *spos) {
+    spdif_frames2<true>(pairs, out, total2, half_frames, block_pos, status_lo, status_hi, rates, n_pairs, spos);
 }
 
 // ---- I2S slots: pico_audio_i2s_multi/audio_i2s_multi.c:217-226 — the same producer words left-justified (<< 8), L then R.
@@ -155,13 +190,20 @@ hipError_t launch_i2s(bool tiled, const int32_t *pairs, uint32_t *out, uint32_t 
 }
 
 hipError_t launch_spdif(bool tiled, const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames, uint32_t row,
-                        uint32_t n_wg, uint32_t block_pos, uint32_t fs, const SpdifRates &rates, hipStream_t stream) {
+                        uint32_t n_wg, uint32_t block_pos, uint32_t fs, const SpdifRates &rates, hipStream_t stream, const uint32_t *stream_pos) {
     // IEC 60958-3 consumer channel status, 5 bytes (audio_spdif.c:83-89, sample-rate byte :250-256): of `fs` for every stream, or
     // (rates.stream_image set) of each stream's own image
     const uint32_t lo = spdif_status_lo(fs), hi = kSpdifStatusHi;
-    if (tiled) hipLaunchKernelGGL(spdif_kernel<true>, dim3(n_wg, n_pairs, (n_frames + kFrameSlice - 1) / kFrameSlice), dim3(128), 0, stream, pairs, out, n_streams, n_pairs, n_frames, row, block_pos, lo, hi, rates);
+    const dim3 lanes(n_wg, n_pairs, (n_frames + kFrameSlice - 1) / kFrameSlice);
+    const uint64_t total = (uint64_t)n_streams * n_pairs * n_frames;
+    if (stream_pos) {      // per-stream positions: the same three shapes
+        if (tiled) hipLaunchKernelGGL(spdif_kernel_v<true>, lanes, dim3(128), 0, stream, pairs, out, n_streams, n_pairs, n_frames, row, block_pos, lo, hi, rates, stream_pos);
+        else if (n_frames % 2 == 0) hipLaunchKernelGGL(spdif_kernel_frames2_v, dim3((uint32_t)((total / 2 + 255) / 256)), dim3(256), 0, stream, pairs, out, total / 2, n_frames / 2, block_pos, lo, hi, rates, n_pairs, stream_pos);
+        else hipLaunchKernelGGL(spdif_kernel_frames_v, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, pairs, out, total, n_frames, block_pos, lo, hi, rates, n_pairs, stream_pos);
+        return hipGetLastError();
+    }
+    if (tiled) hipLaunchKernelGGL(spdif_kernel<true>, lanes, dim3(128), 0, stream, pairs, out, n_streams, n_pairs, n_frames, row, block_pos, lo, hi, rates);
     else {
-        const uint64_t total = (uint64_t)n_streams * n_pairs * n_frames;
         if (n_frames % 2 == 0) hipLaunchKernelGGL(spdif_kernel_frames2, dim3((uint32_t)((total / 2 + 255) / 256)), dim3(256), 0, stream, pairs, out, total / 2, n_frames / 2, block_pos, lo, hi, rates, n_pairs);
         else hipLaunchKernelGGL(spdif_kernel_frames, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, stream, pairs, out, total, n_frames, block_pos, lo, hi, rates, n_pairs);
     }

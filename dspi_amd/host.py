@@ -121,6 +121,10 @@ def lib() -> C.CDLL:
         L.dspi_plan_compaction.argtypes = [vp, vp, u32, u32]
     if hasattr(L, "dspi_boot_streams"):      # (ABI 8 + stream boots: detected by symbol; with it DSPI_BOOT_STREAMS_AS_IS)
         L.dspi_boot_streams.argtypes = [vp, vp, u32, vp, C.c_size_t, u32, C.POINTER(C.c_int)]
+    if hasattr(L, "dspi_spdif_per_stream"):      # (ABI 8 + per-stream S/PDIF positions: detected by symbol; with it dspi_spdif_stream_pos, dspi_spdif_encode_v)
+        L.dspi_spdif_per_stream.argtypes = [vp, C.c_int]
+        L.dspi_spdif_stream_pos.argtypes = [vp, u32, u32, vp, vp]
+        L.dspi_spdif_encode_v.argtypes = [vp, vp, u32, vp, vp, u32]
     _lib = L
     return L
 
@@ -219,6 +223,22 @@ class Dspi:
     def spdif_block_pos(self, set: int = -1) -> int:
         """dspi_spdif_block_pos: position in the 192-frame channel-status block of the next DSPI_OUT_SPDIF call's first frame."""
         return self._ck(self.L.dspi_spdif_block_pos(self.h, set), "spdif_block_pos")
+
+    def spdif_per_stream(self, enable: int = -1) -> bool:
+        """dspi_spdif_per_stream: per-stream S/PDIF block positions on (1) / off (0), or only read (default).  Returns the mode after the call."""
+        return bool(self._ck(self.L.dspi_spdif_per_stream(self.h, enable), "spdif_per_stream"))
+
+    def spdif_stream_pos(self, first: int = 0, count: int | None = None, set=None) -> np.ndarray:
+        """dspi_spdif_stream_pos: sets (set: `count` values 0..191, optional) and returns the block positions of streams [first, first + count),
+        uint32 [count] — for each stream the position of the first frame of its next DSPI_OUT_SPDIF call.  Mode on only."""
+        count = self.n_streams - first if count is None else count
+        get = np.zeros(count, dtype=np.uint32)
+        v = None
+        if set is not None:
+            v = np.ascontiguousarray(np.asarray(set, dtype=np.uint32).reshape(-1))
+            assert len(v) == count, (len(v), count)
+        self._ck(self.L.dspi_spdif_stream_pos(self.h, first, count, v.ctypes.data if v is not None else None, get.ctypes.data), "spdif_stream_pos")
+        return get
 
     def launch_plan(self) -> dict:
         """dspi_debug_launch_plan: work items per kernel path after the last process call."""
@@ -340,6 +360,25 @@ class Dspi:
         nxt = self.L.dspi_spdif_encode(self.h, pairs_ptr, n_frames, block_pos, out_ptr, MEM_DEVICE | (OUT_TILED if tiled else 0))
         self._ck(min(nxt, 0), "spdif_encode")
         return nxt
+
+    def spdif_encode_v_host(self, pairs: np.ndarray, block_pos, tiled: bool = False) -> np.ndarray:
+        """dspi_spdif_encode_v on host arrays: spdif_host with one starting position per stream, block_pos uint32 [n_streams] (each 0..191).
+        Returns the subframes; the next positions are (block_pos + frames) % 192."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+        pos = np.ascontiguousarray(np.asarray(block_pos, dtype=np.uint32).reshape(-1))
+        assert len(pos) == self.n_streams, (len(pos), self.n_streams)
+        if tiled:
+            nt, O, F, R = pairs.shape
+            out = np.zeros((nt, O // 2, F, 4, R), dtype=np.uint32)
+        else:
+            S, P, F, _ = pairs.shape
+            out = np.zeros((S, P, F, 4), dtype=np.uint32)
+        self._ck(self.L.dspi_spdif_encode_v(self.h, pairs.ctypes.data, F, pos.ctypes.data, out.ctypes.data, OUT_TILED if tiled else 0), "spdif_encode_v")
+        return out
+
+    def spdif_encode_v_device(self, pairs_ptr: int, n_frames: int, block_pos_ptr: int, out_ptr: int, tiled: bool = False):
+        """dspi_spdif_encode_v on device pointers (block_pos: uint32 [n_streams] in device memory, taken modulo 192); asynchronous, see sync()."""
+        self._ck(self.L.dspi_spdif_encode_v(self.h, pairs_ptr, n_frames, block_pos_ptr, out_ptr, MEM_DEVICE | (OUT_TILED if tiled else 0)), "spdif_encode_v")
 
     def pdm_restart(self, stream: int = ALL):
         self._ck(self.L.dspi_pdm_restart(self.h, stream), "pdm_restart")

@@ -71,7 +71,8 @@ extern "C" {
                               * 8 + realignment: detect by symbol (dspi_realign_streams; with it DSPI_SNAP_REALIGN and dspi_debug_stream_positions; additions only);
                               * 8 + paused streams: detect by symbol (dspi_pause_streams; with it dspi_resume_streams, dspi_streams_paused, DSPI_RESUME_AS_IS; additions only);
                               * 8 + stream moves: detect by symbol (dspi_move_streams; with it dspi_plan_compaction, dspi_stream_move, DSPI_MOVE_AS_IS, DSPI_COMPACT_ONE_WAY; additions only);
-                              * 8 + stream boots: detect by symbol (dspi_boot_streams; with it DSPI_BOOT_STREAMS_AS_IS; additions only) */
+                              * 8 + stream boots: detect by symbol (dspi_boot_streams; with it DSPI_BOOT_STREAMS_AS_IS; additions only);
+                              * 8 + per-stream S/PDIF positions: detect by symbol (dspi_spdif_per_stream; with it dspi_spdif_stream_pos, dspi_spdif_encode_v; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -260,7 +261,9 @@ int dspi_sync(dspi_ctx *ctx);
  *           long range can be moved in chunks: export / import sub-ranges, each with its own head.
  * A snapshot is a HAND-OVER format, not an archive: only a library of the same build (same fingerprint) takes it.
  * What does NOT travel (per context, not per stream): the S/PDIF block position (dspi_spdif_block_pos), the direct path's polling
- * statistics.  "Has processed audio" does: after an import of running devices the context no longer treats dspi_load_flash_dump as a boot.
+ * statistics.  A stream's OWN S/PDIF block position (dspi_spdif_per_stream below) does not travel either — the record and head formats and
+ * the fingerprint know nothing of it, and an import leaves the slot's position as it is —: a caller that migrates a device carries it with
+ * dspi_spdif_stream_pos, get on the source context, set on the destination.  "Has processed audio" does: after an import of running devices the context no longer treats dspi_load_flash_dump as a boot.
  * With DSPI_MEM_DEVICE the calls are asynchronous on the context's stream like dspi_process: between two contexts, dspi_sync the
  * source after the export and before the import reads `state` (the import's own stream does not wait for the source's).  Without
  * the flag the calls stage through device memory in chunks and return when the bytes are in place.  Flags other than
@@ -430,7 +433,9 @@ int dspi_plan_compaction(const dspi_ctx *ctx, dspi_stream_move *moves, uint32_t 
  *   timing              asynchronous on the context's stream like dspi_move_streams; takes effect at the next dspi_process.
  *   host-only contexts  the call works there (parameter objects, references, selection): that is what a host-only context is for.
  *   not touched         the S/PDIF block position, the direct path's statistics, "has processed audio".
- * Not in scope: choosing which free slot an arrival takes, and per-stream S/PDIF block positions. */
+ *                       (With dspi_spdif_per_stream on, the listed slots' own positions go to 0, with and without DSPI_BOOT_STREAMS_AS_IS: a
+ *                       device that has just been powered on sends frame 0 of a block, preamble Z, first; see there.)
+ * Not in scope: choosing which free slot an arrival takes. */
 #define DSPI_BOOT_STREAMS_AS_IS 0x1u   /* keep the power-on write positions (delay write index 0, ring position 0) */
 int dspi_boot_streams(dspi_ctx *ctx, const uint32_t *streams, uint32_t n,
                       const void *dump, size_t len, uint32_t flags, int *selection);
@@ -462,6 +467,49 @@ int dspi_spdif_encode(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, ui
 /* DSPI_OUT_SPDIF: the position in the 192-frame block of the next dspi_process call's first frame (0 after dspi_create, then advanced by
  * every call made with the flag).  set in 0..191 sets it first; set < 0 only reads.  Returns the position or a negative DSPI_E_*. */
 int dspi_spdif_block_pos(dspi_ctx *ctx, int32_t set);
+/* ---- per-stream S/PDIF block positions: for contexts whose devices come and go ------------------------------------------------------ */
+/* One position per context is right while every stream takes part in every call from dspi_create on.  A paused device shifts nothing out
+ * and must continue its block where its last frame left it; a device made by dspi_boot_streams starts a block; a stream moved or migrated
+ * from elsewhere has a history of its own.  The Z preamble and the 40 channel-status bits are addressed by position, so a receiver of a
+ * stream stamped with its neighbours' position sees blocks of the wrong length and a torn channel status.
+ * Per-stream positions are a MODE OF THE CONTEXT, off after dspi_create.  Off, every call behaves and performs as it always did.
+ *
+ * dspi_spdif_per_stream(ctx, enable)   enable < 0 only reads.  enable = 1 while off: every stream's position becomes the context's current
+ *                       one (dspi_spdif_block_pos), so turning the mode on in mid-run changes no word; while on: nothing changes.
+ *                       enable = 0: the per-stream positions are dropped.  Returns the mode after the call (0 / 1) or a negative DSPI_E_*.
+ *                       Works on host-only contexts.  In BOTH modes the context's own value goes on advancing with every DSPI_OUT_SPDIF
+ *                       call exactly as before (all-paused calls included), and dspi_spdif_block_pos reads and sets that value; while the
+ *                       mode is on it is not used for encoding.
+ * dspi_spdif_stream_pos(ctx, first, count, set, get)   mode on only (off: DSPI_E_INVAL).  set (may be NULL): count values, each 0..191,
+ *                       for streams [first, first + count); get (may be NULL): the positions after the set — for each stream the position
+ *                       of the first frame of its next DSPI_OUT_SPDIF call.  Host memory always.  Everything is validated before anything
+ *                       is written: a range past dspi_num_streams, a count of 0 or a value >= 192 is DSPI_E_INVAL and leaves the context
+ *                       as it was.  Returns count.  Works on host-only contexts.
+ * With the mode on:
+ *   dspi_process        with DSPI_OUT_SPDIF, frame f of stream s is encoded at (pos_s + f) mod 192, and after a successful call pos_s has
+ *                       advanced by the call's frames for every stream that was ACTIVE in it.  Paused streams keep theirs, a failed call
+ *                       moves nobody, calls without the flag move nobody.  Such calls always run in two passes — the chain's pair words
+ *                       into a scratch, then the subframe encoder —, the launches of the latency layout too, whose fused encoder knows one
+ *                       position per launch (a fused per-stream encoder is left out; profiles/spdif_pos.md has the price).  So with
+ *                       DSPI_OUT_ENABLED_ONLY the silent pairs carry the subframes of silence at the stream's own position.
+ *   pause / resume      the position freezes and continues from the frozen value.  It is never realigned: it is the device's own
+ *                       counter, not a property of the row.
+ *   dspi_move_streams   the position travels with the stream, for all entries at once: pos[dst] := old pos[src].  An open-end source
+ *                       keeps its value as a frozen copy.
+ *   dspi_boot_streams   the listed slots go to 0, with and without DSPI_BOOT_STREAMS_AS_IS; the first frame after the boot carries preamble Z.
+ *   snapshots           the position does not travel and an import leaves the slot's position alone (see the snapshot section).
+ *   untouched           dspi_realign_streams, dspi_pdm_modulate, dspi_i2s_encode, dspi_spdif_encode.
+ *
+ * dspi_spdif_encode_v is dspi_spdif_encode with one starting position per stream: block_pos = uint32 [dspi_num_streams] (with
+ * DSPI_OUT_TILED too: the position of tile t, column c is block_pos[t * R + c]; columns past dspi_num_streams have none and are not
+ * encoded), host memory without DSPI_MEM_DEVICE and device memory with it, like the other two pointers.  Host values are validated
+ * (each < 192, else DSPI_E_INVAL) before anything is launched; device values are taken modulo 192.  Stateless, independent of the mode and
+ * unaware of pauses, like dspi_spdif_encode; the sample-rate byte is per stream as there.  Flags other than DSPI_MEM_DEVICE and
+ * DSPI_OUT_TILED are refused.  Returns DSPI_OK or a negative DSPI_E_*; the next positions, (block_pos[s] + n_frames) mod 192, are the
+ * caller's arithmetic. */
+int dspi_spdif_per_stream(dspi_ctx *ctx, int enable);
+int dspi_spdif_stream_pos(dspi_ctx *ctx, uint32_t first, uint32_t count, const uint32_t *set, uint32_t *get);
+int dspi_spdif_encode_v(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos, uint32_t *subframes, uint32_t flags);
 /* ---- I2S slots ----------------------------------------------------------- */
 /* An output slot switched to I2S (REQ_SET_OUTPUT_TYPE 0xC0 / output_types[] of a preset, config.h:286-287) takes the same
  * words as an S/PDIF slot and left-justifies them into 32-bit I2S slots, L then R, MSB first on the wire
