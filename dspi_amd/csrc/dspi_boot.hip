@@ -79,9 +79,9 @@ __global__ __launch_bounds__(kBootThreads) void boot_kernel(const BootKArgs a) {
 
 }  // namespace
 
-hipError_t launch_boot(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, const uint32_t *items, uint32_t n_items, hipStream_t stream) {
+hipError_t launch_boot(int flavor, const StateArrays &arr, const uint32_t *items, uint32_t n_items, hipStream_t stream) {
     if (n_items == 0) return hipSuccess;
-    const BootKArgs a{state, dlines, ring, pdm, reinterpret_cast<const BootRowItem *>(items)};
+    const BootKArgs a{arr.state, arr.dlines, arr.ring, arr.pdm, reinterpret_cast<const BootRowItem *>(items)};
     const dim3 grid(n_items, kBootParts);
     if (flavor) hipLaunchKernelGGL((boot_kernel<128>), grid, dim3(kBootThreads), 0, stream, a);
     else hipLaunchKernelGGL((boot_kernel<64>), grid, dim3(kBootThreads), 0, stream, a);

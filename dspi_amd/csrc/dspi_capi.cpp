@@ -133,6 +133,20 @@ int fail(dspi_ctx *c, int code, const std::string &msg) { if (c) c->err = msg; r
 
 bool valid_stream(const dspi_ctx *c, int32_t s) { return s == DSPI_ALL_STREAMS || (s >= 0 && (uint32_t)s < c->n_streams); }
 
+// The books of the parameter objects.  add_image appends one that no stream uses yet (the next commit uploads it) and returns its slot;
+// assign_image points a stream at a slot.  An object that loses its last stream keeps its slot until the fold-back pass drops it
+// (merge_images): a caller that can cause that asks for the pass (merge_hint).
+int32_t add_image(dspi_ctx *c, std::unique_ptr<Params> p) {
+    p->dirty = true;
+    c->images.push_back(std::move(p)); c->image_refs.push_back(0);
+    return (int32_t)c->images.size() - 1;
+}
+void assign_image(dspi_ctx *c, size_t stream, int32_t slot) {
+    int32_t &si = c->stream_image[stream];
+    c->image_refs[(size_t)si]--; si = slot; c->image_refs[(size_t)slot]++;
+    c->assignment_dirty = true;
+}
+
 // parameter object to mutate for `stream` (copy-on-write when shared)
 Params *writable(dspi_ctx *c, int32_t stream) {
     int32_t idx = c->stream_image[(size_t)stream];
@@ -288,8 +302,18 @@ void for_paused_regions(dspi_ctx *c, const CallBuffer &b, F f) {
 }
 // what the kernels get: null while nothing is paused (they then do what they always did)
 const uint32_t *activity(const dspi_ctx *c) { return c->n_paused ? c->d_active : nullptr; }
-// who is paused, for the modules that keep per-stream books (dspi_move.h, dspi_spdifpos.h); null: every slot is active
+// who is paused, for the modules that keep per-stream books (dspi_move.h, dspi_boot.h, dspi_spdifpos.h); null: every slot is active
 const uint8_t *host_activity(const dspi_ctx *c) { return c->n_paused ? c->active.data() : nullptr; }
+// The books of the paused streams: set_active writes a slot's byte (`active` is allocated by the first pause) and keeps n_paused; after a
+// call that changed one, activity_changed: the lists are rebuilt and the bitmap goes up at the next commit, the paused runs are found again.
+void set_active(dspi_ctx *c, uint32_t s, bool on) {
+    if ((c->active[s] != 0) == on) return;
+    c->active[s] = on ? 1 : 0;
+    if (on) c->n_paused--; else c->n_paused++;
+}
+void activity_changed(dspi_ctx *c) { c->launch_dirty = true; c->active_dirty = true; c->paused_runs_dirty = true; }
+// the four per-stream arrays, for the launchers that address all of them (d_pdm: null until pdm_state has run)
+StateArrays state_arrays(const dspi_ctx *c) { return StateArrays{c->d_state, c->d_dlines, c->d_ring, c->d_pdm}; }
 
 // per-stream S/PDIF positions: the device's copy of the words as the host has them.  Like upload_activity, behind a synchronisation (no
 // encoder may still be reading the words), and only after a call that changed one: sets, pauses, resumes, moves and boots are rare.
@@ -763,6 +787,14 @@ static int pdm_state(dspi_ctx *c) {
     return 0;
 }
 
+// host buffers of the stand-alone encoders (PDM, S/PDIF, I2S): the words come down from their staging buffer and the call waits for them
+// (the way up stays each encoder's own: what goes up besides the input, and what is cleared, differs in every one)
+static int stage_down(dspi_ctx *c, void *host, const void *staged, size_t bytes) {
+    HIPCK(c, hipMemcpyAsync(host, staged, bytes, hipMemcpyDeviceToHost, c->hs));
+    HIPCK(c, hipStreamSynchronize(c->hs));
+    return 0;
+}
+
 int dspi_pdm_modulate(dspi_ctx *c, const int32_t *sub, uint32_t n_frames, uint32_t *words, uint32_t flags) {
     if (!c || !sub || !words || n_frames == 0) return DSPI_E_INVAL;
     if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
@@ -782,11 +814,7 @@ int dspi_pdm_modulate(dspi_ctx *c, const int32_t *sub, uint32_t n_frames, uint32
         if (c->n_paused) HIPCK(c, hipMemsetAsync(c->d_pdm_out, 0, out_b, c->hs));      // paused streams' words stay unwritten: the staging buffer goes back whole, with zeros there
     }
     HIPCK(c, launch_pdm(tiled, c->d_pdm, d_in, d_out, c->n_streams, n_frames, (uint32_t)c->sm.row, c->n_wg, activity(c), c->hs));
-    if (!dev) {
-        HIPCK(c, hipMemcpyAsync(words, c->d_pdm_out, out_b, hipMemcpyDeviceToHost, c->hs));
-        HIPCK(c, hipStreamSynchronize(c->hs));
-    }
-    return DSPI_OK;
+    return dev ? DSPI_OK : stage_down(c, words, c->d_pdm_out, out_b);
 }
 
 int dspi_pdm_restart(dspi_ctx *c, int32_t stream) {
@@ -820,10 +848,23 @@ static uint32_t snap_chunk_end(const dspi_ctx *c, uint32_t s, uint32_t end) {
     return (uint32_t)std::min<uint64_t>(end, ((uint64_t)s / row + rows) * row);
 }
 
+// What a call that takes run-time state through the records does first: the context's device, the modulators' words (the records carry
+// them out and back in; a context that never ran the modulator hands over its power-on words), scratch for `records` records and, for a
+// call that rotates, the shift table — sized for the whole context once: a later, larger call never reallocates it under work in flight.
+static int snap_prepare(dspi_ctx *c, size_t records, bool shifts) {
+    HIPCK(c, hipSetDevice(c->device));
+    int rc = pdm_state(c);
+    if (rc || (rc = ensure(c, c->d_snap, c->d_snap_cap, records * snap_state_bytes(c->flavor, 1)))) return rc;
+    return shifts ? ensure(c, c->d_snap_shift, c->d_snap_shift_cap, (size_t)c->n_streams * 8) : 0;
+}
+// the context's arrays of streams [first, first + count) -> records, on its stream
+static hipError_t snap_gather(dspi_ctx *c, uint32_t *records, uint32_t first, uint32_t count) {
+    return launch_snapshot(c->flavor, false, state_arrays(c), records, first, count, c->hs);
+}
 // records -> the context's arrays on its stream, as they are or realigned to their rows (dspi_snapshot.h snap_row_target)
 static hipError_t snap_scatter(dspi_ctx *c, bool realign, uint32_t *records, uint32_t first, uint32_t count) {
-    if (realign) return launch_snapshot_realign(c->flavor, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, records, first, count, c->n_streams, c->d_snap_shift, c->hs);
-    return launch_snapshot(c->flavor, true, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, records, first, count, c->hs);
+    if (realign) return launch_snapshot_realign(c->flavor, state_arrays(c), records, first, count, c->n_streams, c->d_snap_shift, c->hs);
+    return launch_snapshot(c->flavor, true, state_arrays(c), records, first, count, c->hs);
 }
 
 int dspi_snapshot_sizes(const dspi_ctx *c, uint32_t first, uint32_t count, size_t *head_bytes, size_t *state_bytes) {
@@ -847,8 +888,7 @@ int dspi_export_streams(dspi_ctx *c, uint32_t first, uint32_t count, const dspi_
     const size_t hb = snap_head_bytes(count, (uint32_t)used.size()), sb = snap_state_bytes(c->flavor, count);
     if (snap->head_bytes < hb || snap->state_bytes < sb) return fail(c, DSPI_E_SHORT, "dspi_export_streams: buffer too small (dspi_snapshot_sizes)");
     if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no run-time state to export");
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = pdm_state(c);      // (a context that never ran the modulator hands over its power-on words)
+    int rc = snap_prepare(c, 0, false);      // (host buffers: the chunks below size the scratch, each for itself)
     if (rc) return rc;
     // the head: header, the range's distinct parameter objects as they are (pending state operations included), the streams' indices
     unsigned char *const head = static_cast<unsigned char *>(snap->head);
@@ -859,14 +899,14 @@ int dspi_export_streams(dspi_ctx *c, uint32_t first, uint32_t count, const dspi_
     memcpy(head + sizeof h + used.size() * snap_params_stride(), index.data(), (size_t)count * 4);
     snap_seal(head);
     if (dev) {
-        HIPCK(c, launch_snapshot(c->flavor, false, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, static_cast<uint32_t *>(snap->state), first, count, c->hs));
+        HIPCK(c, snap_gather(c, static_cast<uint32_t *>(snap->state), first, count));
         return (int)count;
     }
     const size_t rec = snap_state_bytes(c->flavor, 1);
     for (uint32_t s = first, end = first + count; s < end;) {
         const uint32_t e = snap_chunk_end(c, s, end);
         if ((rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)(e - s) * rec))) return rc;
-        HIPCK(c, launch_snapshot(c->flavor, false, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, s, e - s, c->hs));
+        HIPCK(c, snap_gather(c, c->d_snap, s, e - s));
         HIPCK(c, hipMemcpyAsync(static_cast<char *>(snap->state) + (size_t)(s - first) * rec, c->d_snap, (size_t)(e - s) * rec, hipMemcpyDeviceToHost, c->hs));
         HIPCK(c, hipStreamSynchronize(c->hs));
         s = e;
@@ -887,13 +927,9 @@ int dspi_import_streams(dspi_ctx *c, uint32_t first, const dspi_snapshot *snap, 
     const bool dev = flags & DSPI_MEM_DEVICE, realign = flags & DSPI_SNAP_REALIGN;
     if (dev && (reinterpret_cast<uintptr_t>(snap->state) & 15u)) return fail(c, DSPI_E_INVAL, "dspi_import_streams: device state buffer must be 16-byte aligned");
     if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no run-time state to import into");
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = pdm_state(c);
+    int rc = snap_prepare(c, dev ? 0 : snap_chunk_end(c, first, first + count) - first, realign);
     if (rc) return rc;
     const size_t rec = snap_state_bytes(c->flavor, 1);
-    if (!dev && (rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)(snap_chunk_end(c, first, first + count) - first) * rec))) return rc;
-    // (the shift table is sized for the whole context once: a later, larger import never reallocates it under work still in flight)
-    if (realign && (rc = ensure(c, c->d_snap_shift, c->d_snap_shift_cap, (size_t)c->n_streams * 8))) return rc;
     // parameters: the streams leave their images, the imported objects are appended dirty, and the fold-back pass (merge_images, at the
     // next commit) drops what nobody uses any more and folds equal objects — the imported ones among themselves and into images already
     // here.  Tiles, launch plan, alpha list and pending state operations follow from the ordinary commit.
@@ -901,19 +937,15 @@ int dspi_import_streams(dspi_ctx *c, uint32_t first, const dspi_snapshot *snap, 
     for (uint32_t i = 0; i < h.n_images; i++) {
         auto p = std::make_unique<Params>(*c->images[0]);
         memcpy(static_cast<void *>(p.get()), snap_params(snap->head, i), sizeof(Params));
-        p->dirty = true;
-        c->images.push_back(std::move(p)); c->image_refs.push_back(0);
+        add_image(c, std::move(p));
     }
     const unsigned char *idx = snap_params(snap->head, h.n_images);
     for (uint32_t k = 0; k < count; k++) {
         uint32_t im;
         memcpy(&im, idx + (size_t)k * 4, 4);
-        int32_t &si = c->stream_image[(size_t)first + k];
-        c->image_refs[(size_t)si]--;
-        si = (int32_t)(base + im);
-        c->image_refs[(size_t)si]++;
+        assign_image(c, (size_t)first + k, (int32_t)(base + im));
     }
-    c->assignment_dirty = true; c->merge_hint = true;
+    c->merge_hint = true;
     if (h.flags & kSnapAudioStarted) c->audio_started = true;      // running devices arrived: dspi_load_flash_dump is no boot any more
     // run-time state, behind whatever the context's stream still has to do (a realigning import reads its rows' resident neighbours
     // there, on the device: their positions are what that work leaves)
@@ -936,19 +968,15 @@ int dspi_realign_streams(dspi_ctx *c, uint32_t first, uint32_t count) {
     if (!c) return DSPI_E_INVAL;
     if (!snap_range_ok(c, first, count)) return fail(c, DSPI_E_INVAL, "dspi_realign_streams: stream range out of bounds");
     if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no run-time state to realign");
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = pdm_state(c);      // (the records carry the modulators' words out and back in)
-    if (rc) return rc;
-    const size_t rec = snap_state_bytes(c->flavor, 1);
     // scratch for a full chunk and the whole context's shifts, once, before anything is enqueued: the loop below never reallocates (a
     // hipFree would wait for the device) and the call stays asynchronous
-    if ((rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)snap_chunk_rows(c) * (uint32_t)c->sm.row * rec))) return rc;
-    if ((rc = ensure(c, c->d_snap_shift, c->d_snap_shift_cap, (size_t)c->n_streams * 8))) return rc;
+    int rc = snap_prepare(c, (size_t)snap_chunk_rows(c) * (uint32_t)c->sm.row, true);
+    if (rc) return rc;
     // run-time state only, chunk by chunk through the records' scratch, all on the context's stream: out as it is, back in rotated.  A
     // chunk holds whole rows of the range, so its rows' targets are those of the whole range.
     for (uint32_t s = first, end = first + count; s < end;) {
         const uint32_t e = snap_chunk_end(c, s, end);
-        HIPCK(c, launch_snapshot(c->flavor, false, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, s, e - s, c->hs));
+        HIPCK(c, snap_gather(c, c->d_snap, s, e - s));
         HIPCK(c, snap_scatter(c, true, c->d_snap, s, e - s));
         s = e;
     }
@@ -961,10 +989,9 @@ int dspi_pause_streams(dspi_ctx *c, uint32_t first, uint32_t count) {
     if (!snap_range_ok(c, first, count)) return fail(c, DSPI_E_INVAL, "dspi_pause_streams: stream range out of bounds");
     if (c->spdif_ps.on) c->spdif_ps.pause(first, count, host_activity(c));      // (the S/PDIF position freezes; it is never realigned)
     if (c->active.empty()) c->active.assign(c->n_streams, 1);
-    bool changed = false;
-    for (uint32_t s = first; s < first + count; s++)
-        if (c->active[s]) { c->active[s] = 0; c->n_paused++; changed = true; }
-    if (changed) { c->launch_dirty = true; c->active_dirty = true; c->paused_runs_dirty = true; }      // the lists are rebuilt and the bitmap goes up at the next commit
+    const uint32_t before = c->n_paused;
+    for (uint32_t s = first; s < first + count; s++) set_active(c, s, false);
+    if (c->n_paused != before) activity_changed(c);
     return (int)count;
 }
 
@@ -983,13 +1010,9 @@ int dspi_resume_streams(dspi_ctx *c, uint32_t first, uint32_t count, uint32_t fl
         // state only, through the records' scratch like dspi_realign_streams — out as it is, back in rotated —, on the context's stream.  The
         // rule reads the bitmap as it stood BEFORE this call: when pauses or resumes were made since the last dspi_process the device's copy
         // is brought up to date first (that upload synchronises; otherwise the call only enqueues).
-        HIPCK(c, hipSetDevice(c->device));
-        int rc = pdm_state(c);
-        if (rc) return rc;
-        const size_t rec = snap_state_bytes(c->flavor, 1);
-        if ((rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)snap_chunk_rows(c) * (uint32_t)c->sm.row * rec))) return rc;
-        if ((rc = ensure(c, c->d_snap_shift, c->d_snap_shift_cap, (size_t)c->n_streams * 8))) return rc;
-        if ((rc = upload_activity(c))) return rc;
+        // (Scratch for a full chunk, once, before anything is enqueued, as there.)
+        int rc = snap_prepare(c, (size_t)snap_chunk_rows(c) * (uint32_t)c->sm.row, true);
+        if (rc || (rc = upload_activity(c))) return rc;
         // Only rows that hold a stream to resume go through the scratch: a piece = [s, e) inside one scratch chunk, from the first such
         // stream to the end of the last such row of the chunk (cut at hi); rows between the pieces are not touched.
         const uint32_t row = (uint32_t)c->sm.row;
@@ -999,16 +1022,14 @@ int dspi_resume_streams(dspi_ctx *c, uint32_t first, uint32_t count, uint32_t fl
             const uint32_t ce = snap_chunk_end(c, s, end);
             uint32_t e = s + 1;
             for (uint32_t t = s; t < ce; t++) if (!c->active[t]) e = std::min(ce, (t / row + 1) * row);
-            HIPCK(c, launch_snapshot(c->flavor, false, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, s, e - s, c->hs));
-            HIPCK(c, launch_snapshot_resume(c->flavor, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, s, e - s, c->n_streams, c->d_active, lo, hi - lo + 1,
-                                            c->d_snap_shift, c->hs));
+            HIPCK(c, snap_gather(c, c->d_snap, s, e - s));
+            HIPCK(c, launch_snapshot_realign(c->flavor, state_arrays(c), c->d_snap, s, e - s, c->n_streams, c->d_snap_shift, c->hs, c->d_active, lo, hi - lo + 1));
             s = e;
         }
     }
     if (c->spdif_ps.on) c->spdif_ps.resume(lo, hi - lo + 1, host_activity(c));      // (... and continues from the frozen value)
-    for (uint32_t s = lo; s <= hi; s++)
-        if (!c->active[s]) { c->active[s] = 1; c->n_paused--; }
-    c->launch_dirty = true; c->active_dirty = true; c->paused_runs_dirty = true;
+    for (uint32_t s = lo; s <= hi; s++) set_active(c, s, true);
+    activity_changed(c);
     return (int)count;
 }
 
@@ -1025,7 +1046,6 @@ int dspi_streams_paused(const dspi_ctx *c, uint32_t first, uint32_t count, uint8
 
 // ---- stream moves (dspi_move.h: validation, compaction rule, targets, batch schedule; dspi_snapshot.hip: the list-addressed kernels) ----
 static_assert(sizeof(dspi_stream_move) == sizeof(StreamMove) && offsetof(dspi_stream_move, dst) == offsetof(StreamMove, dst), "dspi_stream_move is StreamMove");
-static const uint8_t *move_activity(const dspi_ctx *c) { return c->n_paused ? c->active.data() : nullptr; }      // (null: every slot is active)
 
 // one call's work lists into device memory, behind the context's earlier work
 static int move_upload(dspi_ctx *c, const std::vector<uint32_t> &words) {
@@ -1052,25 +1072,22 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
     if (flags & ~DSPI_MOVE_AS_IS) return fail(c, DSPI_E_INVAL, "dspi_move_streams: undefined flag bits");
     // everything is validated before anything is written
     const StreamMove *list = reinterpret_cast<const StreamMove *>(moves);
-    if (const char *why = move_validate(list, n, c->n_streams, move_activity(c))) return fail(c, DSPI_E_INVAL, std::string("dspi_move_streams: ") + why);
+    if (const char *why = move_validate(list, n, c->n_streams, host_activity(c))) return fail(c, DSPI_E_INVAL, std::string("dspi_move_streams: ") + why);
     if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no run-time state to move");
     std::vector<StreamMove> mv;
     for (uint32_t i = 0; i < n; i++) if (list[i].src != list[i].dst) mv.push_back(list[i]);
     if (mv.empty()) return 0;
     const uint32_t nm = (uint32_t)mv.size(), row = (uint32_t)c->sm.row;
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = pdm_state(c);      // (the records carry the modulators' words along)
-    if (rc) return rc;
     const uint32_t cap = c->move_batch ? c->move_batch : snap_chunk_rows(c) * row;
-    if ((rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)cap * snap_state_bytes(c->flavor, 1)))) return rc;
     const bool realign = !(flags & DSPI_MOVE_AS_IS);
-    if (realign && (rc = ensure(c, c->d_snap_shift, c->d_snap_shift_cap, (size_t)c->n_streams * 8))) return rc;
+    int rc = snap_prepare(c, cap, realign);
+    if (rc) return rc;
     // the call's work lists, one upload: the targets (every shift is computed once, by one launch, before anything is written: batches
     // cannot disagree), then per batch the gather's and the scatter's row items and their columns' record indices
     const std::vector<MoveBatch> batches = move_schedule(mv.data(), nm, cap);
     std::vector<uint32_t> words;
     if (realign) {
-        const std::vector<MoveTarget> t = move_targets(mv.data(), nm, c->n_streams, row, move_activity(c));
+        const std::vector<MoveTarget> t = move_targets(mv.data(), nm, c->n_streams, row, host_activity(c));
         words.resize((t.size() * 3 + 3) & ~(size_t)3);
         memcpy(words.data(), t.data(), t.size() * sizeof(MoveTarget));
     }
@@ -1092,10 +1109,9 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
     // run-time state, on the context's stream, behind whatever it still has to do
     if (realign) HIPCK(c, launch_move_targets(c->flavor, c->d_state, c->d_move, nm, c->d_snap_shift, c->hs));
     for (const Span &sp : spans) {
-        HIPCK(c, launch_move_gather(c->flavor, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, c->d_move + items_at + sp.g0 * 4, c->d_move + colrec_at + sp.g0 * row,
-                                    (uint32_t)(sp.g1 - sp.g0), c->hs));
-        HIPCK(c, launch_move_scatter(c->flavor, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_snap, c->d_move + items_at + sp.g1 * 4, c->d_move + colrec_at + sp.g1 * row,
-                                     (uint32_t)(sp.s1 - sp.g1), realign ? c->d_snap_shift : nullptr, c->hs));
+        HIPCK(c, launch_move_gather(c->flavor, state_arrays(c), c->d_snap, c->d_move + items_at + sp.g0 * 4, c->d_move + colrec_at + sp.g0 * row, (uint32_t)(sp.g1 - sp.g0), c->hs));
+        HIPCK(c, launch_move_scatter(c->flavor, state_arrays(c), c->d_snap, c->d_move + items_at + sp.g1 * 4, c->d_move + colrec_at + sp.g1 * row, (uint32_t)(sp.s1 - sp.g1),
+                                     realign ? c->d_snap_shift : nullptr, c->hs));
     }
     // parameters travel by reference, activity travels with the stream: all sources are read before any destination is written.  A
     // destination that is no source loses its occupant (one reference less); a source that is no destination keeps its own and becomes
@@ -1107,22 +1123,20 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
     for (uint32_t i = 0; i < nm; i++) { img[i] = c->stream_image[mv[i].src]; if (have_active) act[i] = c->active[mv[i].src]; is_dst[mv[i].dst] = 1; }
     bool one_way = false;
     for (uint32_t i = 0; i < nm; i++) {
-        int32_t &si = c->stream_image[mv[i].dst];
-        c->image_refs[(size_t)si]--; si = img[i]; c->image_refs[(size_t)si]++;
-        if (have_active) c->active[mv[i].dst] = act[i];
+        assign_image(c, mv[i].dst, img[i]);
+        if (have_active) set_active(c, mv[i].dst, act[i] != 0);
     }
     for (uint32_t i = 0; i < nm; i++)
-        if (!is_dst[mv[i].src]) { c->active[mv[i].src] = 0; one_way = true; }
-    if (have_active) { c->n_paused = 0; for (uint32_t s = 0; s < c->n_streams; s++) c->n_paused += c->active[s] ? 0u : 1u; }
-    c->assignment_dirty = true; c->launch_dirty = true;
-    if (have_active) { c->active_dirty = true; c->paused_runs_dirty = true; }
+        if (!is_dst[mv[i].src]) { set_active(c, mv[i].src, false); one_way = true; }
+    c->launch_dirty = true;
+    if (have_active) activity_changed(c);
     if (one_way) c->merge_hint = true;      // an image may have lost its last stream: the fold-back pass drops it
     return (int)nm;
 }
 
 int dspi_plan_compaction(const dspi_ctx *c, dspi_stream_move *moves, uint32_t cap, uint32_t flags) {
     if (!c || (flags & ~DSPI_COMPACT_ONE_WAY)) return DSPI_E_INVAL;
-    const std::vector<StreamMove> plan = move_compaction(move_activity(c), c->n_streams, flags & DSPI_COMPACT_ONE_WAY);
+    const std::vector<StreamMove> plan = move_compaction(host_activity(c), c->n_streams, flags & DSPI_COMPACT_ONE_WAY);
     if (!moves) return (int)plan.size();
     if (plan.size() > cap) return DSPI_E_SHORT;
     if (!plan.empty()) memcpy(moves, plan.data(), plan.size() * sizeof(StreamMove));
@@ -1141,27 +1155,22 @@ int dspi_boot_streams(dspi_ctx *c, const uint32_t *streams, uint32_t n, const vo
     auto p = std::make_unique<Params>(c->flavor, c->fma, dump ? false : !c->populated);
     int sel = 48;
     if (dump) sel = p->load_flash_dump(dump, len, true);
-    p->dirty = true;
     // run-time state, on the context's stream, behind whatever it still has to do (the kernel reads the rows' residents' positions there)
     if (c->device != DSPI_DEVICE_NONE) {
         HIPCK(c, hipSetDevice(c->device));
-        const std::vector<BootRowItem> items = boot_row_items(streams, n, c->n_streams, (uint32_t)c->sm.row, move_activity(c), (flags & DSPI_BOOT_STREAMS_AS_IS) != 0);
+        const std::vector<BootRowItem> items = boot_row_items(streams, n, c->n_streams, (uint32_t)c->sm.row, host_activity(c), (flags & DSPI_BOOT_STREAMS_AS_IS) != 0);
         std::vector<uint32_t> words(items.size() * (sizeof(BootRowItem) / 4));
         memcpy(words.data(), items.data(), items.size() * sizeof(BootRowItem));
         int rc = move_upload(c, words);
         if (rc) return rc;
-        HIPCK(c, launch_boot(c->flavor, c->d_state, c->d_dlines, c->d_ring, c->d_pdm, c->d_move, (uint32_t)items.size(), c->hs));
+        HIPCK(c, launch_boot(c->flavor, state_arrays(c), c->d_move, (uint32_t)items.size(), c->hs));
     }
     // parameters: the listed streams leave their objects (whose pending state operations never reach them) and share ONE new one, whose
     // own pending operations the next commit applies over the power-on state, as after dspi_create.  An object that lost its last stream
     // is dropped, and a new object equal to one already here folded into it, by the fold-back pass (merge_images).
-    const int32_t slot = (int32_t)c->images.size();
-    c->images.push_back(std::move(p)); c->image_refs.push_back(0);
-    for (uint32_t i = 0; i < n; i++) {
-        int32_t &si = c->stream_image[streams[i]];
-        c->image_refs[(size_t)si]--; si = slot; c->image_refs[(size_t)slot]++;
-    }
-    c->assignment_dirty = true; c->launch_dirty = true; c->merge_hint = true;
+    const int32_t slot = add_image(c, std::move(p));
+    for (uint32_t i = 0; i < n; i++) assign_image(c, streams[i], slot);
+    c->launch_dirty = true; c->merge_hint = true;
     if (c->spdif_ps.on) c->spdif_ps.boot(streams, n, host_activity(c));      // a device that has just been powered on sends frame 0 of a block first
     if (selection) *selection = sel;
     return (int)n;
@@ -1188,6 +1197,19 @@ int dspi_debug_stream_positions(dspi_ctx *c, uint32_t first, uint32_t count, uin
 }
 
 // ---- S/PDIF subframes: pico_audio_spdif_multi sample_encoding.h:27-47 + audio_spdif.c:76-116 (dspi_spdif.hip) ----
+// the sample-rate byte of the channel status is each device's own (audio_spdif.c:250-256): one word for everybody (fs) while every live
+// image runs at one rate, else per stream from the committed images (rates)
+static int spdif_rates(dspi_ctx *c, uint32_t &fs, SpdifRates &rates) {
+    fs = readable(c, DSPI_ALL_STREAMS).freq;
+    rates = SpdifRates{nullptr, nullptr, 0u};
+    bool one_rate = true;
+    for (size_t i = 0; i < c->images.size(); i++) if (c->image_refs[i] > 0 && c->images[i]->freq != fs) one_rate = false;
+    if (one_rate) return 0;
+    int rc = commit_params(c);
+    if (!rc) rates = SpdifRates{c->d_images, c->d_stream_image, 0u};
+    return rc;
+}
+
 int dspi_spdif_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, uint32_t block_pos, uint32_t *subframes, uint32_t flags) {
     if (!c || !pairs || !subframes || n_frames == 0 || block_pos >= 192) return DSPI_E_INVAL;
     if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
@@ -1203,21 +1225,11 @@ int dspi_spdif_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, uint
         HIPCK(c, hipMemcpyAsync(c->d_spdif_in, pairs, in_b, hipMemcpyHostToDevice, c->hs));
         d_in = c->d_spdif_in; d_out = c->d_spdif_out;
     }
-    // the sample-rate byte of the channel status is each device's own (audio_spdif.c:250-256): one word for everybody while every live
-    // image runs at one rate, else per stream from the committed images
-    const uint32_t fs = readable(c, DSPI_ALL_STREAMS).freq;
-    bool one_rate = true;
-    for (size_t i = 0; i < c->images.size(); i++) if (c->image_refs[i] > 0 && c->images[i]->freq != fs) one_rate = false;
-    SpdifRates rates{nullptr, nullptr, 0u};
-    if (!one_rate) {
-        if ((rc = commit_params(c))) return rc;
-        rates = SpdifRates{c->d_images, c->d_stream_image, 0u};
-    }
+    uint32_t fs;
+    SpdifRates rates;
+    if ((rc = spdif_rates(c, fs, rates))) return rc;
     HIPCK(c, launch_spdif(tiled, d_in, d_out, c->n_streams, (uint32_t)c->sm.n_pairs, n_frames, (uint32_t)c->sm.row, c->n_wg, block_pos, fs, rates, c->hs));
-    if (!dev) {
-        HIPCK(c, hipMemcpyAsync(subframes, c->d_spdif_out, out_b, hipMemcpyDeviceToHost, c->hs));
-        HIPCK(c, hipStreamSynchronize(c->hs));
-    }
+    if (!dev && (rc = stage_down(c, subframes, c->d_spdif_out, out_b))) return rc;
     return (int)((block_pos + n_frames) % 192u);
 }
 
@@ -1244,10 +1256,7 @@ int dspi_i2s_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, uint32
         d_in = c->d_spdif_in; d_out = c->d_spdif_out;
     }
     HIPCK(c, launch_i2s(tiled, d_in, d_out, c->n_streams, (uint32_t)c->sm.n_pairs, n_frames, (uint32_t)c->sm.row, c->n_wg, pair_mask, c->hs));
-    if (!dev) {
-        HIPCK(c, hipMemcpyAsync(words, c->d_spdif_out, bytes, hipMemcpyDeviceToHost, c->hs));
-        HIPCK(c, hipStreamSynchronize(c->hs));
-    }
+    if (!dev && (rc = stage_down(c, words, c->d_spdif_out, bytes))) return rc;
     return (int)pair_mask;
 }
 
@@ -1297,21 +1306,11 @@ int dspi_spdif_encode_v(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, co
         HIPCK(c, hipMemcpyAsync(c->d_spdif_vpos, block_pos, pos_b, hipMemcpyHostToDevice, c->hs));
         d_in = c->d_spdif_in; d_out = c->d_spdif_out; d_pos = c->d_spdif_vpos;
     }
-    // the sample-rate byte: per stream, as in dspi_spdif_encode
-    const uint32_t fs = readable(c, DSPI_ALL_STREAMS).freq;
-    bool one_rate = true;
-    for (size_t i = 0; i < c->images.size(); i++) if (c->image_refs[i] > 0 && c->images[i]->freq != fs) one_rate = false;
-    SpdifRates rates{nullptr, nullptr, 0u};
-    if (!one_rate) {
-        if ((rc = commit_params(c))) return rc;
-        rates = SpdifRates{c->d_images, c->d_stream_image, 0u};
-    }
+    uint32_t fs;
+    SpdifRates rates;
+    if ((rc = spdif_rates(c, fs, rates))) return rc;
     HIPCK(c, launch_spdif(tiled, d_in, d_out, c->n_streams, (uint32_t)c->sm.n_pairs, n_frames, (uint32_t)c->sm.row, c->n_wg, 0u, fs, rates, c->hs, d_pos));
-    if (!dev) {
-        HIPCK(c, hipMemcpyAsync(subframes, c->d_spdif_out, out_b, hipMemcpyDeviceToHost, c->hs));
-        HIPCK(c, hipStreamSynchronize(c->hs));
-    }
-    return DSPI_OK;
+    return dev ? DSPI_OK : stage_down(c, subframes, c->d_spdif_out, out_b);
 }
 
 int dspi_sync(dspi_ctx *c) {

@@ -79,19 +79,19 @@ hipError_t launch_i2s(bool tiled, const int32_t *pairs, uint32_t *out, uint32_t 
 hipError_t launch_detmath(int which, const float *a, const float *b, uint32_t n, float *out, hipStream_t stream);      // dspi_status.hip
 hipError_t launch_clip_gather(const uint32_t *state, uint32_t n_streams, uint32_t row, uint32_t n_slots, uint32_t clip_slot, uint16_t *out, hipStream_t stream);
 
+// ---- the context's four per-stream arrays, [W][position][R] each (dspi_snapshot.hip's and dspi_boot.hip's launchers take them as one) ----
+struct StateArrays { uint32_t *state, *dlines, *ring, *pdm; };
+
 // ---- stream snapshots (dspi_snapshot.hip): streams [first, first + count) of the four stream-minor arrays <-> stream-major records
 // (dspi_snapshot.h), `records` = the record of stream `first`, 16-byte aligned.  import: records -> arrays, else arrays -> records.
-hipError_t launch_snapshot(int flavor, bool import, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first,
-                           uint32_t count, hipStream_t stream);
+hipError_t launch_snapshot(int flavor, bool import, const StateArrays &arr, uint32_t *records, uint32_t first, uint32_t count, hipStream_t stream);
 // The realigning import (dspi_snapshot.h snap_row_target): two launches, the per-stream shifts into `shift` (2 words per stream of the range,
 // 8-byte aligned device scratch), then the import rotated by them.  n_streams: the context's, for the rows' resident neighbours.
-hipError_t launch_snapshot_realign(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count,
-                                   uint32_t n_streams, uint32_t *shift, hipStream_t stream);
-// dspi_resume_streams: the same two launches under the activity-aware rule (dspi_snapshot.h snap_row_target_active).  `active`: the bitmap
-// before the call, one bit per stream; [r_first, r_first + r_count): the call's range, of which `records` hold the rows' chunk [first,
-// first + count); streams the call does not resume are written back unrotated.
-hipError_t launch_snapshot_resume(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count,
-                                  uint32_t n_streams, const uint32_t *active, uint32_t r_first, uint32_t r_count, uint32_t *shift, hipStream_t stream);
+// `active` given (dspi_resume_streams): the same two launches under the activity-aware rule (dspi_snapshot.h snap_row_target_active).
+// `active`: the bitmap before the call, one bit per stream; [r_first, r_first + r_count): the call's range, of which `records` hold the
+// rows' chunk [first, first + count); streams the call does not resume are written back unrotated.
+hipError_t launch_snapshot_realign(int flavor, const StateArrays &arr, uint32_t *records, uint32_t first, uint32_t count, uint32_t n_streams, uint32_t *shift, hipStream_t stream,
+                                   const uint32_t *active = nullptr, uint32_t r_first = 0, uint32_t r_count = 0);
 
 // ---- stream moves (dspi_move_streams; dspi_move.h: the lists; dspi_snapshot.hip: the kernels) ----
 // The same transposition addressed by list: `items` = n_items MoveRowItem (one per touched row), `colrec` = per item one record index per
@@ -99,14 +99,13 @@ hipError_t launch_snapshot_resume(int flavor, uint32_t *state, uint32_t *dlines,
 // = record 0 of the scratch.  The gather reads listed columns into their records; the scatter writes records into listed columns, rotated
 // by shift[destination stream] (two words per stream of the context, from launch_move_targets) or, shift == nullptr, as they are.
 hipError_t launch_move_targets(int flavor, const uint32_t *state, const uint32_t *targets, uint32_t n, uint32_t *shift, hipStream_t stream);      // targets: n MoveTarget
-hipError_t launch_move_gather(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, const uint32_t *items, const uint32_t *colrec,
-                              uint32_t n_items, hipStream_t stream);
-hipError_t launch_move_scatter(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, const uint32_t *items, const uint32_t *colrec,
-                               uint32_t n_items, const uint32_t *shift, hipStream_t stream);
+hipError_t launch_move_gather(int flavor, const StateArrays &arr, uint32_t *records, const uint32_t *items, const uint32_t *colrec, uint32_t n_items, hipStream_t stream);
+hipError_t launch_move_scatter(int flavor, const StateArrays &arr, uint32_t *records, const uint32_t *items, const uint32_t *colrec, uint32_t n_items, const uint32_t *shift,
+                               hipStream_t stream);
 
 // ---- stream boots (dspi_boot_streams; dspi_boot.h: the list; dspi_boot.hip: the kernel) ----
 // Power-on words into the listed columns of the four arrays (pdm may be null: a context that never ran the modulator has no array yet):
 // `items` = n_items BootRowItem in device memory, one per touched row.  Reads nothing but the two position words of each item's target.
-hipError_t launch_boot(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, const uint32_t *items, uint32_t n_items, hipStream_t stream);
+hipError_t launch_boot(int flavor, const StateArrays &arr, const uint32_t *items, uint32_t n_items, hipStream_t stream);
 
 }  // namespace dspi

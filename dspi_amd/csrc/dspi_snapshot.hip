@@ -47,6 +47,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
 #include "dspi_kernels.h"
 #include "dspi_move.h"
 #include "dspi_snapshot.h"
@@ -213,53 +214,68 @@ __global__ __launch_bounds__(kSnapThreads) void snapshot_kernel(const typename S
     }
 }
 
-// One thread per stream of a touched row: the row's target positions (dspi_snapshot.h snap_row_target: a resident neighbour's, from the
-// state array as the stream's earlier work left it, or the range's first stream's, from its record) minus the record's own.
+// The records of streams [first, first + count) and where the shifts of their realigning import come from and go to: what both target rules'
+// kernels take (one workgroup per touched row from row0 on, one thread per stream)
+struct SnapTargetArgs {
+    const uint32_t *state, *rec;
+    uint32_t record_words, state_off, first, count, n_streams, row0;
+    uint2 *shift;                      // per stream of [first, first + count)
+};
+
+// How far the record of stream s is rotated to stand at target t's two positions: the target's (a resident neighbour's, from the state
+// array as the stream's earlier work left it, or a stream of the records', from its record) minus the record's own.
 template <uint32_t ROW>
-__global__ __launch_bounds__(ROW) void snapshot_targets_kernel(const uint32_t *state, const uint32_t *rec, uint32_t record_words, uint32_t state_off, uint32_t first,
-                                                               uint32_t count, uint32_t n_streams, uint32_t row0, uint2 *shift) {
+__device__ __forceinline__ uint2 snap_shift_onto(const SnapTargetArgs &a, const SnapTarget t, uint32_t row, uint64_t s) {
     constexpr StateMap sm = make_state_map(ROW == 128 ? 1 : 0);
     constexpr uint32_t kLine = (uint32_t)sm.max_delay, kRing = (uint32_t)kRingLen;
-    const uint32_t row = row0 + blockIdx.x;
-    const SnapTarget t = snap_row_target(row, ROW, n_streams, first, count);
-    const uint32_t *tp = t.resident ? state + (size_t)row * sm.n_slots * ROW + (t.stream - row * ROW) : rec + (size_t)(t.stream - first) * record_words + state_off;
+    const uint32_t *tp = t.resident ? a.state + (size_t)row * sm.n_slots * ROW + (t.stream - row * ROW) : a.rec + (size_t)(t.stream - a.first) * a.record_words + a.state_off;
     const size_t ts = t.resident ? ROW : 1;
     const uint32_t w_t = tp[(size_t)sm.widx * ts] & (kLine - 1u), r_t = tp[(size_t)sm.ring_pos * ts] & (kRing - 1u);
+    const uint32_t *r = a.rec + (size_t)(s - a.first) * a.record_words + a.state_off;
+    return make_uint2(snap_shift(r[sm.widx] & (kLine - 1u), w_t, kLine), snap_shift(r[sm.ring_pos] & (kRing - 1u), r_t, kRing));
+}
+
+// The plain rule (dspi_snapshot.h snap_row_target): every stream of the range moves onto its row's target; nothing is written for threads
+// outside the range.
+template <uint32_t ROW>
+__global__ __launch_bounds__(ROW) void snapshot_targets_kernel(const SnapTargetArgs a) {
+    const uint32_t row = a.row0 + blockIdx.x;
     const uint64_t s = (uint64_t)row * ROW + threadIdx.x;
-    if (s < first || s >= (uint64_t)first + count) return;
-    const uint32_t *r = rec + (size_t)(s - first) * record_words + state_off;
-    shift[s - first] = make_uint2(snap_shift(r[sm.widx] & (kLine - 1u), w_t, kLine), snap_shift(r[sm.ring_pos] & (kRing - 1u), r_t, kRing));
+    if (s < a.first || s >= (uint64_t)a.first + a.count) return;
+    a.shift[s - a.first] = snap_shift_onto<ROW>(a, snap_row_target(row, ROW, a.n_streams, a.first, a.count), row, s);
 }
 
 // ... for dspi_resume_streams: the activity-aware rule (dspi_snapshot.h snap_row_target_active) on the bitmap as it stood before the call.
 // Only the streams the call resumes — in the call's range [r_first, r_first + r_count) and paused — move; every other stream of the
 // records [first, first + count) (a chunk of the range's rows) gets the shift (0, 0) and is written back as it is.
 template <uint32_t ROW>
-__global__ __launch_bounds__(ROW) void snapshot_targets_active_kernel(const uint32_t *state, const uint32_t *rec, uint32_t record_words, uint32_t state_off, uint32_t first,
-                                                                      uint32_t count, uint32_t n_streams, uint32_t row0, const uint32_t *active, uint32_t r_first,
-                                                                      uint32_t r_count, uint2 *shift) {
-    constexpr StateMap sm = make_state_map(ROW == 128 ? 1 : 0);
-    constexpr uint32_t kLine = (uint32_t)sm.max_delay, kRing = (uint32_t)kRingLen;
-    const uint32_t row = row0 + blockIdx.x;
+__global__ __launch_bounds__(ROW) void snapshot_targets_active_kernel(const SnapTargetArgs a, const uint32_t *active, uint32_t r_first, uint32_t r_count) {
+    const uint32_t row = a.row0 + blockIdx.x;
     const uint64_t s = (uint64_t)row * ROW + threadIdx.x;
-    if (s < first || s >= (uint64_t)first + count) return;
+    if (s < a.first || s >= (uint64_t)a.first + a.count) return;
     uint2 d = make_uint2(0u, 0u);
-    if (s >= r_first && s < (uint64_t)r_first + r_count && !snap_stream_active(active, s)) {
-        const SnapTarget t = snap_row_target_active(row, ROW, n_streams, r_first, r_count, active);
-        // (a target from the records lies in this chunk: chunks hold the range's rows whole)
-        const uint32_t *tp = t.resident ? state + (size_t)row * sm.n_slots * ROW + (t.stream - row * ROW) : rec + (size_t)(t.stream - first) * record_words + state_off;
-        const size_t ts = t.resident ? ROW : 1;
-        const uint32_t w_t = tp[(size_t)sm.widx * ts] & (kLine - 1u), r_t = tp[(size_t)sm.ring_pos * ts] & (kRing - 1u);
-        const uint32_t *r = rec + (size_t)(s - first) * record_words + state_off;
-        d = make_uint2(snap_shift(r[sm.widx] & (kLine - 1u), w_t, kLine), snap_shift(r[sm.ring_pos] & (kRing - 1u), r_t, kRing));
-    }
-    shift[s - first] = d;
+    // (a target from the records lies in this chunk: chunks hold the range's rows whole)
+    if (s >= r_first && s < (uint64_t)r_first + r_count && !snap_stream_active(active, s))
+        d = snap_shift_onto<ROW>(a, snap_row_target_active(row, ROW, a.n_streams, r_first, r_count, active), row, s);
+    a.shift[s - a.first] = d;
+}
+
+// the one flavour ladder: f(the flavour's row width as a compile-time constant), for every kernel of this file
+template <class F>
+void for_row_width(int flavor, F f) {
+    if (flavor) f(std::integral_constant<uint32_t, 128>{});
+    else f(std::integral_constant<uint32_t, 64>{});
+}
+// ... and the snapshot_kernel instance of a flavour, launched
+template <bool IMPORT, bool REALIGN, bool LIST>
+void snap_launch(int flavor, dim3 grid, const typename SnapArgsOf<REALIGN, LIST>::type &a, hipStream_t stream) {
+    for_row_width(flavor, [&](auto row) { hipLaunchKernelGGL((snapshot_kernel<decltype(row)::value, IMPORT, REALIGN, LIST>), grid, dim3(kSnapThreads), 0, stream, a); });
 }
 
 struct SnapGrid { dim3 grid; uint32_t rows; };
-SnapGrid snap_kargs(SnapKArgs &a, int flavor, bool import, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count) {
+SnapGrid snap_kargs(SnapKArgs &a, int flavor, bool import, const StateArrays &arr, uint32_t *records, uint32_t first, uint32_t count) {
     const SnapLayout l = make_snap_layout(flavor);
-    uint32_t *const arrs[SEC_COUNT] = {state, dlines, ring, pdm};
+    uint32_t *const arrs[SEC_COUNT] = {arr.state, arr.dlines, arr.ring, arr.pdm};
     const uint32_t pos = import ? kImportPos : kExportPos, cols = import ? kImportCols : kExportCols;
     uint32_t tiles = 0;
     for (int s = 0; s < SEC_COUNT; s++) {
@@ -288,9 +304,8 @@ __global__ __launch_bounds__(kSnapThreads) void move_targets_kernel(const uint32
                               snap_shift(from[(size_t)sm.ring_pos * ROW] & (kRing - 1u), to[(size_t)sm.ring_pos * ROW] & (kRing - 1u), kRing));
 }
 
-dim3 snap_list_kargs(SnapListArgs &a, int flavor, bool import, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, const uint32_t *items,
-                     const uint32_t *colrec, uint32_t n_items) {
-    dim3 grid = snap_kargs(a, flavor, import, state, dlines, ring, pdm, records, 0, 1).grid;
+dim3 snap_list_kargs(SnapListArgs &a, int flavor, bool import, const StateArrays &arr, uint32_t *records, const uint32_t *items, const uint32_t *colrec, uint32_t n_items) {
+    dim3 grid = snap_kargs(a, flavor, import, arr, records, 0, 1).grid;
     a.first = 0; a.count = 0; a.row0 = 0;
     a.items = reinterpret_cast<const MoveRowItem *>(items); a.colrec = colrec; a.shift = nullptr;
     grid.y = n_items;
@@ -303,85 +318,52 @@ hipError_t launch_move_targets(int flavor, const uint32_t *state, const uint32_t
     if (n == 0) return hipSuccess;
     const dim3 grid((n + kSnapThreads - 1) / kSnapThreads);
     const MoveTarget *t = reinterpret_cast<const MoveTarget *>(targets);
-    if (flavor) hipLaunchKernelGGL((move_targets_kernel<128>), grid, dim3(kSnapThreads), 0, stream, state, t, n, reinterpret_cast<uint2 *>(shift));
-    else hipLaunchKernelGGL((move_targets_kernel<64>), grid, dim3(kSnapThreads), 0, stream, state, t, n, reinterpret_cast<uint2 *>(shift));
+    for_row_width(flavor, [&](auto row) { hipLaunchKernelGGL((move_targets_kernel<decltype(row)::value>), grid, dim3(kSnapThreads), 0, stream, state, t, n, reinterpret_cast<uint2 *>(shift)); });
     return hipGetLastError();
 }
 
-hipError_t launch_move_gather(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, const uint32_t *items, const uint32_t *colrec,
-                              uint32_t n_items, hipStream_t stream) {
+hipError_t launch_move_gather(int flavor, const StateArrays &arr, uint32_t *records, const uint32_t *items, const uint32_t *colrec, uint32_t n_items, hipStream_t stream) {
     if (n_items == 0) return hipSuccess;
     SnapListArgs a{};
-    const dim3 grid = snap_list_kargs(a, flavor, false, state, dlines, ring, pdm, records, items, colrec, n_items);
-    if (flavor) hipLaunchKernelGGL((snapshot_kernel<128, false, false, true>), grid, dim3(kSnapThreads), 0, stream, a);
-    else hipLaunchKernelGGL((snapshot_kernel<64, false, false, true>), grid, dim3(kSnapThreads), 0, stream, a);
+    const dim3 grid = snap_list_kargs(a, flavor, false, arr, records, items, colrec, n_items);
+    snap_launch<false, false, true>(flavor, grid, a, stream);
     return hipGetLastError();
 }
 
-hipError_t launch_move_scatter(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, const uint32_t *items, const uint32_t *colrec,
-                               uint32_t n_items, const uint32_t *shift, hipStream_t stream) {
+hipError_t launch_move_scatter(int flavor, const StateArrays &arr, uint32_t *records, const uint32_t *items, const uint32_t *colrec, uint32_t n_items, const uint32_t *shift,
+                               hipStream_t stream) {
     if (n_items == 0) return hipSuccess;
     SnapListArgs a{};
-    const dim3 grid = snap_list_kargs(a, flavor, true, state, dlines, ring, pdm, records, items, colrec, n_items);
+    const dim3 grid = snap_list_kargs(a, flavor, true, arr, records, items, colrec, n_items);
     a.shift = reinterpret_cast<const uint2 *>(shift);
-    if (flavor) {
-        if (shift) hipLaunchKernelGGL((snapshot_kernel<128, true, true, true>), grid, dim3(kSnapThreads), 0, stream, a);
-        else hipLaunchKernelGGL((snapshot_kernel<128, true, false, true>), grid, dim3(kSnapThreads), 0, stream, a);
-    } else {
-        if (shift) hipLaunchKernelGGL((snapshot_kernel<64, true, true, true>), grid, dim3(kSnapThreads), 0, stream, a);
-        else hipLaunchKernelGGL((snapshot_kernel<64, true, false, true>), grid, dim3(kSnapThreads), 0, stream, a);
-    }
+    if (shift) snap_launch<true, true, true>(flavor, grid, a, stream);
+    else snap_launch<true, false, true>(flavor, grid, a, stream);
     return hipGetLastError();
 }
 
-hipError_t launch_snapshot(int flavor, bool import, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first,
-                           uint32_t count, hipStream_t stream) {
+hipError_t launch_snapshot(int flavor, bool import, const StateArrays &arr, uint32_t *records, uint32_t first, uint32_t count, hipStream_t stream) {
     if (count == 0) return hipSuccess;
     SnapKArgs a{};
-    const dim3 grid = snap_kargs(a, flavor, import, state, dlines, ring, pdm, records, first, count).grid;
-    if (flavor) {
-        if (import) hipLaunchKernelGGL((snapshot_kernel<128, true>), grid, dim3(kSnapThreads), 0, stream, a);
-        else hipLaunchKernelGGL((snapshot_kernel<128, false>), grid, dim3(kSnapThreads), 0, stream, a);
-    } else {
-        if (import) hipLaunchKernelGGL((snapshot_kernel<64, true>), grid, dim3(kSnapThreads), 0, stream, a);
-        else hipLaunchKernelGGL((snapshot_kernel<64, false>), grid, dim3(kSnapThreads), 0, stream, a);
-    }
+    const dim3 grid = snap_kargs(a, flavor, import, arr, records, first, count).grid;
+    if (import) snap_launch<true, false, false>(flavor, grid, a, stream);
+    else snap_launch<false, false, false>(flavor, grid, a, stream);
     return hipGetLastError();
 }
 
-hipError_t launch_snapshot_realign(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count,
-                                   uint32_t n_streams, uint32_t *shift, hipStream_t stream) {
+// the shifts of the records' streams under the plain target rule or, `active` given, under the resume's, then the import rotated by them
+hipError_t launch_snapshot_realign(int flavor, const StateArrays &arr, uint32_t *records, uint32_t first, uint32_t count, uint32_t n_streams, uint32_t *shift, hipStream_t stream,
+                                   const uint32_t *active, uint32_t r_first, uint32_t r_count) {
     if (count == 0) return hipSuccess;
     SnapRealignArgs a{};
-    const SnapGrid g = snap_kargs(a, flavor, true, state, dlines, ring, pdm, records, first, count);
+    const SnapGrid g = snap_kargs(a, flavor, true, arr, records, first, count);
     a.shift = reinterpret_cast<const uint2 *>(shift);
-    uint2 *const sh = reinterpret_cast<uint2 *>(shift);
-    if (flavor) {
-        hipLaunchKernelGGL((snapshot_targets_kernel<128>), dim3(g.rows), dim3(128), 0, stream, state, records, a.record_words, a.off[SEC_STATE], first, count, n_streams, a.row0, sh);
-        hipLaunchKernelGGL((snapshot_kernel<128, true, true>), g.grid, dim3(kSnapThreads), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL((snapshot_targets_kernel<64>), dim3(g.rows), dim3(64), 0, stream, state, records, a.record_words, a.off[SEC_STATE], first, count, n_streams, a.row0, sh);
-        hipLaunchKernelGGL((snapshot_kernel<64, true, true>), g.grid, dim3(kSnapThreads), 0, stream, a);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_snapshot_resume(int flavor, uint32_t *state, uint32_t *dlines, uint32_t *ring, uint32_t *pdm, uint32_t *records, uint32_t first, uint32_t count,
-                                  uint32_t n_streams, const uint32_t *active, uint32_t r_first, uint32_t r_count, uint32_t *shift, hipStream_t stream) {
-    if (count == 0) return hipSuccess;
-    SnapRealignArgs a{};
-    const SnapGrid g = snap_kargs(a, flavor, true, state, dlines, ring, pdm, records, first, count);
-    a.shift = reinterpret_cast<const uint2 *>(shift);
-    uint2 *const sh = reinterpret_cast<uint2 *>(shift);
-    if (flavor) {
-        hipLaunchKernelGGL((snapshot_targets_active_kernel<128>), dim3(g.rows), dim3(128), 0, stream, state, records, a.record_words, a.off[SEC_STATE], first, count, n_streams, a.row0,
-                           active, r_first, r_count, sh);
-        hipLaunchKernelGGL((snapshot_kernel<128, true, true>), g.grid, dim3(kSnapThreads), 0, stream, a);
-    } else {
-        hipLaunchKernelGGL((snapshot_targets_active_kernel<64>), dim3(g.rows), dim3(64), 0, stream, state, records, a.record_words, a.off[SEC_STATE], first, count, n_streams, a.row0,
-                           active, r_first, r_count, sh);
-        hipLaunchKernelGGL((snapshot_kernel<64, true, true>), g.grid, dim3(kSnapThreads), 0, stream, a);
-    }
+    const SnapTargetArgs t{arr.state, records, a.record_words, a.off[SEC_STATE], first, count, n_streams, a.row0, reinterpret_cast<uint2 *>(shift)};
+    for_row_width(flavor, [&](auto row) {
+        constexpr uint32_t ROW = decltype(row)::value;
+        if (active) hipLaunchKernelGGL((snapshot_targets_active_kernel<ROW>), dim3(g.rows), dim3(ROW), 0, stream, t, active, r_first, r_count);
+        else hipLaunchKernelGGL((snapshot_targets_kernel<ROW>), dim3(g.rows), dim3(ROW), 0, stream, t);
+    });
+    snap_launch<true, true, false>(flavor, g.grid, a, stream);
     return hipGetLastError();
 }
 
