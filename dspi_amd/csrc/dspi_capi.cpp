@@ -31,6 +31,7 @@
 #include "dspi_boot.h"
 #include "dspi_move.h"
 #include "dspi_plan.h"
+#include "dspi_resize.h"
 #include "dspi_snapshot.h"
 #include "dspi_spdifpos.h"
 
@@ -40,6 +41,7 @@ struct dspi_ctx {
     int flavor = 1;
     bool fma = false;              // DSPI_FLOAT_CONTRACT_FMA: host design and kernels use the firmware build's fused multiply-adds
     uint32_t n_streams = 0, n_wg = 0;
+    uint32_t cap_wg = 0;           // rows the persistent per-stream arrays (d_state, d_dlines, d_ring, d_pdm) are allocated for, >= n_wg (dspi_reserve_streams); no launch goes past n_wg
     int device = DSPI_DEVICE_NONE;
     StateMap sm{};
     std::vector<std::unique_ptr<Params>> images;
@@ -547,6 +549,7 @@ int dspi_create(dspi_ctx **out, int flavor, uint32_t n_streams, int hip_device) 
     c->device = hip_device;
     c->sm = make_state_map(flavor);
     c->n_wg = (n_streams + (uint32_t)c->sm.row - 1) / (uint32_t)c->sm.row;
+    c->cap_wg = c->n_wg;
     c->fma = fma;
     c->populated = populated;
     c->no_direct = getenv("DSPI_NO_DIRECT") != nullptr;
@@ -780,7 +783,7 @@ int dspi_debug_detmath(dspi_ctx *c, int which, const float *a, const float *b, u
 // ---- PDM sub output: pdm_generator.c:351-397 per sample (dspi_pdm.hip) ----
 static int pdm_state(dspi_ctx *c) {
     if (c->d_pdm) return 0;
-    const size_t b = (size_t)c->n_wg * kPdmStateWords * c->sm.row * 4;
+    const size_t b = (size_t)c->cap_wg * kPdmStateWords * c->sm.row * 4;      // (every row of the capacity, like the other three arrays)
     if (hipMalloc((void **)&c->d_pdm, b) != hipSuccess) return fail(c, DSPI_E_NOMEM, "hipMalloc failed (PDM state)");
     HIPCK(c, hipMemsetAsync(c->d_pdm, 0, b, c->hs));
     HIPCK(c, launch_pdm_reset(c->d_pdm, c->n_streams, (uint32_t)c->sm.row, c->n_wg, -1, 1, c->hs));
@@ -1175,6 +1178,119 @@ int dspi_boot_streams(dspi_ctx *c, const uint32_t *streams, uint32_t n, const vo
     if (selection) *selection = sel;
     return (int)n;
 }
+
+// ---- resizing (dspi_resize.h: validation, row arithmetic, the new slots' work items; dspi_boot.hip: the power-on kernel) ----
+// The persistent per-stream arrays are row-outermost, so a context of other rows is a prefix copy.  New arrays of `rows` rows, ALL of them
+// allocated before anything else happens (a refusal leaves the context as it was); the first `copy` rows come over device to device on the
+// context's stream, behind its earlier work; then the stream is waited for, once, and the old arrays are freed.
+static int resize_reallocate(dspi_ctx *c, uint32_t rows, uint32_t copy) {
+    const size_t row = (size_t)c->sm.row;
+    const size_t row_b[4] = {(size_t)c->sm.n_slots * row * 4, (size_t)c->sm.n_out * (size_t)c->sm.max_delay * row * 4, (size_t)kRingLen * 2 * row * 4, (size_t)kPdmStateWords * row * 4};
+    uint32_t **const arr[4] = {&c->d_state, &c->d_dlines, &c->d_ring, &c->d_pdm};
+    void *fresh[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; k++) {
+        if (!*arr[k]) continue;      // (d_pdm before the modulator's first run)
+        size_t b = 0;
+        if (!resize_bytes(rows, row_b[k], &b) || hipMalloc(&fresh[k], b) != hipSuccess) {
+            (void)hipGetLastError();
+            for (int j = 0; j < k; j++) if (fresh[j]) (void)hipFree(fresh[j]);
+            return fail(c, DSPI_E_NOMEM, "hipMalloc failed (resized arrays, " + std::to_string(rows) + " rows)");
+        }
+    }
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 4 && e == hipSuccess; k++)
+        if (fresh[k] && copy) e = hipMemcpyAsync(fresh[k], *arr[k], (size_t)copy * row_b[k], hipMemcpyDeviceToDevice, c->hs);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->hs);
+    if (e != hipSuccess) {
+        for (int k = 0; k < 4; k++) if (fresh[k]) (void)hipFree(fresh[k]);
+        return fail(c, DSPI_E_HIP, std::string("resized arrays: ") + hipGetErrorString(e));
+    }
+    for (int k = 0; k < 4; k++)
+        if (fresh[k]) { (void)hipFree(*arr[k]); *arr[k] = static_cast<uint32_t *>(fresh[k]); }
+    c->cap_wg = rows;
+    return 0;
+}
+// a row count no array's byte size can express is refused with the other rules, before anything is written
+static bool resize_rows_fit(const dspi_ctx *c, uint32_t rows) {
+    const size_t row = (size_t)c->sm.row;
+    size_t b = 0;
+    return resize_bytes(rows, (size_t)c->sm.n_out * (size_t)c->sm.max_delay * row * 4, &b) && resize_bytes(rows, (size_t)c->sm.n_slots * row * 4, &b) &&
+           resize_bytes(rows, (size_t)kRingLen * 2 * row * 4, &b) && resize_bytes(rows, (size_t)kPdmStateWords * row * 4, &b);
+}
+
+// Every per-stream book of the context, extended to or cut at n_new (beside the maintenance books above: stream_image / image_refs,
+// active / n_paused / paused_runs, spdif_ps, and through the dirty flags the device's copies of activity, stream images and S/PDIF
+// positions, the assignment and the launch plan).  Growing: the new slots reference `slot`, a parameter object added for them.
+static void resize_books(dspi_ctx *c, uint32_t n_new, int32_t slot, bool arrive_paused) {
+    const uint32_t n_old = c->n_streams;
+    if (n_new < n_old) {
+        for (uint32_t s = n_new; s < n_old; s++) c->image_refs[(size_t)c->stream_image[s]]--;
+        c->n_paused -= n_old - n_new;      // (every cut slot was paused: resize_validate)
+        c->active.resize(n_new);
+    } else {
+        c->image_refs[(size_t)slot] += n_new - n_old;
+        if (arrive_paused && c->active.empty()) c->active.assign(n_old, 1);
+        if (!c->active.empty()) c->active.resize(n_new, arrive_paused ? 0 : 1);
+        if (arrive_paused) c->n_paused += n_new - n_old;
+    }
+    c->stream_image.resize(n_new, slot);
+    c->n_streams = n_new;
+    c->n_wg = resize_rows_of(n_new, (uint32_t)c->sm.row);
+    if (c->spdif_ps.on) {      // old slots keep their positions; a device that has just been powered on sends frame 0 of a block first
+        c->spdif_ps.word.resize(n_new, 0u);
+        c->spdif_ps.dirty = true;
+        for (uint32_t s = n_old; s < n_new; s++) c->spdif_ps.set(s, 0, host_activity(c));
+    }
+    c->assignment_dirty = true; c->merge_hint = true;      // (an object may have lost its last stream, or the new one equal one already here: the fold-back pass)
+    activity_changed(c);
+}
+
+int dspi_resize_streams(dspi_ctx *c, uint32_t n_streams, uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    // everything is validated before anything is written
+    if (const char *why = resize_validate(c->n_streams, n_streams, flags, host_activity(c))) return fail(c, DSPI_E_INVAL, std::string("dspi_resize_streams: ") + why);
+    const uint32_t n_old = c->n_streams, row = (uint32_t)c->sm.row;
+    const ResizeRows r = resize_rows(n_old, n_streams, c->cap_wg, row);
+    if (!resize_rows_fit(c, r.capacity) || n_streams > 0x7fffffffu) return fail(c, DSPI_E_INVAL, "dspi_resize_streams: the arrays' byte sizes overflow");      // (stream indices are int32_t)
+    if (n_streams == n_old) return (int)n_old;
+    if (n_streams < n_old) { resize_books(c, n_streams, -1, false); return (int)n_streams; }      // no allocation, no free, no wait: the capacity stays
+    if (c->device != DSPI_DEVICE_NONE) {
+        HIPCK(c, hipSetDevice(c->device));
+        // the new slots' work items go up first (scratch of the call, no state of the context), so that nothing can fail between the
+        // reallocation and the power-on launch
+        const std::vector<BootRowItem> items = resize_row_items(n_old, n_streams, row, host_activity(c));
+        std::vector<uint32_t> words(items.size() * (sizeof(BootRowItem) / 4));
+        memcpy(words.data(), items.data(), items.size() * sizeof(BootRowItem));
+        int rc = move_upload(c, words);
+        if (rc || (r.reallocate && (rc = resize_reallocate(c, r.capacity, r.copy)))) return rc;
+        // power-on state into EVERY new slot, whatever its column held (padding columns are dirty after a shrink, new rows unwritten),
+        // behind the context's earlier work: the kernel reads the grown row's resident's positions there
+        HIPCK(c, launch_boot(c->flavor, state_arrays(c), c->d_move, (uint32_t)items.size(), c->hs));
+    } else c->cap_wg = r.capacity;
+    // parameters: the boot's own half with a NULL dump — ONE new object for all new slots, dspi_create's device on this context
+    const int32_t slot = add_image(c, std::make_unique<Params>(c->flavor, c->fma, !c->populated));
+    resize_books(c, n_streams, slot, (flags & DSPI_RESIZE_PAUSED) != 0);
+    return (int)n_streams;
+}
+
+int dspi_reserve_streams(dspi_ctx *c, uint32_t n_streams) {
+    if (!c) return DSPI_E_INVAL;
+    if (const char *why = reserve_validate(c->n_streams, n_streams)) return fail(c, DSPI_E_INVAL, std::string("dspi_reserve_streams: ") + why);
+    const uint32_t row = (uint32_t)c->sm.row;
+    const ResizeRows r = reserve_rows(c->n_streams, n_streams, c->cap_wg, row);
+    if (!resize_rows_fit(c, r.capacity) || (uint64_t)r.capacity * row > 0x7fffffffull) return fail(c, DSPI_E_INVAL, "dspi_reserve_streams: the arrays' byte sizes overflow");
+    if (r.reallocate) {
+        if (c->device == DSPI_DEVICE_NONE) c->cap_wg = r.capacity;
+        else {
+            HIPCK(c, hipSetDevice(c->device));
+            int rc = resize_reallocate(c, r.capacity, r.copy);
+            if (rc) return rc;
+        }
+    }
+    return (int)(c->cap_wg * row);
+}
+
+uint32_t dspi_stream_capacity(const dspi_ctx *c) { return c ? c->cap_wg * (uint32_t)c->sm.row : 0; }
 
 int dspi_debug_stream_positions(dspi_ctx *c, uint32_t first, uint32_t count, uint32_t *widx, uint32_t *ring_pos) {
     if (!c || !widx || !ring_pos) return DSPI_E_INVAL;

@@ -21,6 +21,7 @@ RESUME_AS_IS = 0x1
 MOVE_AS_IS = 0x1
 COMPACT_ONE_WAY = 0x1
 BOOT_STREAMS_AS_IS = 0x1
+RESIZE_PAUSED = 0x1
 OUT_TILED = 0x2
 OUT_ENABLED_ONLY = 0x4
 OUT_I2S_SLOTS = 0x8
@@ -125,6 +126,11 @@ def lib() -> C.CDLL:
         L.dspi_spdif_per_stream.argtypes = [vp, C.c_int]
         L.dspi_spdif_stream_pos.argtypes = [vp, u32, u32, vp, vp]
         L.dspi_spdif_encode_v.argtypes = [vp, vp, u32, vp, vp, u32]
+    if hasattr(L, "dspi_resize_streams"):      # (ABI 8 + resizing: detected by symbol; with it dspi_reserve_streams, dspi_stream_capacity, DSPI_RESIZE_PAUSED)
+        L.dspi_resize_streams.argtypes = [vp, u32, u32]
+        L.dspi_reserve_streams.argtypes = [vp, u32]
+        L.dspi_stream_capacity.argtypes = [vp]
+        L.dspi_stream_capacity.restype = u32
     _lib = L
     return L
 
@@ -476,6 +482,22 @@ class Dspi:
                                               BOOT_STREAMS_AS_IS if as_is else 0, C.byref(sel)), "boot_streams")
         assert n == len(s)
         return sel.value
+
+    # ---- resizing (include/dspi.h: a context gains and gives back slots) ----
+    def resize_streams(self, n: int, paused: bool = False) -> int:
+        """dspi_resize_streams: the context holds n streams from now on.  Growing: slots [old, n) are devices that have just been powered on
+        (paused: DSPI_RESIZE_PAUSED, they arrive paused); shrinking: every slot of [n, old) must be paused.  self.n_streams follows.
+        Works on host-only contexts."""
+        self.n_streams = self._ck(self.L.dspi_resize_streams(self.h, n, RESIZE_PAUSED if paused else 0), "resize_streams")
+        return self.n_streams
+
+    def reserve_streams(self, n: int) -> int:
+        """dspi_reserve_streams: room for n streams (whole rows), more than now or less; returns the new capacity in streams."""
+        return self._ck(self.L.dspi_reserve_streams(self.h, n), "reserve_streams")
+
+    def stream_capacity(self) -> int:
+        """dspi_stream_capacity: the streams the context's arrays have room for (rows x tile_streams())."""
+        return int(self.L.dspi_stream_capacity(self.h))
 
     def sync(self):
         self._ck(self.L.dspi_sync(self.h), "sync")

@@ -72,7 +72,8 @@ extern "C" {
                               * 8 + paused streams: detect by symbol (dspi_pause_streams; with it dspi_resume_streams, dspi_streams_paused, DSPI_RESUME_AS_IS; additions only);
                               * 8 + stream moves: detect by symbol (dspi_move_streams; with it dspi_plan_compaction, dspi_stream_move, DSPI_MOVE_AS_IS, DSPI_COMPACT_ONE_WAY; additions only);
                               * 8 + stream boots: detect by symbol (dspi_boot_streams; with it DSPI_BOOT_STREAMS_AS_IS; additions only);
-                              * 8 + per-stream S/PDIF positions: detect by symbol (dspi_spdif_per_stream; with it dspi_spdif_stream_pos, dspi_spdif_encode_v; additions only) */
+                              * 8 + per-stream S/PDIF positions: detect by symbol (dspi_spdif_per_stream; with it dspi_spdif_stream_pos, dspi_spdif_encode_v; additions only);
+                              * 8 + resizing: detect by symbol (dspi_resize_streams; with it dspi_reserve_streams, dspi_stream_capacity, DSPI_RESIZE_PAUSED; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -439,6 +440,63 @@ int dspi_plan_compaction(const dspi_ctx *ctx, dspi_stream_move *moves, uint32_t 
 #define DSPI_BOOT_STREAMS_AS_IS 0x1u   /* keep the power-on write positions (delay write index 0, ring position 0) */
 int dspi_boot_streams(dspi_ctx *ctx, const uint32_t *streams, uint32_t n,
                       const void *dump, size_t len, uint32_t flags, int *selection);
+
+/* ---- resizing: a context gains and gives back slots ----------------------------------------------------------------------------------- */
+/* n_streams is no constant of dspi_create.  A context that has drained (dspi_plan_compaction with DSPI_COMPACT_ONE_WAY, dspi_move_streams:
+ * the survivors sit in [0, A)) gives the rest back, a full one takes more devices, and contexts of different device classes on one GPU
+ * trade capacity as their population shifts — without a second context and an export and import of everything.
+ * The persistent per-stream arrays (state slots, delay lines, leveller rings, the PDM words once allocated) are rows of R =
+ * dspi_tile_streams streams, row-outermost.  A context has a CAPACITY of rows, at least the rows in use; dspi_stream_capacity returns it
+ * in streams (rows x R).  After dspi_create it is the rows in use.  Capacity is an allocation fact: no kernel launches over rows past
+ * the rows in use.
+ *   what the call does  dspi_resize_streams sets dspi_num_streams to n_streams and returns it.  Above the current count the context GROWS:
+ *                       slots [old, new) appear.  Inside the capacity no allocation is made.  Past it, new arrays of exactly the rows
+ *                       needed are allocated — ALL of them must succeed before anything is written; a failed allocation returns
+ *                       DSPI_E_NOMEM and the context, its capacity included, is bit for bit as it was —, the rows in use are copied device
+ *                       to device on the context's stream behind its earlier work, the stream is synchronised ONCE and the old arrays
+ *                       are freed: during the call both copies exist.  Below the current count the context SHRINKS: the occupants of
+ *                       [new, old) are gone; nothing is allocated, freed or waited for, and the capacity stays.  At the current count the
+ *                       call returns it and does nothing.
+ *                       dspi_reserve_streams sets the capacity to rows(n_streams) x R and returns it, both ways: ahead of a burst of
+ *                       arrivals, or — dspi_reserve_streams(ctx, dspi_num_streams(ctx)) — to return the memory after a shrink.  Where the
+ *                       capacity has that value already nothing happens; otherwise it reallocates, copies and frees as above, with the
+ *                       same atomicity and the same single synchronisation.  dspi_num_streams does not change.
+ *   new slots           the devices dspi_create makes on this context, exactly what dspi_boot_streams makes with a NULL dump: by default
+ *                       a first boot on an erased flash (the 512-sample mute is armed as a pending operation of the new object), on a
+ *                       DSPI_BOOT_POPULATED_FLASH context the populated flash without a selected preset; host settings 44.1 kHz, 0 dB,
+ *                       unmuted.  All new slots share ONE new parameter object.  Every state slot, line word, ring word and — if the
+ *                       context has run the modulator — PDM word of a new slot is written to its power-on word, whatever the column held:
+ *                       a column past dspi_num_streams may be dirty from an earlier shrink, and no padding column is trusted.
+ *   write positions     the boot's rule; the residents are the ACTIVE streams below the old count.  A new slot in a row that has a
+ *                       resident takes the (widx, ring_pos) of the row's lowest-numbered resident, read on the device behind the
+ *                       context's earlier work; a row without a resident — every whole new row — gets (0, 0).  A grown row stays on the
+ *                       kernels' one-access-per-row path.
+ *   activity            new slots are active; with DSPI_RESIZE_PAUSED they are paused, frozen in power-on state until
+ *                       dspi_resume_streams.  The flag has no meaning on a shrink and is accepted there.  With dspi_spdif_per_stream on, the
+ *                       new slots' positions are 0 and the old slots keep theirs; with it off nothing per stream exists.
+ *   open ends           a shrink releases the cut slots' parameter references; an object that lost its last stream is dropped at the
+ *                       next commit, as after a boot; pending operations of objects that are still referenced stay.  Every slot of the
+ *                       cut range must be PAUSED: a resize never destroys an active stream, which is the moves' rule.
+ *   validation          everything is validated before anything is written.  n_streams == 0, an undefined flag bit, an active slot in
+ *                       the cut range, a row count whose byte sizes would overflow size_t (or whose streams an int32_t index cannot
+ *                       name); for dspi_reserve_streams n_streams == 0 or below dspi_num_streams: DSPI_E_INVAL, and the context is bit
+ *                       for bit as it was.
+ *   timing              inside the capacity a grow is asynchronous on the context's stream like dspi_boot_streams, and a shrink is
+ *                       bookkeeping.  A call that reallocates waits for the stream once: it is rare and may wait.  All take effect at
+ *                       the next dspi_process: pcm_in and every dspi_out buffer then span the new dspi_num_streams (tiled buffers the new
+ *                       whole tiles), per-stream calls accept the new range, and the launch plan is rebuilt — a small float context that
+ *                       grows past the latency layout's size rule leaves that layout, one that shrinks below it returns to it; no output
+ *                       word changes either way.
+ *   host-only contexts  both calls work there, as dspi_boot_streams does: objects, references, activity, S/PDIF positions and the
+ *                       capacity number.
+ *   not touched         the context's S/PDIF block position, "has processed audio", the direct path's statistics, the snapshot
+ *                       fingerprint: records are per stream, so a snapshot taken before a resize is importable after it.
+ * Not in scope: growing in place through virtual-memory mapping, chunked arrays, a growth policy (geometric reserve is the caller's
+ * choice), changing a context's flavour. */
+#define DSPI_RESIZE_PAUSED 0x1u   /* dspi_resize_streams, growing: the new slots arrive paused */
+int dspi_resize_streams(dspi_ctx *ctx, uint32_t n_streams, uint32_t flags);   /* returns the new dspi_num_streams */
+int dspi_reserve_streams(dspi_ctx *ctx, uint32_t n_streams);                  /* returns the new capacity */
+uint32_t dspi_stream_capacity(const dspi_ctx *ctx);
 
 /* ---- PDM sub output ---------------------------------------------------- */
 /* The consumer of dspi_out.sub: the firmware's 256x oversampled 2nd-order sigma-delta modulator with noise-shaped
