@@ -68,6 +68,7 @@ struct dspi_ctx {
     bool populated = false;      // DSPI_BOOT_POPULATED_FLASH: the streams are devices whose flash already holds a preset directory
     bool audio_started = false;  // a dspi_process has run: the devices are no longer booting (dspi_load_flash_dump)
     bool no_direct = false;      // DSPI_NO_DIRECT (development / tests, read once at dspi_create): the staged path for small host calls too
+    bool no_emit_lines = false;  // DSPI_NO_EMIT_LINES (development / tests, read once at dspi_create): the emitter wave of the packed float kernel never takes its whole-line path
     // the leveller's alpha^count on the device is step 1 + a table that was generated for the firmware's 18 alphas (include/dspi_detmath.h); the
     // alphas this context has actually built into images, and the block length they were last checked with against the exact form
     std::vector<uint32_t> lv_alphas; uint32_t lv_checked_count = 0; size_t lv_checked_n = 0;
@@ -553,6 +554,7 @@ int dspi_create(dspi_ctx **out, int flavor, uint32_t n_streams, int hip_device) 
     c->fma = fma;
     c->populated = populated;
     c->no_direct = getenv("DSPI_NO_DIRECT") != nullptr;
+    c->no_emit_lines = getenv("DSPI_NO_EMIT_LINES") != nullptr;
     if (const char *e = getenv("DSPI_DIRECT_SPIN_US")) { const long v = atol(e); if (v > 0) c->direct_spin_us = (uint32_t)std::min<long>(v, 1000000L); }
     if (const char *e = getenv("DSPI_MOVE_BATCH")) { const long v = atol(e); if (v > 0) c->move_batch = (uint32_t)std::min<long>(std::max<long>(v, 2L), 65535L); }
     c->images.push_back(std::make_unique<Params>(flavor, fma, !populated));
@@ -721,8 +723,9 @@ int dspi_debug_image(dspi_ctx *c, int32_t stream, void *buf, size_t cap) {
 
 int dspi_debug_launch_plan(dspi_ctx *c, uint32_t *counts, size_t n_counts) {
     if (!c || !counts || n_counts < 5) return DSPI_E_INVAL;
-    const int n = n_counts >= 7 ? 7 : n_counts >= 6 ? 6 : 5;      // [0..5]: items per PathGroup, [6]: the latency layout's items with paired presets
-    uint32_t all[7] = {};
+    const int n = n_counts >= 8 ? 8 : n_counts >= 7 ? 7 : n_counts >= 6 ? 6 : 5;      // [0..5]: items per PathGroup, [6]: the latency layout's items with paired presets, [7]: DSPI_NO_EMIT_LINES
+    uint32_t all[8] = {};
+    all[7] = c->no_emit_lines ? 1u : 0u;
     for (const PathInfo &pi : kPaths) {
         const uint32_t k = (uint32_t)c->plan.items[(int)pi.path].size();
         all[(int)pi.group] += k;
@@ -1730,6 +1733,7 @@ int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_bloc
     a.n_streams = c->n_streams; a.n_blocks = n_blocks; a.block_len = block_len; a.bit_depth = (uint32_t)bit_depth;
     a.tiled_out = tiled ? 1u : 0u;
     a.fma = c->fma ? 1u : 0u;
+    a.no_emit_lines = c->no_emit_lines ? 1u : 0u;
     // (two-pass S/PDIF: the encoder reads the WHOLE scratch chunk, so the chain must write the silent pairs' zero words there as well)
     a.skip_silent = ((flags & DSPI_OUT_ENABLED_ONLY) && !L.spdif_two_pass) ? 1u : 0u;
     a.i2s_slots = (flags & DSPI_OUT_I2S_SLOTS) ? 1u : 0u;

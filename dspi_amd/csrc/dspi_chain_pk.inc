@@ -1301,6 +1301,106 @@ __device__ __forceinline__ void pair_emit_finish(const KArgs &a, ImgPtr img, con
         }
     }
 }
+// ---- the emitter wave, whole pair-buffer lines: pair_lines_load / pair_lines_finish / pair_lines_packet_end ----
+// A line of the stream-major pair buffer is sixteen frames of ONE stream ({L, R} x 16 = 128 bytes).  In the row mapping above a lane holds two
+// streams and all sixteen frames, so each of its 16-byte stores lands in 64 different lines and the pieces have to meet in L2.  The emitter
+// wave owns no output, it only READS rows, so it may read them in the mapping the STORES want: lane = (g = lane >> 3, j = lane & 7), j the
+// frame pair of the chunk; for u = 0..3 the lane serves the stream quad 8u + g of the row (streams 4(8u + g) .. + 3).  One 16-byte load at
+// row 2j + e, words 4(8u + g) .. + 3, gives the lane four adjacent streams of one frame; the 4 x 4 transposition to "four words of one
+// stream" is register naming.  Per instruction: eight rows x one full 128-byte line (eight g), 16 instructions per pair — 128 line requests,
+// the figure of the 32 row loads of pair_emit_load.  A stream's piece {L 2j, R 2j, L 2j+1, R 2j+1} then leaves as one 16-byte store; eight
+// adjacent lanes (j) write one whole line and an instruction writes eight whole lines, so the stores can be non-temporal (a PARTIAL line
+// stored non-temporally is the 24 ms case noted in pair_emit_finish: the path is taken only where every line is whole and aligned).
+// The rows were written by other waves of the workgroup: every load bypasses the CU's L1 (aux 16 = sc1, what ld_agent2 does), as a raw
+// buffer load whose descriptor is wave-uniform (one per (row, output) line or mini line; offsets past the line read as zero, never fault).
+// Running packet peaks would need a register per (stream, side) here; they live in LDS instead (ds_max_u32 on the non-negative float's bit
+// pattern, which orders like an integer): `acc` [pair][side][128], the area of the posted envelopes, which only the split master of the
+// per-lane-filter kernels uses — and that instantiation has no emitter wave.
+// Needs: all 128 streams of the row in the launch, at ONE line write position w0, whole 16-frame chunks (not TAIL), 128-byte aligned lines.
+__device__ __forceinline__ void pair_lines_load(const KArgs &a, ImgPtr img, const StateMap &sm, uint32_t w0, u32x4 (&v)[2][2][4],
+                                                uint32_t wg, uint32_t lane, int p, uint32_t e_cq, uint32_t e_q) {
+    constexpr int N = make_state_map(1).n_out;
+    const uint32_t flags = img->flags;
+    const uint32_t dmask = (uint32_t)sm.max_delay - 1u;
+    uint32_t g8 = lane >> 3, j8 = lane & 7u;
+    asm volatile("" : "+v"(g8), "+v"(j8));      // (addresses formed per chunk, see output_item_pk)
+    __amdgpu_buffer_rsrc_t rs[2];
+    uint32_t off[2][2];      // byte offset of the lane's first quad in row 2j + e of each side
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+        const int oo = 2 * p + side;
+        const int32_t dly_ = img->delay_samples[oo];
+        const bool dl_on_ = (flags & IF_ANY_DELAY) && dly_ > 0;
+        const bool direct_ = dl_on_ && (dly_ >= sm.max_delay || dly_ <= sm.max_delay - 3 * T);      // (output_item_pk: e_direct)
+        uint32_t *src = direct_ ? a.dlines + ((size_t)wg * N + oo) * (size_t)sm.max_delay * ROWP
+                                : a.xwords + (((size_t)wg * 3 + (e_q % 3u)) * kMaxOut + oo) * (T * ROWP);
+        rs[side] = __builtin_amdgcn_make_buffer_rsrc(src, 0, (int)((direct_ ? (uint32_t)sm.max_delay : (uint32_t)T) * ROWP * 4u), 0x00020000);
+        const uint32_t pos0 = direct_ ? w0 + e_cq * T - (uint32_t)dly_ : 0u, pm = direct_ ? dmask : (uint32_t)T - 1u;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) off[side][e] = (((pos0 + 2u * j8 + (uint32_t)e) & pm) * ROWP + 4u * g8) * 4u;      // (the mask per row: a chunk may wrap inside the line)
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)      // quad by quad, the order pair_lines_finish uses them in
+#pragma unroll
+        for (int side = 0; side < 2; ++side)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) v[side][e][u] = __builtin_amdgcn_raw_buffer_load_b128(rs[side], (int)(off[side][e] + (uint32_t)u * 128u), 0, 16);
+}
+__device__ __forceinline__ void pair_lines_finish(const KArgs &a, ImgPtr img, const Geo &g, const u32x4 (&v)[2][2][4], uint32_t *__restrict__ acc,
+                                                  uint32_t wg, uint32_t lane, int p, uint32_t e_kq, uint32_t e_cq) {
+    constexpr int P = make_state_map(1).n_pairs;
+    const size_t F = (size_t)g.n_blocks * g.B;
+    uint32_t g8 = lane >> 3, j8 = lane & 7u;
+    asm volatile("" : "+v"(g8), "+v"(j8));      // (addresses formed per chunk, see output_item_pk)
+    // a pair whose two outputs are both disabled is zero-filled whatever its lines still hold (usb_audio.c:930-933)
+    const float scale = ((img->out_enabled >> (2 * p)) & 3u) ? 8388607.0f : 0.0f;
+    const bool shift = a.i2s_slots && ((img->i2s_pairs >> p) & 1u);      // an I2S slot's words leave left-justified (audio_i2s_multi.c:217-226)
+    auto word = [&](uint32_t l, uint32_t r) {      // {L, R} of one frame, exactly pair_emit_finish's word
+        const v2f d = v2f{clamp_pm1(as_f(l)), clamp_pm1(as_f(r))} * scale;
+        v2u w = v2u{(uint32_t)(int32_t)d.x, (uint32_t)(int32_t)d.y};
+        if (shift) w = w << 8u;
+        return w;
+    };
+    int32_t *dst = a.pairs ? a.pairs + (((size_t)(wg * ROWP + 4u * g8 - a.pairs_stream0) * P + p) * F + (size_t)e_kq * g.B + (size_t)e_cq * T + 2u * j8) * 2 : nullptr;
+    const size_t sstride = (size_t)P * F * 2;      // words from a stream to the next
+    uint32_t *m = acc + 4u * g8;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            // meters (usb_audio.c:915-923): max(|y 2j|, |y 2j+1|) into the stream's packet peak; a NaN leaves a meter alone, as peak_acc does
+            float ml, mr;
+            asm("v_max3_f32 %0, |%1|, |%2|, 0" : "=v"(ml) : "v"(as_f(v[0][0][u][k])), "v"(as_f(v[0][1][u][k])));
+            asm("v_max3_f32 %0, |%1|, |%2|, 0" : "=v"(mr) : "v"(as_f(v[1][0][u][k])), "v"(as_f(v[1][1][u][k])));
+            atomicMax(m + (32 * u + k), as_u(ml));
+            atomicMax(m + (ROWP + 32 * u + k), as_u(mr));
+            if (dst) {
+                const v2u f0 = word(v[0][0][u][k], v[1][0][u][k]), f1 = word(v[0][1][u][k], v[1][1][u][k]);
+                // eight adjacent lanes: one whole line that nobody here reads again
+                __builtin_nontemporal_store(u32x4{f0.x, f0.y, f1.x, f1.y}, reinterpret_cast<u32x4 *>(dst + (size_t)(32 * u + k) * sstride));
+            }
+        }
+}
+// a packet ends: the LDS meters of pair p become peaks, sticky bits and the status slot of the launch's last packet (usb_audio.c:915-923,
+// :945-951), and are cleared for the next packet.  Lane l finishes streams l and l + 64 of the row.
+__device__ __forceinline__ void pair_lines_packet_end(const KArgs &a, const StateMap &sm, const Geo &g, uint32_t *__restrict__ acc, v2u &clip,
+                                                      uint32_t wg, uint32_t lane, int p, uint32_t e_kq) {
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+        const int oo = 2 * p + side;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            uint32_t col = lane + 64u * (uint32_t)h;
+            asm volatile("" : "+v"(col));      // (addresses formed per packet)
+            const float pk = as_f(acc[side * ROWP + col]);
+            acc[side * ROWP + col] = 0u;
+            const uint32_t p16 = (uint32_t)(fminf(1.0f, pk) * 32767.0f);
+            if (pk > 1.001f) clip[h] |= 1u << (2 + oo);
+            if (a.peaks) a.peaks[((size_t)(wg * ROWP + col) * g.n_blocks + e_kq) * sm.n_ch + 2 + oo] = (uint16_t)p16;
+            if (e_kq == g.n_blocks - 1) a.state[((size_t)wg * sm.n_slots + sm.peaks + 2 + oo) * ROWP + col] = p16;
+        }
+    }
+}
 // the pairs of a mask, lowest first (compile-time)
 constexpr int emit_pair_count(unsigned m) { return m ? 1 + emit_pair_count(m & (m - 1)) : 0; }
 constexpr int emit_pair_nth(unsigned m, int n) { return n == 0 ? __builtin_ctz(m | 0x100u) : emit_pair_nth(m & (m - 1), n - 1); }
@@ -1522,39 +1622,84 @@ __global__ __launch_bounds__(64 * kPkWaves, 1) void chain_kernel_pk(KArgs a) {
         WT_FINISH(rank);
         if (rsplit) st2(sm.lev + 1, as_v2u(m.env_r));
     } else if (role.kind == 2 && ext_emit) {
-        // ---- third wave of the master SIMD, stream-major words: the emission of the pairs in DSPI_EMIT_PAIRS (pair_emit_load / _finish) ----
+        // ---- third wave of the master SIMD, stream-major words: the emission of the pairs in DSPI_EMIT_PAIRS ----
+        // whole lines (pair_lines_*) where the row allows it, else the row mapping (pair_emit_load / _finish)
         constexpr int NP = emit_pair_count(ext_mask);
-        v2u widx_e = ld2(sm.widx), clip = v2u{0u, 0u};
-        v2f pk[NP > 0 ? NP : 1][2];
-#pragma unroll
-        for (int j = 0; j < NP; ++j) { pk[j][0] = splat(0.0f); pk[j][1] = splat(0.0f); }
+        v2u widx_e = ld2(sm.widx);
         uint32_t e_kq = 0, e_cq = 0;
         asm volatile("" : "+v"(widx_e));      // (arrived before the time loop: see the output waves below)
         const uint32_t dmask = (uint32_t)sm.max_delay - 1u;
-        WT_DECL;
-        for (uint32_t st = 0; st < g.steps; ++st) {
-            const uint32_t q = st - g.lag - 1;
-            if (st >= g.lag + 3 && q - 2u < g.items) {      // chunk q - 2: its rows are complete behind the barrier that ended step st - 1 (output_item_pk)
-                // two pairs' rows in flight at most (128 of the wave's registers): pair j + 1 is requested before pair j is converted and stored
-                v2f dl[NP > 0 ? NP : 1][2][T];
-                if (NP > 0) pair_emit_load<TAIL>(a, img, sm, widx_e, dl[0], wg, lane, emit_pair_nth(ext_mask, 0), e_cq, q - 2u);
+        // Whole lines: decided once, wave-uniform.  The whole row is in the launch, its 128 streams share one line write position, the chunks
+        // are whole (not TAIL), and every line of the pair buffer is 128-byte aligned (or there is no pair buffer: meters only).
+        static_assert(NP * 2 * ROWP * sizeof(uint32_t) <= 2 * 2 * HALF * sizeof(v2f), "the emitter wave's LDS meters: two pairs fit the posted envelopes' area");
+        uint32_t *acc = reinterpret_cast<uint32_t *>(envpost);      // [NP][2 sides][128 streams] running packet peaks (float bits)
+        uint32_t w0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)widx_e.x);
+        const bool lines = !TAIL && !a.no_emit_lines && item.mask == ~0ull && __all(widx_e.x == widx_e.y && widx_e.x == w0) &&
+                           (!a.pairs || ((reinterpret_cast<uintptr_t>(a.pairs) & 127u) == 0 && (g.n_blocks * g.B) % 16u == 0));
+        // (a time loop each: one loop with both bodies hoists the addresses of both and spills them)
+        if (lines) {
+            if constexpr (!TAIL) {
 #pragma unroll
-                for (int j = 0; j < NP; ++j) {
-                    if (j + 1 < NP) pair_emit_load<TAIL>(a, img, sm, widx_e, dl[j + 1], wg, lane, emit_pair_nth(ext_mask, j + 1), e_cq, q - 2u);
-                    pair_emit_finish<TAIL>(a, img, sm, g, dl[j], pk[j], clip, wg, lane, stream, emit_pair_nth(ext_mask, j), e_kq, e_cq);
+                for (int i = 0; i < NP * 2 * 2; ++i) acc[i * 64 + lane] = 0u;
+                v2u clip = v2u{0u, 0u};
+                WT_DECL;
+                for (uint32_t st = 0; st < g.steps; ++st) {
+                    const uint32_t q = st - g.lag - 1;
+                    if (st >= g.lag + 3 && q - 2u < g.items) {      // chunk q - 2: its rows are complete behind the barrier that ended step st - 1 (output_item_pk)
+                        // two pairs' rows in flight at most (128 of the wave's registers): pair j + 1 is requested before pair j is converted and stored
+                        u32x4 v[NP > 0 ? NP : 1][2][2][4];
+                        if (NP > 0) pair_lines_load(a, img, sm, w0, v[0], wg, lane, emit_pair_nth(ext_mask, 0), e_cq, q - 2u);
+#pragma unroll
+                        for (int j = 0; j < NP; ++j) {
+                            if (j + 1 < NP) pair_lines_load(a, img, sm, w0, v[j + 1], wg, lane, emit_pair_nth(ext_mask, j + 1), e_cq, q - 2u);
+                            pair_lines_finish(a, img, g, v[j], acc + j * 2 * ROWP, wg, lane, emit_pair_nth(ext_mask, j), e_kq, e_cq);
+                        }
+                        if (++e_cq == g.cpb) {
+#pragma unroll
+                            for (int j = 0; j < NP; ++j) pair_lines_packet_end(a, sm, g, acc + j * 2 * ROWP, clip, wg, lane, emit_pair_nth(ext_mask, j), e_kq);
+                            e_cq = 0; ++e_kq;
+                            if (img->flags & IF_ANY_DELAY) w0 = (w0 + g.B) & dmask;      // (usb_audio.c:911)
+                        }
+                    }
+                    WT_BEFORE_BARRIER;
+                    lds_barrier();
+                    WT_AFTER_BARRIER;
                 }
-                if (++e_cq == g.cpb) {
-                    e_cq = 0; ++e_kq;
-                    if (img->flags & IF_ANY_DELAY) widx_e = (widx_e + g.B) & dmask;      // (usb_audio.c:911)
-                }
+                WT_FINISH(rank);
+                uint32_t *cs = a.state + ((size_t)wg * sm.n_slots + sm.clip + 1) * ROWP + lane;      // (clip slots 1..3 are OR-ed by the reader; lane l: streams l and l + 64)
+                atomicOr(cs, clip.x);
+                atomicOr(cs + 64, clip.y);
             }
-            WT_BEFORE_BARRIER;
-            lds_barrier();
-            WT_AFTER_BARRIER;
+        } else {
+            v2u clip = v2u{0u, 0u};
+            v2f pk[NP > 0 ? NP : 1][2];
+#pragma unroll
+            for (int j = 0; j < NP; ++j) { pk[j][0] = splat(0.0f); pk[j][1] = splat(0.0f); }
+            WT_DECL;
+            for (uint32_t st = 0; st < g.steps; ++st) {
+                const uint32_t q = st - g.lag - 1;
+                if (st >= g.lag + 3 && q - 2u < g.items) {      // chunk q - 2, as above
+                    // two pairs' rows in flight at most (128 of the wave's registers): pair j + 1 is requested before pair j is converted and stored
+                    v2f dl[NP > 0 ? NP : 1][2][T];
+                    if (NP > 0) pair_emit_load<TAIL>(a, img, sm, widx_e, dl[0], wg, lane, emit_pair_nth(ext_mask, 0), e_cq, q - 2u);
+#pragma unroll
+                    for (int j = 0; j < NP; ++j) {
+                        if (j + 1 < NP) pair_emit_load<TAIL>(a, img, sm, widx_e, dl[j + 1], wg, lane, emit_pair_nth(ext_mask, j + 1), e_cq, q - 2u);
+                        pair_emit_finish<TAIL>(a, img, sm, g, dl[j], pk[j], clip, wg, lane, stream, emit_pair_nth(ext_mask, j), e_kq, e_cq);
+                    }
+                    if (++e_cq == g.cpb) {
+                        e_cq = 0; ++e_kq;
+                        if (img->flags & IF_ANY_DELAY) widx_e = (widx_e + g.B) & dmask;      // (usb_audio.c:911)
+                    }
+                }
+                WT_BEFORE_BARRIER;
+                lds_barrier();
+                WT_AFTER_BARRIER;
+            }
+            WT_FINISH(rank);
+            atomicOr(gs + (size_t)(sm.clip + 1) * ROWP, clip.x);      // (clip slots 1..3 are OR-ed by the reader)
+            atomicOr(gs + (size_t)(sm.clip + 1) * ROWP + 1, clip.y);
         }
-        WT_FINISH(rank);
-        atomicOr(gs + (size_t)(sm.clip + 1) * ROWP, clip.x);      // (clip slots 1..3 are OR-ed by the reader)
-        atomicOr(gs + (size_t)(sm.clip + 1) * ROWP + 1, clip.y);
     } else if (role.kind != 3) {
         for (uint32_t st = 0; st < g.steps; ++st) lds_barrier();      // idle partner: keeps the barrier count
     } else {

@@ -32,6 +32,7 @@ struct KArgs {
     uint32_t spdif;          // DSPI_OUT_SPDIF (latency layout only): `pairs` takes IEC 60958 subframes, uint32 [stream][pair][frame][4]
     uint32_t spdif_pos;      // position of the launch's first frame in the 192-frame block (the channel status follows each image's own fs_hz)
     uint32_t fma;            // float flavour: the context's contract is DSPI_FLOAT_CONTRACT_FMA (selects the kernel family at launch)
+    uint32_t no_emit_lines;  // DSPI_NO_EMIT_LINES: the packed kernel's emitter wave keeps the row mapping everywhere (dspi_chain_pk.inc pair_lines_*)
 };
 
 size_t chain_lds_bytes(int flavor, int packed);

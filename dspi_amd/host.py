@@ -248,10 +248,11 @@ class Dspi:
 
     def launch_plan(self) -> dict:
         """dspi_debug_launch_plan: work items per kernel path after the last process call."""
-        c = (C.c_uint32 * 7)()
-        self._ck(min(self.L.dspi_debug_launch_plan(self.h, c, 7), 0), "debug_launch_plan")
+        c = (C.c_uint32 * 8)()
+        self._ck(min(self.L.dspi_debug_launch_plan(self.h, c, 8), 0), "debug_launch_plan")
+        # (emit_lines_off: not a count of items — 1 while DSPI_NO_EMIT_LINES keeps the packed kernel's emitter wave off its whole-line path)
         return dict(zip(("q28_shared", "packed_shared", "one_stream_per_lane_images", "packed_per_lane_values_and_bands", "packed_per_lane_values", "latency_layout",
-                         "latency_layout_paired"), list(c)))
+                         "latency_layout_paired", "emit_lines_off"), list(c)))
 
     def direct_stats(self) -> dict:
         """dspi_debug_direct_stats: the one-packet-per-call path's polling record (include/dspi.h)."""

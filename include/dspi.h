@@ -595,8 +595,9 @@ int dspi_debug_image(dspi_ctx *ctx, int32_t stream, void *buf, size_t cap);
  * incl. band coefficients, packed float with per-lane values and shared band coefficients}.  Tests use it to prove that a scenario
  * ran on the path it was written for.  With n_counts >= 6, counts[5] = items of the float chain's latency layout (any of its three
  * shapes: launches small enough to leave the chip underfilled); with n_counts >= 7, counts[6] = those of them that serve several
- * presets of one structure at once (a workgroup's stream slots each read their own image).  Returns the number of counts written
- * (5, 6 or 7) or a negative DSPI_E_*. */
+ * presets of one structure at once (a workgroup's stream slots each read their own image); with n_counts >= 8, counts[7] = 1 if the
+ * context was made with DSPI_NO_EMIT_LINES in the environment (the packed float kernel's emitter wave then never takes its whole-line
+ * path), else 0.  Returns the number of counts written (5 to 8) or a negative DSPI_E_*. */
 int dspi_debug_launch_plan(dspi_ctx *ctx, uint32_t *counts, size_t n_counts);
 /* The delay write index and the leveller ring position of streams [first, first + count), masked to the line / ring length, into host
  * buffers of count words each.  Synchronises the context's stream.  Tests use it to prove that a scenario really was misaligned before
