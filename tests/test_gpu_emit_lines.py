@@ -2,12 +2,13 @@
 16-byte loads in the lane mapping of its stores and writes whole 128-byte pair-buffer lines) and its fallback (pair_emit_load / _finish).
 Every case runs twice, with and without DSPI_NO_EMIT_LINES=1, and both runs are compared with the CPU oracle the way
 tests/test_gpu_parity.py::compare does it — every pair word, sub word, peak, status byte and clip flag — never with each other.  The
-oracle's results of a case are computed once and shared by its runs.  Needs an MI355X."""
+oracle's results of a case are computed once and shared by its runs, and so are those of its reference leg (tests/refleg.py: the reference's
+leaf sources compiled unmodified, held to the GPU's words directly; float only here, so every stream is expected to be held).  Needs an MI355X."""
 import numpy as np
 import pytest
 
 from conftest import has_gpu
-from orclib import Oracle
+import refleg
 from dspi_amd import wire as W, workloads as WL
 from dspi_amd.host import Dspi
 from test_gpu_pause import new_sched
@@ -41,27 +42,49 @@ def samples_ms(n, fs):
 
 
 _REF = {}
+_LEG = {}      # the same keys: {stream: the oracle's reference leg, its words of every call kept}
 
 
 def reference(key, flavor, fs, vol, blob, pcm, per, calls, B, setup, between):
-    """{stream: ([(pairs, sub, peaks, clip) per call], status after the last call)} of the oracle, computed once per case"""
+    """{stream: ([(pairs, sub, peaks, clip) per call], status after the last call)} of the oracle, computed once per case; the reference
+    build runs beside it (refleg.Leg) and keeps its own words of every call for hold_to_reference()"""
     key = key + (bool(getattr(flavor, "fma", False)),)      # (W.F32_FMA compares equal to the int 1)
     if key not in _REF:
-        ref = {}
+        ref, legs = {}, {}
         for s in range(pcm.shape[0]):
-            o = Oracle(flavor, detmath=True)
+            o = refleg.Leg(flavor, f"stream {s}")
             assert o.set_rate(fs) == 0
             o.set_volume(vol)
             assert o.load_bulk(blob) == 0
             if setup: setup(o)
-            parts = []
+            parts, kept = [], []
             for c in range(calls):
                 if between and c in between: between[c](o)
                 parts.append(o.process(np.ascontiguousarray(pcm[s, c * per * B:(c + 1) * per * B]), per, B))
+                kept.append(o.last)
             ref[s] = (parts, o.status())
+            legs[s] = (o, kept)
             o.close()
-        _REF[key] = ref
+        _REF[key], _LEG[key] = ref, legs
     return _REF[key]
+
+
+def left_justified(words, i2s_mask):
+    """pair words [P][frames][2] as DSPI_OUT_I2S_SLOTS hands them back: the pairs of i2s_mask shifted up by eight bits"""
+    words = words.copy()
+    for p in range(words.shape[0]):
+        if i2s_mask >> p & 1: words[p] = (words[p].astype(np.uint32) << np.uint32(8)).astype(np.int32)
+    return words
+
+
+def hold_to_reference(key, flavor, s, c, pairs=None, sub=None, peaks=None, clip=None, status=None, i2s_mask=0):
+    """stream s, call c of a case: the GPU's words against the reference build's (status: after the last call)"""
+    leg, kept = _LEG[key + (bool(getattr(flavor, "fma", False)),)][s]
+    if not leg.on: return
+    (rp, rs, rk, rclip), rstatus, held = kept[c]
+    assert held, f"stream {s}, call {c}: a float->int cast overflowed on the x86 reference build — not expected of the float chain"
+    if i2s_mask: rp = left_justified(rp, i2s_mask)
+    leg.hold(pairs, sub, peaks, status, clip, what=f"call {c}", last=((rp, rs, rk, rclip), rstatus, held))
 
 
 def run_case(monkeypatch, off, key, flavor, fs, B, per, calls, S, blob, pcm=None, vol=-20 * 256, setup=None, between=None, i2s_mask=0,
@@ -89,15 +112,13 @@ def run_case(monkeypatch, off, key, flavor, fs, B, per, calls, S, blob, pcm=None
         for c, (rp, rs, rk, rclip) in enumerate(parts):
             pairs, sub, peaks = outs[c]
             if want_pairs:
-                want = rp
-                if i2s_mask:
-                    want = rp.copy()
-                    for p in range(want.shape[0]):
-                        if i2s_mask >> p & 1: want[p] = (want[p].astype(np.uint32) << np.uint32(8)).astype(np.int32)
+                want = left_justified(rp, i2s_mask) if i2s_mask else rp
                 assert np.array_equal(want, pairs[s]), f"pairs differ, stream {s}, call {c}: {np.argwhere(want != pairs[s])[:3].tolist()}"
             assert np.array_equal(rs, sub[s]), f"sub differs, stream {s}, call {c}"
             if want_peaks: assert np.array_equal(rk, peaks[s]), f"peaks differ, stream {s}, call {c}: {np.argwhere(rk != peaks[s])[:3].tolist()}"
             assert int(clips[c][s]) == rclip, f"clip flags differ, stream {s}, call {c}"
+            hold_to_reference(key, flavor, s, c, pairs[s] if want_pairs else None, sub[s], peaks[s] if want_peaks else None, int(clips[c][s]),
+                              d.status(s) if c == calls - 1 else None, i2s_mask=i2s_mask)
         assert status == d.status(s), f"status differs, stream {s}"
     d.close()
     return ref
@@ -263,6 +284,7 @@ def test_device_pair_buffer_alignment_and_guards(flavor, off, offset_words, monk
             rp, rs, rk, rclip = ref[s][0][c]
             assert np.array_equal(rp, pairs[s]), f"pairs differ, stream {s}, call {c}: {np.argwhere(rp != pairs[s])[:3].tolist()}"
             assert np.array_equal(rs, sub[s]) and np.array_equal(rk, peaks[s]) and int(clip[s]) == rclip, f"stream {s}, call {c}"
+            hold_to_reference(("null", flavor), flavor, s, c, pairs[s], sub[s], peaks[s], int(clip[s]), d.status(s) if c == calls - 1 else None)
     for s in range(S): assert ref[s][1] == d.status(s), f"status differs, stream {s}"
     d.close()
 

@@ -127,15 +127,23 @@ def random_request(rng, flavor, fs):
 def test_random_request_sequences(flavor, seed):
     """Random vendor SET requests between launches — to every stream or to one — with their side effects on audio state
     (filter-path resets, crossfeed / leveller resets, delay changes, mutes), host volume / mute changes, and a sample-rate
-    change in the middle; compared packet by packet with one oracle per stream."""
+    change in the middle; compared packet by packet with one oracle per stream, each with its reference leg (tests/refleg.py)."""
     from dspi_amd.host import Dspi
+    request_sequence(flavor, seed, Dspi(flavor, 5, device=0))
+
+
+def request_sequence(flavor, seed, d):
+    """test_random_request_sequences' sequence on the context d and one oracle per stream; d None: the oracles alone (the CPU replay of
+    tests/test_ref_leg_cpu.py: the same draws in the same order)."""
+    import refleg
     from dspi_amd import workloads as WL
     from orclib import Oracle
     rng = np.random.default_rng(77000 + 100 * flavor + seed)
     fs, Bs = RATES[seed % 3]
     S = 5
-    d = Dspi(flavor, S, device=0); o = [Oracle(flavor, detmath=True) for _ in range(S)]
-    for x in [d] + o:
+    o = [refleg.Leg(flavor, f"stream {s}") for s in range(S)]
+    dev = [d] if d is not None else []
+    for x in dev + o:
         assert x.set_rate(fs) == 0
         x.set_volume(-12 * 256)
         assert x.load_bulk(WL.full_chain_blob(flavor)) == 0
@@ -148,33 +156,36 @@ def test_random_request_sequences(flavor, seed):
             req, wv, payload = random_request(rng, flavor, fs)
             target = None if rng.random() < 0.5 else int(rng.integers(0, S))
             rc_o = [oo.vendor_set(req, wv, payload) for i, oo in enumerate(o) if target is None or i == target]
+            if d is None: continue
             rc_d = d.vendor_set(req, wv, payload) if target is None else d.vendor_set(req, wv, payload, stream=target)
             assert (rc_d == 0) == all(r == 0 for r in rc_o), f"step {k}: request {req:#x} accepted differently"
         if rng.random() < 0.3:
             v = int(rng.choice([0, -256 * 30, -256 * 3, 256 * 2]))
-            d.set_volume(v); [oo.set_volume(v) for oo in o]
+            [x.set_volume(v) for x in dev + o]
         big = rng.random()
         if big < 0.08:                                   # host mute toggles
-            mu = bool(rng.integers(0, 2)); d.set_mute(mu); [oo.set_mute(mu) for oo in o]
+            mu = bool(rng.integers(0, 2)); [x.set_mute(mu) for x in dev + o]
         elif big < 0.14:                                 # a whole-state blob in the middle of the stream (bulk_params_apply)
             blob = random_blob(rng, flavor, fs)
-            assert d.load_bulk(blob) == 0 and all(oo.load_bulk(blob) == 0 for oo in o)
+            assert all(x.load_bulk(blob) == 0 for x in dev + o)
         elif big < 0.18:                                 # preset load: delay lines cleared, preset mute envelope (flash_storage.c:832, main.c:449-458)
             ref = Oracle(flavor); ref.set_rate(fs); ref.load_bulk(random_blob(rng, flavor, fs)); image = ref.save_slot(0); ref.close()
-            assert d.load_slot(image) == 0 and all(oo.load_slot(image) == 0 for oo in o)
+            assert all(x.load_slot(image) == 0 for x in dev + o)
         elif big < 0.21:
-            d.factory_defaults(); [oo.factory_defaults() for oo in o]
+            [x.factory_defaults() for x in dev + o]
         if k == n_steps // 2:
             fs, Bs = RATES[(seed + 1) % 3]
             B = int(rng.choice(Bs))
-            assert d.set_rate(fs) == 0 and all(oo.set_rate(fs) == 0 for oo in o)
+            assert all(x.set_rate(fs) == 0 for x in dev + o)
         chunk = np.ascontiguousarray(pcm[:, pos:pos + per * B]); pos += per * B
-        pairs, sub, peaks = d.process_host(chunk, per, B)
+        if d is not None: pairs, sub, peaks = d.process_host(chunk, per, B)
         for s in range(S):
             rp, rs, rk, _ = o[s].process(chunk[s], per, B)
+            if d is None: continue
             assert np.array_equal(rp, pairs[s]) and np.array_equal(rs, sub[s]) and np.array_equal(rk, peaks[s]), f"step {k} stream {s}"
             assert o[s].status() == d.status(s), f"step {k} stream {s}: status"
-    d.close()
+            o[s].hold(pairs[s], sub[s], peaks[s], d.status(s), what=f"step {k}")
+    for x in dev + o: x.close()
 
 
 @pytest.mark.all_layouts
@@ -217,33 +228,41 @@ def test_random_preset_per_stream(flavor, seed):
     """Every stream loads its own random blob: band kinds, flags, delays and leveller / crossfeed / loudness settings all
     differ from lane to lane inside one workgroup (per-lane parameter kernels, SIMT divergence on the band forms); a few
     streams keep a shared blob so that packed rows and per-lane rows coexist in one launch."""
+    preset_per_stream(flavor, seed)
+
+
+def preset_per_stream(flavor, seed, gpu=True):
+    """test_random_preset_per_stream's case; gpu=False: the sampled streams' oracles alone (tests/test_ref_leg_cpu.py), the same draws"""
+    import refleg
     from dspi_amd.host import Dspi
     from dspi_amd import workloads as WL
-    from orclib import Oracle
     rng = np.random.default_rng(9100 + 100 * flavor + seed)
     fs, Bs = RATES[seed % 3]
     B = int(rng.choice(Bs)); blocks = int(rng.integers(4, 10)); S = int(rng.choice([9, 40, 140]))
     depth = 16 if rng.random() < 0.5 else 24
     shared = random_blob(rng, flavor, fs)
-    d = Dspi(flavor, S, device=0); assert d.set_rate(fs) == 0; d.set_volume(-6 * 256); assert d.load_bulk(shared) == 0
+    if gpu: d = Dspi(flavor, S, device=0); assert d.set_rate(fs) == 0; d.set_volume(-6 * 256); assert d.load_bulk(shared) == 0
     blobs = {}
     for s in range(S):
         if rng.random() < 0.7:
             blobs[s] = random_blob(rng, flavor, fs)
-            assert d.load_bulk(blobs[s], stream=s) == 0
+            if gpu: assert d.load_bulk(blobs[s], stream=s) == 0
     pcm = WL.synth_pcm16(S, B * blocks * 2, fs, first_stream=int(rng.integers(0, 20)))
     data = pcm if depth == 16 else WL.pcm16_to_pcm24_bytes(pcm)
     step = blocks * B * (1 if depth == 16 else 6)        # int16 [S][frames][2] or bytes [S][frames * 6]
-    outs = [d.process_host(np.ascontiguousarray(data[:, c * step:(c + 1) * step]), blocks, B, depth) for c in range(2)]
-    pairs = np.concatenate([o_[0] for o_ in outs], axis=2); sub = np.concatenate([o_[1] for o_ in outs], axis=1); peaks = np.concatenate([o_[2] for o_ in outs], axis=1)
+    if gpu:
+        outs = [d.process_host(np.ascontiguousarray(data[:, c * step:(c + 1) * step]), blocks, B, depth) for c in range(2)]
+        pairs = np.concatenate([o_[0] for o_ in outs], axis=2); sub = np.concatenate([o_[1] for o_ in outs], axis=1); peaks = np.concatenate([o_[2] for o_ in outs], axis=1)
     for s in sorted(set(int(x) for x in rng.integers(0, S, 12))):
-        o = Oracle(flavor, detmath=True); assert o.set_rate(fs) == 0; o.set_volume(-6 * 256); assert o.load_bulk(shared) == 0
+        o = refleg.Leg(flavor, f"stream {s}"); assert o.set_rate(fs) == 0; o.set_volume(-6 * 256); assert o.load_bulk(shared) == 0
         if s in blobs: assert o.load_bulk(blobs[s]) == 0
         rp, rs, rk, _ = o.process(data[s], blocks * 2, B, depth)
-        assert np.array_equal(rp, pairs[s]) and np.array_equal(rs, sub[s]) and np.array_equal(rk, peaks[s]), f"stream {s} ({'own' if s in blobs else 'shared'} blob)"
-        assert o.status() == d.status(s), f"stream {s}: status"
+        if gpu:
+            assert np.array_equal(rp, pairs[s]) and np.array_equal(rs, sub[s]) and np.array_equal(rk, peaks[s]), f"stream {s} ({'own' if s in blobs else 'shared'} blob)"
+            assert o.status() == d.status(s), f"stream {s}: status"
+            o.hold(pairs[s], sub[s], peaks[s], d.status(s))
         o.close()
-    d.close()
+    if gpu: d.close()
 
 
 @pytest.mark.all_layouts
@@ -256,10 +275,15 @@ def test_random_numbers_one_random_structure(flavor, seed):
     stream slots each read their own image), value tiles on the packed kernel.  Where a number does change the structure (a band gone
     flat, a loudness shelf switched by the volume) the workgroup runs once per image: either way every sampled stream must equal its
     own oracle over two launches, with more changes in between."""
+    numbers_one_structure(flavor, seed)
+
+
+def numbers_one_structure(flavor, seed, gpu=True):
+    """test_random_numbers_one_random_structure's case; gpu=False: the watched streams' oracles alone (tests/test_ref_leg_cpu.py), the same draws"""
     import struct
+    import refleg
     from dspi_amd.host import Dspi
     from dspi_amd import workloads as WL
-    from orclib import Oracle
     rng = np.random.default_rng(9900 + 100 * flavor + seed)
     fs, Bs = RATES[seed % 3]
     B = int(rng.choice(list(Bs) + [1, 7])); blocks = int(rng.integers(3, 9)); S = int(rng.choice([7, 33, 70, 140]))
@@ -268,8 +292,8 @@ def test_random_numbers_one_random_structure(flavor, seed):
     R = W.REQ
     f = lambda v: struct.pack("<f", v)
     watch = sorted(set(int(x) for x in rng.integers(0, S, 10)) | {0, S - 1})
-    d = Dspi(flavor, S, device=0); o = {s_: Oracle(flavor, detmath=True) for s_ in watch}
-    for x in [d] + list(o.values()):
+    d = Dspi(flavor, S, device=0) if gpu else None; o = {s_: refleg.Leg(flavor, f"stream {s_}") for s_ in watch}
+    for x in ([d] if gpu else []) + list(o.values()):
         assert x.set_rate(fs) == 0; x.set_volume(-6 * 256); assert x.load_bulk(blob) == 0
 
     def numbers():
@@ -298,19 +322,22 @@ def test_random_numbers_one_random_structure(flavor, seed):
         for s_ in range(S):
             if c == 1 and rng.random() < 0.6: continue
             for req, wv, pl in numbers():
-                rc = d.vendor_set(req, wv, pl, stream=s_)
-                if s_ in o: assert o[s_].vendor_set(req, wv, pl) == rc
+                rc = d.vendor_set(req, wv, pl, stream=s_) if gpu else None
+                if s_ in o: assert o[s_].vendor_set(req, wv, pl) == rc or not gpu
         chunk = np.ascontiguousarray(data[:, c * step:(c + 1) * step])
         # the second launch in a random output form: tiled words, silent outputs left unwritten (into zeroed buffers: what the firmware's
         # zero-fill gives), the sticky clip flags along
         kw = dict(tiled=bool(rng.random() < 0.5), enabled_only=bool(rng.random() < 0.3), clip=True) if c == 1 else {}
-        pairs, sub, peaks = d.process_host(chunk, blocks, B, depth, **kw)
-        if kw.get("tiled"): pairs, sub = d.untile(pairs, sub)
+        if gpu:
+            pairs, sub, peaks = d.process_host(chunk, blocks, B, depth, **kw)
+            if kw.get("tiled"): pairs, sub = d.untile(pairs, sub)
         for s_ in watch:
             rp, rs, rk, _ = o[s_].process(chunk[s_], blocks, B, depth)
+            if not gpu: continue
             assert np.array_equal(rp, pairs[s_]) and np.array_equal(rs, sub[s_]) and np.array_equal(rk, peaks[s_]), f"launch {c}, stream {s_}, {kw}"
             if kw.get("clip"): assert int(d.last_clip[s_]) == int.from_bytes(o[s_].status()[-2:], "little"), f"clip flags, stream {s_}"
             assert o[s_].status() == d.status(s_), f"launch {c}, stream {s_}: status"
+            o[s_].hold(pairs[s_], sub[s_], peaks[s_], d.status(s_), int(d.last_clip[s_]) if kw.get("clip") else None, what=f"launch {c}")
     for x in o.values(): x.close()
-    d.close()
+    if gpu: d.close()
 

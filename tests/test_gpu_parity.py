@@ -10,6 +10,7 @@ import pytest
 
 from conftest import has_gpu
 import orclib
+import refleg
 from orclib import Oracle, PdmOracle
 from dspi_amd import wire as W, workloads as WL
 from dspi_amd.host import Dspi
@@ -31,13 +32,25 @@ def latency_plan(plan) -> bool:
     return plan["latency_layout"] > 0 and plan["packed_shared"] == plan["packed_per_lane_values"] == plan["packed_per_lane_values_and_bands"] == plan["one_stream_per_lane_images"] == 0
 
 
-def oracle_run(flavor, fs, vol, blob, data, blocks, B, depth, setup=None):
-    o = Oracle(flavor, detmath=True)
+def oracle_run(flavor, fs, vol, blob, data, blocks, B, depth, setup=None, gpu=None, since=(0, 0)):
+    """One stream through the oracle, with the reference leg (tests/refleg.py): the restatement with x86 casts and the reference leaf build
+    run beside it and must agree; gpu = (pairs, sub, peaks, status, clip) of that stream from the GPU (None where not fetched) is held to
+    the reference build's words directly wherever no cast overflowed; since = (frame, packet) where the GPU's words are the end of the run."""
+    o = refleg.Leg(flavor)
     assert o.set_rate(fs) == 0
     o.set_volume(vol)
     assert o.load_bulk(blob) == 0
     if setup: setup(o)
-    return o.process(data, blocks, B, depth), o.status()
+    res, status = o.process(data, blocks, B, depth), o.status()
+    if gpu is not None: o.hold(*gpu, since=since)
+    o.close()
+    return res, status
+
+
+def compare_input(fs, B, blocks, S, depth=16, first_stream=0):
+    """compare()'s input: [S][frames][2] int16, or [S][frames * 6] bytes of packed 24-bit frames"""
+    pcm = WL.synth_pcm16(S, B * blocks, fs, first_stream=first_stream)
+    return pcm if depth == 16 else WL.pcm16_to_pcm24_bytes(pcm)
 
 
 def compare(flavor, fs, B, blocks, S, blob, vol=-20 * 256, depth=16, calls=2, check_streams=None, setup=None, first_stream=0):
@@ -46,18 +59,17 @@ def compare(flavor, fs, B, blocks, S, blob, vol=-20 * 256, depth=16, calls=2, ch
     d.set_volume(vol)
     assert d.load_bulk(blob) == 0
     if setup: setup(d)
-    pcm = WL.synth_pcm16(S, B * blocks, fs, first_stream=first_stream)
-    data = pcm if depth == 16 else WL.pcm16_to_pcm24_bytes(pcm)
+    data = compare_input(fs, B, blocks, S, depth, first_stream)
     per = blocks // calls
     outs = []
-    bpf = 2 if depth == 16 else 6
     for c in range(calls):        # several launches: state must carry across dspi_process calls
         sl = data[:, c * per * B:(c + 1) * per * B] if depth == 16 else data[:, c * per * B * 6:(c + 1) * per * B * 6]
         outs.append(d.process_host(np.ascontiguousarray(sl), per, B, depth, clip=True))
     clip_flags = d.last_clip          # dspi_out.clip_flags (DSPI_OUT_CLIP_FLAGS): every stream's sticky bits after the last call
     pairs = np.concatenate([o[0] for o in outs], axis=2); sub = np.concatenate([o[1] for o in outs], axis=1); peaks = np.concatenate([o[2] for o in outs], axis=1)
     for s in (check_streams if check_streams is not None else range(S)):
-        (rp, rs, rk, rclip), status = oracle_run(flavor, fs, vol, blob, data[s], per * calls, B, depth, setup)
+        (rp, rs, rk, rclip), status = oracle_run(flavor, fs, vol, blob, data[s], per * calls, B, depth, setup,
+                                                 gpu=(pairs[s], sub[s], peaks[s], d.status(s), int(clip_flags[s])))
         assert np.array_equal(rp, pairs[s]), f"pairs differ, stream {s}: {np.argwhere(rp != pairs[s])[:3].tolist()}"
         assert np.array_equal(rs, sub[s]), f"sub differs, stream {s}"
         assert np.array_equal(rk, peaks[s]), f"peaks differ, stream {s}"
@@ -78,13 +90,120 @@ def test_config2_master_peq(flavor):
         compare(0, 48000, 48, 20, 5, WL.config1_blob(), vol=0)
 
 
+class Twin:
+    """A context and one oracle per stream, each with its reference leg (tests/refleg.py), driven together call by call.  gpu=False: the
+    oracles alone, for the CPU replay of tests/test_ref_leg_cpu.py — the same sequence, the same inputs, no context."""
+
+    def __init__(self, flavor, S, fs, vol, blob, gpu=True):
+        self.d = Dspi(flavor, S, device=0) if gpu else None
+        self.o = [refleg.Leg(flavor, f"stream {s}") for s in range(S)]
+        for x in self.all():
+            assert x.set_rate(fs) == 0
+            x.set_volume(vol)
+            assert x.load_bulk(blob) == 0
+
+    def all(self):
+        return ([self.d] if self.d is not None else []) + self.o
+
+    def request(self, req, wvalue, payload) -> int:
+        """a vendor SET to every stream: one return code from everybody"""
+        rcs = {x.vendor_set(req, wvalue, payload) for x in self.all()}
+        assert len(rcs) == 1, f"request {req:#x} wValue {wvalue}: return codes {sorted(rcs)}"
+        return rcs.pop()
+
+    def get(self, req, wvalue, cap=64) -> bytes:
+        """a vendor GET: one answer from every oracle and from the context's first, middle and last stream"""
+        got = {o.vendor_get(req, wvalue, cap) for o in self.o}
+        if self.d is not None: got |= {self.d.vendor_get(req, wvalue, cap, stream=s) for s in (0, len(self.o) // 2, len(self.o) - 1)}
+        assert len(got) == 1, f"GET {req:#x} wValue {wvalue}: {got}"
+        return got.pop()
+
+    def run(self, chunk, per, B, what):
+        """one call: every stream's words, sub, peaks, clip flags and status against its oracle, then against the reference build"""
+        if self.d is not None:
+            pairs, sub, peaks = self.d.process_host(chunk, per, B, clip=True)
+            clip = self.d.last_clip
+        for s, o in enumerate(self.o):
+            rp, rs, rk, rclip = o.process(chunk[s], per, B)
+            status = o.status()
+            if self.d is None: continue
+            assert np.array_equal(rp, pairs[s]), f"{what}, stream {s}: pairs differ at {np.argwhere(rp != pairs[s])[:3].tolist()}"
+            assert np.array_equal(rs, sub[s]), f"{what}, stream {s}: sub differs at {np.argwhere(rs != sub[s])[:3].tolist()}"
+            assert np.array_equal(rk, peaks[s]), f"{what}, stream {s}: peaks differ"
+            assert status == self.d.status(s), f"{what}, stream {s}: status differs"
+            assert int(clip[s]) == rclip, f"{what}, stream {s}: clip flags differ"
+            o.hold(pairs[s], sub[s], peaks[s], self.d.status(s), int(clip[s]), what=what)
+
+    def close(self):
+        for x in self.all(): x.close()
+
+
+def test_reference_leg_present():
+    """The reference leg (tests/refleg.py) leaves itself out quietly where oracle/_ref is absent; a GPU suite that ran without it would hide
+    what the leg is there to show, so THIS test fails then: the build makes the three leaf libraries and they travel with the tree."""
+    missing = refleg.missing_libs()
+    assert not missing, f"oracle/_ref lacks {missing}: the GPU tests ran without their reference leg"
+    for flavor in FLAVORS_WITH_KERNEL:
+        leg = refleg.Leg(flavor)
+        assert leg.on and leg.r.lib.orc_is_ref_build() == 1, refleg.lib_name(flavor)
+        leg.close()
+
+
+RATE_CASES = [(96000, 96, 16), (48000, 48, 24), (44100, 45, 16), (44100, 44, 24)]
+
+
 @pytest.mark.both_layouts
 @pytest.mark.parametrize("flavor", FLAVORS_WITH_KERNEL)
-@pytest.mark.parametrize("fs,B,depth", [(96000, 96, 16), (48000, 48, 24), (44100, 45, 16), (44100, 44, 24)])
+@pytest.mark.parametrize("fs,B,depth", RATE_CASES)
 def test_full_chain(flavor, fs, B, depth):
     """BASELINE config 3 / config 5: every stage on; all stream classes of the synthetic generator (noise, sweep, bursts,
     decay to digital silence, full-scale square); ragged stream count; 44/45-frame packets take the tail kernel."""
     compare(flavor, fs, B, 24, 85, WL.full_chain_blob(flavor), depth=depth)
+
+
+@pytest.mark.parametrize("fs,B,depth", RATE_CASES)
+def test_q28_chain_without_leveller_against_the_reference(fs, B, depth):
+    """Q28 where an x86 build of the reference is a valid checker.  The limiter's cast (leveller.c:366-383) overflows on quiet samples in such
+    a build, so the reference leg leaves most streams of the Q28 full chain out; with the leveller off nothing overflows and every stream's
+    words are held to oracle/_ref/libref_q28.so directly (tests/test_ref_leg_cpu.py asserts that all of them are).  The limiter itself:
+    the golden q28_limiter_in_range.  config 5's preset, 70 streams, test_full_chain's rate cases, two calls."""
+    blob = WL.full_chain_blob(0)
+    blob["leveller"]["enabled"] = 0
+    compare(0, fs, B, 24, 70, blob, depth=depth, calls=2)
+
+
+def core1_eq_worker_mode(flavor, gpu=True):
+    """test_core1_eq_worker_mode's sequence (gpu=False: its CPU replay)"""
+    fs, B = (96000, 96) if flavor else (48000, 48)
+    S = 130 if flavor else 70      # float: one whole row of the packed kernel and a row of two
+    R = W.REQ
+    blob = WL.full_chain_blob(flavor)
+    N = W.dims(flavor)[1]
+    blob["outputs"][N - 1]["enabled"] = 0
+    t = Twin(flavor, S, fs, -6 * 256, blob, gpu)
+    assert t.get(R["GET_CORE1_MODE"], 0, 1) == b"\x02"          # CORE1_MODE_EQ_WORKER
+    pcm = WL.synth_pcm16(S, B * 34, fs)
+    for c in range(2): t.run(np.ascontiguousarray(pcm[:, c * 12 * B:(c + 1) * 12 * B]), 12, B, f"EQ worker, call {c}")
+    # enabling the sub while outputs 2.. are on is refused (usb_audio.c:1891-1904) ...
+    t.request(R["SET_OUTPUT_ENABLE"], N - 1, b"\x01")
+    assert t.get(R["GET_OUTPUT_ENABLE"], N - 1, 1) == b"\x00" and t.get(R["GET_CORE1_MODE"], 0, 1) == b"\x02", "the refused sub enable"
+    # ... disabling them and enabling it flips the mode
+    for out in range(2, N - 1): t.request(R["SET_OUTPUT_ENABLE"], out, b"\x00")
+    t.request(R["SET_OUTPUT_ENABLE"], N - 1, b"\x01")
+    assert t.get(R["GET_OUTPUT_ENABLE"], N - 1, 1) == b"\x01" and t.get(R["GET_CORE1_MODE"], 0, 1) == b"\x01"          # CORE1_MODE_PDM
+    t.run(np.ascontiguousarray(pcm[:, 24 * B:]), 10, B, "PDM mode")
+    t.close()
+
+
+@pytest.mark.both_layouts
+@pytest.mark.parametrize("flavor", FLAVORS_WITH_KERNEL)
+def test_core1_eq_worker_mode(flavor):
+    """Sub output off, outputs 2.. on: the reference hands outputs 2..N-2 to Core 1 and leaves the sub's path out of the packet altogether
+    (usb_audio.c:782-872: no sub mix, no sub line, no sub meter).  The full-chain preset with the sub disabled, GET_CORE1_MODE 2 on the
+    context and on the oracle; 24 packets over two calls; then the transitions of tests/test_oracle_vs_fw.py::test_core1_eq_worker_twin:
+    the refused sub enable (usb_audio.c:1891-1904: the same return code, the sub still off, the mode still 2 on both sides), outputs
+    2..N-2 off and the sub on (mode 1), 10 more packets.  Every stream after every call, with the reference leg."""
+    core1_eq_worker_mode(flavor)
 
 
 # delays of every class at 44.1 / 48 / 96 kHz: none, shorter than 64 frames, than a packet, a few packets, within a packet's length of the line's
@@ -201,8 +320,59 @@ def test_latency_layout_lines_of_disabled_outputs(flavor, fs, B, monkeypatch):
             assert np.array_equal(rs, gs[s]) and np.array_equal(rk, gk[s]), (c, s)
             assert ors[s].status() == d.status(s), (c, s)
     d.close()
-    # BASELINE config 2's own preset: two outputs enabled, no user delay — the sub's alignment line is the only one that runs
+    config2_own_preset(flavor, fs, B, per)
+
+
+def config2_own_preset(flavor, fs, B, per):
+    """BASELINE config 2's own preset: two outputs enabled, no user delay — the sub's alignment line is the only one that runs"""
     compare(flavor, fs, B, 2 * per, 19, WL.config2_blob(False), vol=-10 * 256)
+
+
+def disabled_sub_line_sequence(flavor, case, gpu=True):
+    """test_latency_layout_disabled_sub_line_sequences' calls (gpu=False: their CPU replay)"""
+    fs, B, long_, S = 48000, 48, 86, 37      # 86 packets = 4 128 frames: a launch at least as long as the 4 096-position line
+    R = W.REQ
+    delays = list(_EDGE_DELAYS); delays[8] = 20.0
+    blob = _latency_blob(delays=tuple(delays))
+    for o in range(2, 8): blob["outputs"][o]["enabled"] = 0      # (config 2's class: with an output of 2..N-2 on, a disabled sub's path is not run at all)
+    if case == "minus_zero":
+        for inp in (0, 1):
+            blob["crosspoints"][inp, 8]["enabled"] = 1
+            blob["crosspoints"][inp, 8]["phase_invert"] = 1
+    t = Twin(flavor, S, fs, -7 * 256, blob, gpu)
+    sub_on = lambda on: (t.request(R["SET_OUTPUT_ENABLE"], 8, bytes([on])), t.get(R["GET_OUTPUT_ENABLE"], 8, 1))[1] == bytes([on])
+    if case == "audio":
+        calls = [(None, long_), (0, long_), (None, long_), (None, 10), (1, long_)]
+    else:
+        calls = [(None, long_), (0, long_), (None, long_)]
+    pcm = WL.synth_pcm16(S, B * sum(n for _, n in calls), fs)
+    if case == "minus_zero": pcm[:, :B * long_] = 0      # silence while the sub is on: its line fills with what inverted crosspoints make of it
+    at = 0
+    for c, (sub, per) in enumerate(calls):
+        if sub is not None: assert sub_on(sub), f"call {c}: the sub's enable was not taken"
+        t.run(np.ascontiguousarray(pcm[:, at * B:(at + per) * B]), per, B, f"{case}, call {c}")
+        at += per
+        if gpu: assert t.d.launch_plan()["latency_layout"] > 0 and t.d.launch_plan()["packed_shared"] == 0, t.d.launch_plan()
+        # what the next launch finds in the sub's line, by the oracle (orc_tap 8: the delay lines, [output][position])
+        line = np.frombuffer(t.o[0].a.tap(8), dtype=np.uint32).reshape(9, -1)[8]
+        if c == 0: assert line.any() and (case == "audio" or (line == 0x80000000).all()), "the line must not be all zero bits when the sub goes off"
+        if c == 1: assert not line.any(), "a launch as long as the line must leave it all zero for the next"
+    t.close()
+
+
+@pytest.mark.parametrize("flavor", (1, W.F32_FMA), ids=("canonical", "fma"))
+@pytest.mark.parametrize("case", ("audio", "minus_zero"))
+def test_latency_layout_disabled_sub_line_sequences(flavor, case, monkeypatch):
+    """The zero-line shortcut of a disabled sub (dspi_chain_skew.inc, "The line of a disabled sub"): a launch of at least 4 096 frames whose
+    sub line is all zero drops the line's traffic.  The entries other than all-zero: a preset of the latency layout's first shape with the
+    sub ENABLED and delayed, 37 streams (the last pair holds one stream: one output wave has a single live pair), 48-frame packets, 86 per
+    long call.  "audio": a long call with the sub on (the line fills), the sub disabled and a long call (the line is non-zero on entry: the
+    traffic must stay, the line's tail still comes round and is overwritten with zeros), a long call (all zero now: the shortcut), ten
+    packets (shorter than the line: never the shortcut), the sub enabled again and a long call (what the line holds comes out delayed).
+    "minus_zero": silent input through phase-inverted crosspoints while the sub is on — the line holds nothing but -0.0, whose bits are
+    not zero — then the sub disabled and two long calls.  Every stream against its oracle after every call, with the reference leg."""
+    monkeypatch.setenv("DSPI_F32_LAYOUT", "skew")
+    disabled_sub_line_sequence(flavor, case)
 
 
 @pytest.mark.parametrize("flavor", (1, W.F32_FMA), ids=("canonical", "fma"))
@@ -492,7 +662,7 @@ def test_q28_latency_layout_alternates_with_the_chain_kernels(lev, monkeypatch):
     pairs = np.concatenate([o[0] for o in outs], axis=2); sub = np.concatenate([o[1] for o in outs], axis=1); peaks = np.concatenate([o[2] for o in outs], axis=1)
     for s_ in range(S):
         setup = (lambda o, db=own[s_]: o.vendor_set(W.REQ["SET_PREAMP"], 0, struct.pack("<f", db))) if s_ in own else None
-        (rp, rs, rk, _), status = oracle_run(0, fs, -12 * 256, b, pcm[s_], total, B, 16, setup)
+        (rp, rs, rk, _), status = oracle_run(0, fs, -12 * 256, b, pcm[s_], total, B, 16, setup, gpu=(pairs[s_], sub[s_], peaks[s_], d.status(s_)))
         assert np.array_equal(rp, pairs[s_]) and np.array_equal(rs, sub[s_]) and np.array_equal(rk, peaks[s_]), s_
         assert status == d.status(s_), s_
     d.close()
@@ -952,7 +1122,7 @@ def test_full_size_properties(flavor):
     assert torch.equal(pairs[5 + 128 * 37], pairs[5]) and torch.equal(sub[5 + 128 * 400], sub[5])
     assert int(pairs[7777].abs().max()) == 0 and int(sub[7777].abs().max()) == 0
     for s in (0, 63, 64, 4095, 65471):
-        (rp, rs, _, _), _ = oracle_run(flavor, fs, -20 * 256, WL.full_chain_blob(1), base[idx[s]], blocks, B, 16)
+        (rp, rs, _, _), _ = oracle_run(flavor, fs, -20 * 256, WL.full_chain_blob(1), base[idx[s]], blocks, B, 16, gpu=(pairs[s].cpu().numpy(), sub[s].cpu().numpy()))
         assert np.array_equal(rp, pairs[s].cpu().numpy()) and np.array_equal(rs, sub[s].cpu().numpy())
     d.close()
 
@@ -1064,9 +1234,9 @@ def test_full_size_all_tiles_agree(flavor, fs, B, S, monkeypatch):
         assert bool((pk == pk[0:1]).all()), f"launch {c}: a tile's peaks differ from tile 0"
     p0 = pairs[0].cpu().numpy(); s0 = sub[0].cpu().numpy()
     for s in (0, 1, R // 2, R - 1):
-        (rp, rs, _, _), _ = oracle_run(flavor, fs, -20 * 256, WL.full_chain_blob(flavor), base[s], blocks * calls, B, 16)
-        last = rp[:, (calls - 1) * frames:, :]                      # [pair][frame][side] of the last launch
         got = np.stack([np.stack([p0[2 * p, :, s], p0[2 * p + 1, :, s]], axis=-1) for p in range((n_out - 1) // 2)])
+        (rp, rs, _, _), _ = oracle_run(flavor, fs, -20 * 256, WL.full_chain_blob(flavor), base[s], blocks * calls, B, 16, gpu=(got, s0[:, s]), since=((calls - 1) * frames, 0))
+        last = rp[:, (calls - 1) * frames:, :]                      # [pair][frame][side] of the last launch
         assert np.array_equal(last, got) and np.array_equal(rs[(calls - 1) * frames:], s0[:, s])
     d.close()
 
@@ -1098,7 +1268,7 @@ def test_full_size_stream_major_groups_agree(flavor, fs, B, blocks):
         assert bool((kv == kv[0:1]).all()), f"launch {c}: a group's peaks differ from group 0"
     p0, s0 = pairs[:R].cpu().numpy(), sub[:R].cpu().numpy()
     for s in (0, 1, 63, 64, R - 1):
-        (rp, rs, _, _), _ = oracle_run(flavor, fs, -20 * 256, WL.full_chain_blob(1), base[s], blocks * calls, B, 16)
+        (rp, rs, _, _), _ = oracle_run(flavor, fs, -20 * 256, WL.full_chain_blob(1), base[s], blocks * calls, B, 16, gpu=(p0[s], s0[s]), since=((calls - 1) * frames, 0))
         assert np.array_equal(rp[:, (calls - 1) * frames:, :], p0[s]) and np.array_equal(rs[(calls - 1) * frames:], s0[s]), s
     d.close()
 
@@ -1204,7 +1374,8 @@ def test_full_size_config2_latency_layout(two_b):
         got.append((pairs[:R, 0].cpu().numpy().copy(), peaks[:R].cpu().numpy().view(np.uint16).copy()))
     p0 = np.concatenate([g[0] for g in got], axis=1); k0 = np.concatenate([g[1] for g in got], axis=1)
     for s in (0, 1, 7, 8, R - 1):
-        (rp, rs, rk, _), _ = oracle_run(W.F32_FMA, fs, -10 * 256, blob, base[s], blocks * calls, B, 16)
+        words = np.zeros((4,) + p0[s].shape, dtype=np.int32); words[0] = p0[s]      # (the silent outputs were left unwritten: the firmware's zero-fill)
+        (rp, rs, rk, _), _ = oracle_run(W.F32_FMA, fs, -10 * 256, blob, base[s], blocks * calls, B, 16, gpu=(words, None, k0[s]))
         assert np.array_equal(rp[0], p0[s]) and np.array_equal(rk, k0[s]), s
         assert int(np.abs(rp[1:]).max()) == 0 and int(np.abs(rs).max()) == 0
     d.close()
@@ -1275,7 +1446,8 @@ def test_host_buffer_pipeline_chunks(flavor, tiled):
         assert np.array_equal(host_out[1], ts.cpu().numpy()) and np.array_equal(host_out[2].view(np.int16), tk.cpu().numpy()), c
     pairs, sub = (dh.untile(host_out[0], host_out[1]) if tiled else (host_out[0], host_out[1]))
     for s in (0, R - 1, R, 2 * R + 5, S // 2, S - 1):
-        (rp, rs, rk, _), status = oracle_run(flavor, fs, -20 * 256, WL.full_chain_blob(int(flavor)), pcm[s], blocks * 2, B, 16)
+        (rp, rs, rk, _), status = oracle_run(flavor, fs, -20 * 256, WL.full_chain_blob(int(flavor)), pcm[s], blocks * 2, B, 16,
+                                             gpu=(pairs[s], sub[s], host_out[2][s], dh.status(s)), since=(frames, blocks))
         assert np.array_equal(rp[:, frames:, :], pairs[s]) and np.array_equal(rs[frames:], sub[s]) and np.array_equal(rk[blocks:], host_out[2][s]), s
         assert status == dh.status(s)
     dh.close(); dd.close()
