@@ -29,6 +29,7 @@
 #include "dspi_kernels.h"
 #include "dspi_params.h"
 #include "dspi_boot.h"
+#include "dspi_group.h"
 #include "dspi_move.h"
 #include "dspi_plan.h"
 #include "dspi_resize.h"
@@ -1143,6 +1144,48 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
 int dspi_plan_compaction(const dspi_ctx *c, dspi_stream_move *moves, uint32_t cap, uint32_t flags) {
     if (!c || (flags & ~DSPI_COMPACT_ONE_WAY)) return DSPI_E_INVAL;
     const std::vector<StreamMove> plan = move_compaction(host_activity(c), c->n_streams, flags & DSPI_COMPACT_ONE_WAY);
+    if (!moves) return (int)plan.size();
+    if (plan.size() > cap) return DSPI_E_SHORT;
+    if (!plan.empty()) memcpy(moves, plan.data(), plan.size() * sizeof(StreamMove));
+    return (int)plan.size();
+}
+
+// ---- grouping (dspi_group.h: the rule).  Bookkeeping like the compaction plan, but on the parameter objects as they stand folded: two
+// devices that were given the same blob by separate calls are one group.
+int dspi_plan_grouping(dspi_ctx *c, dspi_stream_move *moves, uint32_t cap, uint32_t flags) {
+    if (!c || (flags & ~DSPI_GROUP_ONE_WAY)) return DSPI_E_INVAL;
+    if (c->images.size() > 1) merge_images(c);
+    const size_t ni = c->images.size();
+    std::vector<uint32_t> cls;
+    if (c->flavor && ni > 1) {
+        // the structure of every object that holds an active stream: what the last upload built (plan_in.sig) where the object has not
+        // changed since, else built here, on all host threads when there are many (every stream its own preset)
+        std::vector<uint8_t> grouped(ni, 0);
+        for (uint32_t s = 0; s < c->n_streams; s++) if (!c->n_paused || c->active[s]) grouped[(size_t)c->stream_image[s]] = 1;
+        std::vector<ImageSig> sig(ni);
+        memset(sig.data(), 0xff, ni * sizeof(ImageSig));      // (objects without an active stream form no group: their class is never read)
+        std::vector<size_t> todo;
+        for (size_t i = 0; i < ni; i++) {
+            if (!grouped[i]) continue;
+            if (!c->images[i]->dirty && i < c->plan_in.sig.size()) sig[i] = c->plan_in.sig[i];
+            else todo.push_back(i);
+        }
+        const unsigned csr = _mm_getcsr();      // the workers round and flush exactly like the calling thread
+        auto build = [&](size_t k0, size_t k1) {
+            _mm_setcsr(csr);
+            DevImage img;
+            for (size_t k = k0; k < k1; k++) { c->images[todo[k]]->build_image(img); sig[todo[k]] = make_sig(img); }
+        };
+        const size_t n = todo.size();
+        const size_t nt = n >= 512 ? std::min<size_t>(std::max(1u, std::thread::hardware_concurrency()), std::min<size_t>(32, n / 128)) : 1;
+        if (nt > 1) {
+            std::vector<std::thread> th;
+            for (size_t t = 0; t < nt; t++) th.emplace_back(build, n * t / nt, n * (t + 1) / nt);
+            for (auto &x : th) x.join();
+        } else build(0, n);
+        cls = group_classes(sig.data(), ni);
+    }
+    const std::vector<StreamMove> plan = group_plan(host_activity(c), c->stream_image.data(), cls.empty() ? nullptr : cls.data(), c->n_streams, flags & DSPI_GROUP_ONE_WAY);
     if (!moves) return (int)plan.size();
     if (plan.size() > cap) return DSPI_E_SHORT;
     if (!plan.empty()) memcpy(moves, plan.data(), plan.size() * sizeof(StreamMove));

@@ -20,6 +20,7 @@ SNAP_REALIGN = 0x100
 RESUME_AS_IS = 0x1
 MOVE_AS_IS = 0x1
 COMPACT_ONE_WAY = 0x1
+GROUP_ONE_WAY = 0x1
 BOOT_STREAMS_AS_IS = 0x1
 RESIZE_PAUSED = 0x1
 OUT_TILED = 0x2
@@ -120,6 +121,8 @@ def lib() -> C.CDLL:
     if hasattr(L, "dspi_move_streams"):      # (ABI 8 + stream moves: detected by symbol; with it DSPI_MOVE_AS_IS, DSPI_COMPACT_ONE_WAY)
         L.dspi_move_streams.argtypes = [vp, vp, u32, u32]
         L.dspi_plan_compaction.argtypes = [vp, vp, u32, u32]
+    if hasattr(L, "dspi_plan_grouping"):      # (ABI 8 + grouping: detected by symbol; with it DSPI_GROUP_ONE_WAY)
+        L.dspi_plan_grouping.argtypes = [vp, vp, u32, u32]
     if hasattr(L, "dspi_boot_streams"):      # (ABI 8 + stream boots: detected by symbol; with it DSPI_BOOT_STREAMS_AS_IS)
         L.dspi_boot_streams.argtypes = [vp, vp, u32, vp, C.c_size_t, u32, C.POINTER(C.c_int)]
     if hasattr(L, "dspi_spdif_per_stream"):      # (ABI 8 + per-stream S/PDIF positions: detected by symbol; with it dspi_spdif_stream_pos, dspi_spdif_encode_v)
@@ -470,6 +473,16 @@ class Dspi:
         n = self._ck(self.L.dspi_plan_compaction(self.h, None, 0, flags), "plan_compaction")
         m = np.zeros((n, 2), dtype=np.uint32)
         if n: self._ck(self.L.dspi_plan_compaction(self.h, m.ctypes.data, n, flags), "plan_compaction")
+        return m
+
+    def plan_grouping(self, one_way: bool = False) -> np.ndarray:
+        """dspi_plan_grouping: the (src, dst) list, uint32 [n][2], after which the active streams fill the lowest slots, those of one parameter
+        object in one run and runs of one structure side by side (one_way: DSPI_GROUP_ONE_WAY, paused slots are free and not preserved).
+        Equal parameter objects are folded first.  Works on host-only contexts."""
+        flags = GROUP_ONE_WAY if one_way else 0
+        n = self._ck(self.L.dspi_plan_grouping(self.h, None, 0, flags), "plan_grouping")
+        m = np.zeros((n, 2), dtype=np.uint32)
+        if n: self._ck(self.L.dspi_plan_grouping(self.h, m.ctypes.data, n, flags), "plan_grouping")
         return m
 
     # ---- stream boots (include/dspi.h: a slot is power-cycled inside its running context) ----

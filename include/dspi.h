@@ -73,7 +73,8 @@ extern "C" {
                               * 8 + stream moves: detect by symbol (dspi_move_streams; with it dspi_plan_compaction, dspi_stream_move, DSPI_MOVE_AS_IS, DSPI_COMPACT_ONE_WAY; additions only);
                               * 8 + stream boots: detect by symbol (dspi_boot_streams; with it DSPI_BOOT_STREAMS_AS_IS; additions only);
                               * 8 + per-stream S/PDIF positions: detect by symbol (dspi_spdif_per_stream; with it dspi_spdif_stream_pos, dspi_spdif_encode_v; additions only);
-                              * 8 + resizing: detect by symbol (dspi_resize_streams; with it dspi_reserve_streams, dspi_stream_capacity, DSPI_RESIZE_PAUSED; additions only) */
+                              * 8 + resizing: detect by symbol (dspi_resize_streams; with it dspi_reserve_streams, dspi_stream_capacity, DSPI_RESIZE_PAUSED; additions only);
+                              * 8 + grouping: detect by symbol (dspi_plan_grouping; with it DSPI_GROUP_ONE_WAY; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -389,12 +390,51 @@ int dspi_streams_paused(const dspi_ctx *ctx, uint32_t first, uint32_t count, uin
  * ascending (always equally many); pair i is the swap {T[i] -> H[i]}, {H[i] -> T[i]} — no paused device is lost — or, with
  * DSPI_COMPACT_ONE_WAY (the caller treats paused slots as free), {T[i] -> H[i]} alone.  Returns the number of entries; moves == NULL only
  * counts; a cap below that number is DSPI_E_SHORT and writes nothing.  The caller relocates its own per-stream buffers by the same list.
- * Not in scope: choosing the pairing by parameter image, so that the two streams of a lane share a preset. */
+ * Not in scope here: choosing the pairing by parameter image, so that the two streams of a lane share a preset — that list is
+ * dspi_plan_grouping's (below). */
 typedef struct dspi_stream_move { uint32_t src, dst; } dspi_stream_move;
 #define DSPI_MOVE_AS_IS      0x1u   /* dspi_move_streams: keep the streams' own write positions (no realignment) */
 #define DSPI_COMPACT_ONE_WAY 0x1u   /* dspi_plan_compaction: paused slots are free, do not preserve them */
 int dspi_move_streams(dspi_ctx *ctx, const dspi_stream_move *moves, uint32_t n, uint32_t flags);
 int dspi_plan_compaction(const dspi_ctx *ctx, dspi_stream_move *moves, uint32_t cap, uint32_t flags);
+
+/* ---- grouping: streams of one preset into shared rows ------------------------------------------------------------------------------- */
+/* Compaction keeps a context's active streams in whole rows; it does not look at their parameters.  The launch plan picks the kernel by
+ * who sits beside whom: a float lane whose two streams share a parameter object runs the packed kernel, a row whose streams hold several
+ * objects of one structure runs the per-lane-value kernels, every other lane falls to the one-stream kernel, and a Q28 row with two
+ * objects leaves the workgroup-uniform path whole.  Two structurally different presets assigned alternately put every stream of a context
+ * on the one-stream kernel; devices that arrive by dspi_boot_streams, by import or by per-stream requests land wherever a slot was free.
+ * dspi_plan_grouping writes the list for dspi_move_streams after which
+ *   - slots [0, A) are active and [A, dspi_num_streams) paused, A = the number of active streams, as after compaction,
+ *   - the active streams of every parameter object occupy one contiguous run of slots,
+ *   - runs of objects with the same structure lie next to each other.
+ * The call is bookkeeping: it works on host-only contexts and writes nothing to the device.  The context is not const because the call
+ * first folds equal parameter objects into one (the fold-back pass of dspi_debug_image_count, run here whether or not a broadcast call has
+ * asked for it): two devices loaded with the same blob through separate calls are one group.  Nothing else about the context changes.
+ * Returns the number of entries; moves == NULL only counts; a cap below that number is DSPI_E_SHORT and writes nothing; an undefined flag
+ * bit or a null context is DSPI_E_INVAL.  The caller relocates its own per-stream buffers by the same list, as with compaction.
+ * The rule (deterministic):
+ *   1 groups     a group is the set of active streams of one parameter object, after folding.  Its structure is what the per-lane-value
+ *                kernels need to agree (bypassed channels, enabled and muted outputs, sample rate, delays in samples, band kinds, ...),
+ *                compared bytewise (float); on Q28 all objects form one class.  first(g) = the lowest active slot that holds g,
+ *                first(class) = the minimum over its groups.  Groups are ordered by (first(class), first(g)).
+ *   2 runs       in that order, group g gets the next |g| slots of [0, A).
+ *   3 residents  an active stream of g that already sits inside g's run stays.
+ *   4 movers     the other streams of g, ascending by slot, take the run's remaining slots, ascending.
+ *   5 paused     H = the paused slots below A, T = the slots at or above A that hold an active stream, both ascending (always equally
+ *                many): entry i is {H[i] -> T[i]} — no paused device is lost.  With DSPI_GROUP_ONE_WAY (the caller treats paused slots
+ *                as free, as DSPI_COMPACT_ONE_WAY) these entries are omitted; the vacated slots at and above A then stay behind as paused,
+ *                frozen copies (dspi_move_streams, open ends).
+ *   6 output     identities are never emitted; entries are written ascending by dst.
+ * What follows from it: dspi_move_streams accepts the list in both modes (every active destination is itself a source, no slot is named
+ * twice on either side); for this layout no shorter list exists (the count is the active streams outside their run, plus |H| without the
+ * flag); planning again on the result returns 0, so a context that is already grouped is never disturbed; a context with one object, or
+ * with nothing active, returns 0.  A context with no paused stream and one object per structure class yields a pure permutation of
+ * active slots.
+ * Not in scope: padding groups to whole rows with paused slots (a boundary row between two runs costs one extra workgroup: at most
+ * groups - 1 such rows), choosing the run order to minimise moves globally, choosing the slot an arrival takes. */
+#define DSPI_GROUP_ONE_WAY 0x1u   /* dspi_plan_grouping: paused slots are free, do not preserve them (as DSPI_COMPACT_ONE_WAY) */
+int dspi_plan_grouping(dspi_ctx *ctx, dspi_stream_move *moves, uint32_t cap, uint32_t flags);
 
 /* ---- stream boots: a slot is power-cycled inside its running context -------------------------------------------------------------- */
 /* Devices are unplugged and plugged in again, firmware reboots, and a slot that compaction freed (dspi_plan_compaction with
