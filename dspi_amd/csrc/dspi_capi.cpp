@@ -30,6 +30,7 @@
 #include "dspi_params.h"
 #include "dspi_boot.h"
 #include "dspi_group.h"
+#include "dspi_migrate.h"
 #include "dspi_move.h"
 #include "dspi_plan.h"
 #include "dspi_resize.h"
@@ -122,6 +123,14 @@ struct dspi_ctx {
     uint32_t move_batch = 0;
     uint32_t *d_move = nullptr; size_t d_move_cap = 0;
     uint32_t *h_move = nullptr; size_t h_move_cap = 0; hipEvent_t ev_move = nullptr;
+    // dspi_migrate_streams: the transport (DSPI_MIGRATE_VIA, read once at dspi_create; the DESTINATION context's value decides), the listed
+    // streams' positions (written on the source, read — there or as a copy here — on the destination), the host transport's pinned area,
+    // and "my stream has come this far": recorded on this context's stream, waited for on the other's
+    enum MigrateVia { kViaAuto = 0, kViaCopy = 1, kViaHost = 2 };
+    int migrate_via = kViaAuto;
+    uint32_t *d_mig_pos = nullptr; size_t d_mig_pos_cap = 0;
+    char *h_mig = nullptr; size_t h_mig_cap = 0;
+    hipEvent_t ev_mig = nullptr;
     std::string err;
 };
 
@@ -558,6 +567,7 @@ int dspi_create(dspi_ctx **out, int flavor, uint32_t n_streams, int hip_device) 
     c->no_emit_lines = getenv("DSPI_NO_EMIT_LINES") != nullptr;
     if (const char *e = getenv("DSPI_DIRECT_SPIN_US")) { const long v = atol(e); if (v > 0) c->direct_spin_us = (uint32_t)std::min<long>(v, 1000000L); }
     if (const char *e = getenv("DSPI_MOVE_BATCH")) { const long v = atol(e); if (v > 0) c->move_batch = (uint32_t)std::min<long>(std::max<long>(v, 2L), 65535L); }
+    if (const char *e = getenv("DSPI_MIGRATE_VIA")) c->migrate_via = !strcmp(e, "copy") ? dspi_ctx::kViaCopy : !strcmp(e, "host") ? dspi_ctx::kViaHost : dspi_ctx::kViaAuto;
     c->images.push_back(std::make_unique<Params>(flavor, fma, !populated));
     c->image_refs.push_back(n_streams);
     c->stream_image.assign(n_streams, 0);
@@ -588,13 +598,15 @@ void dspi_destroy(dspi_ctx *c) {
     if (c->device != DSPI_DEVICE_NONE) {
         (void)hipSetDevice(c->device);
         if (c->hs) (void)hipStreamSynchronize(c->hs);
-        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_spdif_ps, (void *)c->d_spdif_vpos, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, (void *)c->d_move, c->d_in,
+        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_spdif_ps, (void *)c->d_spdif_vpos, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, (void *)c->d_move, (void *)c->d_mig_pos, c->d_in,
                         (void *)c->d_pairs, (void *)c->d_sub, (void *)c->d_peaks, (void *)c->d_clip, (void *)c->d_spdif_words})
             if (p) (void)hipFree(p);
         if (c->h_direct) (void)hipHostFree(c->h_direct);
         if (c->h_done) (void)hipHostFree(c->h_done);
         if (c->h_move) (void)hipHostFree(c->h_move);
         if (c->ev_move) (void)hipEventDestroy(c->ev_move);
+        if (c->h_mig) (void)hipHostFree(c->h_mig);
+        if (c->ev_mig) (void)hipEventDestroy(c->ev_mig);
         for (hipEvent_t e : c->pipe_events) (void)hipEventDestroy(e);
         if (c->hs_in) (void)hipStreamDestroy(c->hs_in);
         if (c->hs_out) (void)hipStreamDestroy(c->hs_out);
@@ -837,12 +849,13 @@ int dspi_pdm_restart(dspi_ctx *c, int32_t stream) {
 // ---- stream snapshots (dspi_snapshot.h: the format; dspi_snapshot.hip: the transposition kernels) ----
 static bool snap_range_ok(const dspi_ctx *c, uint32_t first, uint32_t count) { return count != 0 && (uint64_t)first + count <= c->n_streams; }
 
-// the distinct images of streams [first, first + count) in order of first use, and every stream's index into that list
-static void snap_images(const dspi_ctx *c, uint32_t first, uint32_t count, std::vector<int32_t> &used, std::vector<uint32_t> *index) {
+// the distinct images of streams [first, first + count) — or, `list` given, of its `count` sources — in order of first use, and every
+// stream's index into that list
+static void snap_images(const dspi_ctx *c, uint32_t first, uint32_t count, std::vector<int32_t> &used, std::vector<uint32_t> *index, const StreamMove *list = nullptr) {
     std::vector<int32_t> slot(c->images.size(), -1);
     if (index) index->resize(count);
     for (uint32_t k = 0; k < count; k++) {
-        const int32_t im = c->stream_image[(size_t)first + k];
+        const int32_t im = c->stream_image[list ? (size_t)list[k].src : (size_t)first + k];
         if (slot[(size_t)im] < 0) { slot[(size_t)im] = (int32_t)used.size(); used.push_back(im); }
         if (index) (*index)[k] = (uint32_t)slot[(size_t)im];
     }
@@ -1144,6 +1157,159 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
 int dspi_plan_compaction(const dspi_ctx *c, dspi_stream_move *moves, uint32_t cap, uint32_t flags) {
     if (!c || (flags & ~DSPI_COMPACT_ONE_WAY)) return DSPI_E_INVAL;
     const std::vector<StreamMove> plan = move_compaction(host_activity(c), c->n_streams, flags & DSPI_COMPACT_ONE_WAY);
+    if (!moves) return (int)plan.size();
+    if (plan.size() > cap) return DSPI_E_SHORT;
+    if (!plan.empty()) memcpy(moves, plan.data(), plan.size() * sizeof(StreamMove));
+    return (int)plan.size();
+}
+
+// ---- migration between two contexts (dspi_migrate.h: validation, plan, targets, batches; dspi_snapshot.hip: the kernels) ----
+static uint32_t move_batch_records(const dspi_ctx *c) { return c->move_batch ? c->move_batch : snap_chunk_rows(c) * (uint32_t)c->sm.row; }
+
+// both contexts hear why (dspi_last_error on either)
+static int migrate_fail(dspi_ctx *src, dspi_ctx *dst, int code, const std::string &msg) { fail(src, code, msg); return fail(dst, code, msg); }
+
+// "my stream has come this far", and the other context's stream waiting for it: the event is recorded before the wait is enqueued (a wait
+// on an event that was never recorded is no wait)
+static int migrate_signal(dspi_ctx *from, dspi_ctx *to) {
+    HIPCK(from, hipSetDevice(from->device));
+    HIPCK(from, hipEventRecord(from->ev_mig, from->hs));
+    HIPCK(to, hipSetDevice(to->device));
+    HIPCK(to, hipStreamWaitEvent(to->hs, from->ev_mig, 0));
+    return 0;
+}
+
+int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *moves, uint32_t n, uint32_t flags) {
+    if (!src || !dst) { fail(src, DSPI_E_INVAL, "dspi_migrate_streams: null context"); return fail(dst, DSPI_E_INVAL, "dspi_migrate_streams: null context"); }
+    // everything is validated in both contexts before anything is written in either
+    if (src == dst) return fail(src, DSPI_E_INVAL, "dspi_migrate_streams: one context on both sides (dspi_move_streams)");
+    if (src->flavor != dst->flavor || src->fma != dst->fma) return migrate_fail(src, dst, DSPI_E_INVAL, "dspi_migrate_streams: the contexts differ in flavour or float contract");
+    if (flags & ~(DSPI_MIGRATE_AS_IS | DSPI_MIGRATE_PAUSED)) return migrate_fail(src, dst, DSPI_E_INVAL, "dspi_migrate_streams: undefined flag bits");
+    const StreamMove *list = reinterpret_cast<const StreamMove *>(moves);
+    if (const char *why = migrate_validate(list, n, src->n_streams, dst->n_streams, host_activity(dst))) return migrate_fail(src, dst, DSPI_E_INVAL, std::string("dspi_migrate_streams: ") + why);
+    if (src->device == DSPI_DEVICE_NONE || dst->device == DSPI_DEVICE_NONE) return migrate_fail(src, dst, DSPI_E_NODEVICE, "host-only context: no run-time state to migrate");
+    const uint32_t row = (uint32_t)src->sm.row, cap = std::min(move_batch_records(src), move_batch_records(dst));
+    const bool realign = !(flags & DSPI_MIGRATE_AS_IS);
+    const int via = dst->migrate_via;
+    const bool same_device = src->device == dst->device, staged = via != dspi_ctx::kViaAuto || !same_device;      // staged: the records pass through the destination's scratch
+    const size_t rec = snap_state_bytes(src->flavor, 1);
+    // scratch, shift table, position arrays, events and the host transport's area: all before anything is enqueued
+    int rc = snap_prepare(src, cap, false);
+    if (rc || (rc = snap_prepare(dst, staged ? cap : 0, realign))) return rc;
+    for (dspi_ctx *c : {src, dst}) {
+        HIPCK(c, hipSetDevice(c->device));
+        if (!c->ev_mig) HIPCK(c, hipEventCreateWithFlags(&c->ev_mig, hipEventDisableTiming));
+        if (realign && (c == src || staged) && (rc = ensure(c, c->d_mig_pos, c->d_mig_pos_cap, (size_t)n * 8))) return rc;
+    }
+    if (via == dspi_ctx::kViaHost) {
+        const size_t need = std::max((size_t)std::min(cap, n) * rec, (size_t)n * 8);
+        if (need > dst->h_mig_cap) {
+            if (dst->h_mig) HIPCK(dst, hipHostFree(dst->h_mig));
+            dst->h_mig = nullptr; dst->h_mig_cap = 0;
+            void *p = nullptr;
+            if (hipHostMalloc(&p, need, hipHostMallocDefault) != hipSuccess) return fail(dst, DSPI_E_NOMEM, "hipHostMalloc failed (migration area)");
+            dst->h_mig = (char *)p; dst->h_mig_cap = need;
+        }
+    }
+    // the call's work lists, one upload per context through its own staging area: the source gets the listed slots (positions kernel) and
+    // the batches' gather items, the destination the targets (every shift is computed once, before anything is written) and the scatter items
+    const std::vector<MoveBatch> batches = migrate_batches(list, n, cap);
+    struct Side { std::vector<uint32_t> words; std::vector<size_t> item0; size_t items_at = 0, colrec_at = 0; } ss, ds;
+    if (realign) {
+        ss.words.resize(((size_t)n + 3) & ~(size_t)3);
+        for (uint32_t i = 0; i < n; i++) ss.words[i] = list[i].src;
+        const std::vector<MigrateTarget> t = migrate_targets(list, n, dst->n_streams, row, host_activity(dst));
+        ds.words.resize((t.size() * 3 + 3) & ~(size_t)3);
+        memcpy(ds.words.data(), t.data(), t.size() * sizeof(MigrateTarget));
+    }
+    {
+        std::vector<MoveRowItem> si, di;
+        std::vector<uint32_t> sc, dc;
+        for (const MoveBatch &b : batches) {
+            ss.item0.push_back(si.size()); move_row_items(b.gather, row, si, sc);
+            ds.item0.push_back(di.size()); move_row_items(b.scatter, row, di, dc);
+        }
+        ss.item0.push_back(si.size()); ds.item0.push_back(di.size());
+        auto pack = [](Side &s, const std::vector<MoveRowItem> &items, const std::vector<uint32_t> &colrec) {
+            s.items_at = s.words.size(); s.colrec_at = s.items_at + items.size() * 4;
+            s.words.resize(s.colrec_at + colrec.size());
+            memcpy(s.words.data() + s.items_at, items.data(), items.size() * sizeof(MoveRowItem));
+            memcpy(s.words.data() + s.colrec_at, colrec.data(), colrec.size() * 4);
+        };
+        pack(ss, si, sc); pack(ds, di, dc);
+    }
+    HIPCK(src, hipSetDevice(src->device));
+    if ((rc = move_upload(src, ss.words))) return rc;
+    HIPCK(dst, hipSetDevice(dst->device));
+    if ((rc = move_upload(dst, ds.words))) return rc;
+    // the records of one batch from the source's scratch to where the destination scatters them from (on the destination's stream, behind
+    // the source's gather), or the positions the same way
+    auto carry = [&](uint32_t *to, const uint32_t *from, size_t bytes) -> int {
+        if (via == dspi_ctx::kViaHost) {
+            HIPCK(src, hipSetDevice(src->device));
+            HIPCK(src, hipMemcpyAsync(dst->h_mig, from, bytes, hipMemcpyDeviceToHost, src->hs));
+            HIPCK(src, hipStreamSynchronize(src->hs));
+            HIPCK(dst, hipSetDevice(dst->device));
+            HIPCK(dst, hipMemcpyAsync(to, dst->h_mig, bytes, hipMemcpyHostToDevice, dst->hs));
+            return 0;
+        }
+        int r = migrate_signal(src, dst);
+        if (r) return r;
+        if (staged) HIPCK(dst, hipMemcpyPeerAsync(to, dst->device, from, src->device, bytes, dst->hs));
+        return 0;
+    };
+    // the rotations: the sources' pairs on the source's stream, then the shifts on the destination's
+    if (realign) {
+        HIPCK(src, hipSetDevice(src->device));
+        HIPCK(src, launch_migrate_positions(src->flavor, src->d_state, src->d_move, n, src->d_mig_pos, src->hs));
+        if ((rc = carry(dst->d_mig_pos, src->d_mig_pos, (size_t)n * 8))) return rc;
+        HIPCK(dst, hipSetDevice(dst->device));
+        HIPCK(dst, launch_migrate_shifts(dst->flavor, dst->d_state, dst->d_move, staged ? dst->d_mig_pos : src->d_mig_pos, n, dst->d_snap_shift, dst->hs));
+        if (via == dspi_ctx::kViaHost) HIPCK(dst, hipStreamSynchronize(dst->hs));      // (the pinned area is rewritten by the first batch)
+    }
+    // the batches: the source gathers, the destination takes the records and scatters, the source waits before it gathers over the same
+    // scratch again — and once more at the end, so that dspi_sync / dspi_destroy of the source cover the destination's use of its scratch
+    for (size_t b = 0; b < batches.size(); b++) {
+        const uint32_t nb = (uint32_t)batches[b].gather.size();
+        HIPCK(src, hipSetDevice(src->device));
+        HIPCK(src, launch_move_gather(src->flavor, state_arrays(src), src->d_snap, src->d_move + ss.items_at + ss.item0[b] * 4, src->d_move + ss.colrec_at + ss.item0[b] * row,
+                                      (uint32_t)(ss.item0[b + 1] - ss.item0[b]), src->hs));
+        if ((rc = carry(dst->d_snap, src->d_snap, (size_t)nb * rec))) return rc;
+        HIPCK(dst, hipSetDevice(dst->device));
+        HIPCK(dst, launch_move_scatter(dst->flavor, state_arrays(dst), staged ? dst->d_snap : src->d_snap, dst->d_move + ds.items_at + ds.item0[b] * 4,
+                                       dst->d_move + ds.colrec_at + ds.item0[b] * row, (uint32_t)(ds.item0[b + 1] - ds.item0[b]), realign ? dst->d_snap_shift : nullptr, dst->hs));
+        if (via == dspi_ctx::kViaHost) HIPCK(dst, hipStreamSynchronize(dst->hs));
+        else if ((rc = migrate_signal(dst, src))) return rc;
+    }
+    // parameters travel BY VALUE, through the books of an import: each distinct object among the listed streams is copied once, pending
+    // state operations included, and appended to the destination's; the arrivals leave the former occupants' objects.  The fold-back pass
+    // (merge_images, at the destination's next commit) drops what nobody uses any more and folds equal objects.
+    std::vector<int32_t> used;
+    std::vector<uint32_t> index;
+    snap_images(src, 0, n, used, &index, list);
+    const size_t base = dst->images.size();
+    for (int32_t im : used) add_image(dst, std::make_unique<Params>(*src->images[(size_t)im]));
+    for (uint32_t i = 0; i < n; i++) assign_image(dst, list[i].dst, (int32_t)(base + index[i]));
+    dst->merge_hint = true; dst->launch_dirty = true;
+    if (src->audio_started) dst->audio_started = true;      // running devices arrived: dspi_load_flash_dump is no boot any more
+    // the S/PDIF position is the device's own counter, the activity belongs to the stream: both arrive with it (DSPI_MIGRATE_PAUSED: it
+    // arrives paused); every source slot stays behind as a paused, frozen copy, its position frozen with it
+    const uint8_t *const sa = host_activity(src);
+    std::vector<uint8_t> act(n, 1);
+    for (uint32_t i = 0; i < n; i++) act[i] = (flags & DSPI_MIGRATE_PAUSED) ? 0 : (!sa || sa[list[i].src]) ? 1 : 0;
+    if (dst->spdif_ps.on)
+        for (uint32_t i = 0; i < n; i++) dst->spdif_ps.arrive(list[i].dst, src->spdif_ps.on ? src->spdif_ps.get(list[i].src, sa) : src->spdif_pos, act[i] != 0);
+    if (src->spdif_ps.on)
+        for (uint32_t i = 0; i < n; i++) src->spdif_ps.pause(list[i].src, 1, sa);
+    if (src->active.empty()) src->active.assign(src->n_streams, 1);
+    for (uint32_t i = 0; i < n; i++) { set_active(dst, list[i].dst, act[i] != 0); set_active(src, list[i].src, false); }
+    activity_changed(src); activity_changed(dst);
+    return (int)n;
+}
+
+int dspi_plan_migration(const dspi_ctx *src, const dspi_ctx *dst, uint32_t want, dspi_stream_move *moves, uint32_t cap, uint32_t flags) {
+    if (!src || !dst || flags || src->flavor != dst->flavor || src->fma != dst->fma) return DSPI_E_INVAL;
+    const std::vector<StreamMove> plan = migrate_plan(host_activity(src), src->n_streams, host_activity(dst), dst->n_streams, want);
     if (!moves) return (int)plan.size();
     if (plan.size() > cap) return DSPI_E_SHORT;
     if (!plan.empty()) memcpy(moves, plan.data(), plan.size() * sizeof(StreamMove));

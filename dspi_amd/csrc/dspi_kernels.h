@@ -104,6 +104,14 @@ hipError_t launch_move_gather(int flavor, const StateArrays &arr, uint32_t *reco
 hipError_t launch_move_scatter(int flavor, const StateArrays &arr, uint32_t *records, const uint32_t *items, const uint32_t *colrec, uint32_t n_items, const uint32_t *shift,
                                hipStream_t stream);
 
+// ---- migration between two contexts (dspi_migrate_streams; dspi_migrate.h: the lists; dspi_snapshot.hip: the kernels) ----
+// The records go through launch_move_gather on the source context and launch_move_scatter on the destination context.  The shifts of a
+// realigning migration take two launches of one thread per entry: on the source, the listed streams' (delay write index, ring position)
+// pairs into `pos` (n pairs in list order, 8-byte aligned; `slots`: the n source slots); on the destination, shift[dst slot] of its shift
+// table from `pos` (there, or a copy of it) and the destination's state array (`targets`: n MigrateTarget).  All in device memory.
+hipError_t launch_migrate_positions(int flavor, const uint32_t *state, const uint32_t *slots, uint32_t n, uint32_t *pos, hipStream_t stream);
+hipError_t launch_migrate_shifts(int flavor, const uint32_t *state, const uint32_t *targets, const uint32_t *pos, uint32_t n, uint32_t *shift, hipStream_t stream);
+
 // ---- stream boots (dspi_boot_streams; dspi_boot.h: the list; dspi_boot.hip: the kernel) ----
 // Power-on words into the listed columns of the four arrays (pdm may be null: a context that never ran the modulator has no array yet):
 // `items` = n_items BootRowItem in device memory, one per touched row.  Reads nothing but the two position words of each item's target.

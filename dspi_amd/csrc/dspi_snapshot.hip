@@ -44,11 +44,17 @@
 // filled on the gather and never read on the scatter); the scatter's array side stores 16 bytes where all four columns are listed and
 // single words elsewhere, so a touched row's unlisted columns are never written.  The realigning scatter looks its shifts up by destination
 // stream; move_targets_kernel wrote them, once per call, before the first scatter.
+//
+// BETWEEN TWO CONTEXTS (dspi_migrate_streams; the lists: dspi_migrate.h) the gather runs on the source context's arrays and the scatter on the
+// destination's, both unchanged; the shifts need both sides' positions, which no one kernel can read when the contexts sit on two devices:
+// migrate_positions_kernel, on the source, writes every listed stream's pair into an array in list order; that array travels like the
+// records; migrate_shifts_kernel, on the destination, writes shift[destination slot] from it and from the destination's own state array.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
 #include "dspi_kernels.h"
+#include "dspi_migrate.h"
 #include "dspi_move.h"
 #include "dspi_snapshot.h"
 
@@ -56,6 +62,7 @@ namespace dspi {
 
 static_assert(kPdmWords == kPdmStateWords, "the snapshot's PDM section is the modulator's state");
 static_assert(sizeof(MoveRowItem) == 16 && sizeof(MoveTarget) == 12, "the move list's work items go up as 32-bit words");
+static_assert(sizeof(MigrateTarget) == 12, "the migration's targets go up as 32-bit words");
 
 namespace {
 
@@ -304,6 +311,39 @@ __global__ __launch_bounds__(kSnapThreads) void move_targets_kernel(const uint32
                               snap_shift(from[(size_t)sm.ring_pos * ROW] & (kRing - 1u), to[(size_t)sm.ring_pos * ROW] & (kRing - 1u), kRing));
 }
 
+// One thread per entry of a migration list, on the SOURCE context: the (delay write index, ring position) of the stream in slot slots[i], as
+// the source's earlier work left them, masked, into pos[i].
+template <uint32_t ROW>
+__global__ __launch_bounds__(kSnapThreads) void migrate_positions_kernel(const uint32_t *state, const uint32_t *slots, uint32_t n, uint2 *pos) {
+    constexpr StateMap sm = make_state_map(ROW == 128 ? 1 : 0);
+    constexpr uint32_t kLine = (uint32_t)sm.max_delay, kRing = (uint32_t)kRingLen;
+    const uint32_t i = blockIdx.x * kSnapThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t s = slots[i];
+    const uint32_t *from = state + (size_t)(s / ROW) * sm.n_slots * ROW + s % ROW;
+    pos[i] = make_uint2(from[(size_t)sm.widx * ROW] & (kLine - 1u), from[(size_t)sm.ring_pos * ROW] & (kRing - 1u));
+}
+
+// One thread per entry, on the DESTINATION context: how far the stream of entry i (its pair: pos[i]) is rotated to stand at its row's target
+// (dspi_migrate.h migrate_targets) — a resident's pair, read from the destination's state array as its earlier work left it, or another
+// entry's, from pos — before any scatter of the call writes.
+template <uint32_t ROW>
+__global__ __launch_bounds__(kSnapThreads) void migrate_shifts_kernel(const uint32_t *state, const MigrateTarget *t, const uint2 *pos, uint32_t n, uint2 *shift) {
+    constexpr StateMap sm = make_state_map(ROW == 128 ? 1 : 0);
+    constexpr uint32_t kLine = (uint32_t)sm.max_delay, kRing = (uint32_t)kRingLen;
+    const uint32_t i = blockIdx.x * kSnapThreads + threadIdx.x;
+    if (i >= n) return;
+    const MigrateTarget e = t[i];
+    uint2 to;
+    if (e.from_entry) to = pos[e.target];
+    else {
+        const uint32_t *tp = state + (size_t)(e.target / ROW) * sm.n_slots * ROW + e.target % ROW;
+        to = make_uint2(tp[(size_t)sm.widx * ROW] & (kLine - 1u), tp[(size_t)sm.ring_pos * ROW] & (kRing - 1u));
+    }
+    const uint2 from = pos[i];
+    shift[e.dst] = make_uint2(snap_shift(from.x, to.x, kLine), snap_shift(from.y, to.y, kRing));
+}
+
 dim3 snap_list_kargs(SnapListArgs &a, int flavor, bool import, const StateArrays &arr, uint32_t *records, const uint32_t *items, const uint32_t *colrec, uint32_t n_items) {
     dim3 grid = snap_kargs(a, flavor, import, arr, records, 0, 1).grid;
     a.first = 0; a.count = 0; a.row0 = 0;
@@ -319,6 +359,23 @@ hipError_t launch_move_targets(int flavor, const uint32_t *state, const uint32_t
     const dim3 grid((n + kSnapThreads - 1) / kSnapThreads);
     const MoveTarget *t = reinterpret_cast<const MoveTarget *>(targets);
     for_row_width(flavor, [&](auto row) { hipLaunchKernelGGL((move_targets_kernel<decltype(row)::value>), grid, dim3(kSnapThreads), 0, stream, state, t, n, reinterpret_cast<uint2 *>(shift)); });
+    return hipGetLastError();
+}
+
+hipError_t launch_migrate_positions(int flavor, const uint32_t *state, const uint32_t *slots, uint32_t n, uint32_t *pos, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const dim3 grid((n + kSnapThreads - 1) / kSnapThreads);
+    for_row_width(flavor, [&](auto row) { hipLaunchKernelGGL((migrate_positions_kernel<decltype(row)::value>), grid, dim3(kSnapThreads), 0, stream, state, slots, n, reinterpret_cast<uint2 *>(pos)); });
+    return hipGetLastError();
+}
+
+hipError_t launch_migrate_shifts(int flavor, const uint32_t *state, const uint32_t *targets, const uint32_t *pos, uint32_t n, uint32_t *shift, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const dim3 grid((n + kSnapThreads - 1) / kSnapThreads);
+    const MigrateTarget *t = reinterpret_cast<const MigrateTarget *>(targets);
+    for_row_width(flavor, [&](auto row) {
+        hipLaunchKernelGGL((migrate_shifts_kernel<decltype(row)::value>), grid, dim3(kSnapThreads), 0, stream, state, t, reinterpret_cast<const uint2 *>(pos), n, reinterpret_cast<uint2 *>(shift));
+    });
     return hipGetLastError();
 }
 

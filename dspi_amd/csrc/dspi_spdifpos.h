@@ -39,6 +39,9 @@ struct SpdifPos {
     // dspi_move_streams (a validated list): pos[dst] := old pos[src] for all entries at once, the activity travelling with the stream; a
     // source that is no destination keeps its position as a frozen copy (it becomes paused)
     void move(const StreamMove *moves, uint32_t n, const uint8_t *active);
+    // dspi_migrate_streams, the destination context's side: slot s takes a stream that stands at `pos` and is active or paused as `act` says,
+    // whatever the slot was before
+    void arrive(uint32_t s, uint32_t pos, bool act) { put(s, pos % kSpdifBlock, act); }
     // dspi_boot_streams: the listed slots' next frame is frame 0 of a block; a paused slot stays paused
     void boot(const uint32_t *streams, uint32_t n, const uint8_t *active);
 

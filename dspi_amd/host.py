@@ -20,6 +20,8 @@ SNAP_REALIGN = 0x100
 RESUME_AS_IS = 0x1
 MOVE_AS_IS = 0x1
 COMPACT_ONE_WAY = 0x1
+MIGRATE_AS_IS = 0x1
+MIGRATE_PAUSED = 0x2
 GROUP_ONE_WAY = 0x1
 BOOT_STREAMS_AS_IS = 0x1
 RESIZE_PAUSED = 0x1
@@ -121,6 +123,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "dspi_move_streams"):      # (ABI 8 + stream moves: detected by symbol; with it DSPI_MOVE_AS_IS, DSPI_COMPACT_ONE_WAY)
         L.dspi_move_streams.argtypes = [vp, vp, u32, u32]
         L.dspi_plan_compaction.argtypes = [vp, vp, u32, u32]
+    if hasattr(L, "dspi_migrate_streams"):      # (ABI 8 + migration: detected by symbol; with it dspi_plan_migration, DSPI_MIGRATE_AS_IS, DSPI_MIGRATE_PAUSED)
+        L.dspi_migrate_streams.argtypes = [vp, vp, vp, u32, u32]
+        L.dspi_plan_migration.argtypes = [vp, vp, u32, vp, u32, u32]
     if hasattr(L, "dspi_plan_grouping"):      # (ABI 8 + grouping: detected by symbol; with it DSPI_GROUP_ONE_WAY)
         L.dspi_plan_grouping.argtypes = [vp, vp, u32, u32]
     if hasattr(L, "dspi_boot_streams"):      # (ABI 8 + stream boots: detected by symbol; with it DSPI_BOOT_STREAMS_AS_IS)
@@ -473,6 +478,23 @@ class Dspi:
         n = self._ck(self.L.dspi_plan_compaction(self.h, None, 0, flags), "plan_compaction")
         m = np.zeros((n, 2), dtype=np.uint32)
         if n: self._ck(self.L.dspi_plan_compaction(self.h, m.ctypes.data, n, flags), "plan_compaction")
+        return m
+
+    # ---- migration (include/dspi.h: streams change their context; self is the SOURCE context) ----
+    def migrate_streams(self, dst: "Dspi", moves, as_is: bool = False, paused: bool = False) -> int:
+        """dspi_migrate_streams: moves = [(src, dst), ...] (or an (n, 2) array); slot dst of the context `dst` takes the stream slot src of this
+        context held, all entries at once, realigned to its destination row (as_is: DSPI_MIGRATE_AS_IS) and as active as it was (paused:
+        DSPI_MIGRATE_PAUSED, it arrives paused).  The source slots stay behind paused.  Returns the entries applied."""
+        m = np.ascontiguousarray(np.asarray(moves, dtype=np.uint32).reshape(-1, 2))
+        return self._ck(self.L.dspi_migrate_streams(self.h, dst.h, m.ctypes.data if len(m) else None, len(m),
+                                                    (MIGRATE_AS_IS if as_is else 0) | (MIGRATE_PAUSED if paused else 0)), "migrate_streams")
+
+    def plan_migration(self, dst: "Dspi", want: int) -> np.ndarray:
+        """dspi_plan_migration: the (src, dst) list, uint32 [k][2], that shifts k = min(want, active streams here, paused slots of `dst`)
+        streams from the top of this context into the lowest paused slots of `dst`.  Works on host-only contexts."""
+        n = self._ck(self.L.dspi_plan_migration(self.h, dst.h, want, None, 0, 0), "plan_migration")
+        m = np.zeros((n, 2), dtype=np.uint32)
+        if n: self._ck(self.L.dspi_plan_migration(self.h, dst.h, want, m.ctypes.data, n, 0), "plan_migration")
         return m
 
     def plan_grouping(self, one_way: bool = False) -> np.ndarray:

@@ -398,6 +398,67 @@ typedef struct dspi_stream_move { uint32_t src, dst; } dspi_stream_move;
 int dspi_move_streams(dspi_ctx *ctx, const dspi_stream_move *moves, uint32_t n, uint32_t flags);
 int dspi_plan_compaction(const dspi_ctx *ctx, dspi_stream_move *moves, uint32_t cap, uint32_t flags);
 
+/* ---- migration: streams change their context ---------------------------------------------------------------------------------------- */
+/* A node runs one context per GPU, and a device lives where dspi_create put it.  dspi_migrate_streams is dspi_move_streams between two
+ * contexts of one process — on one GPU or on two —, addressed by the same kind of list: in every entry `src` is a slot of the SOURCE
+ * context and `dst` a slot of the DESTINATION context.  dspi_plan_migration writes the list that shifts `want` streams from a fuller
+ * context to an emptier one.  Detected by the symbol dspi_migrate_streams.
+ *   what the call does  after it, slot moves[i].dst of `dst` holds the stream that slot moves[i].src of `src` held before it, for every
+ *                       entry at once.  Returns n.
+ *   what travels        everything a snapshot record carries — every state slot, every delay line at full length, both leveller rings,
+ *                       the PDM modulator words (the power-on words if the source never ran the modulator) —; the stream's parameters BY
+ *                       VALUE: each distinct parameter object among the listed streams is copied once, with its pending state operations,
+ *                       and the copies become objects of `dst` exactly as an import adds them (equal ones fold at dst's next commit); the
+ *                       stream's activity, unless DSPI_MIGRATE_PAUSED is set; "has processed audio", as on an import; and the stream's
+ *                       S/PDIF block position: both contexts in per-stream mode (dspi_spdif_per_stream): the stream's own position; `dst`
+ *                       in the mode and `src` not: src's context position; `dst` not in the mode: nothing per stream exists, so nothing
+ *                       travels.
+ *   source slots        every listed source slot keeps its bytes and its parameter reference as a frozen copy and becomes PAUSED (the open
+ *                       end of dspi_move_streams).  Nothing else in `src` changes.
+ *   destination slots   every listed destination must be PAUSED in `dst` before the call: a migration never overwrites an active stream.
+ *                       The former occupant is gone and its parameter reference is released; the object is dropped at the next commit if
+ *                       that was its last reference.
+ *   realignment         by default every arriving stream takes the (widx, ring_pos) of its destination row, its lines and rings rotated
+ *                       exactly as DSPI_SNAP_REALIGN rotates them.  A resident is a stream below dspi_num_streams(dst) that is active in
+ *                       `dst` before the call (destinations are paused, so none is a resident).  A row's target is the pair of its
+ *                       lowest-numbered resident, read on the device behind dst's earlier work; a row without a resident takes the pair of
+ *                       the stream that arrives at the row's lowest-numbered destination, as it stands at its source: that pair is read on
+ *                       the device behind src's earlier work.  All rotations are fixed once for the whole call before anything is written.
+ *                       DSPI_MIGRATE_AS_IS skips the rotation.
+ *   validation          everything is validated in BOTH contexts before anything is written in either.  A null context, src == dst (use
+ *                       dspi_move_streams), different flavours or float contracts, n == 0 or a null list, a source index at or past
+ *                       dspi_num_streams(src), a destination index at or past dspi_num_streams(dst), a slot named twice as a source, a
+ *                       slot named twice as a destination, an active destination, an undefined flag bit: DSPI_E_INVAL, and both contexts
+ *                       are bit for bit as they were.  A host-only context on either side validates and then returns DSPI_E_NODEVICE, as
+ *                       moves do.  The refusal text is set on both contexts (dspi_last_error).
+ *   timing and threads  takes effect at each context's next dspi_process.  No thread may use either context during the call.  With the
+ *                       device transports the call only enqueues, on both contexts' streams, tied by events: asynchronous like
+ *                       dspi_move_streams; the source's stream ends up waiting for the destination's last scatter, so dspi_sync(src) or
+ *                       dspi_destroy(src) covers dst's use of src's record scratch.  With the host transport it returns when the bytes are
+ *                       in place.  A list of any length goes through the record scratch in batches of the smaller of the two contexts'
+ *                       capacities (DSPI_MOVE_BATCH).
+ *   transports          DSPI_MIGRATE_VIA, read at dspi_create; the destination context's value decides.  Unset: contexts on one device
+ *                       scatter straight out of the source's scratch, contexts on two devices copy device to device into the
+ *                       destination's scratch on the destination's stream.  "copy": always copy into the destination's scratch (on one
+ *                       GPU the two-device code with equal device numbers).  "host": through a pinned host area, synchronising per batch.
+ *   not touched         both contexts' own S/PDIF block positions, the direct path's statistics, the capacities.
+ *
+ * dspi_plan_migration is bookkeeping and works on host-only contexts.  k = min(want, active streams of src, paused slots of dst).  The
+ * sources are the k highest-numbered active slots of `src`, so a compact source stays compact and its top becomes cuttable
+ * (dspi_resize_streams: the vacated top slots are paused, which is what a cut range must be); the destinations are the k lowest-numbered
+ * paused slots of `dst`; entry i pairs the i-th lowest chosen source with the i-th lowest chosen destination, so order is kept and the
+ * runs that grouping made stay runs.  Returns k; moves == NULL only counts; a cap below k is DSPI_E_SHORT and writes nothing; flags != 0,
+ * a null context, or different flavours or float contracts: DSPI_E_INVAL.  It treats EVERY paused slot of `dst` as free, as
+ * DSPI_COMPACT_ONE_WAY does: a caller who parks real devices in paused slots writes their own list.  dspi_migrate_streams accepts every
+ * list it writes.  A rebalance: grow `dst` with DSPI_RESIZE_PAUSED where it is short, plan, migrate, shrink `src`.
+ * Not in scope: a policy that decides when to rebalance or how many streams; dspi_host -g N driving it; migration between processes (that
+ * remains the snapshot's job); a list-addressed dspi_export_streams; padding arrivals to whole rows; choosing sources by preset; any
+ * change to the snapshot format or its fingerprint. */
+#define DSPI_MIGRATE_AS_IS  0x1u   /* keep the streams' own write positions (no realignment) */
+#define DSPI_MIGRATE_PAUSED 0x2u   /* every migrated stream arrives paused, whatever it was at its source */
+int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *moves, uint32_t n, uint32_t flags);
+int dspi_plan_migration(const dspi_ctx *src, const dspi_ctx *dst, uint32_t want, dspi_stream_move *moves, uint32_t cap, uint32_t flags);
+
 /* ---- grouping: streams of one preset into shared rows ------------------------------------------------------------------------------- */
 /* Compaction keeps a context's active streams in whole rows; it does not look at their parameters.  The launch plan picks the kernel by
  * who sits beside whom: a float lane whose two streams share a parameter object runs the packed kernel, a row whose streams hold several
