@@ -19,6 +19,7 @@
 
 #include "dspi_boot.h"
 #include "dspi_kernels.h"
+#include "dspi_snapshot.h"
 
 namespace dspi {
 
@@ -66,9 +67,8 @@ __global__ __launch_bounds__(kBootThreads) void boot_kernel(const BootKArgs a) {
     if (part != 0) return;
     uint32_t widx = 0, ring_pos = 0;
     if (target != kBootNone) {
-        const uint32_t *t = a.state + (size_t)(target / ROW) * sm.n_slots * ROW + target % ROW;
-        widx = t[(size_t)sm.widx * ROW] & ((uint32_t)sm.max_delay - 1u);
-        ring_pos = t[(size_t)sm.ring_pos * ROW] & ((uint32_t)kRingLen - 1u);
+        const SnapPos t = snap_positions(sm, a.state, target);
+        widx = t.widx; ring_pos = t.ring_pos;
     }
     uint32_t *const st = a.state + (size_t)row * sm.n_slots * ROW;
     for (uint32_t p = r; p < (uint32_t)sm.n_slots; p += kPosPerPass)
@@ -83,8 +83,7 @@ hipError_t launch_boot(int flavor, const StateArrays &arr, const uint32_t *items
     if (n_items == 0) return hipSuccess;
     const BootKArgs a{arr.state, arr.dlines, arr.ring, arr.pdm, reinterpret_cast<const BootRowItem *>(items)};
     const dim3 grid(n_items, kBootParts);
-    if (flavor) hipLaunchKernelGGL((boot_kernel<128>), grid, dim3(kBootThreads), 0, stream, a);
-    else hipLaunchKernelGGL((boot_kernel<64>), grid, dim3(kBootThreads), 0, stream, a);
+    for_row_width(flavor, [&](auto row) { hipLaunchKernelGGL((boot_kernel<decltype(row)::value>), grid, dim3(kBootThreads), 0, stream, a); });
     return hipGetLastError();
 }
 

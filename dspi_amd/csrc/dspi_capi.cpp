@@ -122,14 +122,14 @@ struct dspi_ctx {
     // built in a pinned host area, copied up on the context's stream; the event says when the area may be rewritten
     uint32_t move_batch = 0;
     uint32_t *d_move = nullptr; size_t d_move_cap = 0;
-    uint32_t *h_move = nullptr; size_t h_move_cap = 0; hipEvent_t ev_move = nullptr;
+    void *h_move = nullptr; size_t h_move_cap = 0; hipEvent_t ev_move = nullptr;
     // dspi_migrate_streams: the transport (DSPI_MIGRATE_VIA, read once at dspi_create; the DESTINATION context's value decides), the listed
     // streams' positions (written on the source, read — there or as a copy here — on the destination), the host transport's pinned area,
     // and "my stream has come this far": recorded on this context's stream, waited for on the other's
     enum MigrateVia { kViaAuto = 0, kViaCopy = 1, kViaHost = 2 };
     int migrate_via = kViaAuto;
     uint32_t *d_mig_pos = nullptr; size_t d_mig_pos_cap = 0;
-    char *h_mig = nullptr; size_t h_mig_cap = 0;
+    void *h_mig = nullptr; size_t h_mig_cap = 0;
     hipEvent_t ev_mig = nullptr;
     std::string err;
 };
@@ -1067,24 +1067,57 @@ int dspi_streams_paused(const dspi_ctx *c, uint32_t first, uint32_t count, uint8
 // ---- stream moves (dspi_move.h: validation, compaction rule, targets, batch schedule; dspi_snapshot.hip: the list-addressed kernels) ----
 static_assert(sizeof(dspi_stream_move) == sizeof(StreamMove) && offsetof(dspi_stream_move, dst) == offsetof(StreamMove, dst), "dspi_stream_move is StreamMove");
 
+static uint32_t move_batch_records(const dspi_ctx *c) { return c->move_batch ? c->move_batch : snap_chunk_rows(c) * (uint32_t)c->sm.row; }
+
+// a pinned host area (h_move, h_mig) of at least `bytes`: one that is too small is replaced by one of `grow` bytes
+static int pinned_area(dspi_ctx *c, void *&area, size_t &cap, size_t bytes, size_t grow, const char *why) {
+    if (bytes <= cap) return 0;
+    if (area) HIPCK(c, hipHostFree(area));
+    area = nullptr; cap = 0;
+    if (hipHostMalloc(&area, grow, hipHostMallocDefault) != hipSuccess) { area = nullptr; return fail(c, DSPI_E_NOMEM, why); }
+    cap = grow;
+    return 0;
+}
+
 // one call's work lists into device memory, behind the context's earlier work
 static int move_upload(dspi_ctx *c, const std::vector<uint32_t> &words) {
     const size_t bytes = words.size() * 4;
     if (!c->ev_move) HIPCK(c, hipEventCreateWithFlags(&c->ev_move, hipEventDisableTiming));
     HIPCK(c, hipEventSynchronize(c->ev_move));      // the previous call's copy has left the area (long since, as a rule)
-    if (bytes > c->h_move_cap) {
-        if (c->h_move) HIPCK(c, hipHostFree(c->h_move));
-        c->h_move = nullptr; c->h_move_cap = 0;
-        void *p = nullptr;
-        if (hipHostMalloc(&p, bytes * 2, hipHostMallocDefault) != hipSuccess) return fail(c, DSPI_E_NOMEM, "hipHostMalloc failed (move lists)");
-        c->h_move = (uint32_t *)p; c->h_move_cap = bytes * 2;
-    }
-    int rc = ensure(c, c->d_move, c->d_move_cap, bytes);
-    if (rc) return rc;
+    int rc = pinned_area(c, c->h_move, c->h_move_cap, bytes, bytes * 2, "hipHostMalloc failed (move lists)");
+    if (rc || (rc = ensure(c, c->d_move, c->d_move_cap, bytes))) return rc;
     memcpy(c->h_move, words.data(), bytes);
     HIPCK(c, hipMemcpyAsync(c->d_move, c->h_move, bytes, hipMemcpyHostToDevice, c->hs));
     HIPCK(c, hipEventRecord(c->ev_move, c->hs));
     return 0;
+}
+
+// row items and their columns' record indices, appended to a call's work lists: where they begin, in words
+struct PackedItems { size_t items_at, colrec_at; };
+static PackedItems pack_row_items(std::vector<uint32_t> &words, const std::vector<MoveRowItem> &items, const std::vector<uint32_t> &colrec) {
+    const PackedItems at{words.size(), words.size() + items.size() * 4};
+    words.resize(at.colrec_at + colrec.size());
+    memcpy(words.data() + at.items_at, items.data(), items.size() * sizeof(MoveRowItem));
+    memcpy(words.data() + at.colrec_at, colrec.data(), colrec.size() * 4);
+    return at;
+}
+// ... and a call's targets at their head (four words per entry: what follows stays 16-byte aligned)
+static void pack_targets(std::vector<uint32_t> &words, const std::vector<ListTarget> &t) {
+    words.resize(t.size() * 4);
+    memcpy(words.data(), t.data(), t.size() * sizeof(ListTarget));
+}
+// a planned list into the caller's buffer (moves == nullptr: its size only)
+static int plan_out(const std::vector<StreamMove> &plan, dspi_stream_move *moves, uint32_t cap) {
+    if (!moves) return (int)plan.size();
+    if (plan.size() > cap) return DSPI_E_SHORT;
+    if (!plan.empty()) memcpy(moves, plan.data(), plan.size() * sizeof(StreamMove));
+    return (int)plan.size();
+}
+// a boot list's work items into device memory (move_upload)
+static int boot_upload(dspi_ctx *c, const std::vector<BootRowItem> &items) {
+    std::vector<uint32_t> words(items.size() * (sizeof(BootRowItem) / 4));
+    memcpy(words.data(), items.data(), items.size() * sizeof(BootRowItem));
+    return move_upload(c, words);
 }
 
 int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, uint32_t flags) {
@@ -1097,8 +1130,7 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
     std::vector<StreamMove> mv;
     for (uint32_t i = 0; i < n; i++) if (list[i].src != list[i].dst) mv.push_back(list[i]);
     if (mv.empty()) return 0;
-    const uint32_t nm = (uint32_t)mv.size(), row = (uint32_t)c->sm.row;
-    const uint32_t cap = c->move_batch ? c->move_batch : snap_chunk_rows(c) * row;
+    const uint32_t nm = (uint32_t)mv.size(), row = (uint32_t)c->sm.row, cap = move_batch_records(c);
     const bool realign = !(flags & DSPI_MOVE_AS_IS);
     int rc = snap_prepare(c, cap, realign);
     if (rc) return rc;
@@ -1107,9 +1139,9 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
     const std::vector<MoveBatch> batches = move_schedule(mv.data(), nm, cap);
     std::vector<uint32_t> words;
     if (realign) {
-        const std::vector<MoveTarget> t = move_targets(mv.data(), nm, c->n_streams, row, host_activity(c));
-        words.resize((t.size() * 3 + 3) & ~(size_t)3);
-        memcpy(words.data(), t.data(), t.size() * sizeof(MoveTarget));
+        std::vector<uint8_t> listed(c->n_streams, 0);      // neither a source nor a destination is a resident
+        for (const StreamMove &m : mv) listed[m.src] = listed[m.dst] = 1;
+        pack_targets(words, list_targets(mv.data(), nm, c->n_streams, row, host_activity(c), listed.data()));
     }
     std::vector<MoveRowItem> items;
     std::vector<uint32_t> colrec;
@@ -1121,13 +1153,10 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
         move_row_items(b.scatter, row, items, colrec); sp.s1 = items.size();
         spans.push_back(sp);
     }
-    const size_t items_at = words.size(), colrec_at = items_at + items.size() * 4;
-    words.resize(colrec_at + colrec.size());
-    memcpy(words.data() + items_at, items.data(), items.size() * sizeof(MoveRowItem));
-    memcpy(words.data() + colrec_at, colrec.data(), colrec.size() * 4);
+    const auto [items_at, colrec_at] = pack_row_items(words, items, colrec);
     if ((rc = move_upload(c, words))) return rc;
     // run-time state, on the context's stream, behind whatever it still has to do
-    if (realign) HIPCK(c, launch_move_targets(c->flavor, c->d_state, c->d_move, nm, c->d_snap_shift, c->hs));
+    if (realign) HIPCK(c, launch_list_shifts(c->flavor, c->d_state, c->d_move, nullptr, nm, c->d_snap_shift, c->hs));
     for (const Span &sp : spans) {
         HIPCK(c, launch_move_gather(c->flavor, state_arrays(c), c->d_snap, c->d_move + items_at + sp.g0 * 4, c->d_move + colrec_at + sp.g0 * row, (uint32_t)(sp.g1 - sp.g0), c->hs));
         HIPCK(c, launch_move_scatter(c->flavor, state_arrays(c), c->d_snap, c->d_move + items_at + sp.g1 * 4, c->d_move + colrec_at + sp.g1 * row, (uint32_t)(sp.s1 - sp.g1),
@@ -1157,15 +1186,10 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
 int dspi_plan_compaction(const dspi_ctx *c, dspi_stream_move *moves, uint32_t cap, uint32_t flags) {
     if (!c || (flags & ~DSPI_COMPACT_ONE_WAY)) return DSPI_E_INVAL;
     const std::vector<StreamMove> plan = move_compaction(host_activity(c), c->n_streams, flags & DSPI_COMPACT_ONE_WAY);
-    if (!moves) return (int)plan.size();
-    if (plan.size() > cap) return DSPI_E_SHORT;
-    if (!plan.empty()) memcpy(moves, plan.data(), plan.size() * sizeof(StreamMove));
-    return (int)plan.size();
+    return plan_out(plan, moves, cap);
 }
 
-// ---- migration between two contexts (dspi_migrate.h: validation, plan, targets, batches; dspi_snapshot.hip: the kernels) ----
-static uint32_t move_batch_records(const dspi_ctx *c) { return c->move_batch ? c->move_batch : snap_chunk_rows(c) * (uint32_t)c->sm.row; }
-
+// ---- migration between two contexts (dspi_migrate.h: validation, plan, batches; dspi_move.h: targets; dspi_snapshot.hip: the kernels) ----
 // both contexts hear why (dspi_last_error on either)
 static int migrate_fail(dspi_ctx *src, dspi_ctx *dst, int code, const std::string &msg) { fail(src, code, msg); return fail(dst, code, msg); }
 
@@ -1203,24 +1227,16 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
     }
     if (via == dspi_ctx::kViaHost) {
         const size_t need = std::max((size_t)std::min(cap, n) * rec, (size_t)n * 8);
-        if (need > dst->h_mig_cap) {
-            if (dst->h_mig) HIPCK(dst, hipHostFree(dst->h_mig));
-            dst->h_mig = nullptr; dst->h_mig_cap = 0;
-            void *p = nullptr;
-            if (hipHostMalloc(&p, need, hipHostMallocDefault) != hipSuccess) return fail(dst, DSPI_E_NOMEM, "hipHostMalloc failed (migration area)");
-            dst->h_mig = (char *)p; dst->h_mig_cap = need;
-        }
+        if ((rc = pinned_area(dst, dst->h_mig, dst->h_mig_cap, need, need, "hipHostMalloc failed (migration area)"))) return rc;
     }
     // the call's work lists, one upload per context through its own staging area: the source gets the listed slots (positions kernel) and
     // the batches' gather items, the destination the targets (every shift is computed once, before anything is written) and the scatter items
     const std::vector<MoveBatch> batches = migrate_batches(list, n, cap);
-    struct Side { std::vector<uint32_t> words; std::vector<size_t> item0; size_t items_at = 0, colrec_at = 0; } ss, ds;
+    struct Side { std::vector<uint32_t> words; std::vector<size_t> item0; PackedItems at{0, 0}; } ss, ds;
     if (realign) {
         ss.words.resize(((size_t)n + 3) & ~(size_t)3);
         for (uint32_t i = 0; i < n; i++) ss.words[i] = list[i].src;
-        const std::vector<MigrateTarget> t = migrate_targets(list, n, dst->n_streams, row, host_activity(dst));
-        ds.words.resize((t.size() * 3 + 3) & ~(size_t)3);
-        memcpy(ds.words.data(), t.data(), t.size() * sizeof(MigrateTarget));
+        pack_targets(ds.words, list_targets(list, n, dst->n_streams, row, host_activity(dst), nullptr));
     }
     {
         std::vector<MoveRowItem> si, di;
@@ -1230,13 +1246,7 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
             ds.item0.push_back(di.size()); move_row_items(b.scatter, row, di, dc);
         }
         ss.item0.push_back(si.size()); ds.item0.push_back(di.size());
-        auto pack = [](Side &s, const std::vector<MoveRowItem> &items, const std::vector<uint32_t> &colrec) {
-            s.items_at = s.words.size(); s.colrec_at = s.items_at + items.size() * 4;
-            s.words.resize(s.colrec_at + colrec.size());
-            memcpy(s.words.data() + s.items_at, items.data(), items.size() * sizeof(MoveRowItem));
-            memcpy(s.words.data() + s.colrec_at, colrec.data(), colrec.size() * 4);
-        };
-        pack(ss, si, sc); pack(ds, di, dc);
+        ss.at = pack_row_items(ss.words, si, sc); ds.at = pack_row_items(ds.words, di, dc);
     }
     HIPCK(src, hipSetDevice(src->device));
     if ((rc = move_upload(src, ss.words))) return rc;
@@ -1264,7 +1274,7 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
         HIPCK(src, launch_migrate_positions(src->flavor, src->d_state, src->d_move, n, src->d_mig_pos, src->hs));
         if ((rc = carry(dst->d_mig_pos, src->d_mig_pos, (size_t)n * 8))) return rc;
         HIPCK(dst, hipSetDevice(dst->device));
-        HIPCK(dst, launch_migrate_shifts(dst->flavor, dst->d_state, dst->d_move, staged ? dst->d_mig_pos : src->d_mig_pos, n, dst->d_snap_shift, dst->hs));
+        HIPCK(dst, launch_list_shifts(dst->flavor, dst->d_state, dst->d_move, staged ? dst->d_mig_pos : src->d_mig_pos, n, dst->d_snap_shift, dst->hs));
         if (via == dspi_ctx::kViaHost) HIPCK(dst, hipStreamSynchronize(dst->hs));      // (the pinned area is rewritten by the first batch)
     }
     // the batches: the source gathers, the destination takes the records and scatters, the source waits before it gathers over the same
@@ -1272,12 +1282,12 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
     for (size_t b = 0; b < batches.size(); b++) {
         const uint32_t nb = (uint32_t)batches[b].gather.size();
         HIPCK(src, hipSetDevice(src->device));
-        HIPCK(src, launch_move_gather(src->flavor, state_arrays(src), src->d_snap, src->d_move + ss.items_at + ss.item0[b] * 4, src->d_move + ss.colrec_at + ss.item0[b] * row,
+        HIPCK(src, launch_move_gather(src->flavor, state_arrays(src), src->d_snap, src->d_move + ss.at.items_at + ss.item0[b] * 4, src->d_move + ss.at.colrec_at + ss.item0[b] * row,
                                       (uint32_t)(ss.item0[b + 1] - ss.item0[b]), src->hs));
         if ((rc = carry(dst->d_snap, src->d_snap, (size_t)nb * rec))) return rc;
         HIPCK(dst, hipSetDevice(dst->device));
-        HIPCK(dst, launch_move_scatter(dst->flavor, state_arrays(dst), staged ? dst->d_snap : src->d_snap, dst->d_move + ds.items_at + ds.item0[b] * 4,
-                                       dst->d_move + ds.colrec_at + ds.item0[b] * row, (uint32_t)(ds.item0[b + 1] - ds.item0[b]), realign ? dst->d_snap_shift : nullptr, dst->hs));
+        HIPCK(dst, launch_move_scatter(dst->flavor, state_arrays(dst), staged ? dst->d_snap : src->d_snap, dst->d_move + ds.at.items_at + ds.item0[b] * 4,
+                                       dst->d_move + ds.at.colrec_at + ds.item0[b] * row, (uint32_t)(ds.item0[b + 1] - ds.item0[b]), realign ? dst->d_snap_shift : nullptr, dst->hs));
         if (via == dspi_ctx::kViaHost) HIPCK(dst, hipStreamSynchronize(dst->hs));
         else if ((rc = migrate_signal(dst, src))) return rc;
     }
@@ -1310,10 +1320,7 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
 int dspi_plan_migration(const dspi_ctx *src, const dspi_ctx *dst, uint32_t want, dspi_stream_move *moves, uint32_t cap, uint32_t flags) {
     if (!src || !dst || flags || src->flavor != dst->flavor || src->fma != dst->fma) return DSPI_E_INVAL;
     const std::vector<StreamMove> plan = migrate_plan(host_activity(src), src->n_streams, host_activity(dst), dst->n_streams, want);
-    if (!moves) return (int)plan.size();
-    if (plan.size() > cap) return DSPI_E_SHORT;
-    if (!plan.empty()) memcpy(moves, plan.data(), plan.size() * sizeof(StreamMove));
-    return (int)plan.size();
+    return plan_out(plan, moves, cap);
 }
 
 // ---- grouping (dspi_group.h: the rule).  Bookkeeping like the compaction plan, but on the parameter objects as they stand folded: two
@@ -1352,10 +1359,7 @@ int dspi_plan_grouping(dspi_ctx *c, dspi_stream_move *moves, uint32_t cap, uint3
         cls = group_classes(sig.data(), ni);
     }
     const std::vector<StreamMove> plan = group_plan(host_activity(c), c->stream_image.data(), cls.empty() ? nullptr : cls.data(), c->n_streams, flags & DSPI_GROUP_ONE_WAY);
-    if (!moves) return (int)plan.size();
-    if (plan.size() > cap) return DSPI_E_SHORT;
-    if (!plan.empty()) memcpy(moves, plan.data(), plan.size() * sizeof(StreamMove));
-    return (int)plan.size();
+    return plan_out(plan, moves, cap);
 }
 
 // ---- stream boots (dspi_boot.h: validation and the kernel's work items; dspi_boot.hip: the power-on kernel) ----
@@ -1374,9 +1378,7 @@ int dspi_boot_streams(dspi_ctx *c, const uint32_t *streams, uint32_t n, const vo
     if (c->device != DSPI_DEVICE_NONE) {
         HIPCK(c, hipSetDevice(c->device));
         const std::vector<BootRowItem> items = boot_row_items(streams, n, c->n_streams, (uint32_t)c->sm.row, host_activity(c), (flags & DSPI_BOOT_STREAMS_AS_IS) != 0);
-        std::vector<uint32_t> words(items.size() * (sizeof(BootRowItem) / 4));
-        memcpy(words.data(), items.data(), items.size() * sizeof(BootRowItem));
-        int rc = move_upload(c, words);
+        int rc = boot_upload(c, items);
         if (rc) return rc;
         HIPCK(c, launch_boot(c->flavor, state_arrays(c), c->d_move, (uint32_t)items.size(), c->hs));
     }
@@ -1471,9 +1473,7 @@ int dspi_resize_streams(dspi_ctx *c, uint32_t n_streams, uint32_t flags) {
         // the new slots' work items go up first (scratch of the call, no state of the context), so that nothing can fail between the
         // reallocation and the power-on launch
         const std::vector<BootRowItem> items = resize_row_items(n_old, n_streams, row, host_activity(c));
-        std::vector<uint32_t> words(items.size() * (sizeof(BootRowItem) / 4));
-        memcpy(words.data(), items.data(), items.size() * sizeof(BootRowItem));
-        int rc = move_upload(c, words);
+        int rc = boot_upload(c, items);
         if (rc || (r.reallocate && (rc = resize_reallocate(c, r.capacity, r.copy)))) return rc;
         // power-on state into EVERY new slot, whatever its column held (padding columns are dirty after a shrink, new rows unwritten),
         // behind the context's earlier work: the kernel reads the grown row's resident's positions there

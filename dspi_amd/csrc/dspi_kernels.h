@@ -3,6 +3,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include <type_traits>
 #include "dspi_image.h"
 #include "dspi_plan.h"
 
@@ -82,6 +84,13 @@ hipError_t launch_clip_gather(const uint32_t *state, uint32_t n_streams, uint32_
 
 // ---- the context's four per-stream arrays, [W][position][R] each (dspi_snapshot.hip's and dspi_boot.hip's launchers take them as one) ----
 struct StateArrays { uint32_t *state, *dlines, *ring, *pdm; };
+// the one flavour ladder of their launchers (dspi_snapshot.hip, dspi_boot.hip; no chain file uses it): f(the flavour's row width as a
+// compile-time constant)
+template <class F>
+void for_row_width(int flavor, F f) {
+    if (flavor) f(std::integral_constant<uint32_t, 128>{});
+    else f(std::integral_constant<uint32_t, 64>{});
+}
 
 // ---- stream snapshots (dspi_snapshot.hip): streams [first, first + count) of the four stream-minor arrays <-> stream-major records
 // (dspi_snapshot.h), `records` = the record of stream `first`, 16-byte aligned.  import: records -> arrays, else arrays -> records.
@@ -98,19 +107,18 @@ hipError_t launch_snapshot_realign(int flavor, const StateArrays &arr, uint32_t 
 // The same transposition addressed by list: `items` = n_items MoveRowItem (one per touched row), `colrec` = per item one record index per
 // column of the row (kMoveNone: the column is not listed and is neither read into a record nor written), both in device memory; `records`
 // = record 0 of the scratch.  The gather reads listed columns into their records; the scatter writes records into listed columns, rotated
-// by shift[destination stream] (two words per stream of the context, from launch_move_targets) or, shift == nullptr, as they are.
-hipError_t launch_move_targets(int flavor, const uint32_t *state, const uint32_t *targets, uint32_t n, uint32_t *shift, hipStream_t stream);      // targets: n MoveTarget
+// by shift[destination stream] (two words per stream of the context, from launch_list_shifts) or, shift == nullptr, as they are.
 hipError_t launch_move_gather(int flavor, const StateArrays &arr, uint32_t *records, const uint32_t *items, const uint32_t *colrec, uint32_t n_items, hipStream_t stream);
 hipError_t launch_move_scatter(int flavor, const StateArrays &arr, uint32_t *records, const uint32_t *items, const uint32_t *colrec, uint32_t n_items, const uint32_t *shift,
                                hipStream_t stream);
-
-// ---- migration between two contexts (dspi_migrate_streams; dspi_migrate.h: the lists; dspi_snapshot.hip: the kernels) ----
-// The records go through launch_move_gather on the source context and launch_move_scatter on the destination context.  The shifts of a
-// realigning migration take two launches of one thread per entry: on the source, the listed streams' (delay write index, ring position)
-// pairs into `pos` (n pairs in list order, 8-byte aligned; `slots`: the n source slots); on the destination, shift[dst slot] of its shift
-// table from `pos` (there, or a copy of it) and the destination's state array (`targets`: n MigrateTarget).  All in device memory.
+// The shifts of a realigning list, one thread per entry, on the context that is written: shift[dst slot] from `targets` (n ListTarget,
+// dspi_move.h) and `state`, that context's state array.  pos == nullptr (a move): every entry's own pair is read in place; else (a
+// migration) `pos` holds the n pairs in list order, 8-byte aligned, that launch_migrate_positions wrote on the SOURCE context from its
+// state array and the n source `slots` (there, or a copy of it).  All in device memory.
+hipError_t launch_list_shifts(int flavor, const uint32_t *state, const uint32_t *targets, const uint32_t *pos, uint32_t n, uint32_t *shift, hipStream_t stream);
+// ---- migration between two contexts (dspi_migrate_streams; dspi_migrate.h: the lists): the records go through launch_move_gather on the
+// source context and launch_move_scatter on the destination context ----
 hipError_t launch_migrate_positions(int flavor, const uint32_t *state, const uint32_t *slots, uint32_t n, uint32_t *pos, hipStream_t stream);
-hipError_t launch_migrate_shifts(int flavor, const uint32_t *state, const uint32_t *targets, const uint32_t *pos, uint32_t n, uint32_t *shift, hipStream_t stream);
 
 // ---- stream boots (dspi_boot_streams; dspi_boot.h: the list; dspi_boot.hip: the kernel) ----
 // Power-on words into the listed columns of the four arrays (pdm may be null: a context that never ran the modulator has no array yet):

@@ -1,9 +1,6 @@
 // dspi_migrate.cpp — see dspi_migrate.h.
 #include "dspi_migrate.h"
 
-#include <algorithm>
-#include <unordered_map>
-
 namespace dspi {
 
 const char *migrate_validate(const StreamMove *moves, uint32_t n, uint32_t n_src, uint32_t n_dst, const uint8_t *dst_active) {
@@ -13,14 +10,8 @@ const char *migrate_validate(const StreamMove *moves, uint32_t n, uint32_t n_src
         if (moves[i].dst >= n_dst) return "destination index out of range";
     }
     std::vector<uint8_t> is_src(n_src, 0), is_dst(n_dst, 0);
-    for (uint32_t i = 0; i < n; i++) {
-        if (is_src[moves[i].src]) return "a slot is the source of two entries";
-        is_src[moves[i].src] = 1;
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        if (is_dst[moves[i].dst]) return "a slot is the destination of two entries";
-        is_dst[moves[i].dst] = 1;
-    }
+    if (check_slots(&moves->src, 2, n, is_src) == SlotCheck::duplicate) return "a slot is the source of two entries";
+    if (check_slots(&moves->dst, 2, n, is_dst) == SlotCheck::duplicate) return "a slot is the destination of two entries";
     for (uint32_t i = 0; i < n; i++)
         if (!dst_active || dst_active[moves[i].dst]) return "a destination holds an active stream";
     return nullptr;
@@ -36,30 +27,6 @@ std::vector<StreamMove> migrate_plan(const uint8_t *src_active, uint32_t n_src, 
         if (!dst_active[s]) to.push_back(s);
     const size_t k = to.size();      // (<= from.size(): the k highest sources are from's first k)
     for (size_t i = 0; i < k; i++) out.push_back(StreamMove{from[k - 1 - i], to[i]});
-    return out;
-}
-
-std::vector<MigrateTarget> migrate_targets(const StreamMove *moves, uint32_t n, uint32_t n_dst, uint32_t row_streams, const uint8_t *dst_active) {
-    std::vector<MigrateTarget> out(n);
-    struct RowTarget { uint32_t target, from_entry, lowest; };
-    std::unordered_map<uint32_t, RowTarget> rows;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t row = moves[i].dst / row_streams;
-        auto it = rows.find(row);
-        if (it != rows.end()) {
-            if (it->second.from_entry && moves[i].dst < it->second.lowest) { it->second.lowest = moves[i].dst; it->second.target = i; }
-            continue;
-        }
-        const uint64_t r0 = (uint64_t)row * row_streams, r1 = std::min<uint64_t>(r0 + row_streams, n_dst);
-        uint32_t resident = kMoveNone;
-        for (uint64_t s = r0; s < r1 && resident == kMoveNone; s++)
-            if (!dst_active || dst_active[s]) resident = (uint32_t)s;
-        rows[row] = resident != kMoveNone ? RowTarget{resident, 0u, 0u} : RowTarget{i, 1u, moves[i].dst};
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        const RowTarget &t = rows[moves[i].dst / row_streams];
-        out[i] = MigrateTarget{moves[i].dst, t.target, t.from_entry};
-    }
     return out;
 }
 

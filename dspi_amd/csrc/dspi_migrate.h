@@ -1,7 +1,7 @@
 // dspi_migrate.h — moving streams between slots of TWO contexts (dspi_migrate_streams / dspi_plan_migration, include/dspi.h): what a list
-// must satisfy in both contexts, which list rebalances, whose write positions an arriving stream takes, and how the list goes through a
-// scratch of `cap` records.  Plain C++ (no HIP): dspi_capi.cpp and dspi_snapshot.hip include it, tests/migrate_driver.cpp exercises it
-// without a GPU.  In every entry `src` is a slot of the source context and `dst` a slot of the destination context.
+// must satisfy in both contexts, which list rebalances, and how the list goes through a scratch of `cap` records.  Plain C++ (no HIP):
+// dspi_capi.cpp includes it, tests/migrate_driver.cpp exercises it without a GPU.  In every entry `src` is a slot of the source context
+// and `dst` a slot of the destination context.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -26,12 +26,16 @@ const char *migrate_validate(const StreamMove *moves, uint32_t n, uint32_t n_src
 std::vector<StreamMove> migrate_plan(const uint8_t *src_active, uint32_t n_src, const uint8_t *dst_active, uint32_t n_dst, uint32_t want);
 
 // ---- realignment ----
-// Whose (delay write index, ring position) the stream of entry i takes at `dst`: from_entry == 0: those of slot `target` of the
-// DESTINATION context as it stands before the call — the lowest-numbered resident of dst's row (below n_dst and active; destinations are
-// paused, so none is a resident); from_entry == 1: a row without a resident: those of the stream of entry `target` as it stands at its
-// source, the entry whose destination is the row's lowest.  One per entry, in list order.
+// Whose (delay write index, ring position) an arriving stream takes: the row-target rule and list_targets (dspi_move.h), with
+// listed = nullptr — every destination is paused, so none is a resident.
+// For the CPU driver only (tests/migrate_driver.cpp, unchanged since before list_targets): that call without the sources.  Header-only:
+// nothing of it is in the library, and no rule of its own.
 struct MigrateTarget { uint32_t dst, target, from_entry; };
-std::vector<MigrateTarget> migrate_targets(const StreamMove *moves, uint32_t n, uint32_t n_dst, uint32_t row_streams, const uint8_t *dst_active);
+inline std::vector<MigrateTarget> migrate_targets(const StreamMove *moves, uint32_t n, uint32_t n_dst, uint32_t row_streams, const uint8_t *dst_active) {
+    std::vector<MigrateTarget> out;
+    for (const ListTarget &t : list_targets(moves, n, n_dst, row_streams, dst_active, nullptr)) out.push_back(MigrateTarget{t.dst, t.target, t.from_entry});
+    return out;
+}
 
 // ---- the batches ----
 // Two contexts have no cycles and no chains: no slot is read after it was written.  The batches are consecutive pieces of the list of at

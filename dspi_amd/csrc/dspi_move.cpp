@@ -8,19 +8,13 @@ namespace dspi {
 
 const char *move_validate(const StreamMove *moves, uint32_t n, uint32_t n_streams, const uint8_t *active) {
     if (!moves || n == 0) return "empty move list";
+    std::vector<uint8_t> is_src(n_streams, 0), is_dst(n_streams, 0);
+    const SlotCheck src = check_slots(&moves->src, 2, n, is_src), dst = check_slots(&moves->dst, 2, n, is_dst);
+    if (src == SlotCheck::out_of_range || dst == SlotCheck::out_of_range) return "stream index out of range";
+    if (src == SlotCheck::duplicate) return "a slot is the source of two entries";
+    if (dst == SlotCheck::duplicate) return "a slot is the destination of two entries";
     for (uint32_t i = 0; i < n; i++)
-        if (moves[i].src >= n_streams || moves[i].dst >= n_streams) return "stream index out of range";
-    std::vector<uint8_t> mark(n_streams, 0);      // bit 0: a source, bit 1: a destination
-    for (uint32_t i = 0; i < n; i++) {
-        if (mark[moves[i].src] & 1u) return "a slot is the source of two entries";
-        mark[moves[i].src] |= 1u;
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        if (mark[moves[i].dst] & 2u) return "a slot is the destination of two entries";
-        mark[moves[i].dst] |= 2u;
-    }
-    for (uint32_t i = 0; i < n; i++)
-        if (!(mark[moves[i].dst] & 1u) && (!active || active[moves[i].dst])) return "a destination holds an active stream that the list does not move away";
+        if (!is_src[moves[i].dst] && (!active || active[moves[i].dst])) return "a destination holds an active stream that the list does not move away";
     return nullptr;
 }
 
@@ -40,31 +34,22 @@ std::vector<StreamMove> move_compaction(const uint8_t *active, uint32_t n_stream
     return out;
 }
 
-std::vector<MoveTarget> move_targets(const StreamMove *moves, uint32_t n, uint32_t n_streams, uint32_t row_streams, const uint8_t *active) {
-    std::vector<uint8_t> moved(n_streams, 0);
-    std::vector<MoveTarget> out;
+std::vector<ListTarget> list_targets(const StreamMove *moves, uint32_t n, uint32_t n_dst, uint32_t row_streams, const uint8_t *dst_active, const uint8_t *listed) {
+    struct RowTarget { uint32_t target, from_entry; };
+    std::unordered_map<uint32_t, RowTarget> rows;
     for (uint32_t i = 0; i < n; i++) {
-        if (moves[i].src == moves[i].dst) continue;
-        moved[moves[i].src] = moved[moves[i].dst] = 1;
-        out.push_back(MoveTarget{moves[i].src, moves[i].dst, kMoveNone});
+        const uint32_t row = moves[i].dst / row_streams;
+        auto it = rows.find(row);
+        if (it == rows.end()) {
+            const uint32_t resident = row_lowest_resident(row, row_streams, n_dst, dst_active, listed);
+            rows[row] = resident != kMoveNone ? RowTarget{resident, 0u} : RowTarget{i, 1u};
+        } else if (it->second.from_entry && moves[i].dst < moves[it->second.target].dst) it->second.target = i;
     }
-    // per touched row: the lowest resident, else the source of the lowest destination
-    std::unordered_map<uint32_t, uint32_t> row_target, row_lowest;      // row -> slot to read / lowest destination seen
-    for (const MoveTarget &t : out) {
-        const uint32_t row = t.dst / row_streams;
-        if (row_target.count(row)) {
-            auto lo = row_lowest.find(row);
-            if (lo != row_lowest.end() && t.dst < lo->second) { lo->second = t.dst; row_target[row] = t.src; }
-            continue;
-        }
-        const uint64_t r0 = (uint64_t)row * row_streams, r1 = std::min<uint64_t>(r0 + row_streams, n_streams);
-        uint32_t resident = kMoveNone;
-        for (uint64_t s = r0; s < r1 && resident == kMoveNone; s++)
-            if (!moved[s] && (!active || active[s])) resident = (uint32_t)s;
-        if (resident != kMoveNone) row_target[row] = resident;
-        else { row_target[row] = t.src; row_lowest[row] = t.dst; }
+    std::vector<ListTarget> out(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const RowTarget &t = rows[moves[i].dst / row_streams];
+        out[i] = ListTarget{moves[i].src, moves[i].dst, t.target, t.from_entry};
     }
-    for (MoveTarget &t : out) t.target = row_target[t.dst / row_streams];
     return out;
 }
 

@@ -85,8 +85,21 @@ constexpr SnapTarget snap_row_target_active(uint32_t row, uint32_t row_streams, 
     for (uint64_t s = lo; s < hi; s++) if (!snap_stream_active(active, s)) return SnapTarget{(uint32_t)s, false};
     return SnapTarget{(uint32_t)lo, false};      // (the call resumes nobody in this row: never read)
 }
-// how far a stream at position `from` is rotated to stand at `to` (both masked; len a power of two)
+// how far a stream at position `from` is rotated to stand at `to` (both masked; len a power of two); snap_shift_pair: both positions at once
 constexpr uint32_t snap_shift(uint32_t from, uint32_t to, uint32_t len) { return (to - from) & (len - 1u); }
+// A stream's masked (delay write index, ring position) pair, read at `p`, the stream's first state word, with the slots `stride` words
+// apart: a column of the [W][slot][R] state array (snap_positions: stream s of the context, stride StateMap::row) or the state section of
+// a record (stride 1).
+struct SnapPos { uint32_t widx, ring_pos; };
+constexpr SnapPos snap_positions_at(const StateMap &sm, const uint32_t *p, size_t stride) {
+    return SnapPos{p[(size_t)sm.widx * stride] & ((uint32_t)sm.max_delay - 1u), p[(size_t)sm.ring_pos * stride] & ((uint32_t)kRingLen - 1u)};
+}
+constexpr SnapPos snap_positions(const StateMap &sm, const uint32_t *state, uint64_t s) {
+    return snap_positions_at(sm, state + (size_t)(s / (uint32_t)sm.row) * sm.n_slots * sm.row + s % (uint32_t)sm.row, (size_t)sm.row);
+}
+constexpr SnapPos snap_shift_pair(const StateMap &sm, SnapPos from, SnapPos to) {
+    return SnapPos{snap_shift(from.widx, to.widx, (uint32_t)sm.max_delay), snap_shift(from.ring_pos, to.ring_pos, (uint32_t)kRingLen)};
+}
 // the record position whose word lands at position p of a line or ring of `len` words rotated by d: line[(q + d) mod len] = record[q]
 constexpr uint32_t snap_rot_source(uint32_t p, uint32_t d, uint32_t len) { return (p - d) & (len - 1u); }
 

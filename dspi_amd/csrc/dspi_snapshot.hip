@@ -43,26 +43,23 @@
 // are unchanged.  A tile without a listed column returns at once; the record side skips unlisted columns (their LDS words are never
 // filled on the gather and never read on the scatter); the scatter's array side stores 16 bytes where all four columns are listed and
 // single words elsewhere, so a touched row's unlisted columns are never written.  The realigning scatter looks its shifts up by destination
-// stream; move_targets_kernel wrote them, once per call, before the first scatter.
+// stream; list_shifts_kernel wrote them, once per call, before the first scatter.
 //
 // BETWEEN TWO CONTEXTS (dspi_migrate_streams; the lists: dspi_migrate.h) the gather runs on the source context's arrays and the scatter on the
 // destination's, both unchanged; the shifts need both sides' positions, which no one kernel can read when the contexts sit on two devices:
 // migrate_positions_kernel, on the source, writes every listed stream's pair into an array in list order; that array travels like the
-// records; migrate_shifts_kernel, on the destination, writes shift[destination slot] from it and from the destination's own state array.
+// records; list_shifts_kernel, on the destination, writes shift[destination slot] from it and from the destination's own state array.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
 #include "dspi_kernels.h"
-#include "dspi_migrate.h"
 #include "dspi_move.h"
 #include "dspi_snapshot.h"
 
 namespace dspi {
 
 static_assert(kPdmWords == kPdmStateWords, "the snapshot's PDM section is the modulator's state");
-static_assert(sizeof(MoveRowItem) == 16 && sizeof(MoveTarget) == 12, "the move list's work items go up as 32-bit words");
-static_assert(sizeof(MigrateTarget) == 12, "the migration's targets go up as 32-bit words");
+static_assert(sizeof(MoveRowItem) == 16 && sizeof(ListTarget) == 16, "the lists' work items go up as 32-bit words");
 
 namespace {
 
@@ -229,17 +226,15 @@ struct SnapTargetArgs {
     uint2 *shift;                      // per stream of [first, first + count)
 };
 
+__device__ __forceinline__ uint2 as_uint2(SnapPos p) { return make_uint2(p.widx, p.ring_pos); }
+
 // How far the record of stream s is rotated to stand at target t's two positions: the target's (a resident neighbour's, from the state
 // array as the stream's earlier work left it, or a stream of the records', from its record) minus the record's own.
 template <uint32_t ROW>
-__device__ __forceinline__ uint2 snap_shift_onto(const SnapTargetArgs &a, const SnapTarget t, uint32_t row, uint64_t s) {
+__device__ __forceinline__ uint2 snap_shift_onto(const SnapTargetArgs &a, const SnapTarget t, uint64_t s) {
     constexpr StateMap sm = make_state_map(ROW == 128 ? 1 : 0);
-    constexpr uint32_t kLine = (uint32_t)sm.max_delay, kRing = (uint32_t)kRingLen;
-    const uint32_t *tp = t.resident ? a.state + (size_t)row * sm.n_slots * ROW + (t.stream - row * ROW) : a.rec + (size_t)(t.stream - a.first) * a.record_words + a.state_off;
-    const size_t ts = t.resident ? ROW : 1;
-    const uint32_t w_t = tp[(size_t)sm.widx * ts] & (kLine - 1u), r_t = tp[(size_t)sm.ring_pos * ts] & (kRing - 1u);
-    const uint32_t *r = a.rec + (size_t)(s - a.first) * a.record_words + a.state_off;
-    return make_uint2(snap_shift(r[sm.widx] & (kLine - 1u), w_t, kLine), snap_shift(r[sm.ring_pos] & (kRing - 1u), r_t, kRing));
+    auto recorded = [&](uint64_t k) { return snap_positions_at(sm, a.rec + (size_t)(k - a.first) * a.record_words + a.state_off, 1); };
+    return as_uint2(snap_shift_pair(sm, recorded(s), t.resident ? snap_positions(sm, a.state, t.stream) : recorded(t.stream)));
 }
 
 // The plain rule (dspi_snapshot.h snap_row_target): every stream of the range moves onto its row's target; nothing is written for threads
@@ -249,7 +244,7 @@ __global__ __launch_bounds__(ROW) void snapshot_targets_kernel(const SnapTargetA
     const uint32_t row = a.row0 + blockIdx.x;
     const uint64_t s = (uint64_t)row * ROW + threadIdx.x;
     if (s < a.first || s >= (uint64_t)a.first + a.count) return;
-    a.shift[s - a.first] = snap_shift_onto<ROW>(a, snap_row_target(row, ROW, a.n_streams, a.first, a.count), row, s);
+    a.shift[s - a.first] = snap_shift_onto<ROW>(a, snap_row_target(row, ROW, a.n_streams, a.first, a.count), s);
 }
 
 // ... for dspi_resume_streams: the activity-aware rule (dspi_snapshot.h snap_row_target_active) on the bitmap as it stood before the call.
@@ -263,17 +258,11 @@ __global__ __launch_bounds__(ROW) void snapshot_targets_active_kernel(const Snap
     uint2 d = make_uint2(0u, 0u);
     // (a target from the records lies in this chunk: chunks hold the range's rows whole)
     if (s >= r_first && s < (uint64_t)r_first + r_count && !snap_stream_active(active, s))
-        d = snap_shift_onto<ROW>(a, snap_row_target_active(row, ROW, a.n_streams, r_first, r_count, active), row, s);
+        d = snap_shift_onto<ROW>(a, snap_row_target_active(row, ROW, a.n_streams, r_first, r_count, active), s);
     a.shift[s - a.first] = d;
 }
 
-// the one flavour ladder: f(the flavour's row width as a compile-time constant), for every kernel of this file
-template <class F>
-void for_row_width(int flavor, F f) {
-    if (flavor) f(std::integral_constant<uint32_t, 128>{});
-    else f(std::integral_constant<uint32_t, 64>{});
-}
-// ... and the snapshot_kernel instance of a flavour, launched
+// the snapshot_kernel instance of a flavour, launched
 template <bool IMPORT, bool REALIGN, bool LIST>
 void snap_launch(int flavor, dim3 grid, const typename SnapArgsOf<REALIGN, LIST>::type &a, hipStream_t stream) {
     for_row_width(flavor, [&](auto row) { hipLaunchKernelGGL((snapshot_kernel<decltype(row)::value, IMPORT, REALIGN, LIST>), grid, dim3(kSnapThreads), 0, stream, a); });
@@ -296,52 +285,31 @@ SnapGrid snap_kargs(SnapKArgs &a, int flavor, bool import, const StateArrays &ar
     return SnapGrid{dim3(tiles, rows, l.row / cols), rows};
 }
 
-// One thread per entry of a move list: how far the stream arriving at `dst` is rotated to stand at its row's target positions
-// (dspi_move.h move_targets: `target` names the slot whose positions those are), all three read from the state array as the context's
-// earlier work left it and before any scatter of the call writes.
-template <uint32_t ROW>
-__global__ __launch_bounds__(kSnapThreads) void move_targets_kernel(const uint32_t *state, const MoveTarget *t, uint32_t n, uint2 *shift) {
-    constexpr StateMap sm = make_state_map(ROW == 128 ? 1 : 0);
-    constexpr uint32_t kLine = (uint32_t)sm.max_delay, kRing = (uint32_t)kRingLen;
-    const uint32_t i = blockIdx.x * kSnapThreads + threadIdx.x;
-    if (i >= n) return;
-    const MoveTarget e = t[i];
-    const uint32_t *from = state + (size_t)(e.src / ROW) * sm.n_slots * ROW + e.src % ROW, *to = state + (size_t)(e.target / ROW) * sm.n_slots * ROW + e.target % ROW;
-    shift[e.dst] = make_uint2(snap_shift(from[(size_t)sm.widx * ROW] & (kLine - 1u), to[(size_t)sm.widx * ROW] & (kLine - 1u), kLine),
-                              snap_shift(from[(size_t)sm.ring_pos * ROW] & (kRing - 1u), to[(size_t)sm.ring_pos * ROW] & (kRing - 1u), kRing));
-}
-
-// One thread per entry of a migration list, on the SOURCE context: the (delay write index, ring position) of the stream in slot slots[i], as
-// the source's earlier work left them, masked, into pos[i].
+// One thread per entry of a migration list, on the SOURCE context: the pair of the stream in slot slots[i], as the source's earlier work
+// left it, into pos[i].
 template <uint32_t ROW>
 __global__ __launch_bounds__(kSnapThreads) void migrate_positions_kernel(const uint32_t *state, const uint32_t *slots, uint32_t n, uint2 *pos) {
     constexpr StateMap sm = make_state_map(ROW == 128 ? 1 : 0);
-    constexpr uint32_t kLine = (uint32_t)sm.max_delay, kRing = (uint32_t)kRingLen;
     const uint32_t i = blockIdx.x * kSnapThreads + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t s = slots[i];
-    const uint32_t *from = state + (size_t)(s / ROW) * sm.n_slots * ROW + s % ROW;
-    pos[i] = make_uint2(from[(size_t)sm.widx * ROW] & (kLine - 1u), from[(size_t)sm.ring_pos * ROW] & (kRing - 1u));
+    if (i < n) pos[i] = as_uint2(snap_positions(sm, state, slots[i]));
 }
 
-// One thread per entry, on the DESTINATION context: how far the stream of entry i (its pair: pos[i]) is rotated to stand at its row's target
-// (dspi_migrate.h migrate_targets) — a resident's pair, read from the destination's state array as its earlier work left it, or another
-// entry's, from pos — before any scatter of the call writes.
+// One thread per entry of a move or migration list (dspi_move.h list_targets), on the context that is written: how far the stream of entry i
+// is rotated to stand at its row's target — a resident's pair, or another entry's.  An entry's own pair is pos[i] (a migration: the
+// source's pairs, in list order) or, pos == nullptr (a move), read in place from slot `src`; a resident's is read from `state`; all as the
+// context's earlier work left them and before any scatter of the call writes.
 template <uint32_t ROW>
-__global__ __launch_bounds__(kSnapThreads) void migrate_shifts_kernel(const uint32_t *state, const MigrateTarget *t, const uint2 *pos, uint32_t n, uint2 *shift) {
+__global__ __launch_bounds__(kSnapThreads) void list_shifts_kernel(const uint32_t *state, const ListTarget *t, const uint2 *pos, uint32_t n, uint2 *shift) {
     constexpr StateMap sm = make_state_map(ROW == 128 ? 1 : 0);
-    constexpr uint32_t kLine = (uint32_t)sm.max_delay, kRing = (uint32_t)kRingLen;
     const uint32_t i = blockIdx.x * kSnapThreads + threadIdx.x;
     if (i >= n) return;
-    const MigrateTarget e = t[i];
-    uint2 to;
-    if (e.from_entry) to = pos[e.target];
-    else {
-        const uint32_t *tp = state + (size_t)(e.target / ROW) * sm.n_slots * ROW + e.target % ROW;
-        to = make_uint2(tp[(size_t)sm.widx * ROW] & (kLine - 1u), tp[(size_t)sm.ring_pos * ROW] & (kRing - 1u));
-    }
-    const uint2 from = pos[i];
-    shift[e.dst] = make_uint2(snap_shift(from.x, to.x, kLine), snap_shift(from.y, to.y, kRing));
+    const ListTarget e = t[i];
+    auto entry = [&](uint32_t k) {
+        if (!pos) return snap_positions(sm, state, t[k].src);
+        const uint2 p = pos[k];
+        return SnapPos{p.x, p.y};
+    };
+    shift[e.dst] = as_uint2(snap_shift_pair(sm, entry(i), e.from_entry ? entry(e.target) : snap_positions(sm, state, e.target)));
 }
 
 dim3 snap_list_kargs(SnapListArgs &a, int flavor, bool import, const StateArrays &arr, uint32_t *records, const uint32_t *items, const uint32_t *colrec, uint32_t n_items) {
@@ -354,14 +322,6 @@ dim3 snap_list_kargs(SnapListArgs &a, int flavor, bool import, const StateArrays
 
 }  // namespace
 
-hipError_t launch_move_targets(int flavor, const uint32_t *state, const uint32_t *targets, uint32_t n, uint32_t *shift, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    const dim3 grid((n + kSnapThreads - 1) / kSnapThreads);
-    const MoveTarget *t = reinterpret_cast<const MoveTarget *>(targets);
-    for_row_width(flavor, [&](auto row) { hipLaunchKernelGGL((move_targets_kernel<decltype(row)::value>), grid, dim3(kSnapThreads), 0, stream, state, t, n, reinterpret_cast<uint2 *>(shift)); });
-    return hipGetLastError();
-}
-
 hipError_t launch_migrate_positions(int flavor, const uint32_t *state, const uint32_t *slots, uint32_t n, uint32_t *pos, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const dim3 grid((n + kSnapThreads - 1) / kSnapThreads);
@@ -369,12 +329,12 @@ hipError_t launch_migrate_positions(int flavor, const uint32_t *state, const uin
     return hipGetLastError();
 }
 
-hipError_t launch_migrate_shifts(int flavor, const uint32_t *state, const uint32_t *targets, const uint32_t *pos, uint32_t n, uint32_t *shift, hipStream_t stream) {
+hipError_t launch_list_shifts(int flavor, const uint32_t *state, const uint32_t *targets, const uint32_t *pos, uint32_t n, uint32_t *shift, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const dim3 grid((n + kSnapThreads - 1) / kSnapThreads);
-    const MigrateTarget *t = reinterpret_cast<const MigrateTarget *>(targets);
+    const ListTarget *t = reinterpret_cast<const ListTarget *>(targets);
     for_row_width(flavor, [&](auto row) {
-        hipLaunchKernelGGL((migrate_shifts_kernel<decltype(row)::value>), grid, dim3(kSnapThreads), 0, stream, state, t, reinterpret_cast<const uint2 *>(pos), n, reinterpret_cast<uint2 *>(shift));
+        hipLaunchKernelGGL((list_shifts_kernel<decltype(row)::value>), grid, dim3(kSnapThreads), 0, stream, state, t, reinterpret_cast<const uint2 *>(pos), n, reinterpret_cast<uint2 *>(shift));
     });
     return hipGetLastError();
 }

@@ -5,6 +5,7 @@
 //   move_driver validate                   N ACTIVE list       -> "ok" or the refusal
 //   move_driver compact ONE_WAY            ACTIVE              -> the compaction list
 //   move_driver targets ROW                N ACTIVE list       -> "src dst target ..." per applied entry
+//   move_driver list_targets ROW           N ACTIVE LISTED list -> "src dst target from_entry ..." per entry, list_targets as it is (LISTED like ACTIVE, "-": null)
 //   move_driver items ROW                  "slot rec ..."      -> per row item "I ROW Q_ANY Q_ALL colrec..." (colrec: -1 = not listed)
 #include <stdio.h>
 #include <stdlib.h>
@@ -54,6 +55,13 @@ int main(int argc, char **argv) {
                 out << (why ? why : "ok");
             } else
                 for (const MoveTarget &t : move_targets(m.data(), (uint32_t)m.size(), n, arg, a.empty() ? nullptr : a.data())) out << t.src << " " << t.dst << " " << t.target << " ";
+        } else if (cmd == "list_targets") {
+            uint32_t n = 0; std::string act, lst;
+            in >> n >> act >> lst;
+            const std::vector<uint8_t> a = activity(act), l = activity(lst);
+            const std::vector<StreamMove> m = list_of(in);
+            for (const ListTarget &t : list_targets(m.data(), (uint32_t)m.size(), n, arg, a.empty() ? nullptr : a.data(), l.empty() ? nullptr : l.data()))
+                out << t.src << " " << t.dst << " " << t.target << " " << t.from_entry << " ";
         } else if (cmd == "compact") {
             std::string act;
             in >> act;
@@ -70,7 +78,7 @@ int main(int argc, char **argv) {
                 for (uint32_t c = 0; c < arg; c++) out << (int64_t)(colrec[i * arg + c] == kMoveNone ? -1 : (int64_t)colrec[i * arg + c]) << " ";
             }
         } else {
-            fprintf(stderr, "usage: move_driver schedule CAP | validate | compact ONE_WAY | targets ROW | items ROW\n");
+            fprintf(stderr, "usage: move_driver schedule CAP | validate | compact ONE_WAY | targets ROW | list_targets ROW | items ROW\n");
             return 2;
         }
         std::cout << out.str() << "\n";

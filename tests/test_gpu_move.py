@@ -89,6 +89,37 @@ def test_permutation(flavor, as_is):
     d.close()
 
 
+# ---- 1b. a row without a resident -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("flavor", (W.F32_FMA, 0), ids=fid)
+def test_row_without_resident(flavor):
+    """Three active streams, from rows 0, 1 and 0, into the partial last row while all of it is paused: the row has no resident, so every
+    arrival takes the positions of the arrival at the row's lowest destination (dspi_move.h, the row-target rule) — the SECOND entry of the
+    list, whose source stands in row 1, one packet younger than row 0."""
+    S = streams_of(flavor)
+    x = new_sched(flavor, S, FS, B, 16, 12)
+    d, R = x.d, x.d.tile_streams()
+    L = (S - 1) // R * R                                     # the last row's first slot
+    x.run(4)
+    x.pause(L, S - L); x.run(1)                              # nobody in the last row is a resident, and it stands a packet behind the others
+    x.pause(R, R); x.run(1); x.resume(R, R, as_is=True)      # row 1 is one packet younger than row 0, one older than the last
+    w0, r0 = d.stream_positions(0, S)
+    moves = [(3, L + 5), (R + 7, L + 1), (20, L + 3)]
+    dsts = [t for _, t in moves]
+    assert w0[3] != w0[R + 7] and w0[L + 1] not in (w0[3], w0[R + 7]), "the three rows stand at three positions"
+    move(x, moves)
+    w1, r1 = d.stream_positions(0, S)
+    for t in dsts: assert w1[t] == w0[R + 7] and r1[t] == r0[R + 7], f"slot {t}: ({w1[t]}, {r1[t]}), the lowest destination's arrival stood at ({w0[R + 7]}, {r0[R + 7]})"
+    others = np.setdiff1d(np.arange(S), dsts + [s for s, _ in moves])
+    assert np.array_equal(w1[others], w0[others]) and np.array_equal(r1[others], r0[others]), "a slot the list does not name was written"
+    want = np.zeros(S, dtype=np.uint8); want[L:] = 1; want[dsts] = 0; want[[3, R + 7, 20]] = 1
+    assert np.array_equal(d.streams_paused(), want)
+    x.run(1); x.run(1)
+    w2, r2 = d.stream_positions(0, S)
+    assert len(set(w2[dsts].tolist())) == 1 and len(set(r2[dsts].tolist())) == 1, "the row's active streams share one position"
+    x.verify()
+    d.close()
+
+
 # ---- 2. one-way -----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.both_layouts
 @pytest.mark.parametrize("flavor", FLAVORS_WITH_KERNEL, ids=fid)

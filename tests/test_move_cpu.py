@@ -233,6 +233,52 @@ def test_targets(driver):
         assert {(v[i], v[i + 1]): v[i + 2] for i in range(0, len(v), 3)} == want, case
 
 
+def expected_list_targets(moves, n, row, active, listed):
+    """the row-target rule (dspi_move.h) restated: per entry (src, dst, target, from_entry)"""
+    out = []
+    for s, d in moves:
+        r = d // row
+        residents = [x for x in range(r * row, min((r + 1) * row, n)) if (active is None or active[x]) and not (listed is not None and listed[x])]
+        if residents:
+            out.append((s, d, residents[0], 0))
+        else:
+            out.append((s, d, min((i for i, m in enumerate(moves) if m[1] // row == r), key=lambda i: moves[i][1]), 1))
+    return out
+
+
+def test_list_targets_random(driver):
+    """list_targets in both call shapes — a move (no identities; its sources and destinations marked in `listed`) and a migration (listed
+    null, sources in another context, every destination paused) — over 2 000 seeded lists, row width 8, up to 40 slots, mostly paused
+    contexts: those are the ones that have rows without a resident.  The share of lists that reach the from_entry branch is asserted."""
+    rng = np.random.default_rng(2024)
+    row, cases, want = 8, [], []
+    for k in range(2000):
+        n = int(rng.integers(2, 41))
+        active = rng.random(n) < (0.15 if k % 4 else 0.6)
+        paused = np.flatnonzero(~active)
+        if k % 2 == 0:      # a move: some sources; destinations among the paused slots and the sources themselves
+            src = rng.permutation(n)[:int(rng.integers(1, n + 1))]
+            pool = rng.permutation(np.union1d(src, paused))
+            moves = [(int(s), int(d)) for s, d in zip(src, pool) if s != d] or [(0, n - 1)]
+            listed = np.zeros(n, dtype=bool)
+            for s, d in moves: listed[s] = listed[d] = True
+        else:               # a migration: distinct paused destinations, sources from a context of its own
+            if len(paused) == 0: paused = np.array([int(rng.integers(0, n))]); active[paused] = False
+            dst = rng.permutation(paused)[:int(rng.integers(1, len(paused) + 1))]
+            src = rng.permutation(40)[:len(dst)]
+            moves, listed = [(int(s), int(d)) for s, d in zip(src, dst)], None
+        cases.append(f"{n} {bits(active)} {'-' if listed is None else bits(listed)} {flat(moves)}")
+        want.append(expected_list_targets(moves, n, row, active, listed))
+    got = run(driver, "list_targets", row, cases)
+    reached = [0, 0]
+    for k, (case, w, g) in enumerate(zip(cases, want, got)):
+        v = list(map(int, g.split()))
+        assert [tuple(v[i:i + 4]) for i in range(0, len(v), 4)] == w, case
+        reached[k % 2] += any(t[3] for t in w)
+    print("lists that reach from_entry, of 1 000 each: moves", reached[0], "migrations", reached[1])
+    assert reached[0] >= 250 and reached[1] >= 250, reached      # a quarter of either shape's 1 000 lists
+
+
 def test_row_items(driver):
     got = run(driver, "items", 8, ["9 0 3 1 12 2 13 3 14 4 15 5 2 6"])[0].split("I")[1:]
     rows = [list(map(int, g.split())) for g in got]
