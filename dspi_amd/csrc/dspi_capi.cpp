@@ -32,6 +32,7 @@
 #include "dspi_group.h"
 #include "dspi_migrate.h"
 #include "dspi_move.h"
+#include "dspi_pdmlife.h"
 #include "dspi_plan.h"
 #include "dspi_resize.h"
 #include "dspi_snapshot.h"
@@ -107,6 +108,11 @@ struct dspi_ctx {
     uint32_t *d_pdm = nullptr;
     int32_t *d_pdm_in = nullptr; size_t d_pdm_in_cap = 0;
     uint32_t *d_pdm_out = nullptr; size_t d_pdm_out_cap = 0;
+    // dspi_process_pdm (dspi_pdmlife.h): who runs their modulator, the device's copy of the call's work list (it goes up through h_move, behind
+    // ev_move, when the list was rebuilt), and per parameter object the core1_mode it was last uploaded with (a change makes the list dirty)
+    PdmLife pdm_life;
+    uint32_t *d_pdm_list = nullptr; size_t d_pdm_list_cap = 0;
+    std::vector<int8_t> image_core1;
     int32_t *d_spdif_in = nullptr; size_t d_spdif_in_cap = 0;
     uint32_t *d_spdif_out = nullptr; size_t d_spdif_out_cap = 0;
     uint32_t *d_snap = nullptr; size_t d_snap_cap = 0;          // stream snapshots on host buffers: the records of one chunk of rows
@@ -248,7 +254,7 @@ void merge_images(dspi_ctx *c) {
     c->image_refs.assign(keep.size(), 0);
     for (auto &si : c->stream_image) { si = remap[(size_t)si]; c->image_refs[(size_t)si]++; }
     // per-image caches describe the old numbering: drop them, every image goes up again
-    c->image_flags.clear(); c->plan_in.sig.clear(); c->plan_in.bands.clear(); c->image_touched.clear();
+    c->image_flags.clear(); c->plan_in.sig.clear(); c->plan_in.bands.clear(); c->image_touched.clear(); c->image_core1.clear();
     c->assignment_dirty = true; c->launch_dirty = true;
 }
 
@@ -297,12 +303,10 @@ const std::vector<std::pair<uint32_t, uint32_t>> &paused_runs(dspi_ctx *c) {
     }
     return c->paused_runs;
 }
-// the pieces of one buffer of a call that hold paused streams: f(offset, bytes).  Tiled words: the whole tiles that hold one.
+// the pieces of one buffer of a call that hold the streams of `runs` ([first, end), ascending): f(offset, bytes).  Tiled words: the whole
+// tiles that hold one.
 template <class F>
-void for_paused_regions(dspi_ctx *c, const CallBuffer &b, F f) {
-    if (!b.bytes) return;
-    const auto &runs = paused_runs(c);
-    if (runs.empty()) { f((size_t)0, b.bytes); return; }
+void for_run_regions(dspi_ctx *c, const CallBuffer &b, const std::vector<std::pair<uint32_t, uint32_t>> &runs, F f) {
     const size_t row = (size_t)c->sm.row;
     size_t done = 0;      // (tiles: runs in one tile are cleared once)
     for (const auto &r : runs) {
@@ -312,6 +316,21 @@ void for_paused_regions(dspi_ctx *c, const CallBuffer &b, F f) {
         if (hi > lo) f(lo * b.per, (hi - lo) * b.per);
         done = std::max(done, hi);
     }
+}
+// ... that hold paused streams
+template <class F>
+void for_paused_regions(dspi_ctx *c, const CallBuffer &b, F f) {
+    if (!b.bytes) return;
+    const auto &runs = paused_runs(c);
+    if (runs.empty()) { f((size_t)0, b.bytes); return; }
+    for_run_regions(c, b, runs, f);
+}
+// ... of the PDM words that hold streams a dspi_process_pdm call does not list (nothing, while every stream is listed)
+template <class F>
+void for_unlisted_regions(dspi_ctx *c, const CallBuffer &b, const PdmWork &w, F f) {
+    if (!b.bytes || w.unlisted.empty()) return;
+    if (w.unlisted.size() > kMaxPausedRuns) { f((size_t)0, b.bytes); return; }
+    for_run_regions(c, b, w.unlisted, f);
 }
 // what the kernels get: null while nothing is paused (they then do what they always did)
 const uint32_t *activity(const dspi_ctx *c) { return c->n_paused ? c->d_active : nullptr; }
@@ -324,7 +343,7 @@ void set_active(dspi_ctx *c, uint32_t s, bool on) {
     c->active[s] = on ? 1 : 0;
     if (on) c->n_paused--; else c->n_paused++;
 }
-void activity_changed(dspi_ctx *c) { c->launch_dirty = true; c->active_dirty = true; c->paused_runs_dirty = true; }
+void activity_changed(dspi_ctx *c) { c->launch_dirty = true; c->active_dirty = true; c->paused_runs_dirty = true; c->pdm_life.mark_dirty(); }
 // the four per-stream arrays, for the launchers that address all of them (d_pdm: null until pdm_state has run)
 StateArrays state_arrays(const dspi_ctx *c) { return StateArrays{c->d_state, c->d_dlines, c->d_ring, c->d_pdm}; }
 
@@ -357,6 +376,7 @@ int rebuild_assignment(dspi_ctx *c) {
     }
     c->assignment_dirty = false;
     c->launch_dirty = true;
+    c->pdm_life.mark_dirty();      // (which object a stream's "sub on" is read from)
     return 0;
 }
 
@@ -419,6 +439,7 @@ int commit_params(dspi_ctx *c) {
     }
     // dirty images go up in contiguous runs (per-stream presets dirty thousands at once)
     if (c->image_flags.size() < ni) c->image_flags.resize(ni, 0u);
+    if (c->image_core1.size() < ni) c->image_core1.resize(ni, -1);
     if (c->flavor && c->plan_in.sig.size() < ni) {
         ImageSig none; memset(&none, 0xff, sizeof none);
         c->plan_in.sig.resize(ni, none); c->plan_in.bands.resize(ni, BandHash{0, 0}); c->image_touched.resize(ni, 1); c->launch_dirty = true;
@@ -453,6 +474,7 @@ int commit_params(dspi_ctx *c) {
             const size_t ii = i + k;
             if ((c->image_flags[ii] ^ run[k].flags) & IF_LEVELLER_ON) c->launch_dirty = true;
             c->image_flags[ii] = run[k].flags;
+            if (c->image_core1[ii] != (int8_t)c->images[ii]->core1_mode) { c->image_core1[ii] = (int8_t)c->images[ii]->core1_mode; c->pdm_life.mark_dirty(); }
             for (const float al : {run[k].lv_alpha_attack, run[k].lv_alpha_release}) {
                 uint32_t bits; memcpy(&bits, &al, 4);
                 if (std::find(c->lv_alphas.begin(), c->lv_alphas.end(), bits) == c->lv_alphas.end()) c->lv_alphas.push_back(bits);
@@ -571,6 +593,7 @@ int dspi_create(dspi_ctx **out, int flavor, uint32_t n_streams, int hip_device) 
     c->images.push_back(std::make_unique<Params>(flavor, fma, !populated));
     c->image_refs.push_back(n_streams);
     c->stream_image.assign(n_streams, 0);
+    c->pdm_life.create(n_streams);
     *out = c;
     if (hip_device == DSPI_DEVICE_NONE) return DSPI_OK;
 
@@ -598,7 +621,7 @@ void dspi_destroy(dspi_ctx *c) {
     if (c->device != DSPI_DEVICE_NONE) {
         (void)hipSetDevice(c->device);
         if (c->hs) (void)hipStreamSynchronize(c->hs);
-        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_spdif_ps, (void *)c->d_spdif_vpos, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, (void *)c->d_move, (void *)c->d_mig_pos, c->d_in,
+        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_pdm_list, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_spdif_ps, (void *)c->d_spdif_vpos, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, (void *)c->d_move, (void *)c->d_mig_pos, c->d_in,
                         (void *)c->d_pairs, (void *)c->d_sub, (void *)c->d_peaks, (void *)c->d_clip, (void *)c->d_spdif_words})
             if (p) (void)hipFree(p);
         if (c->h_direct) (void)hipHostFree(c->h_direct);
@@ -1166,6 +1189,7 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
     // destination that is no source loses its occupant (one reference less); a source that is no destination keeps its own and becomes
     // a paused, frozen copy.  (Such entries exist only where something is paused: `active` is allocated then.)
     if (c->spdif_ps.on) c->spdif_ps.move(mv.data(), nm, host_activity(c));      // (the S/PDIF position is the device's own counter: it travels too)
+    c->pdm_life.move(mv.data(), nm);      // (... and whether its modulator is running)
     const bool have_active = !c->active.empty();
     std::vector<int32_t> img(nm);
     std::vector<uint8_t> act(nm, 1), is_dst(c->n_streams, 0);
@@ -1311,6 +1335,7 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
         for (uint32_t i = 0; i < n; i++) dst->spdif_ps.arrive(list[i].dst, src->spdif_ps.on ? src->spdif_ps.get(list[i].src, sa) : src->spdif_pos, act[i] != 0);
     if (src->spdif_ps.on)
         for (uint32_t i = 0; i < n; i++) src->spdif_ps.pause(list[i].src, 1, sa);
+    for (uint32_t i = 0; i < n; i++) dst->pdm_life.arrive(list[i].dst, src->pdm_life.running[list[i].src]);      // (a running modulator arrives running)
     if (src->active.empty()) src->active.assign(src->n_streams, 1);
     for (uint32_t i = 0; i < n; i++) { set_active(dst, list[i].dst, act[i] != 0); set_active(src, list[i].src, false); }
     activity_changed(src); activity_changed(dst);
@@ -1389,6 +1414,7 @@ int dspi_boot_streams(dspi_ctx *c, const uint32_t *streams, uint32_t n, const vo
     for (uint32_t i = 0; i < n; i++) assign_image(c, streams[i], slot);
     c->launch_dirty = true; c->merge_hint = true;
     if (c->spdif_ps.on) c->spdif_ps.boot(streams, n, host_activity(c));      // a device that has just been powered on sends frame 0 of a block first
+    c->pdm_life.boot(streams, n);      // ... and has never run its modulator
     if (selection) *selection = sel;
     return (int)n;
 }
@@ -1455,6 +1481,7 @@ static void resize_books(dspi_ctx *c, uint32_t n_new, int32_t slot, bool arrive_
         c->spdif_ps.dirty = true;
         for (uint32_t s = n_old; s < n_new; s++) c->spdif_ps.set(s, 0, host_activity(c));
     }
+    c->pdm_life.resize(n_new);      // (new slots: never ran)
     c->assignment_dirty = true; c->merge_hint = true;      // (an object may have lost its last stream, or the new one equal one already here: the fold-back pass)
     activity_changed(c);
 }
@@ -1709,11 +1736,46 @@ static int gather_clip(dspi_ctx *c, uint16_t *dst) {
     return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("clip gather launch: ") + hipGetErrorString(e));
 }
 
+// ---- dspi_process_pdm: the PDM words of a call (null in the three paths below: dspi_process) ----
+struct PdmCall {
+    uint32_t *words;          // the caller's
+    const PdmWork *work;      // the call's work list (dspi_pdmlife.h); its device copy is c->d_pdm_list
+};
+// the work list as the rule gives it for this call, and its device copy: built and uploaded only when something has changed it.  The
+// words go up through the move calls' pinned area, behind its event, and on the context's stream: behind every launch that reads the old copy.
+static int pdm_prepare(dspi_ctx *c, PdmCall &pc) {
+    int rc = pdm_state(c);
+    if (rc) return rc;
+    const PdmWork &w = c->pdm_life.plan(host_activity(c), [c](uint32_t s) { return c->images[(size_t)c->stream_image[s]]->core1_mode == 1; });
+    pc.work = &w;
+    if (c->pdm_life.uploaded || w.list.empty()) return 0;
+    const size_t bytes = w.list.size() * 4;
+    if (!c->ev_move) HIPCK(c, hipEventCreateWithFlags(&c->ev_move, hipEventDisableTiming));
+    HIPCK(c, hipEventSynchronize(c->ev_move));
+    if ((rc = pinned_area(c, c->h_move, c->h_move_cap, bytes, bytes * 2, "hipHostMalloc failed (PDM work list)")) || (rc = ensure(c, c->d_pdm_list, c->d_pdm_list_cap, bytes))) return rc;
+    memcpy(c->h_move, w.list.data(), bytes);
+    HIPCK(c, hipMemcpyAsync(c->d_pdm_list, c->h_move, bytes, hipMemcpyHostToDevice, c->hs));
+    HIPCK(c, hipEventRecord(c->ev_move, c->hs));
+    c->pdm_life.uploaded = true;
+    return 0;
+}
+// the ONE modulator launch over the listed streams of [s0, s1), behind the chain launches of those rows; `sub` and `words` are addressed
+// by absolute stream.  Nobody listed there: no launch.
+static int launch_pdm_streams(dspi_ctx *c, const PdmCall &pc, const CallLayout &L, bool tiled, const int32_t *sub, uint32_t *words, size_t s0, size_t s1) {
+    const std::pair<size_t, size_t> r = pc.work->range((uint32_t)s0, (uint32_t)s1);
+    hipError_t e = launch_pdm_list(tiled, c->d_pdm, sub, words, c->d_pdm_list + r.first, (uint32_t)(r.second - r.first), c->n_streams, (uint32_t)L.frames, (uint32_t)c->sm.row, c->hs);
+    return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("pdm modulator launch: ") + hipGetErrorString(e));
+}
+// where the chain leaves the Q28 sub words of a dspi_process_pdm call whose caller passed no `sub`: the library's scratch (device memory)
+static int pdm_sub_scratch(dspi_ctx *c, const CallLayout &L) { return ensure(c, c->d_sub, c->d_sub_cap, L.sub_scratch.bytes); }
+
 // ---- device buffers: the caller's own, asynchronous on the context's stream ----
-static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out) {
+static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, const PdmCall *pc) {
     a.pcm = pcm_in; a.pairs = out->pairs; a.sub = out->sub; a.peaks = out->peaks;
     int rc = 0;
+    if (pc && !out->sub) { if ((rc = pdm_sub_scratch(c, L))) return rc; a.sub = c->d_sub; }
     if ((L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) || (rc = launch_rows(c, a, L, 0, c->n_wg))) return rc;
+    if (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, pc->words, 0, c->n_streams))) return rc;
     return clip_out ? gather_clip(c, clip_out) : DSPI_OK;
 }
 
@@ -1746,7 +1808,7 @@ static void completion_word(dspi_ctx *c) {
 }
 
 static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags,
-                          std::chrono::steady_clock::time_point call_t0) {
+                          std::chrono::steady_clock::time_point call_t0, const PdmCall *pc) {
     int rc = direct_area(c, L.direct_bytes);
     if (rc) return rc;
     char *const h = c->h_direct, *const d = c->d_direct;
@@ -1755,6 +1817,8 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     if (out->pairs) a.pairs = reinterpret_cast<int32_t *>(d + L.pairs.off);
     if (out->sub) a.sub = reinterpret_cast<int32_t *>(d + L.sub.off);
     if (out->peaks) a.peaks = reinterpret_cast<uint16_t *>(d + L.peaks.off);
+    if (pc && !out->sub) { if ((rc = pdm_sub_scratch(c, L))) return rc; a.sub = c->d_sub; }
+    if (pc) for_unlisted_regions(c, L.pdm_words, *pc->work, [&](size_t at, size_t n) { memset(h + L.pdm_words.off + at, 0, n); });      // (unlisted streams' words stay unwritten: zeros, there only)
     if (flags & DSPI_OUT_ENABLED_ONLY) {      // (silent parts stay unwritten by the kernels: the caller finds zeros, the firmware's own fill)
         if (out->pairs) memset(h + L.pairs.off, 0, L.pairs.bytes);
         if (out->sub) memset(h + L.sub.off, 0, L.sub.bytes);
@@ -1765,6 +1829,7 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
         if (out->peaks) for_paused_regions(c, L.peaks, [&](size_t at, size_t n) { memset(h + L.peaks.off + at, 0, n); });
     }
     if ((L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) || (rc = launch_rows(c, a, L, 0, c->n_wg)) ||
+        (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, reinterpret_cast<uint32_t *>(d + L.pdm_words.off), 0, c->n_streams))) ||
         (clip_out && (rc = gather_clip(c, reinterpret_cast<uint16_t *>(d + L.clip.off))))) return rc;
     // the launches take tens of microseconds: polling answers within a microsecond of their end, a blocking wait adds a wake-up — but only
     // for as long as such launches can take: past the budget the call falls back to the blocking wait (a hung queue, or a host running
@@ -1814,6 +1879,7 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     if (out->sub) memcpy(out->sub, h + L.sub.off, L.sub.bytes);
     if (out->peaks) memcpy(out->peaks, h + L.peaks.off, L.peaks.bytes);
     if (clip_out) memcpy(clip_out, h + L.clip.off, L.clip.bytes);
+    if (pc) memcpy(pc->words, h + L.pdm_words.off, L.pdm_words.bytes);
     return DSPI_OK;
 }
 
@@ -1822,7 +1888,7 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
 // cut into chunks and chunk i's D2H runs while chunk i+1 computes and chunk i+2 uploads (three streams, events).  The caller's
 // buffers are pinned for the duration of the call (hipHostRegister: ~8 ms per GiB) so that the copies are asynchronous DMA; when
 // that is refused (already registered, read-only mapping ...) the copies still work, just synchronously. ----
-static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags) {
+static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags, const PdmCall *pc) {
     int rc;
     if ((rc = ensure(c, c->d_in, c->d_in_cap, L.pcm.bytes))) return rc;
     a.pcm = c->d_in;
@@ -1830,6 +1896,9 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     if (out->sub) { if ((rc = ensure(c, c->d_sub, c->d_sub_cap, L.sub.bytes))) return rc; a.sub = c->d_sub; }
     if (out->peaks) { if ((rc = ensure(c, c->d_peaks, c->d_peaks_cap, L.peaks.bytes))) return rc; a.peaks = c->d_peaks; }
     if (clip_out && (rc = ensure(c, c->d_clip, c->d_clip_cap, L.clip.bytes))) return rc;
+    // dspi_process_pdm: the words' staging buffer is dspi_pdm_modulate's; without `sub` from the caller the chain writes one chunk's Q28 words
+    // into the scratch (set per chunk, below: the kernels index by absolute stream)
+    if (pc && ((rc = ensure(c, c->d_pdm_out, c->d_pdm_out_cap, L.pdm_words.bytes)) || (!out->sub && (rc = pdm_sub_scratch(c, L))))) return rc;
     // DSPI_OUT_ENABLED_ONLY leaves the silent parts of pairs / sub unwritten: the staging buffers are copied back whole, so what the
     // caller finds there is zeros (the firmware's own fill), not stale staging memory
     if (flags & DSPI_OUT_ENABLED_ONLY) {
@@ -1845,12 +1914,18 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
         if (a.peaks) for_paused_regions(c, L.peaks, clear(a.peaks));
         HIPCK(c, me);
     }
+    if (pc) {      // ... and for the words of the streams the call does not list
+        hipError_t me = hipSuccess;
+        for_unlisted_regions(c, L.pdm_words, *pc->work, [&](size_t at, size_t n) { if (me == hipSuccess) me = hipMemsetAsync(reinterpret_cast<char *>(c->d_pdm_out) + at, 0, n, c->hs); });
+        HIPCK(c, me);
+    }
     if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) return rc;
     const uint32_t n_chunks = L.n_chunks, row = (uint32_t)c->sm.row;
     // the caller's buffers and the staging buffers: a row range is one contiguous piece of each (tiled words: whole tiles; else streams)
     struct Buf { void *host; void *dev; const CallBuffer &b; const char *what; bool pinned; };
-    Buf bufs[4] = {{const_cast<void *>(pcm_in), c->d_in, L.pcm, "H2D", false}, {out->pairs, a.pairs, L.pairs, "D2H pairs", false},
-                   {out->sub, a.sub, L.sub, "D2H sub", false}, {out->peaks, a.peaks, L.peaks, "D2H peaks", false}};
+    Buf bufs[5] = {{const_cast<void *>(pcm_in), c->d_in, L.pcm, "H2D", false}, {out->pairs, a.pairs, L.pairs, "D2H pairs", false},
+                   {out->sub, a.sub, L.sub, "D2H sub", false}, {out->peaks, a.peaks, L.peaks, "D2H peaks", false},
+                   {pc ? pc->words : nullptr, c->d_pdm_out, L.pdm_words, "D2H pdm words", false}};
     if (n_chunks > 1)
         for (Buf &bf : bufs)
             if (bf.host && bf.b.bytes >= (1u << 20)) {
@@ -1889,11 +1964,12 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
         if (n_chunks > 1) {
             if ((he = hipEventRecord(c->pipe_events[2 * ch], sin)) != hipSuccess || (he = hipStreamWaitEvent(c->hs, c->pipe_events[2 * ch], 0)) != hipSuccess) return fail_hip(he, "event");
         }
-        if ((rc = launch_rows(c, a, L, r0, r1))) { unpin(); return rc; }
+        if (pc && !out->sub) a.sub = c->d_sub - s0 * L.frames;      // (the chunk's first stream or tile stands at the scratch's start, in both layouts)
+        if ((rc = launch_rows(c, a, L, r0, r1)) || (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, c->d_pdm_out, s0, s1)))) { unpin(); return rc; }
         if (n_chunks > 1) {
             if ((he = hipEventRecord(c->pipe_events[2 * ch + 1], c->hs)) != hipSuccess || (he = hipStreamWaitEvent(sout, c->pipe_events[2 * ch + 1], 0)) != hipSuccess) return fail_hip(he, "event");
         }
-        for (int k = 1; k < 4; k++)
+        for (int k = 1; k < 5; k++)
             if (bufs[k].host && (he = copy(bufs[k], hipMemcpyDeviceToHost, sout)) != hipSuccess) return fail_hip(he, bufs[k].what);
     }
     if (clip_out) {
@@ -1909,7 +1985,8 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     return DSPI_OK;
 }
 
-int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t flags) {
+// the one body of dspi_process (pdm_words == nullptr) and dspi_process_pdm
+static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
     if (!c || !pcm_in || !out) return DSPI_E_INVAL;
     // undefined flag bits are refused, not ignored: a later ABI may give them a meaning that reads further members of dspi_out
     constexpr uint32_t kKnownFlags = DSPI_MEM_DEVICE | DSPI_OUT_TILED | DSPI_OUT_ENABLED_ONLY | DSPI_OUT_I2S_SLOTS | DSPI_OUT_SPDIF | DSPI_OUT_CLIP_FLAGS;
@@ -1928,13 +2005,16 @@ int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_bloc
     in.n_streams = c->n_streams; in.n_wg = c->n_wg; in.row = (uint32_t)c->sm.row; in.n_ch = (uint32_t)c->sm.n_ch; in.n_out = (uint32_t)c->sm.n_out;
     in.n_pairs = (uint32_t)c->sm.n_pairs; in.n_blocks = n_blocks; in.block_len = block_len; in.bit_depth = (uint32_t)bit_depth; in.flags = flags;
     in.pairs = out->pairs; in.sub = out->sub; in.peaks = out->peaks; in.clip = clip_out; in.no_direct = c->no_direct;
-    in.all_latency = c->flavor != 0; in.spdif_per_stream = c->spdif_ps.on;
+    in.all_latency = c->flavor != 0; in.spdif_per_stream = c->spdif_ps.on; in.pdm_words = pdm_words != nullptr;
     for (const PathInfo &pi : kPaths)
         if (pi.group != PathGroup::Latency && !c->plan.items[(int)pi.path].empty()) in.all_latency = false;
     const CallLayout L = plan_call(in);
     const bool tiled = flags & DSPI_OUT_TILED, spdif = flags & DSPI_OUT_SPDIF;
     if (spdif && (tiled || (flags & DSPI_OUT_I2S_SLOTS))) return fail(c, DSPI_E_INVAL, "DSPI_OUT_SPDIF goes with neither DSPI_OUT_TILED nor DSPI_OUT_I2S_SLOTS");
     if (L.spdif_two_pass && c->spdif_ps.on && (rc = upload_spdif_pos(c))) return rc;
+    PdmCall pdm{pdm_words, nullptr};
+    const PdmCall *const pc = pdm_words ? &pdm : nullptr;
+    if (pc && (rc = pdm_prepare(c, pdm))) return rc;
 
     KArgs a{};
     a.img = c->d_images; a.stream_image = c->d_stream_image; a.vals = c->d_vals;
@@ -1954,15 +2034,31 @@ int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_bloc
     }
 
     switch (L.mem) {
-    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out); break;
-    case CallMem::Direct: rc = process_direct(c, L, a, pcm_in, out, clip_out, flags, call_t0); break;
-    case CallMem::Staged: rc = process_staged(c, L, a, pcm_in, out, clip_out, flags); break;
+    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out, pc); break;
+    case CallMem::Direct: rc = process_direct(c, L, a, pcm_in, out, clip_out, flags, call_t0, pc); break;
+    case CallMem::Staged: rc = process_staged(c, L, a, pcm_in, out, clip_out, flags, pc); break;
     }
+    if (rc == DSPI_OK && pc) c->pdm_life.commit();      // a failed call leaves the running bytes alone
     if (rc == DSPI_OK && spdif) {      // a failed call leaves the block positions alone
         c->spdif_pos = (uint32_t)((c->spdif_pos + L.frames) % 192u);
         if (c->spdif_ps.on) c->spdif_ps.advance(L.frames);      // every stream that was active in the call; the paused ones hold their own
     }
     return rc;
+}
+
+int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t flags) {
+    return process_call(c, pcm_in, bit_depth, n_blocks, block_len, out, nullptr, flags);
+}
+
+int dspi_process_pdm(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
+    if (!c || !pdm_words) return DSPI_E_INVAL;
+    return process_call(c, pcm_in, bit_depth, n_blocks, block_len, out, pdm_words, flags);
+}
+
+int dspi_pdm_running(dspi_ctx *c, uint32_t first, uint32_t count, const uint8_t *set, uint8_t *get) {
+    if (!c) return DSPI_E_INVAL;
+    if (const char *why = c->pdm_life.set_get(first, count, set, get)) return fail(c, DSPI_E_INVAL, std::string("dspi_pdm_running: ") + why);
+    return (int)count;
 }
 
 }  // extern "C"

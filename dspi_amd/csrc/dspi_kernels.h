@@ -61,6 +61,10 @@ constexpr uint32_t pdm_power_on_word(int i) { return i == kPdmRngWord ? 12345678
 // active: the context's activity bitmap (one bit per stream) or null = every stream; a paused stream's state and words are not touched
 hipError_t launch_pdm(bool tiled, uint32_t *state, const int32_t *sub, uint32_t *words, uint32_t n_streams, uint32_t n_frames, uint32_t row,
                       uint32_t n_wg, const uint32_t *active, hipStream_t stream);
+// the same modulator over a work list in device memory (dspi_pdmlife.h: n_list words, ascending streams, bit 31 = start from the re-enable
+// state): lane g serves list[g]; `sub` and `words` are the call's, addressed by absolute stream.  n_list == 0 launches nothing.
+hipError_t launch_pdm_list(bool tiled, uint32_t *state, const int32_t *sub, uint32_t *words, const uint32_t *list, uint32_t n_list, uint32_t n_streams,
+                           uint32_t n_frames, uint32_t row, hipStream_t stream);
 hipError_t launch_pdm_reset(uint32_t *state, uint32_t n_streams, uint32_t row, uint32_t n_wg, int32_t only_stream, int init, hipStream_t stream);
 
 // ---- S/PDIF subframe encoder (dspi_spdif.hip)

@@ -14,6 +14,8 @@
 //
 // Paused streams (dspi_pause_streams): a lane whose stream's bit in the activity bitmap is clear returns before it reads anything — its
 // modulator state stays frozen, its `sub` is not read and its `words` are not written (both layouts).  No bitmap (null): every stream runs.
+//
+// dspi_process_pdm runs the same per-sample body over a LIST of streams (pdm_list_kernel): only the devices whose sub output is on cost lanes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -36,20 +38,27 @@ __device__ __forceinline__ int32_t wmul(int32_t a, int32_t b) { return (int32_t)
 // dispatcher put both workgroups of a CU on the same two SIMDs and left the other two idle (measured: exactly 2x).
 constexpr int kPdmThreads = 256;
 
-template <bool TILED>
-__global__ __launch_bounds__(kPdmThreads) void pdm_kernel(uint32_t *state, const int32_t *sub, uint32_t *words, uint32_t n_streams, uint32_t n_frames,
-                                                           uint32_t row, const uint32_t *active) {
-    const uint32_t wg = blockIdx.x * (kPdmThreads / row) + threadIdx.x / row, col = threadIdx.x % row;
-    const uint32_t stream = wg * row + col;
-    if (stream >= n_streams) return;
-    if (active && !((active[stream >> 5] >> (stream & 31u)) & 1u)) return;
-    uint32_t *gs = state + (size_t)wg * kPdmStateWords * row + col;
-    int32_t err = (int32_t)gs[0 * row], err2 = (int32_t)gs[1 * row];
-    int32_t x1 = (int32_t)gs[2 * row], x2 = (int32_t)gs[3 * row], y1 = (int32_t)gs[4 * row], y2 = (int32_t)gs[5 * row], err_acc = (int32_t)gs[6 * row];
-    uint32_t rng = gs[7 * row], fade = gs[8 * row];
+// A modulator's nine words in registers, and the one statement of the per-sample arithmetic: both kernels below load the words, run
+// pdm_samples over their stream's frames and store the words back.
+struct PdmRegs {
+    int32_t err, err2, x1, x2, y1, y2, err_acc;
+    uint32_t rng, fade;
+};
+__device__ __forceinline__ PdmRegs pdm_load(const uint32_t *gs, uint32_t row) {
+    return PdmRegs{(int32_t)gs[0 * row], (int32_t)gs[1 * row], (int32_t)gs[2 * row], (int32_t)gs[3 * row], (int32_t)gs[4 * row], (int32_t)gs[5 * row],
+                   (int32_t)gs[6 * row], gs[7 * row], gs[8 * row]};
+}
+__device__ __forceinline__ void pdm_store(uint32_t *gs, uint32_t row, const PdmRegs &r) {
+    gs[0 * row] = (uint32_t)r.err; gs[1 * row] = (uint32_t)r.err2;
+    gs[2 * row] = (uint32_t)r.x1; gs[3 * row] = (uint32_t)r.x2; gs[4 * row] = (uint32_t)r.y1; gs[5 * row] = (uint32_t)r.y2; gs[6 * row] = (uint32_t)r.err_acc;
+    gs[7 * row] = r.rng; gs[8 * row] = r.fade;
+}
 
-    const int32_t *in = TILED ? sub + (size_t)wg * n_frames * row + col : sub + (size_t)stream * n_frames;
-    uint32_t *out = TILED ? words + (size_t)wg * n_frames * 8 * row + col : words + (size_t)stream * n_frames * 8;
+// `in` / `out`: the stream's first sample / first word; TILED: frames at stride row, the 8 words of a frame at stride row too
+template <bool TILED>
+__device__ __forceinline__ void pdm_samples(PdmRegs &r, const int32_t *in, uint32_t *out, uint32_t n_frames, uint32_t row) {
+    int32_t err = r.err, err2 = r.err2, x1 = r.x1, x2 = r.x2, y1 = r.y1, y2 = r.y2, err_acc = r.err_acc;
+    uint32_t rng = r.rng, fade = r.fade;
     const size_t in_step = TILED ? row : 1, out_step = TILED ? row : 1;
 
     int32_t next = n_frames ? in[0] : 0;
@@ -108,9 +117,46 @@ __global__ __launch_bounds__(kPdmThreads) void pdm_kernel(uint32_t *state, const
             *reinterpret_cast<u4 *>(o + 4) = u4{w[4], w[5], w[6], w[7]};
         }
     }
-    gs[0 * row] = (uint32_t)err; gs[1 * row] = (uint32_t)err2;
-    gs[2 * row] = (uint32_t)x1; gs[3 * row] = (uint32_t)x2; gs[4 * row] = (uint32_t)y1; gs[5 * row] = (uint32_t)y2; gs[6 * row] = (uint32_t)err_acc;
-    gs[7 * row] = rng; gs[8 * row] = fade;
+    r = PdmRegs{err, err2, x1, x2, y1, y2, err_acc, rng, fade};
+}
+
+template <bool TILED>
+__global__ __launch_bounds__(kPdmThreads) void pdm_kernel(uint32_t *state, const int32_t *sub, uint32_t *words, uint32_t n_streams, uint32_t n_frames,
+                                                           uint32_t row, const uint32_t *active) {
+    const uint32_t wg = blockIdx.x * (kPdmThreads / row) + threadIdx.x / row, col = threadIdx.x % row;
+    const uint32_t stream = wg * row + col;
+    if (stream >= n_streams) return;
+    if (active && !((active[stream >> 5] >> (stream & 31u)) & 1u)) return;
+    uint32_t *gs = state + (size_t)wg * kPdmStateWords * row + col;
+    PdmRegs r = pdm_load(gs, row);
+    const int32_t *in = TILED ? sub + (size_t)wg * n_frames * row + col : sub + (size_t)stream * n_frames;
+    uint32_t *out = TILED ? words + (size_t)wg * n_frames * 8 * row + col : words + (size_t)stream * n_frames * 8;
+    pdm_samples<TILED>(r, in, out, n_frames, row);
+    pdm_store(gs, row, r);
+}
+
+// The modulator over a list (dspi_process_pdm; dspi_pdmlife.h): lane g of the grid serves the stream in list[g], so the launch costs the
+// lanes of the streams that run their modulator, whatever the context's size.  Bit 31 of the word (kPdmListReset): the lane starts from
+// the re-enable state (pdm_generator.c:241-252: the power-on words, the RNG running on) instead of the stored words — the reset is part
+// of this launch.  The list is ascending, so the lanes of a fully listed row read and write whole rows as pdm_kernel's do.  `sub` and
+// `words` are addressed by absolute stream in the call's layout; an unlisted stream's state, sub and words are not touched.
+template <bool TILED>
+__global__ __launch_bounds__(kPdmThreads) void pdm_list_kernel(uint32_t *state, const int32_t *sub, uint32_t *words, const uint32_t *list, uint32_t n_list,
+                                                                uint32_t n_streams, uint32_t n_frames, uint32_t row) {
+    const uint32_t g = blockIdx.x * kPdmThreads + threadIdx.x;
+    if (g >= n_list) return;
+    const uint32_t word = list[g], stream = word & 0x7fffffffu;
+    if (stream >= n_streams) return;
+    const uint32_t wg = stream / row, col = stream % row;
+    uint32_t *gs = state + (size_t)wg * kPdmStateWords * row + col;
+    PdmRegs r = pdm_load(gs, row);
+    if (word >> 31)      // (selects, not a branch: reset and carried lanes share their waves)
+        r = PdmRegs{(int32_t)pdm_power_on_word(0), (int32_t)pdm_power_on_word(1), (int32_t)pdm_power_on_word(2), (int32_t)pdm_power_on_word(3),
+                    (int32_t)pdm_power_on_word(4), (int32_t)pdm_power_on_word(5), (int32_t)pdm_power_on_word(6), r.rng, pdm_power_on_word(8)};
+    const int32_t *in = TILED ? sub + (size_t)wg * n_frames * row + col : sub + (size_t)stream * n_frames;
+    uint32_t *out = TILED ? words + (size_t)wg * n_frames * 8 * row + col : words + (size_t)stream * n_frames * 8;
+    pdm_samples<TILED>(r, in, out, n_frames, row);
+    pdm_store(gs, row, r);
 }
 
 // power-on (init != 0: pdm_power_on_word, dspi_kernels.h) or the re-enable path (pdm_generator.c:241-252: everything but the RNG)
@@ -130,6 +176,15 @@ hipError_t launch_pdm(bool tiled, uint32_t *state, const int32_t *sub, uint32_t 
     const uint32_t per = kPdmThreads / row, blocks = (n_wg + per - 1) / per;
     if (tiled) hipLaunchKernelGGL(pdm_kernel<true>, dim3(blocks), dim3(kPdmThreads), 0, stream, state, sub, words, n_streams, n_frames, row, active);
     else hipLaunchKernelGGL(pdm_kernel<false>, dim3(blocks), dim3(kPdmThreads), 0, stream, state, sub, words, n_streams, n_frames, row, active);
+    return hipGetLastError();
+}
+
+hipError_t launch_pdm_list(bool tiled, uint32_t *state, const int32_t *sub, uint32_t *words, const uint32_t *list, uint32_t n_list, uint32_t n_streams,
+                           uint32_t n_frames, uint32_t row, hipStream_t stream) {
+    if (n_list == 0) return hipSuccess;
+    const uint32_t blocks = (n_list + kPdmThreads - 1) / kPdmThreads;
+    if (tiled) hipLaunchKernelGGL(pdm_list_kernel<true>, dim3(blocks), dim3(kPdmThreads), 0, stream, state, sub, words, list, n_list, n_streams, n_frames, row);
+    else hipLaunchKernelGGL(pdm_list_kernel<false>, dim3(blocks), dim3(kPdmThreads), 0, stream, state, sub, words, list, n_list, n_streams, n_frames, row);
     return hipGetLastError();
 }
 

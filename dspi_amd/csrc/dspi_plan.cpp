@@ -330,6 +330,7 @@ CallLayout plan_call(const CallInput &in) {
     L.sub = buffer(in.sub, tiled, F * 4);
     L.peaks = buffer(in.peaks, false, (size_t)in.n_blocks * in.n_ch * 2);
     L.clip = buffer(in.clip, false, 2);
+    L.pdm_words = buffer(in.pdm_words, tiled, F * 32);      // dspi_process_pdm: 8 words per frame, in the layout of the sub words
 
     // The latency layout's output waves encode the subframes themselves.  A launch with lanes on any other kernel (the flag is a property
     // of the output, not of the stream count) runs the chain into a scratch buffer of pair words, row chunk by row chunk, and the subframe
@@ -349,14 +350,22 @@ CallLayout plan_call(const CallInput &in) {
     // the direct area: every buffer of the call at a 256-byte boundary, up to 2 MiB
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     L.pairs.off = up(L.pcm.bytes); L.sub.off = L.pairs.off + up(L.pairs.bytes); L.peaks.off = L.sub.off + up(L.sub.bytes);
-    L.clip.off = L.peaks.off + up(L.peaks.bytes); L.direct_bytes = L.clip.off + up(L.clip.bytes);
+    L.clip.off = L.peaks.off + up(L.peaks.bytes); L.pdm_words.off = L.clip.off + up(L.clip.bytes); L.direct_bytes = L.pdm_words.off + up(L.pdm_words.bytes);
     L.mem = (in.flags & DSPI_MEM_DEVICE) ? CallMem::Device : !in.no_direct && L.direct_bytes <= (2u << 20) ? CallMem::Direct : CallMem::Staged;
 
     // staged: from 32 MiB through the link, one chunk per 16 MiB, at most 8, and none without rows
-    const size_t moved = L.pcm.bytes + L.pairs.bytes + L.sub.bytes + L.peaks.bytes;
+    const size_t moved = L.pcm.bytes + L.pairs.bytes + L.sub.bytes + L.peaks.bytes + L.pdm_words.bytes;
     if (moved >= (32u << 20) && in.n_wg >= 2) L.n_chunks = (uint32_t)std::min<size_t>({(size_t)8, (size_t)in.n_wg, moved / (16u << 20)});
     L.rows_per_chunk = (in.n_wg + L.n_chunks - 1) / L.n_chunks;
     L.n_chunks = (in.n_wg + L.rows_per_chunk - 1) / L.rows_per_chunk;
+
+    // dspi_process_pdm without out->sub: the chain's Q28 sub words go to a scratch of the library's, in device memory and in the call's
+    // layout, and the modulator reads them there.  The whole call's — an eighth of the words buffer the caller passes anyway —, but on
+    // the staged path one chunk's: the chain and the modulator of a chunk run back to back on one stream.
+    if (in.pdm_words && !in.sub) {
+        L.sub_scratch = buffer(true, tiled, F * 4);
+        if (L.mem == CallMem::Staged) L.sub_scratch.bytes = (size_t)L.rows_per_chunk * in.row * L.sub_scratch.per;
+    }
     return L;
 }
 

@@ -116,6 +116,7 @@ struct CallInput {
     bool pairs = false, sub = false, peaks = false, clip = false;      // the outputs the caller passed (clip: with DSPI_OUT_CLIP_FLAGS)
     bool no_direct = false;                           // DSPI_NO_DIRECT
     bool all_latency = false;                         // float, and every non-empty path of the launch plan is on the latency layout
+    bool pdm_words = false;                           // dspi_process_pdm: the caller's PDM words, beside the outputs above
     bool spdif_per_stream = false;                    // dspi_spdif_per_stream is on: the latency layout's fused encoder knows one position per launch
 };
 
@@ -132,10 +133,12 @@ enum class CallMem : uint8_t { Device, Direct, Staged };
 struct CallLayout {
     size_t frames = 0;
     CallBuffer pcm, pairs, sub, peaks, clip;
+    CallBuffer pdm_words;                             // dspi_process_pdm (0 bytes: dspi_process): uint32 [unit][F][8], tiled [tile][F][8][R]
+    CallBuffer sub_scratch;                           // ... when the caller passed no `sub`: the library's own Q28 sub words (device memory; `off` unused); staged: one chunk's
     bool spdif_two_pass = false;                      // DSPI_OUT_SPDIF off the latency layout, or with per-stream positions: the chain's pair words, then the encoder
     uint32_t two_pass_rows = 0; size_t two_pass_bytes = 0;      // rows per pass, their scratch of pair words
     CallMem mem = CallMem::Staged;
-    size_t direct_bytes = 0;                          // the direct area: pcm, pairs, sub, peaks, clip at their `off`
+    size_t direct_bytes = 0;                          // the direct area: pcm, pairs, sub, peaks, clip, pdm_words at their `off`
     uint32_t n_chunks = 1, rows_per_chunk = 0;        // staged: chunk k = rows [k * rows_per_chunk, min(n_wg, (k + 1) * rows_per_chunk))
 };
 

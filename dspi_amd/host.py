@@ -139,6 +139,9 @@ def lib() -> C.CDLL:
         L.dspi_reserve_streams.argtypes = [vp, u32]
         L.dspi_stream_capacity.argtypes = [vp]
         L.dspi_stream_capacity.restype = u32
+    if hasattr(L, "dspi_process_pdm"):
+        L.dspi_process_pdm.argtypes = [vp, vp, C.c_int, u32, u32, C.POINTER(_Out), vp, u32]
+        L.dspi_pdm_running.argtypes = [vp, u32, u32, vp, vp]
     _lib = L
     return L
 
@@ -329,6 +332,45 @@ class Dspi:
         """Zero-copy path: raw device pointers (e.g. torch.Tensor.data_ptr()); asynchronous, see sync().  clip_ptr: uint16 [S] (DSPI_OUT_CLIP_FLAGS)."""
         out = _Out(pairs_ptr or None, sub_ptr or None, peaks_ptr or None, clip_ptr or None)
         self._ck(self.L.dspi_process(self.h, pcm_ptr, bit_depth, n_blocks, block_len, C.byref(out), MEM_DEVICE | (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_I2S_SLOTS if i2s_slots else 0) | (OUT_SPDIF if spdif else 0) | (OUT_CLIP_FLAGS if clip_ptr else 0)), "process")
+
+    def process_pdm_host(self, pcm: np.ndarray, n_blocks: int, block_len: int, bit_depth: int = 16, want_pairs=True, want_sub=True, want_peaks=True,
+                         tiled=False, enabled_only=False, words=None):
+        """dspi_process_pdm on host arrays: process_host's (pairs, sub, peaks) and the PDM words, uint32 [S][F][8] (tiled: [tiles][F][8][R]).
+        words: an array of that shape to write into (what a stream that is not modulated leaves there is the library's to decide)."""
+        S, F = self.n_streams, n_blocks * block_len
+        pcm = np.ascontiguousarray(pcm)
+        assert pcm.nbytes == S * F * (6 if bit_depth == 24 else 4), (pcm.shape, S, F)
+        R = self.tile_streams(); nt = (S + R - 1) // R
+        if tiled:
+            pairs = np.zeros((nt, self.P * 2, F, R), dtype=np.int32) if want_pairs else None
+            sub = np.zeros((nt, F, R), dtype=np.int32) if want_sub else None
+        else:
+            pairs = np.zeros((S, self.P, F, 2), dtype=np.int32) if want_pairs else None
+            sub = np.zeros((S, F), dtype=np.int32) if want_sub else None
+        peaks = np.zeros((S, n_blocks, self.C), dtype=np.uint16) if want_peaks else None
+        if words is None: words = np.zeros((nt, F, 8, R) if tiled else (S, F, 8), dtype=np.uint32)
+        assert words.dtype == np.uint32 and words.flags.c_contiguous and words.size == (nt * R if tiled else S) * F * 8
+        out = _Out(pairs.ctypes.data if want_pairs else None, sub.ctypes.data if want_sub else None, peaks.ctypes.data if want_peaks else None, None)
+        self._ck(self.L.dspi_process_pdm(self.h, pcm.ctypes.data, bit_depth, n_blocks, block_len, C.byref(out), words.ctypes.data,
+                                         (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0)), "process_pdm")
+        return pairs, sub, peaks, words
+
+    def process_pdm_device(self, pcm_ptr: int, n_blocks: int, block_len: int, words_ptr: int, bit_depth: int = 16, pairs_ptr: int = 0, sub_ptr: int = 0,
+                           peaks_ptr: int = 0, tiled: bool = False, enabled_only: bool = False):
+        """dspi_process_pdm on raw device pointers; asynchronous, see sync()."""
+        out = _Out(pairs_ptr or None, sub_ptr or None, peaks_ptr or None, None)
+        self._ck(self.L.dspi_process_pdm(self.h, pcm_ptr, bit_depth, n_blocks, block_len, C.byref(out), words_ptr,
+                                         MEM_DEVICE | (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0)), "process_pdm")
+
+    def pdm_running(self, first: int = 0, count: int | None = None, set=None) -> np.ndarray:
+        """dspi_pdm_running: the running bytes of streams [first, first + count) (default: to the end), after writing `set` (0 / 1 each) if given."""
+        if count is None: count = self.n_streams - first
+        get = np.zeros(count, dtype=np.uint8)
+        if set is not None:
+            set = np.ascontiguousarray(set, dtype=np.uint8)
+            assert set.size == count
+        self._ck(self.L.dspi_pdm_running(self.h, first, count, set.ctypes.data if set is not None else None, get.ctypes.data), "pdm_running")
+        return get
 
     def pdm_host(self, sub: np.ndarray, tiled: bool = False) -> np.ndarray:
         """PDM sub output (dspi_pdm_modulate) on host arrays: sub int32 [streams][frames] -> uint32 [streams][frames][8];

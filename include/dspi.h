@@ -74,7 +74,8 @@ extern "C" {
                               * 8 + stream boots: detect by symbol (dspi_boot_streams; with it DSPI_BOOT_STREAMS_AS_IS; additions only);
                               * 8 + per-stream S/PDIF positions: detect by symbol (dspi_spdif_per_stream; with it dspi_spdif_stream_pos, dspi_spdif_encode_v; additions only);
                               * 8 + resizing: detect by symbol (dspi_resize_streams; with it dspi_reserve_streams, dspi_stream_capacity, DSPI_RESIZE_PAUSED; additions only);
-                              * 8 + grouping: detect by symbol (dspi_plan_grouping; with it DSPI_GROUP_ONE_WAY; additions only) */
+                              * 8 + grouping: detect by symbol (dspi_plan_grouping; with it DSPI_GROUP_ONE_WAY; additions only);
+                              * 8 + PDM words from the call: detect by symbol (dspi_process_pdm; with it dspi_pdm_running; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -611,6 +612,47 @@ uint32_t dspi_stream_capacity(const dspi_ctx *ctx);
 int dspi_pdm_modulate(dspi_ctx *ctx, const int32_t *sub, uint32_t n_frames, uint32_t *words, uint32_t flags);
 /* the re-enable path (pdm_generator.c:241-252): integrators, noise shaper and fade-in restart, the dither RNG runs on */
 int dspi_pdm_restart(dspi_ctx *ctx, int32_t stream);
+/* ---- the PDM words straight out of the call, per-stream on/off ------------------------------------------------------------------- */
+/* dspi_process_pdm is dspi_process plus pdm_words: the same arguments, the same flags with the same meanings and refusals (no new flag
+ * bit), the same three memory paths and the same outputs in `out`, all optional, out->sub included.  pdm_words has the layout of
+ * dspi_pdm_modulate's words — uint32 [stream][F][8], with DSPI_OUT_TILED [tile][F][8][R] — in host or device memory as the other
+ * pointers.  NULL pdm_words: DSPI_E_INVAL; a host-only context: DSPI_E_NODEVICE.  The chain's Q28 sub words go to out->sub when the caller
+ * passed one and to a scratch of the library's otherwise; the modulator reads them where they are, and the words do not depend on which.
+ *
+ * In the firmware the modulator runs only while the device's last output is enabled (derive_core1_mode, usb_audio.c:1620-1629:
+ * GET_CORE1_MODE == 1); a device whose sub is off has its PDM hardware stopped.  The context keeps one byte per stream, RUNNING, 0 after
+ * dspi_create, and at every successful dspi_process_pdm each ACTIVE stream is handled by it:
+ *   sub on, not running   modulated AFTER THE RE-ENABLE RESET (pdm_generator.c:239-252): every modulator word at its power-on value except
+ *                         the dither RNG, which runs on; the fade-in restarts.  The byte becomes 1.  On a stream that never ran, this is
+ *                         the power-on state.
+ *   sub on, running       modulated, its state carried over.
+ *   sub off               not modulated: its state and RNG stay frozen, its `sub` is not read, its words are NOT WRITTEN in a device buffer
+ *                         and are zeros in a host buffer.  The byte becomes 0.
+ * A paused stream is not modulated either, its words are handled as a stopped stream's, and its byte is left alone: a device that
+ * receives no packets is frozen, like everything else about it.  A failed or refused call changes nothing.  Only the streams that are
+ * modulated cost anything: the modulator runs over a list of them, one lane each, in one launch behind the chain's.
+ * dspi_process and dspi_pdm_modulate neither read nor write the byte; dspi_pdm_restart resets the device words as always and leaves it alone.
+ *
+ * NOT MODELLED: the fade-out on disable (pdm_generator.c:223-228, :323-348).  It needs a word of per-stream device state (fade_base_pcm)
+ * that the snapshot record's nine PDM words have no room for, so a disable is an IMMEDIATE STOP.  Its consequence: after a disable the
+ * firmware's dither RNG has advanced through the fade-out's 1,023 samples and ours has not — exactly as with dspi_pdm_restart — so the
+ * words after the next re-enable are those of a device whose RNG stood where the disable found it.
+ *
+ * The byte is the stream's own and travels where the per-stream S/PDIF position does:
+ *   pause / resume        unchanged.
+ *   dspi_move_streams     running[dst] := old running[src], for all entries at once; an open-end source keeps its value.
+ *   dspi_migrate_streams  the arrival takes the source's value (the source slot keeps its own, as a frozen copy).
+ *   dspi_boot_streams     the listed slots go to 0.
+ *   dspi_resize_streams   growing: the new slots are 0.
+ *   snapshots             the byte does not travel and an import leaves the slot's byte alone: carry it with dspi_pdm_running, get on the
+ *                         source context, set on the destination.  An imported running stream whose byte stays 0 comes up through the reset.
+ * dspi_pdm_running(ctx, first, count, set, get)   set (may be NULL): count values, each 0 or 1, for streams [first, first + count); get (may
+ *                       be NULL): the bytes after the set.  Host memory always.  Everything is validated before anything is written: a range
+ *                       past dspi_num_streams, a count of 0 or a value above 1 is DSPI_E_INVAL and leaves the context as it was.  Returns
+ *                       count.  Works on host-only contexts. */
+int dspi_process_pdm(dspi_ctx *ctx, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len,
+                     const dspi_out *out, uint32_t *pdm_words, uint32_t flags);
+int dspi_pdm_running(dspi_ctx *ctx, uint32_t first, uint32_t count, const uint8_t *set, uint8_t *get);
 
 /* ---- S/PDIF subframes ---------------------------------------------------- */
 /* What the firmware's S/PDIF outputs do to the words of dspi_out.pairs before the PIO shifts them out
