@@ -32,6 +32,7 @@
 #include "dspi_group.h"
 #include "dspi_migrate.h"
 #include "dspi_move.h"
+#include "dspi_pdmfade.h"
 #include "dspi_pdmlife.h"
 #include "dspi_plan.h"
 #include "dspi_resize.h"
@@ -113,6 +114,11 @@ struct dspi_ctx {
     PdmLife pdm_life;
     uint32_t *d_pdm_list = nullptr; size_t d_pdm_list_cap = 0;
     std::vector<int8_t> image_core1;
+    // dspi_pdm_fade (dspi_pdmfade.h): the mode and the fade positions; the fade bases [cap_wg * row] (allocated when the mode is first enabled, they
+    // follow the capacity like d_pdm); the packed temporary the bases travel through.  The call's aux words stand behind the list in d_pdm_list.
+    PdmFade pdm_fade;
+    int32_t *d_pdm_base = nullptr;
+    int32_t *d_pdm_pack = nullptr; size_t d_pdm_pack_cap = 0;
     int32_t *d_spdif_in = nullptr; size_t d_spdif_in_cap = 0;
     uint32_t *d_spdif_out = nullptr; size_t d_spdif_out_cap = 0;
     uint32_t *d_snap = nullptr; size_t d_snap_cap = 0;          // stream snapshots on host buffers: the records of one chunk of rows
@@ -594,6 +600,7 @@ int dspi_create(dspi_ctx **out, int flavor, uint32_t n_streams, int hip_device) 
     c->image_refs.push_back(n_streams);
     c->stream_image.assign(n_streams, 0);
     c->pdm_life.create(n_streams);
+    c->pdm_fade.create(n_streams);
     *out = c;
     if (hip_device == DSPI_DEVICE_NONE) return DSPI_OK;
 
@@ -621,7 +628,7 @@ void dspi_destroy(dspi_ctx *c) {
     if (c->device != DSPI_DEVICE_NONE) {
         (void)hipSetDevice(c->device);
         if (c->hs) (void)hipStreamSynchronize(c->hs);
-        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_pdm_list, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_spdif_ps, (void *)c->d_spdif_vpos, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, (void *)c->d_move, (void *)c->d_mig_pos, c->d_in,
+        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_pdm_list, (void *)c->d_pdm_base, (void *)c->d_pdm_pack, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_spdif_ps, (void *)c->d_spdif_vpos, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, (void *)c->d_move, (void *)c->d_mig_pos, c->d_in,
                         (void *)c->d_pairs, (void *)c->d_sub, (void *)c->d_peaks, (void *)c->d_clip, (void *)c->d_spdif_words})
             if (p) (void)hipFree(p);
         if (c->h_direct) (void)hipHostFree(c->h_direct);
@@ -1137,9 +1144,11 @@ static int plan_out(const std::vector<StreamMove> &plan, dspi_stream_move *moves
     return (int)plan.size();
 }
 // a boot list's work items into device memory (move_upload)
-static int boot_upload(dspi_ctx *c, const std::vector<BootRowItem> &items) {
+// ... and behind them `slots` (dspi_boot_streams in the fade mode: the slots whose fade base becomes 0)
+static int boot_upload(dspi_ctx *c, const std::vector<BootRowItem> &items, const uint32_t *slots = nullptr, uint32_t n_slots = 0) {
     std::vector<uint32_t> words(items.size() * (sizeof(BootRowItem) / 4));
     memcpy(words.data(), items.data(), items.size() * sizeof(BootRowItem));
+    if (n_slots) words.insert(words.end(), slots, slots + n_slots);
     return move_upload(c, words);
 }
 
@@ -1177,7 +1186,19 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
         spans.push_back(sp);
     }
     const auto [items_at, colrec_at] = pack_row_items(words, items, colrec);
+    // the fade mode's bases travel too (dspi_pdmfade.h): the sources, then the destinations, behind the other lists
+    const bool bases = c->pdm_fade.on && c->d_pdm_base;
+    const size_t slots_at = words.size();
+    if (bases) {
+        for (const StreamMove &m : mv) words.push_back(m.src);
+        for (const StreamMove &m : mv) words.push_back(m.dst);
+        if ((rc = ensure(c, c->d_pdm_pack, c->d_pdm_pack_cap, (size_t)nm * 4))) return rc;
+    }
     if ((rc = move_upload(c, words))) return rc;
+    if (bases) {      // (through the packed temporary: swaps and cycles are safe)
+        HIPCK(c, launch_pdm_base_gather(c->d_pdm_base, c->d_move + slots_at, nm, c->n_streams, c->d_pdm_pack, c->hs));
+        HIPCK(c, launch_pdm_base_scatter(c->d_pdm_base, c->d_move + slots_at + nm, nm, c->n_streams, c->d_pdm_pack, c->hs));
+    }
     // run-time state, on the context's stream, behind whatever it still has to do
     if (realign) HIPCK(c, launch_list_shifts(c->flavor, c->d_state, c->d_move, nullptr, nm, c->d_snap_shift, c->hs));
     for (const Span &sp : spans) {
@@ -1190,6 +1211,7 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
     // a paused, frozen copy.  (Such entries exist only where something is paused: `active` is allocated then.)
     if (c->spdif_ps.on) c->spdif_ps.move(mv.data(), nm, host_activity(c));      // (the S/PDIF position is the device's own counter: it travels too)
     c->pdm_life.move(mv.data(), nm);      // (... and whether its modulator is running)
+    c->pdm_fade.move(mv.data(), nm);      // (... and how far it has faded)
     const bool have_active = !c->active.empty();
     std::vector<int32_t> img(nm);
     std::vector<uint8_t> act(nm, 1), is_dst(c->n_streams, 0);
@@ -1272,6 +1294,17 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
         ss.item0.push_back(si.size()); ds.item0.push_back(di.size());
         ss.at = pack_row_items(ss.words, si, sc); ds.at = pack_row_items(ds.words, di, dc);
     }
+    // the fade mode's bases (dspi_pdmfade.h) travel while both contexts have the mode; with the mode at the destination only, the arrivals' bases are 0
+    const bool base_to = dst->pdm_fade.on && dst->d_pdm_base, base_from = base_to && src->pdm_fade.on && src->d_pdm_base;
+    const size_t src_slots_at = ss.words.size(), dst_slots_at = ds.words.size();
+    if (base_from) for (uint32_t i = 0; i < n; i++) ss.words.push_back(list[i].src);
+    if (base_to) for (uint32_t i = 0; i < n; i++) ds.words.push_back(list[i].dst);
+    if (base_from) {
+        HIPCK(src, hipSetDevice(src->device));
+        if ((rc = ensure(src, src->d_pdm_pack, src->d_pdm_pack_cap, (size_t)n * 4))) return rc;
+        HIPCK(dst, hipSetDevice(dst->device));
+        if (staged && (rc = ensure(dst, dst->d_pdm_pack, dst->d_pdm_pack_cap, (size_t)n * 4))) return rc;
+    }
     HIPCK(src, hipSetDevice(src->device));
     if ((rc = move_upload(src, ss.words))) return rc;
     HIPCK(dst, hipSetDevice(dst->device));
@@ -1300,6 +1333,18 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
         HIPCK(dst, hipSetDevice(dst->device));
         HIPCK(dst, launch_list_shifts(dst->flavor, dst->d_state, dst->d_move, staged ? dst->d_mig_pos : src->d_mig_pos, n, dst->d_snap_shift, dst->hs));
         if (via == dspi_ctx::kViaHost) HIPCK(dst, hipStreamSynchronize(dst->hs));      // (the pinned area is rewritten by the first batch)
+    }
+    // the fade bases, the same way and inside the same ordering: gathered on the source's stream, carried, scattered on the destination's (the
+    // batches' closing signal covers the source's packed buffer as it covers its scratch)
+    if (base_from) {
+        HIPCK(src, hipSetDevice(src->device));
+        HIPCK(src, launch_pdm_base_gather(src->d_pdm_base, src->d_move + src_slots_at, n, src->n_streams, src->d_pdm_pack, src->hs));
+        if ((rc = carry(reinterpret_cast<uint32_t *>(dst->d_pdm_pack), reinterpret_cast<const uint32_t *>(src->d_pdm_pack), (size_t)n * 4))) return rc;
+    }
+    if (base_to) {
+        HIPCK(dst, hipSetDevice(dst->device));
+        HIPCK(dst, launch_pdm_base_scatter(dst->d_pdm_base, dst->d_move + dst_slots_at, n, dst->n_streams, !base_from ? nullptr : staged ? dst->d_pdm_pack : src->d_pdm_pack, dst->hs));
+        if (base_from && via == dspi_ctx::kViaHost) HIPCK(dst, hipStreamSynchronize(dst->hs));      // (the pinned area is rewritten by the first batch)
     }
     // the batches: the source gathers, the destination takes the records and scatters, the source waits before it gathers over the same
     // scratch again — and once more at the end, so that dspi_sync / dspi_destroy of the source cover the destination's use of its scratch
@@ -1336,6 +1381,8 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
     if (src->spdif_ps.on)
         for (uint32_t i = 0; i < n; i++) src->spdif_ps.pause(list[i].src, 1, sa);
     for (uint32_t i = 0; i < n; i++) dst->pdm_life.arrive(list[i].dst, src->pdm_life.running[list[i].src]);      // (a running modulator arrives running)
+    // ... and a fading one fading, where both contexts fade; else the position arrives as 0, and a fade in flight has ended as an immediate stop
+    for (uint32_t i = 0; i < n; i++) dst->pdm_fade.arrive(dst->pdm_life, list[i].dst, src->pdm_fade.on ? src->pdm_fade.pos[list[i].src] : 0u);
     if (src->active.empty()) src->active.assign(src->n_streams, 1);
     for (uint32_t i = 0; i < n; i++) { set_active(dst, list[i].dst, act[i] != 0); set_active(src, list[i].src, false); }
     activity_changed(src); activity_changed(dst);
@@ -1403,9 +1450,11 @@ int dspi_boot_streams(dspi_ctx *c, const uint32_t *streams, uint32_t n, const vo
     if (c->device != DSPI_DEVICE_NONE) {
         HIPCK(c, hipSetDevice(c->device));
         const std::vector<BootRowItem> items = boot_row_items(streams, n, c->n_streams, (uint32_t)c->sm.row, host_activity(c), (flags & DSPI_BOOT_STREAMS_AS_IS) != 0);
-        int rc = boot_upload(c, items);
+        const bool bases = c->pdm_fade.on && c->d_pdm_base;
+        int rc = boot_upload(c, items, streams, bases ? n : 0);
         if (rc) return rc;
         HIPCK(c, launch_boot(c->flavor, state_arrays(c), c->d_move, (uint32_t)items.size(), c->hs));
+        if (bases) HIPCK(c, launch_pdm_base_scatter(c->d_pdm_base, c->d_move + items.size() * (sizeof(BootRowItem) / 4), n, c->n_streams, nullptr, c->hs));      // fade_base_pcm at power-on: 0
     }
     // parameters: the listed streams leave their objects (whose pending state operations never reach them) and share ONE new one, whose
     // own pending operations the next commit applies over the power-on state, as after dspi_create.  An object that lost its last stream
@@ -1415,6 +1464,7 @@ int dspi_boot_streams(dspi_ctx *c, const uint32_t *streams, uint32_t n, const vo
     c->launch_dirty = true; c->merge_hint = true;
     if (c->spdif_ps.on) c->spdif_ps.boot(streams, n, host_activity(c));      // a device that has just been powered on sends frame 0 of a block first
     c->pdm_life.boot(streams, n);      // ... and has never run its modulator
+    c->pdm_fade.boot(streams, n);      // ... nor faded it
     if (selection) *selection = sel;
     return (int)n;
 }
@@ -1425,11 +1475,11 @@ int dspi_boot_streams(dspi_ctx *c, const uint32_t *streams, uint32_t n, const vo
 // context's stream, behind its earlier work; then the stream is waited for, once, and the old arrays are freed.
 static int resize_reallocate(dspi_ctx *c, uint32_t rows, uint32_t copy) {
     const size_t row = (size_t)c->sm.row;
-    const size_t row_b[4] = {(size_t)c->sm.n_slots * row * 4, (size_t)c->sm.n_out * (size_t)c->sm.max_delay * row * 4, (size_t)kRingLen * 2 * row * 4, (size_t)kPdmStateWords * row * 4};
-    uint32_t **const arr[4] = {&c->d_state, &c->d_dlines, &c->d_ring, &c->d_pdm};
-    void *fresh[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 4; k++) {
-        if (!*arr[k]) continue;      // (d_pdm before the modulator's first run)
+    const size_t row_b[5] = {(size_t)c->sm.n_slots * row * 4, (size_t)c->sm.n_out * (size_t)c->sm.max_delay * row * 4, (size_t)kRingLen * 2 * row * 4, (size_t)kPdmStateWords * row * 4, row * 4};
+    uint32_t **const arr[5] = {&c->d_state, &c->d_dlines, &c->d_ring, &c->d_pdm, reinterpret_cast<uint32_t **>(&c->d_pdm_base)};
+    void *fresh[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 5; k++) {
+        if (!*arr[k]) continue;      // (d_pdm before the modulator's first run, d_pdm_base before the fade mode's first enable)
         size_t b = 0;
         if (!resize_bytes(rows, row_b[k], &b) || hipMalloc(&fresh[k], b) != hipSuccess) {
             (void)hipGetLastError();
@@ -1438,14 +1488,14 @@ static int resize_reallocate(dspi_ctx *c, uint32_t rows, uint32_t copy) {
         }
     }
     hipError_t e = hipSuccess;
-    for (int k = 0; k < 4 && e == hipSuccess; k++)
+    for (int k = 0; k < 5 && e == hipSuccess; k++)
         if (fresh[k] && copy) e = hipMemcpyAsync(fresh[k], *arr[k], (size_t)copy * row_b[k], hipMemcpyDeviceToDevice, c->hs);
     if (e == hipSuccess) e = hipStreamSynchronize(c->hs);
     if (e != hipSuccess) {
-        for (int k = 0; k < 4; k++) if (fresh[k]) (void)hipFree(fresh[k]);
+        for (int k = 0; k < 5; k++) if (fresh[k]) (void)hipFree(fresh[k]);
         return fail(c, DSPI_E_HIP, std::string("resized arrays: ") + hipGetErrorString(e));
     }
-    for (int k = 0; k < 4; k++)
+    for (int k = 0; k < 5; k++)
         if (fresh[k]) { (void)hipFree(*arr[k]); *arr[k] = static_cast<uint32_t *>(fresh[k]); }
     c->cap_wg = rows;
     return 0;
@@ -1482,6 +1532,7 @@ static void resize_books(dspi_ctx *c, uint32_t n_new, int32_t slot, bool arrive_
         for (uint32_t s = n_old; s < n_new; s++) c->spdif_ps.set(s, 0, host_activity(c));
     }
     c->pdm_life.resize(n_new);      // (new slots: never ran)
+    c->pdm_fade.resize(n_new);      // (... never faded)
     c->assignment_dirty = true; c->merge_hint = true;      // (an object may have lost its last stream, or the new one equal one already here: the fold-back pass)
     activity_changed(c);
 }
@@ -1505,6 +1556,7 @@ int dspi_resize_streams(dspi_ctx *c, uint32_t n_streams, uint32_t flags) {
         // power-on state into EVERY new slot, whatever its column held (padding columns are dirty after a shrink, new rows unwritten),
         // behind the context's earlier work: the kernel reads the grown row's resident's positions there
         HIPCK(c, launch_boot(c->flavor, state_arrays(c), c->d_move, (uint32_t)items.size(), c->hs));
+        if (c->d_pdm_base) HIPCK(c, hipMemsetAsync(c->d_pdm_base + n_old, 0, (size_t)(n_streams - n_old) * 4, c->hs));      // (... and fade base 0)
     } else c->cap_wg = r.capacity;
     // parameters: the boot's own half with a NULL dump — ONE new object for all new slots, dspi_create's device on this context
     const int32_t slot = add_image(c, std::make_unique<Params>(c->flavor, c->fma, !c->populated));
@@ -1746,14 +1798,19 @@ struct PdmCall {
 static int pdm_prepare(dspi_ctx *c, PdmCall &pc) {
     int rc = pdm_state(c);
     if (rc) return rc;
-    const PdmWork &w = c->pdm_life.plan(host_activity(c), [c](uint32_t s) { return c->images[(size_t)c->stream_image[s]]->core1_mode == 1; });
+    // (in the fade mode a stream that fades, or is about to, stays listed: dspi_pdmfade.h says beside the list what its lane does)
+    const auto sub_on = [c](uint32_t s) { return c->images[(size_t)c->stream_image[s]]->core1_mode == 1; };
+    const PdmWork &w = c->pdm_life.plan(host_activity(c), [c, &sub_on](uint32_t s) { return c->pdm_fade.wants(c->pdm_life, s, sub_on(s)); });
+    c->pdm_fade.plan(c->pdm_life, sub_on);
     pc.work = &w;
     if (c->pdm_life.uploaded || w.list.empty()) return 0;
-    const size_t bytes = w.list.size() * 4;
+    const bool aux = c->pdm_fade.any_aux;      // the aux words go up behind the list, only when one of them says anything
+    const size_t bytes = w.list.size() * (aux ? 8 : 4);
     if (!c->ev_move) HIPCK(c, hipEventCreateWithFlags(&c->ev_move, hipEventDisableTiming));
     HIPCK(c, hipEventSynchronize(c->ev_move));
     if ((rc = pinned_area(c, c->h_move, c->h_move_cap, bytes, bytes * 2, "hipHostMalloc failed (PDM work list)")) || (rc = ensure(c, c->d_pdm_list, c->d_pdm_list_cap, bytes))) return rc;
-    memcpy(c->h_move, w.list.data(), bytes);
+    memcpy(c->h_move, w.list.data(), w.list.size() * 4);
+    if (aux) memcpy(static_cast<uint32_t *>(c->h_move) + w.list.size(), c->pdm_fade.aux.data(), w.list.size() * 4);
     HIPCK(c, hipMemcpyAsync(c->d_pdm_list, c->h_move, bytes, hipMemcpyHostToDevice, c->hs));
     HIPCK(c, hipEventRecord(c->ev_move, c->hs));
     c->pdm_life.uploaded = true;
@@ -1763,7 +1820,11 @@ static int pdm_prepare(dspi_ctx *c, PdmCall &pc) {
 // by absolute stream.  Nobody listed there: no launch.
 static int launch_pdm_streams(dspi_ctx *c, const PdmCall &pc, const CallLayout &L, bool tiled, const int32_t *sub, uint32_t *words, size_t s0, size_t s1) {
     const std::pair<size_t, size_t> r = pc.work->range((uint32_t)s0, (uint32_t)s1);
-    hipError_t e = launch_pdm_list(tiled, c->d_pdm, sub, words, c->d_pdm_list + r.first, (uint32_t)(r.second - r.first), c->n_streams, (uint32_t)L.frames, (uint32_t)c->sm.row, c->hs);
+    hipError_t e;
+    if (c->pdm_fade.on)      // (each chunk of the staged path gets its slice of both arrays)
+        e = launch_pdm_list_fade(tiled, c->d_pdm, sub, words, c->d_pdm_list + r.first, c->pdm_fade.any_aux ? c->d_pdm_list + pc.work->list.size() + r.first : nullptr, c->d_pdm_base,
+                                 (uint32_t)(r.second - r.first), c->n_streams, (uint32_t)L.frames, (uint32_t)c->sm.row, c->hs);
+    else e = launch_pdm_list(tiled, c->d_pdm, sub, words, c->d_pdm_list + r.first, (uint32_t)(r.second - r.first), c->n_streams, (uint32_t)L.frames, (uint32_t)c->sm.row, c->hs);
     return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("pdm modulator launch: ") + hipGetErrorString(e));
 }
 // where the chain leaves the Q28 sub words of a dspi_process_pdm call whose caller passed no `sub`: the library's scratch (device memory)
@@ -2038,7 +2099,7 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     case CallMem::Direct: rc = process_direct(c, L, a, pcm_in, out, clip_out, flags, call_t0, pc); break;
     case CallMem::Staged: rc = process_staged(c, L, a, pcm_in, out, clip_out, flags, pc); break;
     }
-    if (rc == DSPI_OK && pc) c->pdm_life.commit();      // a failed call leaves the running bytes alone
+    if (rc == DSPI_OK && pc) { c->pdm_life.commit(); c->pdm_fade.commit(c->pdm_life, (uint32_t)L.frames); }      // a failed call leaves the running bytes and the fade positions alone
     if (rc == DSPI_OK && spdif) {      // a failed call leaves the block positions alone
         c->spdif_pos = (uint32_t)((c->spdif_pos + L.frames) % 192u);
         if (c->spdif_ps.on) c->spdif_ps.advance(L.frames);      // every stream that was active in the call; the paused ones hold their own
@@ -2058,6 +2119,40 @@ int dspi_process_pdm(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_
 int dspi_pdm_running(dspi_ctx *c, uint32_t first, uint32_t count, const uint8_t *set, uint8_t *get) {
     if (!c) return DSPI_E_INVAL;
     if (const char *why = c->pdm_life.set_get(first, count, set, get)) return fail(c, DSPI_E_INVAL, std::string("dspi_pdm_running: ") + why);
+    return (int)count;
+}
+
+// ---- the fade-out on disable (dspi_pdmfade.h: the mode, the positions, the aux words; dspi_pdm.hip: the FADE kernels and the bases' travel) ----
+int dspi_pdm_fade(dspi_ctx *c, int enable) {
+    if (!c) return DSPI_E_INVAL;
+    if (enable > 0 && !c->pdm_fade.on) {
+        if (c->device != DSPI_DEVICE_NONE) {      // every stream: base 0
+            HIPCK(c, hipSetDevice(c->device));
+            const size_t b = (size_t)c->cap_wg * c->sm.row * 4;
+            if (!c->d_pdm_base && hipMalloc((void **)&c->d_pdm_base, b) != hipSuccess) { c->d_pdm_base = nullptr; (void)hipGetLastError(); return fail(c, DSPI_E_NOMEM, "hipMalloc failed (PDM fade bases)"); }
+            HIPCK(c, hipMemsetAsync(c->d_pdm_base, 0, b, c->hs));
+        }
+        c->pdm_fade.enable(c->pdm_life);
+    } else if (enable == 0) c->pdm_fade.disable(c->pdm_life);
+    return c->pdm_fade.on ? 1 : 0;
+}
+
+int dspi_pdm_fade_state(dspi_ctx *c, uint32_t first, uint32_t count, const uint32_t *set, uint32_t *get) {
+    if (!c) return DSPI_E_INVAL;
+    if (!c->pdm_fade.on) return fail(c, DSPI_E_INVAL, "dspi_pdm_fade_state: the fade mode is off (dspi_pdm_fade)");
+    // everything is validated before anything is written
+    if (const char *why = c->pdm_fade.check(first, count, set)) return fail(c, DSPI_E_INVAL, std::string("dspi_pdm_fade_state: ") + why);
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no fade bases");
+    HIPCK(c, hipSetDevice(c->device));
+    HIPCK(c, hipStreamSynchronize(c->hs));
+    std::vector<int32_t> base(count);
+    if (set) {
+        for (uint32_t k = 0; k < count; k++) base[k] = (int16_t)(uint16_t)(set[k] >> 16);
+        HIPCK(c, hipMemcpy(c->d_pdm_base + first, base.data(), (size_t)count * 4, hipMemcpyHostToDevice));
+        for (uint32_t k = 0; k < count; k++) c->pdm_fade.pos[first + k] = (uint16_t)(set[k] & 0xffffu);
+        c->pdm_life.mark_dirty();
+    } else if (get) HIPCK(c, hipMemcpy(base.data(), c->d_pdm_base + first, (size_t)count * 4, hipMemcpyDeviceToHost));
+    if (get) for (uint32_t k = 0; k < count; k++) get[k] = (uint32_t)c->pdm_fade.pos[first + k] | (uint32_t)(uint16_t)base[k] << 16;
     return (int)count;
 }
 

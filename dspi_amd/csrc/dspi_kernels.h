@@ -65,6 +65,12 @@ hipError_t launch_pdm(bool tiled, uint32_t *state, const int32_t *sub, uint32_t 
 // state): lane g serves list[g]; `sub` and `words` are the call's, addressed by absolute stream.  n_list == 0 launches nothing.
 hipError_t launch_pdm_list(bool tiled, uint32_t *state, const int32_t *sub, uint32_t *words, const uint32_t *list, uint32_t n_list, uint32_t n_streams,
                            uint32_t n_frames, uint32_t row, hipStream_t stream);
+// ... in the fade mode (dspi_pdm_fade; dspi_pdmfade.h): `aux` holds one word per list entry (null: all zero), `base` the fade bases [stream]
+hipError_t launch_pdm_list_fade(bool tiled, uint32_t *state, const int32_t *sub, uint32_t *words, const uint32_t *list, const uint32_t *aux, int32_t *base,
+                                uint32_t n_list, uint32_t n_streams, uint32_t n_frames, uint32_t row, hipStream_t stream);
+// the fade bases of the n listed slots into `packed`, and `packed` (null: zeros) into the n listed slots
+hipError_t launch_pdm_base_gather(const int32_t *base, const uint32_t *slots, uint32_t n, uint32_t n_streams, int32_t *packed, hipStream_t stream);
+hipError_t launch_pdm_base_scatter(int32_t *base, const uint32_t *slots, uint32_t n, uint32_t n_streams, const int32_t *packed, hipStream_t stream);
 hipError_t launch_pdm_reset(uint32_t *state, uint32_t n_streams, uint32_t row, uint32_t n_wg, int32_t only_stream, int init, hipStream_t stream);
 
 // ---- S/PDIF subframe encoder (dspi_spdif.hip)

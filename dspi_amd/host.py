@@ -142,6 +142,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "dspi_process_pdm"):
         L.dspi_process_pdm.argtypes = [vp, vp, C.c_int, u32, u32, C.POINTER(_Out), vp, u32]
         L.dspi_pdm_running.argtypes = [vp, u32, u32, vp, vp]
+    if hasattr(L, "dspi_pdm_fade"):      # (ABI 8 + the PDM fade-out on disable: detected by symbol; with it dspi_pdm_fade_state)
+        L.dspi_pdm_fade.argtypes = [vp, C.c_int]
+        L.dspi_pdm_fade_state.argtypes = [vp, u32, u32, vp, vp]
     _lib = L
     return L
 
@@ -370,6 +373,21 @@ class Dspi:
             set = np.ascontiguousarray(set, dtype=np.uint8)
             assert set.size == count
         self._ck(self.L.dspi_pdm_running(self.h, first, count, set.ctypes.data if set is not None else None, get.ctypes.data), "pdm_running")
+        return get
+
+    def pdm_fade(self, enable: int = -1) -> bool:
+        """dspi_pdm_fade: the PDM fade-out on disable on (1) / off (0), or only read (default).  Returns the mode after the call."""
+        return bool(self._ck(self.L.dspi_pdm_fade(self.h, enable), "pdm_fade"))
+
+    def pdm_fade_state(self, first: int = 0, count: int | None = None, set=None) -> np.ndarray:
+        """dspi_pdm_fade_state: the fade words (fade_out_pos | (uint16)base << 16) of streams [first, first + count) (default: to the end), after
+        writing `set` if given."""
+        if count is None: count = self.n_streams - first
+        get = np.zeros(count, dtype=np.uint32)
+        if set is not None:
+            set = np.ascontiguousarray(set, dtype=np.uint32)
+            assert set.size == count
+        self._ck(self.L.dspi_pdm_fade_state(self.h, first, count, set.ctypes.data if set is not None else None, get.ctypes.data), "pdm_fade_state")
         return get
 
     def pdm_host(self, sub: np.ndarray, tiled: bool = False) -> np.ndarray:

@@ -636,7 +636,38 @@ int dspi_pdm_restart(dspi_ctx *ctx, int32_t stream);
  * NOT MODELLED: the fade-out on disable (pdm_generator.c:223-228, :323-348).  It needs a word of per-stream device state (fade_base_pcm)
  * that the snapshot record's nine PDM words have no room for, so a disable is an IMMEDIATE STOP.  Its consequence: after a disable the
  * firmware's dither RNG has advanced through the fade-out's 1,023 samples and ours has not — exactly as with dspi_pdm_restart — so the
- * words after the next re-enable are those of a device whose RNG stood where the disable found it.
+ * words after the next re-enable are those of a device whose RNG stood where the disable found it.  That is the DEFAULT.
+ *
+ * THE FADE-OUT, OPT-IN: dspi_pdm_fade(ctx, enable)   enable 0 or 1, -1 queries; returns the mode after the call.  A property of the context
+ * (like dspi_spdif_per_stream), off after dspi_create, no flag bit of dspi_process_pdm; detect it by this symbol.  Works on host-only
+ * contexts.  With the mode off nothing is different from the paragraphs above.  With it on, fade_base_pcm lives BESIDE the nine words, in
+ * an array of the context's own, and every successful dspi_process_pdm handles each active stream by the rule above plus:
+ *   sub off, running, not fading   the stream starts a fade: fade_out_pos = 1024.
+ *   fading                for each frame of the call while fade_out_pos > 1: fade_out_pos--, target = ((fade_base_pcm * fade_out_pos) >> 10)
+ *                         + 32768 (pdm_generator.c:326-327), then the 8 chunks of dither, noise shaper and 32 modulator steps and the leaky
+ *                         integrators of a normal sample (:366-397) on the stream's carried state; 8 words are written; `sub` is not read;
+ *                         the fade-in position is not touched.  A whole fade is 1023 frames (positions 1023..1) and may span calls.
+ *                         THE RUNNING BYTE STAYS 1 WHILE THE STREAM FADES.
+ *   the end of a fade     once position 1 has been written the fade is over: the byte becomes 0 (a later enable goes through the re-enable
+ *                         reset, with the RNG where the fade left it) and the rest of THAT call's frames of the stream are ZERO WORDS, in
+ *                         device buffers too.  From the next call on it is a stopped stream as above.  A fade that has written its 1023
+ *                         samples is over even if the re-enable arrives before the next call (the firmware would need that request
+ *                         to land inside one sample period).
+ *   sub on while fading   (:233-237) no reset, state carried: fade-in position := 1024 - fade_out_pos (the fade samples already written),
+ *                         the fade ends, and the stream is modulated normally from its first frame of this call.
+ * Requests made between two calls count as arriving before the first frame of the next call.  fade_base_pcm is the pcm value of the stream's
+ * last normally modulated sample, after the limiter and the fade-in scaling (:352-362); 0 at power-on and when the mode is enabled.  Only
+ * dspi_process_pdm with the mode on maintains it: dspi_pdm_modulate and dspi_pdm_restart neither read nor write it (nor the position).
+ * A paused stream is frozen, fade position included, and continues on resume.  Enabling the mode gives every stream base 0 and "not
+ * fading"; disabling it ends every fade in flight at once: byte 0, no more words.
+ * The position and the base travel where the byte does: dspi_move_streams (all entries at once), dspi_migrate_streams (the arrival takes
+ * the source's; if either context has the mode off the position arrives as 0, the base is dropped, and a fade in flight has ended as an
+ * immediate stop, byte 0), dspi_boot_streams and new slots of a grow (0).  Snapshots are unchanged and carry neither:
+ * dspi_pdm_fade_state(ctx, first, count, set, get)   one word per stream: fade_out_pos | (uint32_t)(uint16_t)fade_base_pcm << 16; set and get
+ *                       (each may be NULL) as with dspi_pdm_running, host memory always; the context's stream is synchronised.  Validated
+ *                       before anything is written: the mode off, a range past dspi_num_streams, a count of 0, a position above 1023 (the
+ *                       largest a stream holds between two calls) or |base| > 29500 is DSPI_E_INVAL; a host-only context has no bases:
+ *                       DSPI_E_NODEVICE.  Carry a fading stream through a snapshot with this call and dspi_pdm_running.  Returns count.
  *
  * The byte is the stream's own and travels where the per-stream S/PDIF position does:
  *   pause / resume        unchanged.
@@ -653,6 +684,8 @@ int dspi_pdm_restart(dspi_ctx *ctx, int32_t stream);
 int dspi_process_pdm(dspi_ctx *ctx, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len,
                      const dspi_out *out, uint32_t *pdm_words, uint32_t flags);
 int dspi_pdm_running(dspi_ctx *ctx, uint32_t first, uint32_t count, const uint8_t *set, uint8_t *get);
+int dspi_pdm_fade(dspi_ctx *ctx, int enable);
+int dspi_pdm_fade_state(dspi_ctx *ctx, uint32_t first, uint32_t count, const uint32_t *set, uint32_t *get);
 
 /* ---- S/PDIF subframes ---------------------------------------------------- */
 /* What the firmware's S/PDIF outputs do to the words of dspi_out.pairs before the PIO shifts them out
