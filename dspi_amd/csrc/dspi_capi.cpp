@@ -30,6 +30,7 @@
 #include "dspi_params.h"
 #include "dspi_boot.h"
 #include "dspi_group.h"
+#include "dspi_intake.h"
 #include "dspi_migrate.h"
 #include "dspi_move.h"
 #include "dspi_pdmfade.h"
@@ -119,6 +120,17 @@ struct dspi_ctx {
     PdmFade pdm_fade;
     int32_t *d_pdm_base = nullptr;
     int32_t *d_pdm_pack = nullptr; size_t d_pdm_pack_cap = 0;
+    // dspi_process_mixed (dspi_intake.h).  d_mixed: device buffers only — a scratch of n_streams * 6F bytes that the intake kernel writes and the
+    // chain reads, both on `hs`, asynchronously.  d_mixed_up: staged host buffers only — where a chunk's bytes go up as they are (on hs_in when
+    // the call has several chunks), the intake then writes d_in.  THE RULE: whatever a stream other than `hs` touches (hs_in: d_in, d_mixed_up)
+    // belongs to the staged path alone, which ends synchronised; nothing that an asynchronous call leaves in flight on `hs` is touched from
+    // another stream.  That is why the two paths do not share one scratch.  d_mixed_tab: the device's table of the call's layout, (n + 1) uint64
+    // offsets with the n depths behind them, read and written on `hs` only; it goes up through h_move, behind ev_move, and stays while the
+    // depths and the frame count repeat: mixed_depths / mixed_frames say what it holds (0 frames: nothing)
+    uint8_t *d_mixed = nullptr; size_t d_mixed_cap = 0;
+    uint8_t *d_mixed_up = nullptr; size_t d_mixed_up_cap = 0;
+    uint64_t *d_mixed_tab = nullptr; size_t d_mixed_tab_cap = 0;
+    std::vector<uint8_t> mixed_depths; uint64_t mixed_frames = 0;
     int32_t *d_spdif_in = nullptr; size_t d_spdif_in_cap = 0;
     uint32_t *d_spdif_out = nullptr; size_t d_spdif_out_cap = 0;
     uint32_t *d_snap = nullptr; size_t d_snap_cap = 0;          // stream snapshots on host buffers: the records of one chunk of rows
@@ -628,7 +640,7 @@ void dspi_destroy(dspi_ctx *c) {
     if (c->device != DSPI_DEVICE_NONE) {
         (void)hipSetDevice(c->device);
         if (c->hs) (void)hipStreamSynchronize(c->hs);
-        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_pdm_list, (void *)c->d_pdm_base, (void *)c->d_pdm_pack, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_spdif_ps, (void *)c->d_spdif_vpos, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, (void *)c->d_move, (void *)c->d_mig_pos, c->d_in,
+        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_pdm_list, (void *)c->d_pdm_base, (void *)c->d_pdm_pack, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_spdif_ps, (void *)c->d_spdif_vpos, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, (void *)c->d_move, (void *)c->d_mig_pos, c->d_in, (void *)c->d_mixed, (void *)c->d_mixed_up, (void *)c->d_mixed_tab,
                         (void *)c->d_pairs, (void *)c->d_sub, (void *)c->d_peaks, (void *)c->d_clip, (void *)c->d_spdif_words})
             if (p) (void)hipFree(p);
         if (c->h_direct) (void)hipHostFree(c->h_direct);
@@ -1830,12 +1842,44 @@ static int launch_pdm_streams(dspi_ctx *c, const PdmCall &pc, const CallLayout &
 // where the chain leaves the Q28 sub words of a dspi_process_pdm call whose caller passed no `sub`: the library's scratch (device memory)
 static int pdm_sub_scratch(dspi_ctx *c, const CallLayout &L) { return ensure(c, c->d_sub, c->d_sub_cap, L.sub_scratch.bytes); }
 
+// ---- dspi_process_mixed: the call's layout (null in the three paths below: one depth for the call) ----
+// A mixed call is planned as the 24-bit call it becomes (plan_call knows nothing of it); only the way its `pcm` area is filled differs.
+struct MixedIn {
+    const uint8_t *depths;             // the caller's, validated
+    std::vector<uint64_t> offsets;     // [n_streams + 1] (dspi_intake.h)
+};
+// the path's scratch (d_mixed or d_mixed_up, `bytes`) and the device's table, before the first launch of the call (all-or-nothing: a call
+// that cannot have them runs nothing)
+static int intake_prepare(dspi_ctx *c, const MixedIn &mx, uint64_t frames, uint8_t *&scratch, size_t &scratch_cap, size_t scratch_bytes) {
+    int rc = ensure(c, scratch, scratch_cap, scratch_bytes);
+    if (rc) return rc;
+    const size_t n = c->n_streams, bytes = (n + 1) * 8 + n;
+    if (c->mixed_frames == frames && c->mixed_depths.size() == n && !memcmp(c->mixed_depths.data(), mx.depths, n)) return 0;
+    c->mixed_frames = 0;
+    if (!c->ev_move) HIPCK(c, hipEventCreateWithFlags(&c->ev_move, hipEventDisableTiming));
+    HIPCK(c, hipEventSynchronize(c->ev_move));
+    if ((rc = pinned_area(c, c->h_move, c->h_move_cap, bytes, bytes * 2, "hipHostMalloc failed (mixed input table)")) || (rc = ensure(c, c->d_mixed_tab, c->d_mixed_tab_cap, bytes))) return rc;
+    memcpy(c->h_move, mx.offsets.data(), (n + 1) * 8);
+    memcpy(static_cast<char *>(c->h_move) + (n + 1) * 8, mx.depths, n);
+    HIPCK(c, hipMemcpyAsync(c->d_mixed_tab, c->h_move, bytes, hipMemcpyHostToDevice, c->hs));      // (on the context's stream: behind every launch that reads the old table)
+    HIPCK(c, hipEventRecord(c->ev_move, c->hs));
+    c->mixed_depths.assign(mx.depths, mx.depths + n); c->mixed_frames = frames;
+    return 0;
+}
+// the intake launch for streams [s0, s1): `src` holds the caller's bytes at their offsets, `dst` is what the chain reads
+static int launch_intake_streams(dspi_ctx *c, uint64_t frames, const void *src, void *dst, size_t s0, size_t s1) {
+    hipError_t e = launch_intake(src, c->d_mixed_tab, reinterpret_cast<const uint8_t *>(c->d_mixed_tab + c->n_streams + 1), activity(c), dst, frames, (uint32_t)s0, (uint32_t)(s1 - s0), c->hs);
+    return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("intake launch: ") + hipGetErrorString(e));
+}
+
 // ---- device buffers: the caller's own, asynchronous on the context's stream ----
-static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, const PdmCall *pc) {
+static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, const PdmCall *pc, const MixedIn *mx) {
     a.pcm = pcm_in; a.pairs = out->pairs; a.sub = out->sub; a.peaks = out->peaks;
     int rc = 0;
     if (pc && !out->sub) { if ((rc = pdm_sub_scratch(c, L))) return rc; a.sub = c->d_sub; }
-    if ((L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) || (rc = launch_rows(c, a, L, 0, c->n_wg))) return rc;
+    if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) return rc;
+    if (mx) { if ((rc = launch_intake_streams(c, L.frames, pcm_in, c->d_mixed, 0, c->n_streams))) return rc; a.pcm = c->d_mixed; }
+    if ((rc = launch_rows(c, a, L, 0, c->n_wg))) return rc;
     if (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, pc->words, 0, c->n_streams))) return rc;
     return clip_out ? gather_clip(c, clip_out) : DSPI_OK;
 }
@@ -1869,11 +1913,15 @@ static void completion_word(dspi_ctx *c) {
 }
 
 static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags,
-                          std::chrono::steady_clock::time_point call_t0, const PdmCall *pc) {
+                          std::chrono::steady_clock::time_point call_t0, const PdmCall *pc, const MixedIn *mx) {
     int rc = direct_area(c, L.direct_bytes);
     if (rc) return rc;
     char *const h = c->h_direct, *const d = c->d_direct;
-    memcpy(h, pcm_in, L.pcm.bytes);
+    if (mx) {      // the copy widens as it copies (a paused stream's bytes are not read, and nobody reads its run of the area)
+        for (uint32_t s = 0; s < c->n_streams; s++)
+            if (!c->n_paused || c->active[s])
+                intake_widen_cpu(reinterpret_cast<uint8_t *>(h) + (size_t)s * L.pcm.per, static_cast<const uint8_t *>(pcm_in) + mx->offsets[s], mx->depths[s], L.frames);
+    } else memcpy(h, pcm_in, L.pcm.bytes);
     a.pcm = d;
     if (out->pairs) a.pairs = reinterpret_cast<int32_t *>(d + L.pairs.off);
     if (out->sub) a.sub = reinterpret_cast<int32_t *>(d + L.sub.off);
@@ -1949,7 +1997,7 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
 // cut into chunks and chunk i's D2H runs while chunk i+1 computes and chunk i+2 uploads (three streams, events).  The caller's
 // buffers are pinned for the duration of the call (hipHostRegister: ~8 ms per GiB) so that the copies are asynchronous DMA; when
 // that is refused (already registered, read-only mapping ...) the copies still work, just synchronously. ----
-static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags, const PdmCall *pc) {
+static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags, const PdmCall *pc, const MixedIn *mx) {
     int rc;
     if ((rc = ensure(c, c->d_in, c->d_in_cap, L.pcm.bytes))) return rc;
     a.pcm = c->d_in;
@@ -1983,8 +2031,11 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) return rc;
     const uint32_t n_chunks = L.n_chunks, row = (uint32_t)c->sm.row;
     // the caller's buffers and the staging buffers: a row range is one contiguous piece of each (tiled words: whole tiles; else streams)
+    // (dspi_process_mixed: the caller's PCM is as long as its depths make it, and a chunk's piece of it goes up to the same place of d_mixed_up)
+    CallBuffer pcm_b = L.pcm;
+    if (mx) pcm_b.bytes = (size_t)mx->offsets.back();
     struct Buf { void *host; void *dev; const CallBuffer &b; const char *what; bool pinned; };
-    Buf bufs[5] = {{const_cast<void *>(pcm_in), c->d_in, L.pcm, "H2D", false}, {out->pairs, a.pairs, L.pairs, "D2H pairs", false},
+    Buf bufs[5] = {{const_cast<void *>(pcm_in), mx ? (void *)c->d_mixed_up : c->d_in, pcm_b, "H2D", false}, {out->pairs, a.pairs, L.pairs, "D2H pairs", false},
                    {out->sub, a.sub, L.sub, "D2H sub", false}, {out->peaks, a.peaks, L.peaks, "D2H peaks", false},
                    {pc ? pc->words : nullptr, c->d_pdm_out, L.pdm_words, "D2H pdm words", false}};
     if (n_chunks > 1)
@@ -2021,11 +2072,17 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
             return kind == hipMemcpyHostToDevice ? hipMemcpyAsync(d, h, n, kind, s) : hipMemcpyAsync(h, d, n, kind, s);
         };
         hipStream_t sin = n_chunks > 1 ? c->hs_in : c->hs, sout = n_chunks > 1 ? c->hs_out : c->hs;
-        if ((he = copy(bufs[0], hipMemcpyHostToDevice, sin)) != hipSuccess) return fail_hip(he, bufs[0].what);
+        if (mx) {
+            uint64_t b0, b1;
+            intake_row_range(mx->offsets.data(), c->n_streams, row, r0, r1, &b0, &b1);
+            he = hipMemcpyAsync(c->d_mixed_up + b0, static_cast<const char *>(pcm_in) + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, sin);
+        } else he = copy(bufs[0], hipMemcpyHostToDevice, sin);
+        if (he != hipSuccess) return fail_hip(he, bufs[0].what);
         if (n_chunks > 1) {
             if ((he = hipEventRecord(c->pipe_events[2 * ch], sin)) != hipSuccess || (he = hipStreamWaitEvent(c->hs, c->pipe_events[2 * ch], 0)) != hipSuccess) return fail_hip(he, "event");
         }
         if (pc && !out->sub) a.sub = c->d_sub - s0 * L.frames;      // (the chunk's first stream or tile stands at the scratch's start, in both layouts)
+        if (mx && (rc = launch_intake_streams(c, L.frames, c->d_mixed_up, c->d_in, s0, s1))) { unpin(); return rc; }
         if ((rc = launch_rows(c, a, L, r0, r1)) || (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, c->d_pdm_out, s0, s1)))) { unpin(); return rc; }
         if (n_chunks > 1) {
             if ((he = hipEventRecord(c->pipe_events[2 * ch + 1], c->hs)) != hipSuccess || (he = hipStreamWaitEvent(sout, c->pipe_events[2 * ch + 1], 0)) != hipSuccess) return fail_hip(he, "event");
@@ -2046,19 +2103,30 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     return DSPI_OK;
 }
 
-// the one body of dspi_process (pdm_words == nullptr) and dspi_process_pdm
-static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
-    if (!c || !pcm_in || !out) return DSPI_E_INVAL;
+// the one body of dspi_process (pdm_words == nullptr), dspi_process_pdm and (mx: its layout) dspi_process_mixed on depths that differ
+// What the audio calls refuse about their flags: the two rules, each in one place.  process_call applies them where dspi_process always
+// has (the bits first of all, the combinations behind the host-only context's refusal: tests/test_capi.py pins that order);
+// dspi_process_mixed applies both ahead of its own refusals, as its contract orders them.  A new flag rule goes INTO one of the two.
+static int check_flag_bits(dspi_ctx *c, uint32_t flags) {
     // undefined flag bits are refused, not ignored: a later ABI may give them a meaning that reads further members of dspi_out
     constexpr uint32_t kKnownFlags = DSPI_MEM_DEVICE | DSPI_OUT_TILED | DSPI_OUT_ENABLED_ONLY | DSPI_OUT_I2S_SLOTS | DSPI_OUT_SPDIF | DSPI_OUT_CLIP_FLAGS;
-    if (flags & ~kKnownFlags) return fail(c, DSPI_E_INVAL, "dspi_process: undefined flag bits");
+    return (flags & ~kKnownFlags) ? fail(c, DSPI_E_INVAL, "dspi_process: undefined flag bits") : 0;
+}
+static int check_flag_combinations(dspi_ctx *c, uint32_t flags) {
+    if ((flags & DSPI_OUT_SPDIF) && (flags & (DSPI_OUT_TILED | DSPI_OUT_I2S_SLOTS))) return fail(c, DSPI_E_INVAL, "DSPI_OUT_SPDIF goes with neither DSPI_OUT_TILED nor DSPI_OUT_I2S_SLOTS");
+    return 0;
+}
+static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags,
+                        const MixedIn *mx = nullptr) {
+    if (!c || !pcm_in || !out) return DSPI_E_INVAL;
+    int rc = check_flag_bits(c, flags);
+    if (rc) return rc;
     if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
     if ((bit_depth != 16 && bit_depth != 24) || n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN)
         return fail(c, DSPI_E_INVAL, "bit_depth must be 16/24, 1 <= block_len <= 192, n_blocks >= 1");
     const auto call_t0 = std::chrono::steady_clock::now();
     HIPCK(c, hipSetDevice(c->device));
-    int rc = commit_params(c);
-    if (rc || (rc = check_leveller_alphas(c, block_len))) return rc;
+    if ((rc = commit_params(c)) || (rc = check_leveller_alphas(c, block_len))) return rc;
 
     // DSPI_OUT_CLIP_FLAGS: the caller's dspi_out has the ABI-7 member `clip_flags`
     uint16_t *const clip_out = (flags & DSPI_OUT_CLIP_FLAGS) ? out->clip_flags : nullptr;
@@ -2071,11 +2139,13 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
         if (pi.group != PathGroup::Latency && !c->plan.items[(int)pi.path].empty()) in.all_latency = false;
     const CallLayout L = plan_call(in);
     const bool tiled = flags & DSPI_OUT_TILED, spdif = flags & DSPI_OUT_SPDIF;
-    if (spdif && (tiled || (flags & DSPI_OUT_I2S_SLOTS))) return fail(c, DSPI_E_INVAL, "DSPI_OUT_SPDIF goes with neither DSPI_OUT_TILED nor DSPI_OUT_I2S_SLOTS");
+    if ((rc = check_flag_combinations(c, flags))) return rc;
     if (L.spdif_two_pass && c->spdif_ps.on && (rc = upload_spdif_pos(c))) return rc;
     PdmCall pdm{pdm_words, nullptr};
     const PdmCall *const pc = pdm_words ? &pdm : nullptr;
     if (pc && (rc = pdm_prepare(c, pdm))) return rc;
+    if (mx && L.mem == CallMem::Device && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed, c->d_mixed_cap, L.pcm.bytes))) return rc;
+    if (mx && L.mem == CallMem::Staged && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed_up, c->d_mixed_up_cap, (size_t)mx->offsets.back()))) return rc;
 
     KArgs a{};
     a.img = c->d_images; a.stream_image = c->d_stream_image; a.vals = c->d_vals;
@@ -2095,9 +2165,9 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     }
 
     switch (L.mem) {
-    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out, pc); break;
-    case CallMem::Direct: rc = process_direct(c, L, a, pcm_in, out, clip_out, flags, call_t0, pc); break;
-    case CallMem::Staged: rc = process_staged(c, L, a, pcm_in, out, clip_out, flags, pc); break;
+    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out, pc, mx); break;
+    case CallMem::Direct: rc = process_direct(c, L, a, pcm_in, out, clip_out, flags, call_t0, pc, mx); break;
+    case CallMem::Staged: rc = process_staged(c, L, a, pcm_in, out, clip_out, flags, pc, mx); break;
     }
     if (rc == DSPI_OK && pc) { c->pdm_life.commit(); c->pdm_fade.commit(c->pdm_life, (uint32_t)L.frames); }      // a failed call leaves the running bytes and the fade positions alone
     if (rc == DSPI_OK && spdif) {      // a failed call leaves the block positions alone
@@ -2114,6 +2184,62 @@ int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_bloc
 int dspi_process_pdm(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
     if (!c || !pdm_words) return DSPI_E_INVAL;
     return process_call(c, pcm_in, bit_depth, n_blocks, block_len, out, pdm_words, flags);
+}
+
+// ---- 16- and 24-bit devices in one call (dspi_intake.h: the layout and why widening is exact; dspi_intake.hip: the kernel) ----
+// what both calls refuse about their arguments, in dspi_process's words
+static int mixed_check(dspi_ctx *c, const uint8_t *depths, uint32_t n_blocks, uint32_t block_len, const char *who) {
+    const uint32_t bad = intake_check_depths(depths, c->n_streams);
+    if (bad < c->n_streams) return fail(c, DSPI_E_INVAL, std::string(who) + ": the depth of stream " + std::to_string(bad) + " is neither 16 nor 24");
+    if (n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN) return fail(c, DSPI_E_INVAL, std::string(who) + ": 1 <= block_len <= 192, n_blocks >= 1");
+    return 0;
+}
+
+int dspi_mixed_pcm_bytes(const dspi_ctx *c, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len, uint64_t *total_bytes, uint64_t *offsets) {
+    if (!c || !bit_depths) return DSPI_E_INVAL;
+    int rc = mixed_check(const_cast<dspi_ctx *>(c), bit_depths, n_blocks, block_len, "dspi_mixed_pcm_bytes");
+    if (rc) return rc;
+    if (!intake_offsets(bit_depths, c->n_streams, (uint64_t)n_blocks * block_len, total_bytes, offsets)) return fail(const_cast<dspi_ctx *>(c), DSPI_E_INVAL, "dspi_mixed_pcm_bytes: the buffer's size overflows");
+    return DSPI_OK;
+}
+
+int dspi_process_mixed(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
+    if (!c || !pcm_in || !bit_depths || !out) return DSPI_E_INVAL;
+    int rc = mixed_check(c, bit_depths, n_blocks, block_len, "dspi_process_mixed");
+    if (rc) return rc;
+    // every entry equal: the call IS dspi_process / dspi_process_pdm at that depth (which refuses a bad flag bit and a host-only context itself)
+    if (const uint8_t depth = intake_uniform_depth(bit_depths, c->n_streams)) return process_call(c, pcm_in, depth, n_blocks, block_len, out, pdm_words, flags);
+    if ((rc = check_flag_bits(c, flags)) || (rc = check_flag_combinations(c, flags))) return rc;
+    MixedIn mx{bit_depths, std::vector<uint64_t>((size_t)c->n_streams + 1)};
+    if (!intake_offsets(bit_depths, c->n_streams, (uint64_t)n_blocks * block_len, nullptr, mx.offsets.data())) return fail(c, DSPI_E_INVAL, "dspi_process_mixed: the buffer's size overflows");
+    // the one case in which a 16-bit sample and its widened twin part ways (dspi_intake.h): refused, not approximated
+    if (c->flavor)
+        for (uint32_t s = 0; s < c->n_streams; s++) {
+            if (bit_depths[s] != 16 || (c->n_paused && !c->active[s])) continue;
+            for (const float p : readable(c, (int32_t)s).preamp_linear) {
+                uint32_t w; memcpy(&w, &p, 4);
+                if (intake_preamp_breaks_widening(w))
+                    return fail(c, DSPI_E_UNSUPPORTED, "dspi_process_mixed: stream " + std::to_string(s) + " takes 16-bit input with a preamp below 2^-103, where widening to 24 bit is not exact");
+            }
+        }
+    return process_call(c, pcm_in, 24, n_blocks, block_len, out, pdm_words, flags, &mx);
+}
+
+// the prepass of a device-buffer mixed call alone, into the context's scratch: what tools/bench_mixed.py times (no chain, nothing advanced)
+int dspi_debug_intake(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len) {
+    if (!c || !pcm_in || !bit_depths) return DSPI_E_INVAL;
+    int rc = mixed_check(c, bit_depths, n_blocks, block_len, "dspi_debug_intake");
+    if (rc) return rc;
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no intake");
+    const uint64_t frames = (uint64_t)n_blocks * block_len;
+    MixedIn mx{bit_depths, std::vector<uint64_t>((size_t)c->n_streams + 1)};
+    uint64_t out_bytes = 0;
+    if (!intake_offsets(bit_depths, c->n_streams, frames, nullptr, mx.offsets.data()) || __builtin_mul_overflow((uint64_t)c->n_streams * kIntakeOutFrame, frames, &out_bytes))
+        return fail(c, DSPI_E_INVAL, "dspi_debug_intake: the buffer's size overflows");
+    HIPCK(c, hipSetDevice(c->device));
+    if (c->n_paused && (rc = upload_activity(c))) return rc;
+    if ((rc = intake_prepare(c, mx, frames, c->d_mixed, c->d_mixed_cap, (size_t)out_bytes))) return rc;
+    return launch_intake_streams(c, frames, pcm_in, c->d_mixed, 0, c->n_streams);
 }
 
 int dspi_pdm_running(dspi_ctx *c, uint32_t first, uint32_t count, const uint8_t *set, uint8_t *get) {

@@ -135,4 +135,11 @@ hipError_t launch_migrate_positions(int flavor, const uint32_t *state, const uin
 // `items` = n_items BootRowItem in device memory, one per touched row.  Reads nothing but the two position words of each item's target.
 hipError_t launch_boot(int flavor, const StateArrays &arr, const uint32_t *items, uint32_t n_items, hipStream_t stream);
 
+// ---- the intake of dspi_process_mixed (dspi_intake.h: the layout; dspi_intake.hip: the kernel) ----
+// Streams [first, first + count) of the caller's mixed-depth bytes (stream s at src + offsets[s], depths[s] = 16 or 24; offsets [n_streams + 1]
+// and depths [n_streams] in device memory, addressed by absolute stream like `active`, the activity bitmap or null) into dst + 6 frames s,
+// packed 24 bit.  src and dst are 2-byte aligned; a paused stream is neither read nor written.
+hipError_t launch_intake(const void *src, const uint64_t *offsets, const uint8_t *depths, const uint32_t *active, void *dst, uint64_t frames,
+                         uint32_t first, uint32_t count, hipStream_t stream);
+
 }  // namespace dspi

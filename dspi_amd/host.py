@@ -145,6 +145,10 @@ def lib() -> C.CDLL:
     if hasattr(L, "dspi_pdm_fade"):      # (ABI 8 + the PDM fade-out on disable: detected by symbol; with it dspi_pdm_fade_state)
         L.dspi_pdm_fade.argtypes = [vp, C.c_int]
         L.dspi_pdm_fade_state.argtypes = [vp, u32, u32, vp, vp]
+    if hasattr(L, "dspi_process_mixed"):      # (ABI 8 + mixed input formats: detected by symbol; with it dspi_mixed_pcm_bytes)
+        L.dspi_mixed_pcm_bytes.argtypes = [vp, vp, u32, u32, C.POINTER(C.c_uint64), vp]
+        L.dspi_process_mixed.argtypes = [vp, vp, vp, u32, u32, C.POINTER(_Out), vp, u32]
+        L.dspi_debug_intake.argtypes = [vp, vp, vp, u32, u32]
     _lib = L
     return L
 
@@ -364,6 +368,58 @@ class Dspi:
         out = _Out(pairs_ptr or None, sub_ptr or None, peaks_ptr or None, None)
         self._ck(self.L.dspi_process_pdm(self.h, pcm_ptr, bit_depth, n_blocks, block_len, C.byref(out), words_ptr,
                                          MEM_DEVICE | (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0)), "process_pdm")
+
+    # ---- 16- and 24-bit devices in one call (include/dspi.h: dspi_process_mixed) ----
+    def _depths(self, bit_depths) -> np.ndarray:
+        d = np.ascontiguousarray(np.asarray(bit_depths, dtype=np.uint8).reshape(-1))
+        assert d.size == self.n_streams, (d.size, self.n_streams)
+        return d
+
+    def mixed_pcm_bytes(self, bit_depths, n_blocks: int, block_len: int):
+        """dspi_mixed_pcm_bytes: (total bytes, offsets uint64 [n_streams + 1]) of the PCM buffer of a dspi_process_mixed call with these depths
+        (uint8 [n_streams], each 16 or 24).  Works on host-only contexts."""
+        d = self._depths(bit_depths)
+        total, off = C.c_uint64(0), np.zeros(self.n_streams + 1, dtype=np.uint64)
+        self._ck(self.L.dspi_mixed_pcm_bytes(self.h, d.ctypes.data, n_blocks, block_len, C.byref(total), off.ctypes.data), "mixed_pcm_bytes")
+        return total.value, off
+
+    def process_mixed_host(self, pcm: np.ndarray, bit_depths, n_blocks: int, block_len: int, want_pairs=True, want_sub=True, want_peaks=True,
+                           tiled=False, enabled_only=False, spdif=False, clip=False, pdm=False, words=None):
+        """dspi_process_mixed on host arrays: pcm = one flat uint8 array, every stream's run of frames at its own depth back to back
+        (mixed_pcm_bytes); bit_depths uint8 [n_streams].  Returns process_host's (pairs, sub, peaks); with pdm=True (or `words` given)
+        process_pdm_host's (pairs, sub, peaks, words).  clip=True: self.last_clip as after process_host."""
+        S, F = self.n_streams, n_blocks * block_len
+        d = self._depths(bit_depths)
+        pcm = np.ascontiguousarray(pcm, dtype=np.uint8).reshape(-1)
+        if np.isin(d, (16, 24)).all(): assert pcm.nbytes == F * int(np.where(d == 24, 6, 4).sum()), (pcm.nbytes, S, F)      # (bad depths are the library's to refuse)
+        R = self.tile_streams(); nt = (S + R - 1) // R
+        if tiled:
+            pairs = np.zeros((nt, self.P * 2, F, R), dtype=np.int32) if want_pairs else None
+            sub = np.zeros((nt, F, R), dtype=np.int32) if want_sub else None
+        else:
+            pairs = (np.zeros((S, self.P, F, 4), dtype=np.uint32) if spdif else np.zeros((S, self.P, F, 2), dtype=np.int32)) if want_pairs else None
+            sub = np.zeros((S, F), dtype=np.int32) if want_sub else None
+        peaks = np.zeros((S, n_blocks, self.C), dtype=np.uint16) if want_peaks else None
+        if (pdm or words is not None) and words is None: words = np.zeros((nt, F, 8, R) if tiled else (S, F, 8), dtype=np.uint32)
+        if words is not None: assert words.dtype == np.uint32 and words.flags.c_contiguous and words.size == (nt * R if tiled else S) * F * 8
+        self.last_clip = np.zeros(S, dtype=np.uint16) if clip else None
+        out = _Out(pairs.ctypes.data if want_pairs else None, sub.ctypes.data if want_sub else None, peaks.ctypes.data if want_peaks else None, self.last_clip.ctypes.data if clip else None)
+        self._ck(self.L.dspi_process_mixed(self.h, pcm.ctypes.data, d.ctypes.data, n_blocks, block_len, C.byref(out), words.ctypes.data if words is not None else None,
+                                           (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_SPDIF if spdif else 0) | (OUT_CLIP_FLAGS if clip else 0)), "process_mixed")
+        return (pairs, sub, peaks) if words is None else (pairs, sub, peaks, words)
+
+    def process_mixed_device(self, pcm_ptr: int, bit_depths, n_blocks: int, block_len: int, pairs_ptr: int = 0, sub_ptr: int = 0, peaks_ptr: int = 0,
+                             words_ptr: int = 0, tiled: bool = False, enabled_only: bool = False, spdif: bool = False, clip_ptr: int = 0):
+        """dspi_process_mixed on raw device pointers (the depths stay a host array); asynchronous, see sync().  words_ptr: as process_pdm_device."""
+        d = self._depths(bit_depths)
+        out = _Out(pairs_ptr or None, sub_ptr or None, peaks_ptr or None, clip_ptr or None)
+        self._ck(self.L.dspi_process_mixed(self.h, pcm_ptr, d.ctypes.data, n_blocks, block_len, C.byref(out), words_ptr or None,
+                                           MEM_DEVICE | (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_SPDIF if spdif else 0) | (OUT_CLIP_FLAGS if clip_ptr else 0)), "process_mixed")
+
+    def debug_intake(self, pcm_ptr: int, bit_depths, n_blocks: int, block_len: int):
+        """dspi_debug_intake: the widening pass of process_mixed_device alone, into the context's scratch; asynchronous, see sync()."""
+        d = self._depths(bit_depths)
+        self._ck(self.L.dspi_debug_intake(self.h, pcm_ptr, d.ctypes.data, n_blocks, block_len), "debug_intake")
 
     def pdm_running(self, first: int = 0, count: int | None = None, set=None) -> np.ndarray:
         """dspi_pdm_running: the running bytes of streams [first, first + count) (default: to the end), after writing `set` (0 / 1 each) if given."""

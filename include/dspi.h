@@ -75,7 +75,8 @@ extern "C" {
                               * 8 + per-stream S/PDIF positions: detect by symbol (dspi_spdif_per_stream; with it dspi_spdif_stream_pos, dspi_spdif_encode_v; additions only);
                               * 8 + resizing: detect by symbol (dspi_resize_streams; with it dspi_reserve_streams, dspi_stream_capacity, DSPI_RESIZE_PAUSED; additions only);
                               * 8 + grouping: detect by symbol (dspi_plan_grouping; with it DSPI_GROUP_ONE_WAY; additions only);
-                              * 8 + PDM words from the call: detect by symbol (dspi_process_pdm; with it dspi_pdm_running; additions only) */
+                              * 8 + PDM words from the call: detect by symbol (dspi_process_pdm; with it dspi_pdm_running; additions only);
+                              * 8 + mixed input formats: detect by symbol (dspi_process_mixed; with it dspi_mixed_pcm_bytes; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -687,6 +688,45 @@ int dspi_pdm_running(dspi_ctx *ctx, uint32_t first, uint32_t count, const uint8_
 int dspi_pdm_fade(dspi_ctx *ctx, int enable);
 int dspi_pdm_fade_state(dspi_ctx *ctx, uint32_t first, uint32_t count, const uint32_t *set, uint32_t *get);
 
+/* ---- 16- and 24-bit devices in one call ------------------------------------------------------------------------------------------ */
+/* A device's USB host chooses its input format (the alternate setting sets usb_input_bit_depth, usb_audio.c:1575-1585; process_audio_packet
+ * reads it per packet, :528-530).  dspi_process_mixed is dspi_process (pdm_words NULL) or dspi_process_pdm (else) with the format per
+ * STREAM instead of per call:
+ *   bit_depths   uint8 [dspi_num_streams], HOST memory always (like the lists of dspi_move_streams), every entry 16 or 24 — a paused stream's
+ *                too: its entry sizes its slot.  An argument of the call, as the PCM is: no context state, nothing travels with a stream.
+ *   pcm_in       the [stream][F] frames of dspi_process, F = n_blocks * block_len, each stream at its own frame size, tight:
+ *                offset[0] = 0, offset[s + 1] = offset[s] + F * (bit_depths[s] == 24 ? 6 : 4).  A stream's run is only 2-byte aligned (so is
+ *                pcm_in itself).  A paused stream's bytes are present and never read.  Host or device memory as `flags` says.
+ * dspi_mixed_pcm_bytes gives the buffer's size (*total_bytes, may be NULL) and the n_streams + 1 offsets (may be NULL) for a depth vector;
+ * it works on host-only contexts.  Outputs, flags, the three memory paths, asynchrony, the S/PDIF and PDM bookkeeping and "a failed call
+ * changes nothing" are exactly those of dspi_process / dspi_process_pdm.
+ *
+ * WHY THIS IS EXACT.  A 16-bit sample s and the 24-bit sample s << 8 go through the firmware's arithmetic identically, so the library
+ * widens the 16-bit runs (s becomes the bytes 00 lo hi) in front of the unchanged 24-bit chain:
+ *   float (usb_audio.c:601-603 against :680-681)   the gains are 2^-23 p and 2^-15 p (p: the channel's preamp); (float)(s << 8) =
+ *         256 (float)s exactly; both products are therefore roundings of the same real number — while both gains are exact, which they
+ *         are while 2^-23 p is a normal binary32: p >= 2^-103.
+ *   Q28 (usb_audio.c:1001-1002 against :1010-1011)   the 24-bit route is (s24 << 8) >> 2; (s16 << 8) through it equals s16 << 14, the
+ *         16-bit route.
+ * The one case where the identity fails is refused: update_preamp (usb_audio.c:244-250) does not clamp, and a preamp below 2^-103 (about
+ * -620 dB) makes the 24-bit gain subnormal.
+ *
+ * REFUSALS, each before anything is written or advanced, in this order:
+ *   DSPI_E_INVAL        a NULL pointer (ctx, pcm_in, bit_depths, out); a depth that is neither 16 nor 24; n_blocks, block_len or a flag bit
+ *                       that dspi_process refuses.
+ *   DSPI_E_UNSUPPORTED  on a float context, an ACTIVE 16-bit stream whose parameter object has a preamp p with 0 < p < 2^-103 on either input
+ *                       channel; dspi_last_error names the stream.  24-bit streams, paused streams and Q28 contexts are never refused for this.
+ *   DSPI_E_NODEVICE     a host-only context.
+ * UNIFORM DEPTHS: when every entry is equal the call IS dspi_process / dspi_process_pdm at that depth — no widening pass, no scratch, no
+ * preamp refusal.  Otherwise: device buffers go through one more launch (dspi_intake.hip) into a scratch of n_streams * 6F bytes that the
+ * context owns (DSPI_E_NOMEM all-or-nothing); small host calls widen on the CPU while copying into the pinned area, no extra launch; large
+ * host calls upload each chunk's bytes as they are and widen on the device.
+ * The ABI stays 8: detect by symbol (dspi_process_mixed; with it dspi_mixed_pcm_bytes; additions only). */
+int dspi_mixed_pcm_bytes(const dspi_ctx *ctx, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len,
+                         uint64_t *total_bytes, uint64_t *offsets /* [n_streams + 1] or NULL */);
+int dspi_process_mixed(dspi_ctx *ctx, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len,
+                       const dspi_out *out, uint32_t *pdm_words /* NULL: as dspi_process; else as dspi_process_pdm */, uint32_t flags);
+
 /* ---- S/PDIF subframes ---------------------------------------------------- */
 /* What the firmware's S/PDIF outputs do to the words of dspi_out.pairs before the PIO shifts them out
  * (pico_audio_spdif_multi: spdif_update_subframe, sample_encoding.h:27-47; preambles Z/X/Y, consumer channel status with
@@ -807,6 +847,12 @@ int dspi_debug_image_count(dspi_ctx *ctx);
  *                          same input and the same filter state: the per-stage rounding difference between the two
  * Host buffers; n <= 2^20.  The chain's own state is not touched. */
 int dspi_debug_eq_taps(dspi_ctx *ctx, int32_t stream, int channel, const float *x, uint32_t n, float *taps, float *other);
+
+/* The widening pass of a dspi_process_mixed call on device buffers, alone: pcm_in (DEVICE memory) and bit_depths (host memory) as in that
+ * call, one launch on the context's stream into the context's scratch, asynchronous.  No chain runs, nothing is advanced, no preamp is looked
+ * at; uniform depths are widened like any others.  For timing the pass (tools/bench_mixed.py); comes with dspi_process_mixed.
+ * DSPI_E_INVAL as for that call's pointers, depths and lengths; DSPI_E_NODEVICE on a host-only context. */
+int dspi_debug_intake(dspi_ctx *ctx, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len);
 
 #ifdef __cplusplus
 }
