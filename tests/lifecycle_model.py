@@ -491,14 +491,23 @@ class Life(BootSched):
         self.sp[to:to + len(stash["sp"])] = stash["sp"]
 
     # -- one dspi_process call in any form
-    def run(self, n, mem="host", tiled=False, enabled_only=False, clip=True, i2s=False, spdif=False, **_):
-        d, B, depth = self.d, self.B, self.depth
+    # (lib_host, lib_device, call and part_form are the seams a subclass with other calls overrides: tests/lifecycle_wide.py)
+    def lib_host(self, pcm, n, **flags):
+        return self.d.process_host(pcm, n, self.B, self.depth, **flags)
+
+    def lib_device(self, pcm_ptr, n, pairs_ptr, sub_ptr, peaks_ptr, **flags):
+        self.d.process_device(pcm_ptr, n, self.B, self.depth, pairs_ptr, sub_ptr, peaks_ptr, **flags)
+
+    def part_form(self, s):
+        return {}
+
+    def call(self, pcm, n, mem, tiled, enabled_only, clip, i2s, spdif):
+        """the library call on host or device buffers: (pairs, sub, peaks, clip flags or None, the value of an unwritten word, of an unwritten peak), stream-major"""
+        d, B = self.d, self.B
         S, F, P, R = d.n_streams, n * B, d.P, d.tile_streams()
-        pcm, paused = self.input(n)
-        assert np.array_equal(paused, self.paused)
         nt = -(-S // R)
         if mem == "host":
-            pairs, sub, peaks = d.process_host(pcm, n, B, depth, tiled=tiled, enabled_only=enabled_only, i2s_slots=i2s, spdif=spdif, clip=clip)
+            pairs, sub, peaks = self.lib_host(pcm, n, tiled=tiled, enabled_only=enabled_only, i2s_slots=i2s, spdif=spdif, clip=clip)
             flags = d.last_clip.copy() if clip else None
             fill, kfill = 0, 0
         else:
@@ -510,8 +519,8 @@ class Life(BootSched):
             t_peaks = torch.full((S, n, d.C), 0x5A5A, dtype=torch.int16, device=dev)
             t_clip = torch.full((S,), 0x5A5A, dtype=torch.int16, device=dev)
             torch.cuda.synchronize()
-            d.process_device(t_pcm.data_ptr(), n, B, depth, t_pairs.data_ptr(), t_sub.data_ptr(), t_peaks.data_ptr(), tiled=tiled, enabled_only=enabled_only,
-                             i2s_slots=i2s, spdif=spdif, clip_ptr=t_clip.data_ptr() if clip else 0)
+            self.lib_device(t_pcm.data_ptr(), n, t_pairs.data_ptr(), t_sub.data_ptr(), t_peaks.data_ptr(), tiled=tiled, enabled_only=enabled_only,
+                            i2s_slots=i2s, spdif=spdif, clip_ptr=t_clip.data_ptr() if clip else 0)
             d.sync()
             pairs, sub, peaks = t_pairs.cpu().numpy(), t_sub.cpu().numpy(), t_peaks.cpu().numpy().view(np.uint16)
             flags = t_clip.cpu().numpy().view(np.uint16) if clip else None
@@ -521,6 +530,14 @@ class Life(BootSched):
                 assert (pairs.transpose(0, 3, 1, 2).reshape(nt * R, -1)[S:] == fill).all() and (sub.transpose(0, 2, 1).reshape(nt * R, -1)[S:] == fill).all(), "columns past the last stream were written"
             pairs, sub = d.untile(pairs, sub)
         if spdif: pairs = pairs.view(np.uint32)
+        return pairs, sub, peaks, flags, fill, kfill
+
+    def run(self, n, mem="host", tiled=False, enabled_only=False, clip=True, i2s=False, spdif=False, **_):
+        d, B = self.d, self.B
+        F = n * B
+        pcm, paused = self.input(n)
+        assert np.array_equal(paused, self.paused)
+        pairs, sub, peaks, flags, fill, kfill = self.call(pcm, n, mem, tiled, enabled_only, clip, i2s, spdif)
         # paused regions: zeros in host buffers, the untouched fill in device buffers (tiled: the column); frozen status bytes and clip flags
         for s in np.flatnonzero(paused):
             assert (pairs[s].view(np.int32) == fill).all() and (sub[s] == fill).all() and (peaks[s] == kfill).all(), f"paused stream {s}: its regions of the {mem} buffers were written"
@@ -532,22 +549,26 @@ class Life(BootSched):
             p0 = int(self.pos[s])
             status = d.status(int(s))
             self.last_clip[s] = int.from_bytes(status[-2:], "little")
-            self.parts[s].append((p0, p0 + n, (pairs[s], sub[s], peaks[s], flags[s] if flags is not None else None), status, dict(form, spdif=int(self.sp[s]) if spdif else None)))
+            self.parts[s].append((p0, p0 + n, (pairs[s], sub[s], peaks[s], flags[s] if flags is not None else None), status, dict(form, spdif=int(self.sp[s]) if spdif else None, **self.part_form(int(s)))))
             self.pos[s] += n
             if spdif: self.sp[s] = (self.sp[s] + F) % 192
         self.last_sub = sub
         return pairs, sub, peaks, flags
 
+    def modulated(self, sub, tiled=False):
+        """dspi_pdm_modulate's words for sub [S][F] (host buffers), stream-major"""
+        d = self.d
+        S, R = d.n_streams, d.tile_streams()
+        if not tiled: return d.pdm_host(sub)
+        nt = -(-S // R)
+        t = np.zeros((nt * R, sub.shape[1]), dtype=np.int32); t[:S] = sub
+        words = d.pdm_host(np.ascontiguousarray(t.reshape(nt, R, -1).transpose(0, 2, 1)), tiled=True)      # [tile][frame][8][R]
+        return words.transpose(0, 3, 1, 2).reshape(nt * R, sub.shape[1], 8)[:S]
+
     def modulate(self, tiled=False):
         """dspi_pdm_modulate on the sub words of the last run (host buffers)"""
-        d, sub = self.d, self.last_sub
-        S, R = d.n_streams, d.tile_streams()
-        if tiled:
-            nt = -(-S // R)
-            t = np.zeros((nt * R, sub.shape[1]), dtype=np.int32); t[:S] = sub
-            words = d.pdm_host(np.ascontiguousarray(t.reshape(nt, R, -1).transpose(0, 2, 1)), tiled=True)      # [tile][frame][8][R]
-            words = words.transpose(0, 3, 1, 2).reshape(nt * R, sub.shape[1], 8)[:S]
-        else: words = d.pdm_host(sub)
+        sub, S = self.last_sub, self.d.n_streams
+        words = self.modulated(sub, tiled)
         for s in range(S):
             if self.paused[s]: assert not words[s].any(), f"paused stream {s}: PDM words written"
             else: self.pdm[s].append((sub[s].copy(), words[s].copy()))
@@ -567,8 +588,15 @@ class Life(BootSched):
         assert distinct <= n <= d.n_streams, f"{what}: {n} parameter objects for {distinct} distinct parameter sets on {d.n_streams} streams"
 
     # -- the replay
+    def fed(self, s, p0, p1, form):
+        """(the bytes slot s's stream was fed in packets [p0, p1), their bit depth)"""
+        return packets(self.data[s], self.depth, self.B, p0, p1), self.depth
+
+    def at_part(self, o, s, form, at):
+        """(a subclass's own look at the replayed oracle before a part is fed)"""
+
     def verify(self, streams=None, what=""):
-        P, B, depth = self.d.P, self.B, self.depth
+        P, B = self.d.P, self.B
         for s in (range(self.d.n_streams) if streams is None else streams):
             s = int(s)
             tag = f"{what}{'booted ' if s in self.booted else ''}stream in slot {s}"
@@ -582,8 +610,10 @@ class Life(BootSched):
 
             for p0, p1, (pairs, sub, peaks, clip), status, form in self.parts[s]:
                 apply(p0)
-                rp, rs, rk, rclip = o.process(packets(self.data[s], depth, B, p0, p1), p1 - p0, B, depth)
                 at = f"{tag}, packets [{p0}, {p1})"
+                self.at_part(o, s, form, at)
+                pcm, depth = self.fed(s, p0, p1, form)
+                rp, rs, rk, rclip = o.process(pcm, p1 - p0, B, depth)
                 want = rp
                 if form["spdif"] is not None:      # the subframes of the oracle's words at the slot's recorded position and the stream's rate
                     want = np.stack([orclib.spdif_encode(rp[p], form["spdif"], rate[0])[0] for p in range(P)])
@@ -630,14 +660,16 @@ def new_lives(cfg, sizes_=None):
     return lives
 
 
-def execute(cfg, ops, lives, stashes=None):
-    """runs the ops on the contexts, the cheap checks after each; returns the stashes"""
+def execute(cfg, ops, lives, stashes=None, step=None):
+    """runs the ops on the contexts, the cheap checks after each; returns the stashes.  step(op, lives, stashes, what): a caller's own
+    executor for the kinds it adds (True where it has done the op)"""
     stashes = {} if stashes is None else stashes
     dump, code = flash_cases(FLAVORS[cfg["flavor"]])[0]
     for i, op in enumerate(ops):
         x, k = lives[op["ctx"]], op["op"]
         what = f"seed {cfg['seed']}, op {i} ({k})"
-        if k == "run": x.run(**{a: v for a, v in op.items() if a not in ("op", "ctx", "warm")})
+        if step and step(op, lives, stashes, what): pass
+        elif k == "run": x.run(**{a: v for a, v in op.items() if a not in ("op", "ctx", "warm")})
         elif k == "pdm": x.modulate(op["tiled"])
         elif k == "pause": x.pause(op["first"], op["count"])
         elif k == "resume": x.resume(op["first"], op["count"], op["as_is"])
