@@ -39,6 +39,7 @@
 #include "dspi_resize.h"
 #include "dspi_snapshot.h"
 #include "dspi_spdifpos.h"
+#include "dspi_wire.h"
 
 using namespace dspi;
 
@@ -1775,7 +1776,9 @@ static int launch_paths(dspi_ctx *c, KArgs &a, uint32_t r0, uint32_t r1) {
 
 // ... of a call (a: its arguments, a.pairs the caller's words).  Two-pass S/PDIF: L.two_pass_rows rows at a time into the scratch of pair
 // words, then the subframe encoder from there into a.pairs.  Paused streams: the chain leaves their words in the scratch stale, and the
-// ENCODER SKIPS them (SpdifRates::active) — the scratch is not zeroed —, so that in the caller's device buffer their subframes stay unwritten
+// ENCODER SKIPS them (SpdifRates::active) — the scratch is not zeroed —, so that in the caller's device buffer their subframes stay unwritten.
+// dspi_process_wire with an I2S slot in play (L.wire_encoder): the same route with the wire encoder (dspi_wire.hip) as the second pass; on the
+// host-buffer paths it also zeroes the I2S regions' second halves, which no word of the call reaches
 static int launch_rows(dspi_ctx *c, KArgs a, const CallLayout &L, uint32_t r0, uint32_t r1) {
     if (!L.spdif_two_pass) return launch_paths(c, a, r0, r1);
     char *const subframes = reinterpret_cast<char *>(a.pairs);
@@ -1786,10 +1789,15 @@ static int launch_rows(dspi_ctx *c, KArgs a, const CallLayout &L, uint32_t r0, u
         a.pairs = c->d_spdif_words; a.pairs_stream0 = (uint32_t)s0;      // the kernels index by absolute stream: stream s0 lands at the scratch's start
         int rc = launch_paths(c, a, q0, q1);
         if (rc) return rc;
-        hipError_t e = launch_spdif(false, c->d_spdif_words, reinterpret_cast<uint32_t *>(subframes + s0 * L.pairs.per), (uint32_t)(s1 - s0), (uint32_t)c->sm.n_pairs,
-                                    (uint32_t)L.frames, row, q1 - q0, c->spdif_ps.on ? c->spdif_ps.clock : c->spdif_pos, 0u,
-                                    SpdifRates{c->d_images, c->d_stream_image, (uint32_t)s0, activity(c)}, c->hs, c->spdif_ps.on ? c->d_spdif_ps : nullptr);
-        if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string("spdif encoder launch: ") + hipGetErrorString(e));
+        uint32_t *const dst = reinterpret_cast<uint32_t *>(subframes + s0 * L.pairs.per);
+        const uint32_t pos = c->spdif_ps.on ? c->spdif_ps.clock : c->spdif_pos;
+        const SpdifRates rates{c->d_images, c->d_stream_image, (uint32_t)s0, activity(c)};
+        const uint32_t *const stream_pos = c->spdif_ps.on ? c->d_spdif_ps : nullptr;
+        hipError_t e = L.wire_encoder ? launch_wire(c->d_spdif_words, dst, (uint32_t)(s1 - s0), (uint32_t)c->sm.n_pairs, (uint32_t)L.frames, pos, rates, L.mem != CallMem::Device,
+                                                    c->hs, stream_pos)
+                                      : launch_spdif(false, c->d_spdif_words, dst, (uint32_t)(s1 - s0), (uint32_t)c->sm.n_pairs, (uint32_t)L.frames, row, q1 - q0, pos, 0u, rates,
+                                                     c->hs, stream_pos);
+        if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string(L.wire_encoder ? "wire encoder launch: " : "spdif encoder launch: ") + hipGetErrorString(e));
     }
     return 0;
 }
@@ -2116,8 +2124,15 @@ static int check_flag_combinations(dspi_ctx *c, uint32_t flags) {
     if ((flags & DSPI_OUT_SPDIF) && (flags & (DSPI_OUT_TILED | DSPI_OUT_I2S_SLOTS))) return fail(c, DSPI_E_INVAL, "DSPI_OUT_SPDIF goes with neither DSPI_OUT_TILED nor DSPI_OUT_I2S_SLOTS");
     return 0;
 }
+// does an active stream's parameter object carry an I2S slot (dspi_wire.h)?  From the host's objects and its record of pauses: no commit needed
+static bool wire_slots_in_play(const dspi_ctx *c) {
+    std::vector<uint32_t> image_i2s(c->images.size(), 0u);
+    for (size_t i = 0; i < c->images.size(); i++) if (c->images[i]) image_i2s[i] = wire_i2s_mask(c->images[i]->output_types, (uint32_t)c->sm.n_pairs);
+    return wire_any_i2s(c->stream_image.data(), c->n_streams, host_activity(c), image_i2s.data());
+}
+// wire: dspi_process_wire (flags carry DSPI_OUT_SPDIF, which the wire layout implies): out->pairs in the wire layout
 static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags,
-                        const MixedIn *mx = nullptr) {
+                        const MixedIn *mx = nullptr, bool wire = false) {
     if (!c || !pcm_in || !out) return DSPI_E_INVAL;
     int rc = check_flag_bits(c, flags);
     if (rc) return rc;
@@ -2135,6 +2150,7 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     in.n_pairs = (uint32_t)c->sm.n_pairs; in.n_blocks = n_blocks; in.block_len = block_len; in.bit_depth = (uint32_t)bit_depth; in.flags = flags;
     in.pairs = out->pairs; in.sub = out->sub; in.peaks = out->peaks; in.clip = clip_out; in.no_direct = c->no_direct;
     in.all_latency = c->flavor != 0; in.spdif_per_stream = c->spdif_ps.on; in.pdm_words = pdm_words != nullptr;
+    in.wire_slots = wire && wire_slots_in_play(c);      // none in play: the call IS the DSPI_OUT_SPDIF call, route and bytes
     for (const PathInfo &pi : kPaths)
         if (pi.group != PathGroup::Latency && !c->plan.items[(int)pi.path].empty()) in.all_latency = false;
     const CallLayout L = plan_call(in);
@@ -2184,6 +2200,40 @@ int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_bloc
 int dspi_process_pdm(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
     if (!c || !pdm_words) return DSPI_E_INVAL;
     return process_call(c, pcm_in, bit_depth, n_blocks, block_len, out, pdm_words, flags);
+}
+
+// ---- S/PDIF and I2S slots in one call, per device (dspi_wire.h: the layout and the rules; dspi_wire.hip: the encoder) ----
+int dspi_process_wire(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    if (!wire_process_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_process_wire: the flags are DSPI_MEM_DEVICE, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
+    return process_call(c, pcm_in, bit_depth, n_blocks, block_len, out, pdm_words, flags | DSPI_OUT_SPDIF, nullptr, true);
+}
+
+int dspi_wire_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos, uint32_t *wire, uint32_t flags) {
+    if (!c || !pairs || !wire || !block_pos || n_frames == 0) return DSPI_E_INVAL;
+    if (!wire_encode_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_wire_encode: the only flag is DSPI_MEM_DEVICE");
+    const bool dev = flags & DSPI_MEM_DEVICE;
+    // host positions are validated before anything is launched; device positions are the kernel's to reduce modulo 192
+    if (!dev) for (uint32_t s = 0; s < c->n_streams; s++) if (block_pos[s] >= kSpdifBlock) return fail(c, DSPI_E_INVAL, "dspi_wire_encode: a position is 0..191");
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    HIPCK(c, hipSetDevice(c->device));
+    const size_t in_b = (size_t)c->n_streams * c->sm.n_pairs * n_frames * 8, out_b = in_b * 2, pos_b = (size_t)c->n_streams * 4;
+    const int32_t *d_in = pairs;
+    uint32_t *d_out = wire;
+    const uint32_t *d_pos = block_pos;
+    int rc;
+    if (!dev) {
+        if ((rc = ensure(c, c->d_spdif_in, c->d_spdif_in_cap, in_b)) || (rc = ensure(c, c->d_spdif_out, c->d_spdif_out_cap, out_b)) ||
+            (rc = ensure(c, c->d_spdif_vpos, c->d_spdif_vpos_cap, pos_b))) return rc;
+        HIPCK(c, hipMemcpyAsync(c->d_spdif_in, pairs, in_b, hipMemcpyHostToDevice, c->hs));
+        HIPCK(c, hipMemcpyAsync(c->d_spdif_vpos, block_pos, pos_b, hipMemcpyHostToDevice, c->hs));
+        d_in = c->d_spdif_in; d_out = c->d_spdif_out; d_pos = c->d_spdif_vpos;
+    }
+    // every stream's types and rate are its own image's: committed first (unaware of pauses, like dspi_spdif_encode_v)
+    if ((rc = commit_params(c))) return rc;
+    // (host buffers: the staging buffer comes back whole, so the encoder zeroes the I2S regions' second halves there)
+    HIPCK(c, launch_wire(d_in, d_out, c->n_streams, (uint32_t)c->sm.n_pairs, n_frames, 0u, SpdifRates{c->d_images, c->d_stream_image, 0u}, !dev, c->hs, d_pos));
+    return dev ? DSPI_OK : stage_down(c, wire, c->d_spdif_out, out_b);
 }
 
 // ---- 16- and 24-bit devices in one call (dspi_intake.h: the layout and why widening is exact; dspi_intake.hip: the kernel) ----

@@ -84,6 +84,12 @@ struct SpdifRates { const DevImage *img; const uint32_t *stream_image; uint32_t 
 // frame stands at (block_pos + stream_pos[..] mod 192) mod 192, block_pos < 192.
 hipError_t launch_spdif(bool tiled, const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames, uint32_t row,
                         uint32_t n_wg, uint32_t block_pos, uint32_t fs, const SpdifRates &rates, hipStream_t stream, const uint32_t *stream_pos = nullptr);
+// ---- the wire encoder (dspi_wire.hip; dspi_wire.h: the layout): launch_spdif's stream-major form with the TYPE of every pair taken from the
+// stream's own image (DevImage::i2s_pairs, beside the fs_hz the encoder reads there): subframes for an S/PDIF slot, slot words (word << 8) in
+// the first half of the region for an I2S slot.  rates.img and rates.stream_image are required; stream0, active and stream_pos as above.
+// zero_tails (the host-buffer paths): I2S lanes also store zeros over the second half of their region; else nothing writes it.
+hipError_t launch_wire(const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames, uint32_t block_pos, const SpdifRates &rates,
+                       bool zero_tails, hipStream_t stream, const uint32_t *stream_pos = nullptr);
 // I2S slots (audio_i2s_multi.c:217-226): words << 8 for the pairs in pair_mask; same layouts as the pair words themselves
 hipError_t launch_i2s(bool tiled, const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames, uint32_t row,
                       uint32_t n_wg, uint32_t pair_mask, hipStream_t stream);

@@ -338,7 +338,9 @@ CallLayout plan_call(const CallInput &in) {
     // worth of rows; one workgroup per CU (256 rows) only while that stays within 2 GiB; never less than one row.
     // With per-stream block positions (dspi_spdif_per_stream) every flagged call goes this way, the latency layout's launches too: its
     // kernels write plain pair words into the scratch (KArgs::pairs_stream0) and the encoder alone knows the streams' positions.
-    L.spdif_two_pass = spdif && in.pairs && (!in.all_latency || in.spdif_per_stream);
+    // dspi_process_wire with an I2S slot on an active stream (CallInput::wire_slots) goes this way for the same reason: the type is the stream's.
+    L.spdif_two_pass = spdif && in.pairs && (!in.all_latency || in.spdif_per_stream || in.wire_slots);
+    L.wire_encoder = L.spdif_two_pass && in.wire_slots;
     if (L.spdif_two_pass) {
         const size_t row_b = (size_t)in.row * in.n_pairs * F * 8;
         size_t rows = std::max<size_t>(1, ((size_t)1 << 30) / row_b);

@@ -149,6 +149,9 @@ def lib() -> C.CDLL:
         L.dspi_mixed_pcm_bytes.argtypes = [vp, vp, u32, u32, C.POINTER(C.c_uint64), vp]
         L.dspi_process_mixed.argtypes = [vp, vp, vp, u32, u32, C.POINTER(_Out), vp, u32]
         L.dspi_debug_intake.argtypes = [vp, vp, vp, u32, u32]
+    if hasattr(L, "dspi_process_wire"):      # (ABI 8 + wire words per device: detected by symbol; with it dspi_wire_encode)
+        L.dspi_process_wire.argtypes = [vp, vp, C.c_int, u32, u32, C.POINTER(_Out), vp, u32]
+        L.dspi_wire_encode.argtypes = [vp, vp, u32, vp, vp, u32]
     _lib = L
     return L
 
@@ -510,6 +513,48 @@ class Dspi:
     def spdif_encode_v_device(self, pairs_ptr: int, n_frames: int, block_pos_ptr: int, out_ptr: int, tiled: bool = False):
         """dspi_spdif_encode_v on device pointers (block_pos: uint32 [n_streams] in device memory, taken modulo 192); asynchronous, see sync()."""
         self._ck(self.L.dspi_spdif_encode_v(self.h, pairs_ptr, n_frames, block_pos_ptr, out_ptr, MEM_DEVICE | (OUT_TILED if tiled else 0)), "spdif_encode_v")
+
+    # ---- S/PDIF and I2S slots in one call, per device (include/dspi.h: dspi_process_wire / dspi_wire_encode) ----
+    def process_wire_host(self, pcm: np.ndarray, n_blocks: int, block_len: int, bit_depth: int = 16, want_sub=True, want_peaks=True, enabled_only=False,
+                          clip=False, pdm=False):
+        """dspi_process_wire on host arrays: (wire, sub, peaks) — wire uint32 [S][P][F][4] in the wire layout: an S/PDIF slot's region holds its
+        F x 4 subframe words, an I2S slot's region F x 2 slot words in its first half (wire[s, p].reshape(-1)[:2 * F]) and zeros behind.
+        pdm=True: (wire, sub, peaks, words) with the PDM words uint32 [S][F][8].  clip=True: self.last_clip as after process_host."""
+        S, F = self.n_streams, n_blocks * block_len
+        pcm = np.ascontiguousarray(pcm)
+        assert pcm.nbytes == S * F * (6 if bit_depth == 24 else 4), (pcm.shape, S, F)
+        wire = np.zeros((S, self.P, F, 4), dtype=np.uint32)
+        sub = np.zeros((S, F), dtype=np.int32) if want_sub else None
+        peaks = np.zeros((S, n_blocks, self.C), dtype=np.uint16) if want_peaks else None
+        words = np.zeros((S, F, 8), dtype=np.uint32) if pdm else None
+        self.last_clip = np.zeros(S, dtype=np.uint16) if clip else None
+        out = _Out(wire.ctypes.data, sub.ctypes.data if want_sub else None, peaks.ctypes.data if want_peaks else None, self.last_clip.ctypes.data if clip else None)
+        self._ck(self.L.dspi_process_wire(self.h, pcm.ctypes.data, bit_depth, n_blocks, block_len, C.byref(out), words.ctypes.data if pdm else None,
+                                          (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_CLIP_FLAGS if clip else 0)), "process_wire")
+        return (wire, sub, peaks, words) if pdm else (wire, sub, peaks)
+
+    def process_wire_device(self, pcm_ptr: int, n_blocks: int, block_len: int, wire_ptr: int, bit_depth: int = 16, sub_ptr: int = 0, peaks_ptr: int = 0,
+                            words_ptr: int = 0, enabled_only: bool = False, clip_ptr: int = 0):
+        """dspi_process_wire on raw device pointers (wire: uint32 [S][P][F][4]; the second half of an I2S slot's region is not written);
+        asynchronous, see sync()."""
+        out = _Out(wire_ptr or None, sub_ptr or None, peaks_ptr or None, clip_ptr or None)
+        self._ck(self.L.dspi_process_wire(self.h, pcm_ptr, bit_depth, n_blocks, block_len, C.byref(out), words_ptr or None,
+                                          MEM_DEVICE | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_CLIP_FLAGS if clip_ptr else 0)), "process_wire")
+
+    def wire_encode_host(self, pairs: np.ndarray, block_pos) -> np.ndarray:
+        """dspi_wire_encode on host arrays: pairs int32 [S][P][F][2], block_pos uint32 [S] (each 0..191) -> uint32 [S][P][F][4] in the wire layout
+        (process_wire_host), every stream's types and rate its own."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+        pos = np.ascontiguousarray(np.asarray(block_pos, dtype=np.uint32).reshape(-1))
+        assert len(pos) == self.n_streams, (len(pos), self.n_streams)
+        S, P, F, _ = pairs.shape
+        out = np.zeros((S, P, F, 4), dtype=np.uint32)
+        self._ck(self.L.dspi_wire_encode(self.h, pairs.ctypes.data, F, pos.ctypes.data, out.ctypes.data, 0), "wire_encode")
+        return out
+
+    def wire_encode_device(self, pairs_ptr: int, n_frames: int, block_pos_ptr: int, out_ptr: int):
+        """dspi_wire_encode on device pointers (block_pos: uint32 [S] in device memory, taken modulo 192); asynchronous, see sync()."""
+        self._ck(self.L.dspi_wire_encode(self.h, pairs_ptr, n_frames, block_pos_ptr, out_ptr, MEM_DEVICE), "wire_encode")
 
     def pdm_restart(self, stream: int = ALL):
         self._ck(self.L.dspi_pdm_restart(self.h, stream), "pdm_restart")

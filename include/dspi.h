@@ -76,7 +76,8 @@ extern "C" {
                               * 8 + resizing: detect by symbol (dspi_resize_streams; with it dspi_reserve_streams, dspi_stream_capacity, DSPI_RESIZE_PAUSED; additions only);
                               * 8 + grouping: detect by symbol (dspi_plan_grouping; with it DSPI_GROUP_ONE_WAY; additions only);
                               * 8 + PDM words from the call: detect by symbol (dspi_process_pdm; with it dspi_pdm_running; additions only);
-                              * 8 + mixed input formats: detect by symbol (dspi_process_mixed; with it dspi_mixed_pcm_bytes; additions only) */
+                              * 8 + mixed input formats: detect by symbol (dspi_process_mixed; with it dspi_mixed_pcm_bytes; additions only);
+                              * 8 + wire words per device: detect by symbol (dspi_process_wire; with it dspi_wire_encode; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -793,6 +794,44 @@ int dspi_spdif_encode_v(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, 
  * pair_mask = DSPI_I2S_PAIRS_BY_TYPE (0): the pairs whose current output type is I2S in stream 0's parameters (the type of a
  * slot is a property of the device, like the sample rate).  Returns the mask that was encoded (>= 0) or a negative DSPI_E_*. */
 #define DSPI_I2S_PAIRS_BY_TYPE 0u
+/* ---- S/PDIF and I2S slots in one call, per device ------------------------------------------------------------------------------------ */
+/* The driver a pair's words are for is a property of the DEVICE, per slot: output_types[slot], set by REQ_SET_OUTPUT_TYPE 0xC0 and carried
+ * by presets (config.h:286-287, main.c:230-424).  DSPI_OUT_SPDIF, DSPI_OUT_I2S_SLOTS and dspi_i2s_encode's DSPI_I2S_PAIRS_BY_TYPE take it
+ * from the call or from stream 0; the two calls below take it from every stream's OWN parameters, so a context whose devices differ in
+ * their types (slots 0-1 on S/PDIF and 2-3 on I2S here, all I2S there) gets what its drivers shift out from one call.
+ *
+ * THE WIRE LAYOUT has the size and the regions of DSPI_OUT_SPDIF: pair p of stream s owns the 16 F bytes at word offset
+ * ((s * P + p) * F) * 4, F = the call's frames, P = dspi_num_pairs.
+ *   S/PDIF slot   uint32 [F][4], exactly DSPI_OUT_SPDIF's subframes: the block position is the context's, or the stream's own while
+ *                 dspi_spdif_per_stream is on; the sample-rate byte is the stream's own.
+ *   I2S slot      (output_types[p] == 1)  uint32 [F][2], word << 8, L then R, in the FIRST 8 F bytes of the region: the words of dspi_i2s_encode
+ *                 / DSPI_OUT_I2S_SLOTS, contiguous as a DMA buffer wants them.  The LAST 8 F bytes of the region are never written in a
+ *                 caller's device buffer (DSPI_MEM_DEVICE) and come back as zeros in host buffers.
+ *   paused stream the existing rule: its regions are untouched in device buffers and zero in host buffers.
+ * A tiled wire layout is left out: both calls refuse DSPI_OUT_TILED.
+ *
+ * dspi_process_wire is dspi_process (pdm_words NULL) or dspi_process_pdm (else, out->sub optional as there) with out->pairs in the wire
+ * layout.  Flags: DSPI_MEM_DEVICE, DSPI_OUT_ENABLED_ONLY, DSPI_OUT_CLIP_FLAGS.  Refused with DSPI_E_INVAL before anything else is looked
+ * at: DSPI_OUT_SPDIF (it is implied), DSPI_OUT_I2S_SLOTS, DSPI_OUT_TILED and every undefined bit; then the refusals of dspi_process in
+ * their order (DSPI_E_INVAL for its arguments, DSPI_E_NODEVICE on a host-only context).  A refused or failed call writes and advances
+ * nothing.  The block positions move exactly as for a DSPI_OUT_SPDIF call: the context's value by F, with dspi_spdif_per_stream on every
+ * ACTIVE stream's by F — a device whose slots are all I2S counts on too: the position is the device's frame counter.
+ * WHEN NO ACTIVE STREAM'S PARAMETER OBJECT HAS AN I2S SLOT the call IS dspi_process / dspi_process_pdm with DSPI_OUT_SPDIF: the same route
+ * (the latency layout's fused encoder included), the same bytes.  Otherwise it runs in two passes, as per-stream positions make a
+ * DSPI_OUT_SPDIF call run: the chain's pair words into a scratch, then the wire encoder; with DSPI_OUT_ENABLED_ONLY the silent pairs then
+ * carry silence in their own format, the subframes of silence at the stream's position or zero slot words.
+ * Not combined with dspi_process_mixed.
+ *
+ * dspi_wire_encode is the stateless twin (as dspi_spdif_encode_v is DSPI_OUT_SPDIF's): pairs = int32 [stream][pair][n_frames][2] exactly
+ * as dspi_process wrote them, block_pos = uint32 [dspi_num_streams], required, wire = the layout above; all three in host memory, or in
+ * device memory with DSPI_MEM_DEVICE, the only flag.  Host positions are validated (each < 192, else DSPI_E_INVAL) before anything is
+ * launched; device positions are taken modulo 192.  Every stream's types and rate are its own parameters' at the time of the call.
+ * Independent of the per-stream mode, unaware of pauses.  Returns DSPI_OK or a negative DSPI_E_*.
+ * The ABI stays 8: detect by symbol (dspi_process_wire; with it dspi_wire_encode; additions only). */
+int dspi_process_wire(dspi_ctx *ctx, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len,
+                      const dspi_out *out, uint32_t *pdm_words /* may be NULL */, uint32_t flags);
+int dspi_wire_encode(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos,
+                     uint32_t *wire, uint32_t flags);
 int dspi_i2s_encode(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, uint32_t pair_mask, uint32_t *words, uint32_t flags);
 /* the HIP stream (hipStream_t) the context launches on, for event timing by the caller */
 void *dspi_hip_stream(dspi_ctx *ctx);
