@@ -29,6 +29,7 @@
 #include "dspi_kernels.h"
 #include "dspi_params.h"
 #include "dspi_boot.h"
+#include "dspi_devmem.h"
 #include "dspi_group.h"
 #include "dspi_intake.h"
 #include "dspi_migrate.h"
@@ -50,6 +51,7 @@ struct dspi_ctx {
     uint32_t cap_wg = 0;           // rows the persistent per-stream arrays (d_state, d_dlines, d_ring, d_pdm) are allocated for, >= n_wg (dspi_reserve_streams); no launch goes past n_wg
     int device = DSPI_DEVICE_NONE;
     StateMap sm{};
+    DevMem mem;                    // every DevBuf / PinnedBuf below registers here; dspi_destroy releases through it (no member destructor makes a HIP call)
     std::vector<std::unique_ptr<Params>> images;
     std::vector<uint32_t> image_refs;
     std::vector<int32_t> stream_image;
@@ -62,15 +64,15 @@ struct dspi_ctx {
     // however many presets are in play; uploaded to d_litems at plan.offset
     PlanInput plan_in;             // its sig / bands: per image, what the last upload built (commit_params)
     LaunchPlan plan;
-    WgItem *d_litems = nullptr; size_t d_litems_cap = 0;
-    uint32_t *d_stream_image = nullptr; size_t d_stream_image_cap = 0;   // image index per stream (per-lane parameter kernel)
+    DevBuf<WgItem> d_litems{mem};
+    DevBuf<uint32_t> d_stream_image{mem};   // image index per stream (per-lane parameter kernel)
     bool launch_dirty = true;
     uint32_t spdif_pos = 0;      // DSPI_OUT_SPDIF: block position of the next call's first frame
     // dspi_spdif_per_stream: while on, DSPI_OUT_SPDIF encodes stream s at its own position (dspi_spdifpos.h) and spdif_pos above only counts;
     // the device's copy of the per-stream words goes up behind the context's stream when a call has changed one (upload_spdif_pos)
     SpdifPos spdif_ps;
-    uint32_t *d_spdif_ps = nullptr; size_t d_spdif_ps_cap = 0;
-    uint32_t *d_spdif_vpos = nullptr; size_t d_spdif_vpos_cap = 0;      // dspi_spdif_encode_v on host buffers: the caller's positions
+    DevBuf<uint32_t> d_spdif_ps{mem};
+    DevBuf<uint32_t> d_spdif_vpos{mem};      // dspi_spdif_encode_v on host buffers: the caller's positions
     bool populated = false;      // DSPI_BOOT_POPULATED_FLASH: the streams are devices whose flash already holds a preset directory
     bool audio_started = false;  // a dspi_process has run: the devices are no longer booting (dspi_load_flash_dump)
     bool no_direct = false;      // DSPI_NO_DIRECT (development / tests, read once at dspi_create): the staged path for small host calls too
@@ -85,42 +87,42 @@ struct dspi_ctx {
     // host-buffer dspi_process: H2D, kernels and D2H of consecutive row chunks overlap on three streams (created on first use)
     hipStream_t hs_in = nullptr, hs_out = nullptr;
     std::vector<hipEvent_t> pipe_events;
-    uint32_t *d_state = nullptr, *d_dlines = nullptr, *d_ring = nullptr;
-    uint32_t *d_xwords = nullptr; size_t d_xwords_cap = 0;      // exchange area of the packed kernel's copy wave (stream-major output)
-    DevImage *d_images = nullptr;
+    DevBuf<uint32_t> d_state{mem}, d_dlines{mem}, d_ring{mem};
+    DevBuf<uint32_t> d_xwords{mem};      // exchange area of the packed kernel's copy wave (stream-major output)
+    DevBuf<DevImage> d_images{mem};
     std::vector<uint32_t> image_flags;             // DevImage::flags of each uploaded image (kernel variant selection)
     std::vector<uint8_t> image_touched;            // images uploaded since the tiles were last built
-    float *d_vals = nullptr; size_t d_vals_cap = 0;
-    uint32_t *d_pv_rows = nullptr; size_t d_pv_rows_cap = 0;
-    size_t d_images_cap = 0;
-    WgItem *d_items = nullptr;
-    size_t d_items_cap = 0;
+    DevBuf<float> d_vals{mem};
+    DevBuf<uint32_t> d_pv_rows{mem};
+    DevBuf<WgItem> d_items{mem};
     // staging buffers for host-memory dspi_process
-    void *d_in = nullptr; size_t d_in_cap = 0;
-    int32_t *d_pairs = nullptr; size_t d_pairs_cap = 0;
-    int32_t *d_sub = nullptr; size_t d_sub_cap = 0;
-    uint16_t *d_peaks = nullptr; size_t d_peaks_cap = 0;
-    uint16_t *d_clip = nullptr; size_t d_clip_cap = 0;          // DSPI_OUT_CLIP_FLAGS on host buffers
+    DevBuf<void> d_in{mem};
+    DevBuf<int32_t> d_pairs{mem};
+    DevBuf<int32_t> d_sub{mem};
+    DevBuf<uint16_t> d_peaks{mem};
+    DevBuf<uint16_t> d_clip{mem};          // DSPI_OUT_CLIP_FLAGS on host buffers
     // small calls on host buffers (one packet per call, the firmware's own rhythm): a pinned host area the kernels read and write directly
-    char *h_direct = nullptr; char *d_direct = nullptr; size_t direct_cap = 0;
+    PinnedBuf<char> h_direct{mem};      // (.device(): what the kernels address)
     // ... and a completion word of its own next to that area (round 6): the stream writes the call's sequence number there once the launches
     // have ended (hipStreamWriteValue32) and the host polls MEMORY instead of calling into the runtime (hipStreamQuery) thousands of times
-    uint32_t *h_done = nullptr; uint32_t *d_done = nullptr; uint32_t direct_seq = 0; int direct_flag = -1;      // -1: untried, 0: not available / DSPI_DIRECT_POLL=query, 1: in use
-    int32_t *d_spdif_words = nullptr; size_t d_spdif_words_cap = 0;      // DSPI_OUT_SPDIF on launches the latency layout does not serve: the chain's pair words of one row chunk
+    PinnedBuf<uint32_t> h_done{mem}; uint32_t direct_seq = 0; int direct_flag = -1;      // -1: untried, 0: not available / DSPI_DIRECT_POLL=query, 1: in use
+    DevBuf<int32_t> d_spdif_words{mem};      // DSPI_OUT_SPDIF on launches the latency layout does not serve: the chain's pair words of one row chunk
     // PDM sub output (dspi_pdm.hip): modulator state per stream, allocated on first use; staging for host buffers
-    uint32_t *d_pdm = nullptr;
-    int32_t *d_pdm_in = nullptr; size_t d_pdm_in_cap = 0;
-    uint32_t *d_pdm_out = nullptr; size_t d_pdm_out_cap = 0;
+    DevBuf<uint32_t> d_pdm{mem};
+    DevBuf<int32_t> d_pdm_in{mem};
+    DevBuf<uint32_t> d_pdm_out{mem};
     // dspi_process_pdm (dspi_pdmlife.h): who runs their modulator, the device's copy of the call's work list (it goes up through h_move, behind
     // ev_move, when the list was rebuilt), and per parameter object the core1_mode it was last uploaded with (a change makes the list dirty)
     PdmLife pdm_life;
-    uint32_t *d_pdm_list = nullptr; size_t d_pdm_list_cap = 0;
+    DevBuf<uint32_t> d_pdm_list{mem};
     std::vector<int8_t> image_core1;
     // dspi_pdm_fade (dspi_pdmfade.h): the mode and the fade positions; the fade bases [cap_wg * row] (allocated when the mode is first enabled, they
     // follow the capacity like d_pdm); the packed temporary the bases travel through.  The call's aux words stand behind the list in d_pdm_list.
     PdmFade pdm_fade;
-    int32_t *d_pdm_base = nullptr;
-    int32_t *d_pdm_pack = nullptr; size_t d_pdm_pack_cap = 0;
+    DevBuf<int32_t> d_pdm_base{mem};
+    DevBuf<int32_t> d_pdm_pack{mem};
+    // the arrays that follow the row capacity cap_wg, in the order of their table (dspi_devmem.h kPersist): dspi_create, pdm_state, dspi_pdm_fade and the resizes walk it
+    MemNode *const persist[kNumPersist] = {&d_state, &d_dlines, &d_ring, &d_pdm, &d_pdm_base};
     // dspi_process_mixed (dspi_intake.h).  d_mixed: device buffers only — a scratch of n_streams * 6F bytes that the intake kernel writes and the
     // chain reads, both on `hs`, asynchronously.  d_mixed_up: staged host buffers only — where a chunk's bytes go up as they are (on hs_in when
     // the call has several chunks), the intake then writes d_in.  THE RULE: whatever a stream other than `hs` touches (hs_in: d_in, d_mixed_up)
@@ -128,33 +130,33 @@ struct dspi_ctx {
     // another stream.  That is why the two paths do not share one scratch.  d_mixed_tab: the device's table of the call's layout, (n + 1) uint64
     // offsets with the n depths behind them, read and written on `hs` only; it goes up through h_move, behind ev_move, and stays while the
     // depths and the frame count repeat: mixed_depths / mixed_frames say what it holds (0 frames: nothing)
-    uint8_t *d_mixed = nullptr; size_t d_mixed_cap = 0;
-    uint8_t *d_mixed_up = nullptr; size_t d_mixed_up_cap = 0;
-    uint64_t *d_mixed_tab = nullptr; size_t d_mixed_tab_cap = 0;
+    DevBuf<uint8_t> d_mixed{mem};
+    DevBuf<uint8_t> d_mixed_up{mem};
+    DevBuf<uint64_t> d_mixed_tab{mem};
     std::vector<uint8_t> mixed_depths; uint64_t mixed_frames = 0;
-    int32_t *d_spdif_in = nullptr; size_t d_spdif_in_cap = 0;
-    uint32_t *d_spdif_out = nullptr; size_t d_spdif_out_cap = 0;
-    uint32_t *d_snap = nullptr; size_t d_snap_cap = 0;          // stream snapshots on host buffers: the records of one chunk of rows
-    uint32_t *d_snap_shift = nullptr; size_t d_snap_shift_cap = 0;      // realigning imports: two rotations per stream of a launch (dspi_snapshot.hip)
+    DevBuf<int32_t> d_spdif_in{mem};
+    DevBuf<uint32_t> d_spdif_out{mem};
+    DevBuf<uint32_t> d_snap{mem};          // stream snapshots on host buffers: the records of one chunk of rows
+    DevBuf<uint32_t> d_snap_shift{mem};      // realigning imports: two rotations per stream of a launch (dspi_snapshot.hip)
     // paused streams (dspi_pause_streams): a property of the SLOT.  `active` is the truth (one byte per stream, 1 = takes part in dspi_process;
     // empty until the first pause); the launch plan is built from it (PlanInput::active) and the kernels that walk every stream whatever the
     // plan says (PDM modulator, two-pass S/PDIF encoder, value-tile builder, the resume's target rule) read one bit per stream on the device,
     // uploaded when it has changed and something needs it (upload_activity)
     std::vector<uint8_t> active; uint32_t n_paused = 0;
     std::vector<std::pair<uint32_t, uint32_t>> paused_runs; bool paused_runs_dirty = false;      // [first, end) of consecutive paused streams: what the host-buffer paths zero
-    uint32_t *d_active = nullptr; size_t d_active_cap = 0; bool active_dirty = false;
+    DevBuf<uint32_t> d_active{mem}; bool active_dirty = false;
     // dspi_move_streams: records per batch (DSPI_MOVE_BATCH, read once at dspi_create; 0 = the snapshot chunk), and one call's work lists —
     // built in a pinned host area, copied up on the context's stream; the event says when the area may be rewritten
     uint32_t move_batch = 0;
-    uint32_t *d_move = nullptr; size_t d_move_cap = 0;
-    void *h_move = nullptr; size_t h_move_cap = 0; hipEvent_t ev_move = nullptr;
+    DevBuf<uint32_t> d_move{mem};
+    PinnedBuf<char> h_move{mem}; hipEvent_t ev_move = nullptr;
     // dspi_migrate_streams: the transport (DSPI_MIGRATE_VIA, read once at dspi_create; the DESTINATION context's value decides), the listed
     // streams' positions (written on the source, read — there or as a copy here — on the destination), the host transport's pinned area,
     // and "my stream has come this far": recorded on this context's stream, waited for on the other's
     enum MigrateVia { kViaAuto = 0, kViaCopy = 1, kViaHost = 2 };
     int migrate_via = kViaAuto;
-    uint32_t *d_mig_pos = nullptr; size_t d_mig_pos_cap = 0;
-    void *h_mig = nullptr; size_t h_mig_cap = 0;
+    DevBuf<uint32_t> d_mig_pos{mem};
+    PinnedBuf<char> h_mig{mem};
     hipEvent_t ev_mig = nullptr;
     std::string err;
 };
@@ -281,14 +283,60 @@ const Params &readable(const dspi_ctx *c, int32_t stream) {
     return *c->images[(size_t)c->stream_image[stream == DSPI_ALL_STREAMS ? 0 : (size_t)stream]];
 }
 
-template <class P>
-int ensure(dspi_ctx *c, P *&ptr, size_t &cap, size_t bytes) {
-    if (bytes <= cap) return 0;
-    if (ptr) HIPCK(c, hipFree(ptr));
-    ptr = nullptr; cap = 0;
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return fail(c, DSPI_E_NOMEM, "hipMalloc failed (" + std::to_string(bytes) + " bytes)");
-    ptr = (P *)p; cap = bytes;
+// The allocator of dspi_devmem.h on HIP — the one place that allocates and frees.  hipFree and hipHostFree wait for the device, and growing
+// a buffer that earlier asynchronous calls may still be using rests on that: no asynchronous, pooled or deferred free may take their place.
+struct HipAlloc {
+    hipError_t last = hipSuccess;      // what the call that failed answered
+    bool ok(hipError_t e) { last = e; if (e != hipSuccess) (void)hipGetLastError(); return e == hipSuccess; }
+    bool dev_alloc(void **p, size_t bytes) { return ok(hipMalloc(p, bytes)); }
+    bool dev_free(void *p) { return ok(hipFree(p)); }
+    bool dev_copy(void *dst, const void *src, size_t bytes) { return ok(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice)); }
+    bool host_alloc(void **p, size_t bytes) { return ok(hipHostMalloc(p, bytes, hipHostMallocDefault)); }
+    bool host_free(void *p) { return ok(hipHostFree(p)); }
+    bool host_device_ptr(void **dp, void *hp) { return ok(hipHostGetDevicePointer(dp, hp, 0)); }
+};
+// scratch of one call: a DevMem on the stack, its buffers, then this — it goes first and takes their memory with it on every return path
+struct ReleaseOnReturn { DevMem &m; ~ReleaseOnReturn() { HipAlloc a; devmem_release(a, m); } };
+
+// what a refused or failed growth answers (`why`: the refused allocation's words)
+int mem_fail(dspi_ctx *c, Mem m, const HipAlloc &a, const std::string &why) {
+    if (m == Mem::AllocFailed) return fail(c, DSPI_E_NOMEM, why);
+    return fail(c, DSPI_E_HIP, std::string(m == Mem::FreeFailed ? "hipFree(ptr): " : m == Mem::CopyFailed ? "hipMemcpy: " : "hipHostGetDevicePointer: ") + hipGetErrorString(a.last));
+}
+// device buffer b holds at least `bytes` (devmem_grow: contents are not kept)
+int ensure(dspi_ctx *c, MemNode &b, size_t bytes) {
+    if (bytes <= b.cap) return 0;
+    HipAlloc a;
+    const Mem m = devmem_grow(a, b, bytes);
+    return m == Mem::Ok ? 0 : mem_fail(c, m, a, "hipMalloc failed (" + std::to_string(bytes) + " bytes)");
+}
+// a pinned host area (h_move, h_mig) of at least `bytes`: one that is too small is replaced by one of `grow` bytes
+int pinned_area(dspi_ctx *c, MemNode &area, size_t bytes, size_t grow, const char *why) {
+    if (bytes <= area.cap) return 0;
+    HipAlloc a;
+    const Mem m = devmem_grow_pinned(a, area, bytes, grow, false);
+    return m == Mem::Ok ? 0 : mem_fail(c, m, a, why);
+}
+// array k of the persistent per-stream arrays (dspi_devmem.h kPersist), every row of the capacity, where the context does not have it yet
+int persist_alloc(dspi_ctx *c, int k, const char *why) {
+    size_t b = 0;
+    HipAlloc a;
+    if (c->persist[k]->p) return 0;
+    return persist_bytes(k, c->sm, c->cap_wg, &b) && devmem_grow(a, *c->persist[k], b) == Mem::Ok ? 0 : fail(c, DSPI_E_NOMEM, why);
+}
+
+// One call's words (`parts`, back to back) into device buffer dst, behind the context's earlier work: through the pinned area h_move and on
+// the context's stream, so behind every launch that reads dst's old contents; ev_move says when the area may be rewritten.
+int upload_via_move_area(dspi_ctx *c, MemNode &dst, const char *why, std::initializer_list<std::pair<const void *, size_t>> parts) {
+    size_t bytes = 0, at = 0;
+    for (const auto &p : parts) bytes += p.second;
+    if (!c->ev_move) HIPCK(c, hipEventCreateWithFlags(&c->ev_move, hipEventDisableTiming));
+    HIPCK(c, hipEventSynchronize(c->ev_move));      // the previous call's copy has left the area (long since, as a rule)
+    int rc = pinned_area(c, c->h_move, bytes, bytes * 2, why);
+    if (rc || (rc = ensure(c, dst, bytes))) return rc;
+    for (const auto &p : parts) { if (p.second) memcpy(c->h_move + at, p.first, p.second); at += p.second; }
+    HIPCK(c, hipMemcpyAsync(dst.p, c->h_move, bytes, hipMemcpyHostToDevice, c->hs));
+    HIPCK(c, hipEventRecord(c->ev_move, c->hs));
     return 0;
 }
 
@@ -297,7 +345,7 @@ int upload_activity(dspi_ctx *c) {
     if (!c->active_dirty) return 0;
     std::vector<uint32_t> bits(((size_t)c->n_streams + 31) / 32, 0u);
     for (uint32_t s = 0; s < c->n_streams; s++) if (c->active[s]) bits[s >> 5] |= 1u << (s & 31u);
-    int rc = ensure(c, c->d_active, c->d_active_cap, bits.size() * 4);
+    int rc = ensure(c, c->d_active, bits.size() * 4);
     if (rc) return rc;
     HIPCK(c, hipStreamSynchronize(c->hs));
     HIPCK(c, hipMemcpy(c->d_active, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
@@ -370,7 +418,7 @@ StateArrays state_arrays(const dspi_ctx *c) { return StateArrays{c->d_state, c->
 // encoder may still be reading the words), and only after a call that changed one: sets, pauses, resumes, moves and boots are rare.
 int upload_spdif_pos(dspi_ctx *c) {
     if (!c->spdif_ps.dirty && c->d_spdif_ps) return 0;
-    int rc = ensure(c, c->d_spdif_ps, c->d_spdif_ps_cap, (size_t)c->n_streams * 4);
+    int rc = ensure(c, c->d_spdif_ps, (size_t)c->n_streams * 4);
     if (rc) return rc;
     HIPCK(c, hipStreamSynchronize(c->hs));
     HIPCK(c, hipMemcpy(c->d_spdif_ps, c->spdif_ps.word.data(), (size_t)c->n_streams * 4, hipMemcpyHostToDevice));
@@ -384,7 +432,7 @@ int rebuild_assignment(dspi_ctx *c) {
     c->image_rows_offset.assign(ni, 0);
     size_t total = 0;
     for (size_t i = 0; i < ni; i++) { c->image_rows_offset[i] = (uint32_t)total; total += c->image_rows[i].size(); }
-    int rc = ensure(c, c->d_items, c->d_items_cap, total * sizeof(WgItem));
+    int rc = ensure(c, c->d_items, total * sizeof(WgItem));
     if (rc) return rc;
     HIPCK(c, hipStreamSynchronize(c->hs));      // no state_ops launch may still be reading the list
     {   // one upload (per-stream presets: tens of thousands of one-item lists)
@@ -420,9 +468,9 @@ int rebuild_launch_lists(dspi_ctx *c) {
     };
     c->plan = plan_launches(in);
     in.same_filters = nullptr;
-    int rc = ensure(c, c->d_litems, c->d_litems_cap, c->plan.total * sizeof(WgItem));
+    int rc = ensure(c, c->d_litems, c->plan.total * sizeof(WgItem));
     if (rc) return rc;
-    if ((rc = ensure(c, c->d_stream_image, c->d_stream_image_cap, (size_t)c->n_streams * 4))) return rc;
+    if ((rc = ensure(c, c->d_stream_image, (size_t)c->n_streams * 4))) return rc;
     HIPCK(c, hipStreamSynchronize(c->hs));      // no launch may still be reading the lists we overwrite
     for (int p = 0; p < kNumPaths; p++)
         if (!c->plan.items[p].empty())
@@ -447,13 +495,11 @@ int commit_params(dspi_ctx *c) {
     const size_t ni = c->images.size();
     bool any_dirty = false;
     for (size_t i = 0; i < ni; i++) if (c->images[i]->dirty) any_dirty = true;
-    if (any_dirty || ni * sizeof(DevImage) > c->d_images_cap) HIPCK(c, hipStreamSynchronize(c->hs));   // no launch may still be reading an image we overwrite
-    if (ni * sizeof(DevImage) > c->d_images_cap) {
-        DevImage *old = c->d_images; size_t oldcap = c->d_images_cap;
-        c->d_images = nullptr; c->d_images_cap = 0;
-        int rc = ensure(c, c->d_images, c->d_images_cap, (ni + 8) * sizeof(DevImage));
-        if (rc) return rc;
-        if (old) { HIPCK(c, hipMemcpy(c->d_images, old, oldcap, hipMemcpyDeviceToDevice)); HIPCK(c, hipFree(old)); }
+    if (any_dirty || ni * sizeof(DevImage) > c->d_images.cap) HIPCK(c, hipStreamSynchronize(c->hs));   // no launch may still be reading an image we overwrite
+    if (ni * sizeof(DevImage) > c->d_images.cap) {      // the table grows with its images in it (a refusal leaves it as it was)
+        HipAlloc a;
+        const Mem m = devmem_grow_keep(a, c->d_images, (ni + 8) * sizeof(DevImage));
+        if (m != Mem::Ok) return mem_fail(c, m, a, "hipMalloc failed (" + std::to_string((ni + 8) * sizeof(DevImage)) + " bytes)");
         for (auto &p : c->images) p->dirty = true;
     }
     // dirty images go up in contiguous runs (per-stream presets dirty thousands at once)
@@ -534,9 +580,9 @@ int commit_params(dspi_ctx *c) {
                 if (c->plan.row_pv[it.wg] && !seen[it.wg]) { seen[it.wg] = 1; rows.push_back(it.wg); }
         }
         if (!rows.empty()) {
-            int rc = ensure(c, c->d_vals, c->d_vals_cap, (size_t)c->n_wg * kPvTileFloats * sizeof(float));
+            int rc = ensure(c, c->d_vals, (size_t)c->n_wg * kPvTileFloats * sizeof(float));
             if (rc) return rc;
-            if ((rc = ensure(c, c->d_pv_rows, c->d_pv_rows_cap, (size_t)c->n_wg * 4))) return rc;
+            if ((rc = ensure(c, c->d_pv_rows, (size_t)c->n_wg * 4))) return rc;
             HIPCK(c, hipStreamSynchronize(c->hs));      // no launch may still be reading the tiles or the row list
             HIPCK(c, hipMemcpy(c->d_pv_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
             static const bool all_differ = getenv("DSPI_DEBUG") && (strtoul(getenv("DSPI_DEBUG"), nullptr, 0) & 1u);      // development switch (timing of the worst case)
@@ -622,17 +668,11 @@ int dspi_create(dspi_ctx **out, int flavor, uint32_t n_streams, int hip_device) 
     auto bail = [&](int code) { dspi_destroy(c); *out = nullptr; return code; };
     if (hipSetDevice(hip_device) != hipSuccess) return bail(DSPI_E_NODEVICE);
     if (hipStreamCreateWithFlags(&c->hs, hipStreamNonBlocking) != hipSuccess) return bail(DSPI_E_HIP);
-    const size_t row = (size_t)c->sm.row;
-    const size_t state_b = (size_t)c->n_wg * c->sm.n_slots * row * 4;
-    const size_t dl_b = (size_t)c->n_wg * c->sm.n_out * (size_t)c->sm.max_delay * row * 4;
-    const size_t ring_b = (size_t)c->n_wg * kRingLen * 2 * row * 4;
-    if (hipMalloc((void **)&c->d_state, state_b) != hipSuccess || hipMalloc((void **)&c->d_dlines, dl_b) != hipSuccess ||
-        hipMalloc((void **)&c->d_ring, ring_b) != hipSuccess)
-        return bail(DSPI_E_NOMEM);
-    if (hipMemsetAsync(c->d_state, 0, state_b, c->hs) != hipSuccess || hipMemsetAsync(c->d_dlines, 0, dl_b, c->hs) != hipSuccess ||
-        hipMemsetAsync(c->d_ring, 0, ring_b, c->hs) != hipSuccess || launch_state_init(flavor, c->d_state, c->n_wg, c->hs) != hipSuccess ||
-        hipStreamSynchronize(c->hs) != hipSuccess)
-        return bail(DSPI_E_HIP);
+    for (int k = 0; k < kNumPersist; k++)
+        if (kPersist[k].at_create && persist_alloc(c, k, "hipMalloc failed (per-stream arrays)")) return bail(DSPI_E_NOMEM);
+    for (int k = 0; k < kNumPersist; k++)
+        if (kPersist[k].at_create && hipMemsetAsync(c->persist[k]->p, 0, c->persist[k]->cap, c->hs) != hipSuccess) return bail(DSPI_E_HIP);
+    if (launch_state_init(flavor, c->d_state, c->n_wg, c->hs) != hipSuccess || hipStreamSynchronize(c->hs) != hipSuccess) return bail(DSPI_E_HIP);
     return DSPI_OK;
 }
 
@@ -641,14 +681,9 @@ void dspi_destroy(dspi_ctx *c) {
     if (c->device != DSPI_DEVICE_NONE) {
         (void)hipSetDevice(c->device);
         if (c->hs) (void)hipStreamSynchronize(c->hs);
-        for (void *p : {(void *)c->d_state, (void *)c->d_dlines, (void *)c->d_ring, (void *)c->d_xwords, (void *)c->d_vals, (void *)c->d_pv_rows, (void *)c->d_images, (void *)c->d_items, (void *)c->d_litems, (void *)c->d_stream_image, (void *)c->d_pdm, (void *)c->d_pdm_in, (void *)c->d_pdm_out, (void *)c->d_pdm_list, (void *)c->d_pdm_base, (void *)c->d_pdm_pack, (void *)c->d_spdif_in, (void *)c->d_spdif_out, (void *)c->d_spdif_ps, (void *)c->d_spdif_vpos, (void *)c->d_snap, (void *)c->d_snap_shift, (void *)c->d_active, (void *)c->d_move, (void *)c->d_mig_pos, c->d_in, (void *)c->d_mixed, (void *)c->d_mixed_up, (void *)c->d_mixed_tab,
-                        (void *)c->d_pairs, (void *)c->d_sub, (void *)c->d_peaks, (void *)c->d_clip, (void *)c->d_spdif_words})
-            if (p) (void)hipFree(p);
-        if (c->h_direct) (void)hipHostFree(c->h_direct);
-        if (c->h_done) (void)hipHostFree(c->h_done);
-        if (c->h_move) (void)hipHostFree(c->h_move);
+        HipAlloc a;
+        devmem_release(a, c->mem);      // every buffer and pinned area, here: with the context's device current and its streams still alive
         if (c->ev_move) (void)hipEventDestroy(c->ev_move);
-        if (c->h_mig) (void)hipHostFree(c->h_mig);
         if (c->ev_mig) (void)hipEventDestroy(c->ev_mig);
         for (hipEvent_t e : c->pipe_events) (void)hipEventDestroy(e);
         if (c->hs_in) (void)hipStreamDestroy(c->hs_in);
@@ -810,41 +845,38 @@ int dspi_debug_eq_taps(dspi_ctx *c, int32_t stream, int channel, const float *x,
     HIPCK(c, hipSetDevice(c->device));
     DevImage img;
     readable(c, stream).build_image(img);
-    DevImage *d_img = nullptr; float *d_x = nullptr, *d_t = nullptr, *d_o = nullptr;
+    DevMem mem; DevBuf<DevImage> d_img{mem}; DevBuf<float> d_x{mem}, d_t{mem}, d_o{mem}; ReleaseOnReturn scratch{mem};
+    HipAlloc a;
     const size_t nb = (size_t)n * sizeof(float);
-    auto done = [&](int rc) { (void)hipFree(d_img); (void)hipFree(d_x); (void)hipFree(d_t); (void)hipFree(d_o); return rc; };
-    if (hipMalloc((void **)&d_img, sizeof img) != hipSuccess || hipMalloc((void **)&d_x, nb) != hipSuccess ||
-        hipMalloc((void **)&d_t, nb * (kBands + 1)) != hipSuccess || hipMalloc((void **)&d_o, nb * kBands) != hipSuccess)
-        return done(fail(c, DSPI_E_NOMEM, "hipMalloc failed (EQ taps)"));
+    if (devmem_grow(a, d_img, sizeof img) != Mem::Ok || devmem_grow(a, d_x, nb) != Mem::Ok || devmem_grow(a, d_t, nb * (kBands + 1)) != Mem::Ok || devmem_grow(a, d_o, nb * kBands) != Mem::Ok)
+        return fail(c, DSPI_E_NOMEM, "hipMalloc failed (EQ taps)");
     if (hipMemcpy(d_img, &img, sizeof img, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_x, x, nb, hipMemcpyHostToDevice) != hipSuccess ||
         launch_eq_taps(c->fma, d_img, channel, d_x, n, d_t, d_o, c->hs) != hipSuccess || hipStreamSynchronize(c->hs) != hipSuccess ||
         hipMemcpy(taps, d_t, nb * (kBands + 1), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(other, d_o, nb * kBands, hipMemcpyDeviceToHost) != hipSuccess)
-        return done(fail(c, DSPI_E_HIP, "EQ taps failed"));
-    return done(DSPI_OK);
+        return fail(c, DSPI_E_HIP, "EQ taps failed");
+    return DSPI_OK;
 }
 
 int dspi_debug_detmath(dspi_ctx *c, int which, const float *a, const float *b, uint32_t n, float *out) {
     if (!c || !a || !out || ((which == 1 || which == 4) && !b) || n == 0 || n > (1u << 24) || which < 0 || which > 4) return DSPI_E_INVAL;
     if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
     HIPCK(c, hipSetDevice(c->device));
-    float *d_a = nullptr, *d_b = nullptr, *d_o = nullptr;
+    DevMem mem; DevBuf<float> d_a{mem}, d_b{mem}, d_o{mem}; ReleaseOnReturn scratch{mem};
+    HipAlloc al;
     const size_t nb = (size_t)n * sizeof(float);
-    auto done = [&](int rc) { (void)hipFree(d_a); (void)hipFree(d_b); (void)hipFree(d_o); return rc; };
-    if (hipMalloc((void **)&d_a, nb) != hipSuccess || hipMalloc((void **)&d_b, nb) != hipSuccess || hipMalloc((void **)&d_o, nb) != hipSuccess)
-        return done(fail(c, DSPI_E_NOMEM, "hipMalloc failed (detmath)"));
+    if (devmem_grow(al, d_a, nb) != Mem::Ok || devmem_grow(al, d_b, nb) != Mem::Ok || devmem_grow(al, d_o, nb) != Mem::Ok) return fail(c, DSPI_E_NOMEM, "hipMalloc failed (detmath)");
     if (hipMemcpy(d_a, a, nb, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_b, (which == 1 || which == 4) ? b : a, nb, hipMemcpyHostToDevice) != hipSuccess ||
         launch_detmath(which, d_a, d_b, n, d_o, c->hs) != hipSuccess || hipStreamSynchronize(c->hs) != hipSuccess ||
         hipMemcpy(out, d_o, nb, hipMemcpyDeviceToHost) != hipSuccess)
-        return done(fail(c, DSPI_E_HIP, "detmath kernel failed"));
-    return done(DSPI_OK);
+        return fail(c, DSPI_E_HIP, "detmath kernel failed");
+    return DSPI_OK;
 }
 
 // ---- PDM sub output: pdm_generator.c:351-397 per sample (dspi_pdm.hip) ----
 static int pdm_state(dspi_ctx *c) {
     if (c->d_pdm) return 0;
-    const size_t b = (size_t)c->cap_wg * kPdmStateWords * c->sm.row * 4;      // (every row of the capacity, like the other three arrays)
-    if (hipMalloc((void **)&c->d_pdm, b) != hipSuccess) return fail(c, DSPI_E_NOMEM, "hipMalloc failed (PDM state)");
-    HIPCK(c, hipMemsetAsync(c->d_pdm, 0, b, c->hs));
+    if (int rc = persist_alloc(c, kArrPdm, "hipMalloc failed (PDM state)")) return rc;      // (every row of the capacity, like the other arrays)
+    HIPCK(c, hipMemsetAsync(c->d_pdm, 0, c->d_pdm.cap, c->hs));
     HIPCK(c, launch_pdm_reset(c->d_pdm, c->n_streams, (uint32_t)c->sm.row, c->n_wg, -1, 1, c->hs));
     return 0;
 }
@@ -870,7 +902,7 @@ int dspi_pdm_modulate(dspi_ctx *c, const int32_t *sub, uint32_t n_frames, uint32
     const int32_t *d_in = sub;
     uint32_t *d_out = words;
     if (!dev) {
-        if ((rc = ensure(c, c->d_pdm_in, c->d_pdm_in_cap, in_b)) || (rc = ensure(c, c->d_pdm_out, c->d_pdm_out_cap, out_b))) return rc;
+        if ((rc = ensure(c, c->d_pdm_in, in_b)) || (rc = ensure(c, c->d_pdm_out, out_b))) return rc;
         HIPCK(c, hipMemcpyAsync(c->d_pdm_in, sub, in_b, hipMemcpyHostToDevice, c->hs));
         d_in = c->d_pdm_in; d_out = c->d_pdm_out;
         if (c->n_paused) HIPCK(c, hipMemsetAsync(c->d_pdm_out, 0, out_b, c->hs));      // paused streams' words stay unwritten: the staging buffer goes back whole, with zeros there
@@ -917,8 +949,8 @@ static uint32_t snap_chunk_end(const dspi_ctx *c, uint32_t s, uint32_t end) {
 static int snap_prepare(dspi_ctx *c, size_t records, bool shifts) {
     HIPCK(c, hipSetDevice(c->device));
     int rc = pdm_state(c);
-    if (rc || (rc = ensure(c, c->d_snap, c->d_snap_cap, records * snap_state_bytes(c->flavor, 1)))) return rc;
-    return shifts ? ensure(c, c->d_snap_shift, c->d_snap_shift_cap, (size_t)c->n_streams * 8) : 0;
+    if (rc || (rc = ensure(c, c->d_snap, records * snap_state_bytes(c->flavor, 1)))) return rc;
+    return shifts ? ensure(c, c->d_snap_shift, (size_t)c->n_streams * 8) : 0;
 }
 // the context's arrays of streams [first, first + count) -> records, on its stream
 static hipError_t snap_gather(dspi_ctx *c, uint32_t *records, uint32_t first, uint32_t count) {
@@ -968,7 +1000,7 @@ int dspi_export_streams(dspi_ctx *c, uint32_t first, uint32_t count, const dspi_
     const size_t rec = snap_state_bytes(c->flavor, 1);
     for (uint32_t s = first, end = first + count; s < end;) {
         const uint32_t e = snap_chunk_end(c, s, end);
-        if ((rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)(e - s) * rec))) return rc;
+        if ((rc = ensure(c, c->d_snap, (size_t)(e - s) * rec))) return rc;
         HIPCK(c, snap_gather(c, c->d_snap, s, e - s));
         HIPCK(c, hipMemcpyAsync(static_cast<char *>(snap->state) + (size_t)(s - first) * rec, c->d_snap, (size_t)(e - s) * rec, hipMemcpyDeviceToHost, c->hs));
         HIPCK(c, hipStreamSynchronize(c->hs));
@@ -1018,7 +1050,7 @@ int dspi_import_streams(dspi_ctx *c, uint32_t first, const dspi_snapshot *snap, 
     }
     for (uint32_t s = first, end = first + count; s < end;) {
         const uint32_t e = snap_chunk_end(c, s, end);
-        if ((rc = ensure(c, c->d_snap, c->d_snap_cap, (size_t)(e - s) * rec))) return rc;
+        if ((rc = ensure(c, c->d_snap, (size_t)(e - s) * rec))) return rc;
         HIPCK(c, hipMemcpyAsync(c->d_snap, static_cast<const char *>(snap->state) + (size_t)(s - first) * rec, (size_t)(e - s) * rec, hipMemcpyHostToDevice, c->hs));
         HIPCK(c, snap_scatter(c, realign, c->d_snap, s, e - s));      // (chunks end on row boundaries: a row's target is the same in whichever chunk)
         HIPCK(c, hipStreamSynchronize(c->hs));
@@ -1112,27 +1144,9 @@ static_assert(sizeof(dspi_stream_move) == sizeof(StreamMove) && offsetof(dspi_st
 
 static uint32_t move_batch_records(const dspi_ctx *c) { return c->move_batch ? c->move_batch : snap_chunk_rows(c) * (uint32_t)c->sm.row; }
 
-// a pinned host area (h_move, h_mig) of at least `bytes`: one that is too small is replaced by one of `grow` bytes
-static int pinned_area(dspi_ctx *c, void *&area, size_t &cap, size_t bytes, size_t grow, const char *why) {
-    if (bytes <= cap) return 0;
-    if (area) HIPCK(c, hipHostFree(area));
-    area = nullptr; cap = 0;
-    if (hipHostMalloc(&area, grow, hipHostMallocDefault) != hipSuccess) { area = nullptr; return fail(c, DSPI_E_NOMEM, why); }
-    cap = grow;
-    return 0;
-}
-
 // one call's work lists into device memory, behind the context's earlier work
 static int move_upload(dspi_ctx *c, const std::vector<uint32_t> &words) {
-    const size_t bytes = words.size() * 4;
-    if (!c->ev_move) HIPCK(c, hipEventCreateWithFlags(&c->ev_move, hipEventDisableTiming));
-    HIPCK(c, hipEventSynchronize(c->ev_move));      // the previous call's copy has left the area (long since, as a rule)
-    int rc = pinned_area(c, c->h_move, c->h_move_cap, bytes, bytes * 2, "hipHostMalloc failed (move lists)");
-    if (rc || (rc = ensure(c, c->d_move, c->d_move_cap, bytes))) return rc;
-    memcpy(c->h_move, words.data(), bytes);
-    HIPCK(c, hipMemcpyAsync(c->d_move, c->h_move, bytes, hipMemcpyHostToDevice, c->hs));
-    HIPCK(c, hipEventRecord(c->ev_move, c->hs));
-    return 0;
+    return upload_via_move_area(c, c->d_move, "hipHostMalloc failed (move lists)", {{words.data(), words.size() * 4}});
 }
 
 // row items and their columns' record indices, appended to a call's work lists: where they begin, in words
@@ -1205,7 +1219,7 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
     if (bases) {
         for (const StreamMove &m : mv) words.push_back(m.src);
         for (const StreamMove &m : mv) words.push_back(m.dst);
-        if ((rc = ensure(c, c->d_pdm_pack, c->d_pdm_pack_cap, (size_t)nm * 4))) return rc;
+        if ((rc = ensure(c, c->d_pdm_pack, (size_t)nm * 4))) return rc;
     }
     if ((rc = move_upload(c, words))) return rc;
     if (bases) {      // (through the packed temporary: swaps and cycles are safe)
@@ -1282,11 +1296,11 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
     for (dspi_ctx *c : {src, dst}) {
         HIPCK(c, hipSetDevice(c->device));
         if (!c->ev_mig) HIPCK(c, hipEventCreateWithFlags(&c->ev_mig, hipEventDisableTiming));
-        if (realign && (c == src || staged) && (rc = ensure(c, c->d_mig_pos, c->d_mig_pos_cap, (size_t)n * 8))) return rc;
+        if (realign && (c == src || staged) && (rc = ensure(c, c->d_mig_pos, (size_t)n * 8))) return rc;
     }
     if (via == dspi_ctx::kViaHost) {
         const size_t need = std::max((size_t)std::min(cap, n) * rec, (size_t)n * 8);
-        if ((rc = pinned_area(dst, dst->h_mig, dst->h_mig_cap, need, need, "hipHostMalloc failed (migration area)"))) return rc;
+        if ((rc = pinned_area(dst, dst->h_mig, need, need, "hipHostMalloc failed (migration area)"))) return rc;
     }
     // the call's work lists, one upload per context through its own staging area: the source gets the listed slots (positions kernel) and
     // the batches' gather items, the destination the targets (every shift is computed once, before anything is written) and the scatter items
@@ -1314,9 +1328,9 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
     if (base_to) for (uint32_t i = 0; i < n; i++) ds.words.push_back(list[i].dst);
     if (base_from) {
         HIPCK(src, hipSetDevice(src->device));
-        if ((rc = ensure(src, src->d_pdm_pack, src->d_pdm_pack_cap, (size_t)n * 4))) return rc;
+        if ((rc = ensure(src, src->d_pdm_pack, (size_t)n * 4))) return rc;
         HIPCK(dst, hipSetDevice(dst->device));
-        if (staged && (rc = ensure(dst, dst->d_pdm_pack, dst->d_pdm_pack_cap, (size_t)n * 4))) return rc;
+        if (staged && (rc = ensure(dst, dst->d_pdm_pack, (size_t)n * 4))) return rc;
     }
     HIPCK(src, hipSetDevice(src->device));
     if ((rc = move_upload(src, ss.words))) return rc;
@@ -1352,7 +1366,7 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
     if (base_from) {
         HIPCK(src, hipSetDevice(src->device));
         HIPCK(src, launch_pdm_base_gather(src->d_pdm_base, src->d_move + src_slots_at, n, src->n_streams, src->d_pdm_pack, src->hs));
-        if ((rc = carry(reinterpret_cast<uint32_t *>(dst->d_pdm_pack), reinterpret_cast<const uint32_t *>(src->d_pdm_pack), (size_t)n * 4))) return rc;
+        if ((rc = carry(reinterpret_cast<uint32_t *>(dst->d_pdm_pack.get()), reinterpret_cast<const uint32_t *>(src->d_pdm_pack.get()), (size_t)n * 4))) return rc;
     }
     if (base_to) {
         HIPCK(dst, hipSetDevice(dst->device));
@@ -1487,39 +1501,21 @@ int dspi_boot_streams(dspi_ctx *c, const uint32_t *streams, uint32_t n, const vo
 // allocated before anything else happens (a refusal leaves the context as it was); the first `copy` rows come over device to device on the
 // context's stream, behind its earlier work; then the stream is waited for, once, and the old arrays are freed.
 static int resize_reallocate(dspi_ctx *c, uint32_t rows, uint32_t copy) {
-    const size_t row = (size_t)c->sm.row;
-    const size_t row_b[5] = {(size_t)c->sm.n_slots * row * 4, (size_t)c->sm.n_out * (size_t)c->sm.max_delay * row * 4, (size_t)kRingLen * 2 * row * 4, (size_t)kPdmStateWords * row * 4, row * 4};
-    uint32_t **const arr[5] = {&c->d_state, &c->d_dlines, &c->d_ring, &c->d_pdm, reinterpret_cast<uint32_t **>(&c->d_pdm_base)};
-    void *fresh[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 5; k++) {
-        if (!*arr[k]) continue;      // (d_pdm before the modulator's first run, d_pdm_base before the fade mode's first enable)
-        size_t b = 0;
-        if (!resize_bytes(rows, row_b[k], &b) || hipMalloc(&fresh[k], b) != hipSuccess) {
-            (void)hipGetLastError();
-            for (int j = 0; j < k; j++) if (fresh[j]) (void)hipFree(fresh[j]);
-            return fail(c, DSPI_E_NOMEM, "hipMalloc failed (resized arrays, " + std::to_string(rows) + " rows)");
-        }
-    }
+    HipAlloc a;
     hipError_t e = hipSuccess;
-    for (int k = 0; k < 5 && e == hipSuccess; k++)
-        if (fresh[k] && copy) e = hipMemcpyAsync(fresh[k], *arr[k], (size_t)copy * row_b[k], hipMemcpyDeviceToDevice, c->hs);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->hs);
-    if (e != hipSuccess) {
-        for (int k = 0; k < 5; k++) if (fresh[k]) (void)hipFree(fresh[k]);
-        return fail(c, DSPI_E_HIP, std::string("resized arrays: ") + hipGetErrorString(e));
-    }
-    for (int k = 0; k < 5; k++)
-        if (fresh[k]) { (void)hipFree(*arr[k]); *arr[k] = static_cast<uint32_t *>(fresh[k]); }
-    c->cap_wg = rows;
+    // (d_pdm before the modulator's first run and d_pdm_base before the fade mode's first enable are absent, and stay so)
+    const Mem m = persist_reallocate(a, c->persist, c->sm, rows, c->cap_wg, [&](void *const *fresh) {
+        for (int k = 0; k < kNumPersist && e == hipSuccess; k++)
+            if (fresh[k] && copy) e = hipMemcpyAsync(fresh[k], c->persist[k]->p, (size_t)copy * kPersist[k].row_bytes(c->sm), hipMemcpyDeviceToDevice, c->hs);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->hs);
+        return e == hipSuccess;
+    });
+    if (m == Mem::AllocFailed) return fail(c, DSPI_E_NOMEM, "hipMalloc failed (resized arrays, " + std::to_string(rows) + " rows)");
+    if (m != Mem::Ok) return fail(c, DSPI_E_HIP, std::string("resized arrays: ") + hipGetErrorString(e));
     return 0;
 }
 // a row count no array's byte size can express is refused with the other rules, before anything is written
-static bool resize_rows_fit(const dspi_ctx *c, uint32_t rows) {
-    const size_t row = (size_t)c->sm.row;
-    size_t b = 0;
-    return resize_bytes(rows, (size_t)c->sm.n_out * (size_t)c->sm.max_delay * row * 4, &b) && resize_bytes(rows, (size_t)c->sm.n_slots * row * 4, &b) &&
-           resize_bytes(rows, (size_t)kRingLen * 2 * row * 4, &b) && resize_bytes(rows, (size_t)kPdmStateWords * row * 4, &b);
-}
+static bool resize_rows_fit(const dspi_ctx *c, uint32_t rows) { return persist_rows_fit(c->sm, rows); }
 
 // Every per-stream book of the context, extended to or cut at n_new (beside the maintenance books above: stream_image / image_refs,
 // active / n_paused / paused_runs, spdif_ps, and through the dirty flags the device's copies of activity, stream images and S/PDIF
@@ -1641,7 +1637,7 @@ int dspi_spdif_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, uint
     uint32_t *d_out = subframes;
     int rc;
     if (!dev) {
-        if ((rc = ensure(c, c->d_spdif_in, c->d_spdif_in_cap, in_b)) || (rc = ensure(c, c->d_spdif_out, c->d_spdif_out_cap, out_b))) return rc;
+        if ((rc = ensure(c, c->d_spdif_in, in_b)) || (rc = ensure(c, c->d_spdif_out, out_b))) return rc;
         HIPCK(c, hipMemcpyAsync(c->d_spdif_in, pairs, in_b, hipMemcpyHostToDevice, c->hs));
         d_in = c->d_spdif_in; d_out = c->d_spdif_out;
     }
@@ -1670,7 +1666,7 @@ int dspi_i2s_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, uint32
     uint32_t *d_out = words;
     int rc;
     if (!dev) {
-        if ((rc = ensure(c, c->d_spdif_in, c->d_spdif_in_cap, bytes)) || (rc = ensure(c, c->d_spdif_out, c->d_spdif_out_cap, bytes))) return rc;
+        if ((rc = ensure(c, c->d_spdif_in, bytes)) || (rc = ensure(c, c->d_spdif_out, bytes))) return rc;
         HIPCK(c, hipMemcpyAsync(c->d_spdif_in, pairs, bytes, hipMemcpyHostToDevice, c->hs));
         HIPCK(c, hipMemcpyAsync(c->d_spdif_out, words, bytes, hipMemcpyHostToDevice, c->hs));     // pairs outside the mask keep the caller's words
         d_in = c->d_spdif_in; d_out = c->d_spdif_out;
@@ -1720,8 +1716,8 @@ int dspi_spdif_encode_v(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, co
     const uint32_t *d_pos = block_pos;
     int rc;
     if (!dev) {
-        if ((rc = ensure(c, c->d_spdif_in, c->d_spdif_in_cap, in_b)) || (rc = ensure(c, c->d_spdif_out, c->d_spdif_out_cap, out_b)) ||
-            (rc = ensure(c, c->d_spdif_vpos, c->d_spdif_vpos_cap, pos_b))) return rc;
+        if ((rc = ensure(c, c->d_spdif_in, in_b)) || (rc = ensure(c, c->d_spdif_out, out_b)) ||
+            (rc = ensure(c, c->d_spdif_vpos, pos_b))) return rc;
         HIPCK(c, hipMemcpyAsync(c->d_spdif_in, pairs, in_b, hipMemcpyHostToDevice, c->hs));
         HIPCK(c, hipMemcpyAsync(c->d_spdif_vpos, block_pos, pos_b, hipMemcpyHostToDevice, c->hs));
         d_in = c->d_spdif_in; d_out = c->d_spdif_out; d_pos = c->d_spdif_vpos;
@@ -1825,14 +1821,7 @@ static int pdm_prepare(dspi_ctx *c, PdmCall &pc) {
     pc.work = &w;
     if (c->pdm_life.uploaded || w.list.empty()) return 0;
     const bool aux = c->pdm_fade.any_aux;      // the aux words go up behind the list, only when one of them says anything
-    const size_t bytes = w.list.size() * (aux ? 8 : 4);
-    if (!c->ev_move) HIPCK(c, hipEventCreateWithFlags(&c->ev_move, hipEventDisableTiming));
-    HIPCK(c, hipEventSynchronize(c->ev_move));
-    if ((rc = pinned_area(c, c->h_move, c->h_move_cap, bytes, bytes * 2, "hipHostMalloc failed (PDM work list)")) || (rc = ensure(c, c->d_pdm_list, c->d_pdm_list_cap, bytes))) return rc;
-    memcpy(c->h_move, w.list.data(), w.list.size() * 4);
-    if (aux) memcpy(static_cast<uint32_t *>(c->h_move) + w.list.size(), c->pdm_fade.aux.data(), w.list.size() * 4);
-    HIPCK(c, hipMemcpyAsync(c->d_pdm_list, c->h_move, bytes, hipMemcpyHostToDevice, c->hs));
-    HIPCK(c, hipEventRecord(c->ev_move, c->hs));
+    if ((rc = upload_via_move_area(c, c->d_pdm_list, "hipHostMalloc failed (PDM work list)", {{w.list.data(), w.list.size() * 4}, {c->pdm_fade.aux.data(), aux ? w.list.size() * 4 : 0}}))) return rc;
     c->pdm_life.uploaded = true;
     return 0;
 }
@@ -1848,7 +1837,7 @@ static int launch_pdm_streams(dspi_ctx *c, const PdmCall &pc, const CallLayout &
     return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("pdm modulator launch: ") + hipGetErrorString(e));
 }
 // where the chain leaves the Q28 sub words of a dspi_process_pdm call whose caller passed no `sub`: the library's scratch (device memory)
-static int pdm_sub_scratch(dspi_ctx *c, const CallLayout &L) { return ensure(c, c->d_sub, c->d_sub_cap, L.sub_scratch.bytes); }
+static int pdm_sub_scratch(dspi_ctx *c, const CallLayout &L) { return ensure(c, c->d_sub, L.sub_scratch.bytes); }
 
 // ---- dspi_process_mixed: the call's layout (null in the three paths below: one depth for the call) ----
 // A mixed call is planned as the 24-bit call it becomes (plan_call knows nothing of it); only the way its `pcm` area is filled differs.
@@ -1858,19 +1847,13 @@ struct MixedIn {
 };
 // the path's scratch (d_mixed or d_mixed_up, `bytes`) and the device's table, before the first launch of the call (all-or-nothing: a call
 // that cannot have them runs nothing)
-static int intake_prepare(dspi_ctx *c, const MixedIn &mx, uint64_t frames, uint8_t *&scratch, size_t &scratch_cap, size_t scratch_bytes) {
-    int rc = ensure(c, scratch, scratch_cap, scratch_bytes);
+static int intake_prepare(dspi_ctx *c, const MixedIn &mx, uint64_t frames, DevBuf<uint8_t> &scratch, size_t scratch_bytes) {
+    int rc = ensure(c, scratch, scratch_bytes);
     if (rc) return rc;
-    const size_t n = c->n_streams, bytes = (n + 1) * 8 + n;
+    const size_t n = c->n_streams;
     if (c->mixed_frames == frames && c->mixed_depths.size() == n && !memcmp(c->mixed_depths.data(), mx.depths, n)) return 0;
     c->mixed_frames = 0;
-    if (!c->ev_move) HIPCK(c, hipEventCreateWithFlags(&c->ev_move, hipEventDisableTiming));
-    HIPCK(c, hipEventSynchronize(c->ev_move));
-    if ((rc = pinned_area(c, c->h_move, c->h_move_cap, bytes, bytes * 2, "hipHostMalloc failed (mixed input table)")) || (rc = ensure(c, c->d_mixed_tab, c->d_mixed_tab_cap, bytes))) return rc;
-    memcpy(c->h_move, mx.offsets.data(), (n + 1) * 8);
-    memcpy(static_cast<char *>(c->h_move) + (n + 1) * 8, mx.depths, n);
-    HIPCK(c, hipMemcpyAsync(c->d_mixed_tab, c->h_move, bytes, hipMemcpyHostToDevice, c->hs));      // (on the context's stream: behind every launch that reads the old table)
-    HIPCK(c, hipEventRecord(c->ev_move, c->hs));
+    if ((rc = upload_via_move_area(c, c->d_mixed_tab, "hipHostMalloc failed (mixed input table)", {{mx.offsets.data(), (n + 1) * 8}, {mx.depths, n}}))) return rc;
     c->mixed_depths.assign(mx.depths, mx.depths + n); c->mixed_frames = frames;
     return 0;
 }
@@ -1885,7 +1868,7 @@ static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     a.pcm = pcm_in; a.pairs = out->pairs; a.sub = out->sub; a.peaks = out->peaks;
     int rc = 0;
     if (pc && !out->sub) { if ((rc = pdm_sub_scratch(c, L))) return rc; a.sub = c->d_sub; }
-    if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) return rc;
+    if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, L.two_pass_bytes))) return rc;
     if (mx) { if ((rc = launch_intake_streams(c, L.frames, pcm_in, c->d_mixed, 0, c->n_streams))) return rc; a.pcm = c->d_mixed; }
     if ((rc = launch_rows(c, a, L, 0, c->n_wg))) return rc;
     if (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, pc->words, 0, c->n_streams))) return rc;
@@ -1897,14 +1880,11 @@ static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
 // from, and write their words to, a pinned host area directly (fine-grained, GPU-visible: hipHostMalloc), so the call is two memcpys on
 // the CPU, the launches, and a spin on the stream: its latency is the kernel's. ----
 static int direct_area(dspi_ctx *c, size_t bytes) {
-    if (bytes <= c->direct_cap) return 0;
-    if (c->h_direct) { HIPCK(c, hipStreamSynchronize(c->hs)); (void)hipHostFree(c->h_direct); c->h_direct = nullptr; c->direct_cap = 0; }
-    const size_t want = std::max<size_t>(bytes, 64u << 10);
-    void *hp = nullptr, *dp = nullptr;
-    if (hipHostMalloc(&hp, want, hipHostMallocDefault) != hipSuccess) return fail(c, DSPI_E_NOMEM, "hipHostMalloc failed (direct host area)");
-    if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { (void)hipHostFree(hp); return fail(c, DSPI_E_HIP, "hipHostGetDevicePointer failed"); }
-    c->h_direct = (char *)hp; c->d_direct = (char *)dp; c->direct_cap = want;
-    return 0;
+    if (bytes <= c->h_direct.cap) return 0;
+    if (c->h_direct) HIPCK(c, hipStreamSynchronize(c->hs));      // (no launch may still be using the area that is about to be freed)
+    HipAlloc a;
+    const Mem m = devmem_grow_pinned(a, c->h_direct, bytes, std::max<size_t>(bytes, 64u << 10), true);
+    return m == Mem::Ok ? 0 : mem_fail(c, m, a, "hipHostMalloc failed (direct host area)");
 }
 
 // What a direct call polls (round 6): a word in pinned host memory that the stream itself sets to the call's sequence number behind the
@@ -1914,17 +1894,15 @@ static void completion_word(dspi_ctx *c) {
     const char *e = getenv("DSPI_DIRECT_POLL");
     c->direct_flag = 0;
     if (e && !strcmp(e, "query")) return;
-    void *hp = nullptr, *dp = nullptr;
-    if (hipHostMalloc(&hp, 64, hipHostMallocDefault) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-        c->h_done = (uint32_t *)hp; c->d_done = (uint32_t *)dp; *c->h_done = 0u; c->direct_flag = 1;
-    } else { if (hp) (void)hipHostFree(hp); (void)hipGetLastError(); }
+    HipAlloc a;
+    if (devmem_grow_pinned(a, c->h_done, 64, 64, true) == Mem::Ok) { *c->h_done = 0u; c->direct_flag = 1; }
 }
 
 static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags,
                           std::chrono::steady_clock::time_point call_t0, const PdmCall *pc, const MixedIn *mx) {
     int rc = direct_area(c, L.direct_bytes);
     if (rc) return rc;
-    char *const h = c->h_direct, *const d = c->d_direct;
+    char *const h = c->h_direct, *const d = c->h_direct.device();
     if (mx) {      // the copy widens as it copies (a paused stream's bytes are not read, and nobody reads its run of the area)
         for (uint32_t s = 0; s < c->n_streams; s++)
             if (!c->n_paused || c->active[s])
@@ -1945,7 +1923,7 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
         if (out->sub && !(flags & DSPI_OUT_ENABLED_ONLY)) for_paused_regions(c, L.sub, [&](size_t at, size_t n) { memset(h + L.sub.off + at, 0, n); });
         if (out->peaks) for_paused_regions(c, L.peaks, [&](size_t at, size_t n) { memset(h + L.peaks.off + at, 0, n); });
     }
-    if ((L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) || (rc = launch_rows(c, a, L, 0, c->n_wg)) ||
+    if ((L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, L.two_pass_bytes))) || (rc = launch_rows(c, a, L, 0, c->n_wg)) ||
         (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, reinterpret_cast<uint32_t *>(d + L.pdm_words.off), 0, c->n_streams))) ||
         (clip_out && (rc = gather_clip(c, reinterpret_cast<uint16_t *>(d + L.clip.off))))) return rc;
     // the launches take tens of microseconds: polling answers within a microsecond of their end, a blocking wait adds a wake-up — but only
@@ -1958,7 +1936,7 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     bool flagged = false;
     if (c->direct_flag == 1) {
         ++c->direct_seq;
-        if (hipStreamWriteValue32(c->hs, c->d_done, c->direct_seq, 0) == hipSuccess) flagged = true;
+        if (hipStreamWriteValue32(c->hs, c->h_done.device(), c->direct_seq, 0) == hipSuccess) flagged = true;
         else { (void)hipGetLastError(); c->direct_flag = 0; }      // (this runtime / device cannot: the stream is polled from here on)
     }
     hipError_t q = hipSuccess;
@@ -2007,15 +1985,15 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
 // that is refused (already registered, read-only mapping ...) the copies still work, just synchronously. ----
 static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags, const PdmCall *pc, const MixedIn *mx) {
     int rc;
-    if ((rc = ensure(c, c->d_in, c->d_in_cap, L.pcm.bytes))) return rc;
+    if ((rc = ensure(c, c->d_in, L.pcm.bytes))) return rc;
     a.pcm = c->d_in;
-    if (out->pairs) { if ((rc = ensure(c, c->d_pairs, c->d_pairs_cap, L.pairs.bytes))) return rc; a.pairs = c->d_pairs; }
-    if (out->sub) { if ((rc = ensure(c, c->d_sub, c->d_sub_cap, L.sub.bytes))) return rc; a.sub = c->d_sub; }
-    if (out->peaks) { if ((rc = ensure(c, c->d_peaks, c->d_peaks_cap, L.peaks.bytes))) return rc; a.peaks = c->d_peaks; }
-    if (clip_out && (rc = ensure(c, c->d_clip, c->d_clip_cap, L.clip.bytes))) return rc;
+    if (out->pairs) { if ((rc = ensure(c, c->d_pairs, L.pairs.bytes))) return rc; a.pairs = c->d_pairs; }
+    if (out->sub) { if ((rc = ensure(c, c->d_sub, L.sub.bytes))) return rc; a.sub = c->d_sub; }
+    if (out->peaks) { if ((rc = ensure(c, c->d_peaks, L.peaks.bytes))) return rc; a.peaks = c->d_peaks; }
+    if (clip_out && (rc = ensure(c, c->d_clip, L.clip.bytes))) return rc;
     // dspi_process_pdm: the words' staging buffer is dspi_pdm_modulate's; without `sub` from the caller the chain writes one chunk's Q28 words
     // into the scratch (set per chunk, below: the kernels index by absolute stream)
-    if (pc && ((rc = ensure(c, c->d_pdm_out, c->d_pdm_out_cap, L.pdm_words.bytes)) || (!out->sub && (rc = pdm_sub_scratch(c, L))))) return rc;
+    if (pc && ((rc = ensure(c, c->d_pdm_out, L.pdm_words.bytes)) || (!out->sub && (rc = pdm_sub_scratch(c, L))))) return rc;
     // DSPI_OUT_ENABLED_ONLY leaves the silent parts of pairs / sub unwritten: the staging buffers are copied back whole, so what the
     // caller finds there is zeros (the firmware's own fill), not stale staging memory
     if (flags & DSPI_OUT_ENABLED_ONLY) {
@@ -2033,10 +2011,10 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     }
     if (pc) {      // ... and for the words of the streams the call does not list
         hipError_t me = hipSuccess;
-        for_unlisted_regions(c, L.pdm_words, *pc->work, [&](size_t at, size_t n) { if (me == hipSuccess) me = hipMemsetAsync(reinterpret_cast<char *>(c->d_pdm_out) + at, 0, n, c->hs); });
+        for_unlisted_regions(c, L.pdm_words, *pc->work, [&](size_t at, size_t n) { if (me == hipSuccess) me = hipMemsetAsync(reinterpret_cast<char *>(c->d_pdm_out.get()) + at, 0, n, c->hs); });
         HIPCK(c, me);
     }
-    if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, c->d_spdif_words_cap, L.two_pass_bytes))) return rc;
+    if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, L.two_pass_bytes))) return rc;
     const uint32_t n_chunks = L.n_chunks, row = (uint32_t)c->sm.row;
     // the caller's buffers and the staging buffers: a row range is one contiguous piece of each (tiled words: whole tiles; else streams)
     // (dspi_process_mixed: the caller's PCM is as long as its depths make it, and a chunk's piece of it goes up to the same place of d_mixed_up)
@@ -2160,8 +2138,8 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     PdmCall pdm{pdm_words, nullptr};
     const PdmCall *const pc = pdm_words ? &pdm : nullptr;
     if (pc && (rc = pdm_prepare(c, pdm))) return rc;
-    if (mx && L.mem == CallMem::Device && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed, c->d_mixed_cap, L.pcm.bytes))) return rc;
-    if (mx && L.mem == CallMem::Staged && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed_up, c->d_mixed_up_cap, (size_t)mx->offsets.back()))) return rc;
+    if (mx && L.mem == CallMem::Device && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed, L.pcm.bytes))) return rc;
+    if (mx && L.mem == CallMem::Staged && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed_up, (size_t)mx->offsets.back()))) return rc;
 
     KArgs a{};
     a.img = c->d_images; a.stream_image = c->d_stream_image; a.vals = c->d_vals;
@@ -2176,7 +2154,7 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     if (spdif) { a.spdif = L.spdif_two_pass ? 0u : 1u; a.spdif_pos = c->spdif_pos; }
     if (c->flavor && !tiled) {      // stream-major layout, packed kernel: the mini lines of the outputs whose rows do not reach the emit wave through their delay line (dspi_chain_pk.inc)
         const size_t xb = (size_t)c->n_wg * 3 * kMaxOut * kChunk * c->sm.row * 4;
-        if ((rc = ensure(c, c->d_xwords, c->d_xwords_cap, xb))) return rc;
+        if ((rc = ensure(c, c->d_xwords, xb))) return rc;
         a.xwords = c->d_xwords;
     }
 
@@ -2223,8 +2201,8 @@ int dspi_wire_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, const
     const uint32_t *d_pos = block_pos;
     int rc;
     if (!dev) {
-        if ((rc = ensure(c, c->d_spdif_in, c->d_spdif_in_cap, in_b)) || (rc = ensure(c, c->d_spdif_out, c->d_spdif_out_cap, out_b)) ||
-            (rc = ensure(c, c->d_spdif_vpos, c->d_spdif_vpos_cap, pos_b))) return rc;
+        if ((rc = ensure(c, c->d_spdif_in, in_b)) || (rc = ensure(c, c->d_spdif_out, out_b)) ||
+            (rc = ensure(c, c->d_spdif_vpos, pos_b))) return rc;
         HIPCK(c, hipMemcpyAsync(c->d_spdif_in, pairs, in_b, hipMemcpyHostToDevice, c->hs));
         HIPCK(c, hipMemcpyAsync(c->d_spdif_vpos, block_pos, pos_b, hipMemcpyHostToDevice, c->hs));
         d_in = c->d_spdif_in; d_out = c->d_spdif_out; d_pos = c->d_spdif_vpos;
@@ -2288,7 +2266,7 @@ int dspi_debug_intake(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths
         return fail(c, DSPI_E_INVAL, "dspi_debug_intake: the buffer's size overflows");
     HIPCK(c, hipSetDevice(c->device));
     if (c->n_paused && (rc = upload_activity(c))) return rc;
-    if ((rc = intake_prepare(c, mx, frames, c->d_mixed, c->d_mixed_cap, (size_t)out_bytes))) return rc;
+    if ((rc = intake_prepare(c, mx, frames, c->d_mixed, (size_t)out_bytes))) return rc;
     return launch_intake_streams(c, frames, pcm_in, c->d_mixed, 0, c->n_streams);
 }
 
@@ -2304,9 +2282,8 @@ int dspi_pdm_fade(dspi_ctx *c, int enable) {
     if (enable > 0 && !c->pdm_fade.on) {
         if (c->device != DSPI_DEVICE_NONE) {      // every stream: base 0
             HIPCK(c, hipSetDevice(c->device));
-            const size_t b = (size_t)c->cap_wg * c->sm.row * 4;
-            if (!c->d_pdm_base && hipMalloc((void **)&c->d_pdm_base, b) != hipSuccess) { c->d_pdm_base = nullptr; (void)hipGetLastError(); return fail(c, DSPI_E_NOMEM, "hipMalloc failed (PDM fade bases)"); }
-            HIPCK(c, hipMemsetAsync(c->d_pdm_base, 0, b, c->hs));
+            if (int rc = persist_alloc(c, kArrPdmBase, "hipMalloc failed (PDM fade bases)")) return rc;
+            HIPCK(c, hipMemsetAsync(c->d_pdm_base, 0, c->d_pdm_base.cap, c->hs));
         }
         c->pdm_fade.enable(c->pdm_life);
     } else if (enable == 0) c->pdm_fade.disable(c->pdm_life);
