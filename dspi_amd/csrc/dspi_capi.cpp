@@ -10,6 +10,7 @@
 
 #include <string.h>
 
+#include <map>
 #include <memory>
 #include <new>
 #include <cstdlib>
@@ -30,6 +31,7 @@
 #include "dspi_params.h"
 #include "dspi_boot.h"
 #include "dspi_devmem.h"
+#include "dspi_flash.h"
 #include "dspi_group.h"
 #include "dspi_intake.h"
 #include "dspi_migrate.h"
@@ -158,6 +160,9 @@ struct dspi_ctx {
     DevBuf<uint32_t> d_mig_pos{mem};
     PinnedBuf<char> h_mig{mem};
     hipEvent_t ev_mig = nullptr;
+    // dspi_device_flash (dspi_flash.h): while on, every stream holds a flash of its own (shared until written) and the preset directory requests
+    // are served from it.  Host memory only; consulted in request and maintenance paths, never by dspi_process.
+    FlashBook flash;
     std::string err;
 };
 
@@ -281,6 +286,71 @@ void merge_images(dspi_ctx *c) {
 
 const Params &readable(const dspi_ctx *c, int32_t stream) {
     return *c->images[(size_t)c->stream_image[stream == DSPI_ALL_STREAMS ? 0 : (size_t)stream]];
+}
+
+// ---- the streams' own flashes (dspi_device_flash; the model and the book are dspi_flash.h) ----
+// A request that may write the flash, for one stream (both objects clone on write) or for all: once per distinct (parameter object, flash
+// object) pair, after an object that stands in several pairs got a clone per further pair, so that streams that shared both keep sharing
+// both.  f(Params &, Flash &) answers like Params::vendor_get; a broadcast answers with stream 0's device.
+template <class F>
+int for_flash_targets(dspi_ctx *c, int32_t stream, F f) {
+    if (stream != DSPI_ALL_STREAMS) { Params *p = writable(c, stream); return f(*p, *c->flash.writable((uint32_t)stream)); }
+    std::vector<uint32_t> pair_of;
+    const std::vector<FlashPair> pairs = flash_pairs(c->stream_image, c->flash.index, &pair_of);
+    std::vector<int32_t> image(pairs.size()), obj(pairs.size());
+    std::vector<uint8_t> image_seen(c->images.size(), 0), obj_seen(c->flash.objects.size(), 0);
+    bool split = false;
+    for (size_t k = 0; k < pairs.size(); k++) {
+        image[k] = pairs[k].image; obj[k] = pairs[k].flash;
+        if (image_seen[(size_t)pairs[k].image]) { image[k] = add_image(c, std::make_unique<Params>(*c->images[(size_t)pairs[k].image])); split = true; }
+        if (obj_seen[(size_t)pairs[k].flash]) { obj[k] = c->flash.add(std::make_unique<Flash>(*c->flash.objects[(size_t)pairs[k].flash])); split = true; }
+        image_seen[(size_t)pairs[k].image] = obj_seen[(size_t)pairs[k].flash] = 1;
+    }
+    if (split)
+        for (uint32_t s = 0; s < c->n_streams; s++) {
+            const uint32_t k = pair_of[s];
+            if (image[k] != c->stream_image[s]) assign_image(c, s, image[k]);
+            if (obj[k] != c->flash.index[s]) c->flash.assign(s, obj[k]);
+        }
+    if (c->images.size() > 1) c->merge_hint = true;
+    int rc = 0;
+    for (size_t k = pairs.size(); k-- > 0;) rc = f(*c->images[(size_t)image[k]], *c->flash.objects[(size_t)obj[k]]);      // (stream 0's pair last: its answer stands)
+    return rc;
+}
+
+// The mirrors of the parameter objects of [first, first + count) follow their slots' directories: where they disagree (objects that came
+// from elsewhere: an import), the streams of one (object, flash) pair move to one clone that agrees.
+void flash_resync(dspi_ctx *c, const uint32_t *streams, uint32_t first, uint32_t count) {      // streams == nullptr: the range from `first`
+    std::map<std::pair<int32_t, int32_t>, int32_t> fixed;
+    for (uint32_t i = 0; i < count; i++) {
+        const uint32_t s = streams ? streams[i] : first + i;
+        const Flash &fl = c->flash.readable(s);
+        const PresetDir d = fl.directory();
+        const Params &r = *c->images[(size_t)c->stream_image[s]];
+        if (r.dir_master_volume_mode == d.master_volume_mode && r.dir_include_pins == d.include_pins && memcmp(&r.dir_master_volume_db, &d.master_volume_db, 4) == 0) continue;
+        const std::pair<int32_t, int32_t> key(c->stream_image[s], c->flash.index[s]);
+        auto it = fixed.find(key);
+        if (it == fixed.end()) {
+            auto p = std::make_unique<Params>(r);
+            flash_sync_mirrors(fl, *p);
+            it = fixed.emplace(key, add_image(c, std::move(p))).first;
+        }
+        assign_image(c, s, it->second);
+        c->merge_hint = true;
+    }
+}
+void flash_resync(dspi_ctx *c, uint32_t first, uint32_t count) { flash_resync(c, nullptr, first, count); }
+
+// one new flash object per distinct parameter object among the streams of [first, first + count): the first-boot flash with that object's
+// mirrored master-volume fields (dspi_device_flash(1), arrivals from a context without the mode)
+void flash_first_boot_range(dspi_ctx *c, uint32_t first, uint32_t count) {
+    std::vector<int32_t> of_image(c->images.size(), -1);
+    for (uint32_t s = first; s < first + count; s++) {
+        int32_t &o = of_image[(size_t)c->stream_image[s]];
+        if (o < 0) o = c->flash.add(Flash::first_boot(c->flavor, c->populated, c->images[(size_t)c->stream_image[s]].get()));
+        c->flash.assign(s, o);
+    }
+    flash_resync(c, first, count);
 }
 
 // The allocator of dspi_devmem.h on HIP — the one place that allocates and frees.  hipFree and hipHostFree wait for the device, and growing
@@ -723,7 +793,18 @@ int dspi_load_flash_dump(dspi_ctx *c, int32_t stream, const void *dump, size_t l
     // (preset_boot_load -> apply_slot_to_live, flash_storage.c:1047-1082: no mute, no line zeroing): exact against the firmware from
     // frame 0.  Every other context is a running device that switches to the preset the dump selects (preset_load, :794-849).
     const bool as_boot = c->populated && !c->audio_started;
-    return for_targets(c, stream, [&](Params &p) { return p.load_flash_dump(dump, len, as_boot); });
+    const int rc = for_targets(c, stream, [&](Params &p) { return p.load_flash_dump(dump, len, as_boot); });
+    // dspi_device_flash: the dump becomes the streams' flash (one shared object), with the writes of a boot over it (dspi_flash.h boot_writes)
+    if (c && c->flash.on && valid_stream(c, stream)) {
+        auto f = std::make_unique<Flash>();
+        f->set_bytes(dump);
+        f->boot_writes(c->flavor);
+        const int32_t obj = c->flash.add(std::move(f));
+        const uint32_t s0 = stream == DSPI_ALL_STREAMS ? 0u : (uint32_t)stream, n = stream == DSPI_ALL_STREAMS ? c->n_streams : 1u;
+        for (uint32_t s = s0; s < s0 + n; s++) c->flash.assign(s, obj);
+        flash_resync(c, s0, n);
+    }
+    return rc;
 }
 int dspi_flash_read_directory(const void *dump, size_t len, dspi_flash_dir *out) {
     if (!dump || !out) return DSPI_E_INVAL;
@@ -742,10 +823,19 @@ int dspi_save_preset_slot(dspi_ctx *c, int32_t stream, void *image, size_t cap, 
 }
 int dspi_vendor_set(dspi_ctx *c, int32_t stream, uint8_t req, uint16_t wValue, const void *payload, uint16_t len) {
     if (len && !payload) return DSPI_E_INVAL;
+    if (c && c->flash.on && flash_request_out(req)) {      // dspi_device_flash: the directory's setters write the stream's own flash
+        if (!valid_stream(c, stream)) return fail(c, DSPI_E_INVAL, "stream index out of range");
+        return for_flash_targets(c, stream, [&](Params &p, Flash &f) { return flash_vendor_set(f, p, req, wValue, payload, len); });
+    }
     return for_targets(c, stream, [&](Params &p) { return p.vendor_set(req, wValue, payload, len); });
 }
 int dspi_vendor_get(dspi_ctx *c, int32_t stream, uint8_t req, uint16_t wValue, void *buf, uint16_t cap) {
     if (!c || !buf || !valid_stream(c, stream)) return DSPI_E_INVAL;
+    if (c->flash.on && flash_request_in(req)) {      // dspi_device_flash: the preset directory, served from the stream's own flash
+        if (!flash_request_writes(req)) return flash_vendor_read(c->flash.readable(stream == DSPI_ALL_STREAMS ? 0u : (uint32_t)stream), req, wValue, buf, cap);
+        if (cap < 1) return DSPI_E_SHORT;
+        return for_flash_targets(c, stream, [&](Params &p, Flash &f) { return flash_vendor_get(f, p, req, wValue, buf, cap); });
+    }
     uint16_t peaks[kMaxCh], clip = 0;
     const bool needs_status = (req == 0x50 || req == 0x83);
     if (needs_status) { int rc = fetch_status(c, stream, peaks, &clip); if (rc) return rc; }
@@ -1041,6 +1131,7 @@ int dspi_import_streams(dspi_ctx *c, uint32_t first, const dspi_snapshot *snap, 
         assign_image(c, (size_t)first + k, (int32_t)(base + im));
     }
     c->merge_hint = true;
+    if (c->flash.on) flash_resync(c, first, count);      // (a snapshot carries no flash: the slots keep theirs, and the arrivals' directory mirrors follow it)
     if (h.flags & kSnapAudioStarted) c->audio_started = true;      // running devices arrived: dspi_load_flash_dump is no boot any more
     // run-time state, behind whatever the context's stream still has to do (a realigning import reads its rows' resident neighbours
     // there, on the device: their positions are what that work leaves)
@@ -1239,6 +1330,7 @@ int dspi_move_streams(dspi_ctx *c, const dspi_stream_move *moves, uint32_t n, ui
     if (c->spdif_ps.on) c->spdif_ps.move(mv.data(), nm, host_activity(c));      // (the S/PDIF position is the device's own counter: it travels too)
     c->pdm_life.move(mv.data(), nm);      // (... and whether its modulator is running)
     c->pdm_fade.move(mv.data(), nm);      // (... and how far it has faded)
+    if (c->flash.on) c->flash.move(mv.data(), nm);      // (... and its flash, by reference)
     const bool have_active = !c->active.empty();
     std::vector<int32_t> img(nm);
     std::vector<uint8_t> act(nm, 1), is_dst(c->n_streams, 0);
@@ -1284,6 +1376,7 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
     if (flags & ~(DSPI_MIGRATE_AS_IS | DSPI_MIGRATE_PAUSED)) return migrate_fail(src, dst, DSPI_E_INVAL, "dspi_migrate_streams: undefined flag bits");
     const StreamMove *list = reinterpret_cast<const StreamMove *>(moves);
     if (const char *why = migrate_validate(list, n, src->n_streams, dst->n_streams, host_activity(dst))) return migrate_fail(src, dst, DSPI_E_INVAL, std::string("dspi_migrate_streams: ") + why);
+    if (src->flash.on && !dst->flash.on) return migrate_fail(src, dst, DSPI_E_INVAL, "dspi_migrate_streams: the source's streams own flashes (dspi_device_flash), the destination's do not");
     if (src->device == DSPI_DEVICE_NONE || dst->device == DSPI_DEVICE_NONE) return migrate_fail(src, dst, DSPI_E_NODEVICE, "host-only context: no run-time state to migrate");
     const uint32_t row = (uint32_t)src->sm.row, cap = std::min(move_batch_records(src), move_batch_records(dst));
     const bool realign = !(flags & DSPI_MIGRATE_AS_IS);
@@ -1397,6 +1490,21 @@ int dspi_migrate_streams(dspi_ctx *src, dspi_ctx *dst, const dspi_stream_move *m
     for (int32_t im : used) add_image(dst, std::make_unique<Params>(*src->images[(size_t)im]));
     for (uint32_t i = 0; i < n; i++) assign_image(dst, list[i].dst, (int32_t)(base + index[i]));
     dst->merge_hint = true; dst->launch_dirty = true;
+    // the flashes travel by value too (dspi_flash.h); arrivals from a context without the mode get the flash a first boot leaves
+    if (dst->flash.on) {
+        if (src->flash.on) { src->flash.leave(list, n); dst->flash.arrive(src->flash, list, n); }
+        else {
+            std::vector<int32_t> fresh(used.size(), -1);
+            for (uint32_t i = 0; i < n; i++) {
+                int32_t &o = fresh[index[i]];
+                if (o < 0) o = dst->flash.add(Flash::first_boot(dst->flavor, dst->populated, dst->images[base + index[i]].get()));
+                dst->flash.assign(list[i].dst, o);
+            }
+        }
+        std::vector<uint32_t> arrived(n);
+        for (uint32_t i = 0; i < n; i++) arrived[i] = list[i].dst;
+        flash_resync(dst, arrived.data(), 0, n);
+    }
     if (src->audio_started) dst->audio_started = true;      // running devices arrived: dspi_load_flash_dump is no boot any more
     // the S/PDIF position is the device's own counter, the activity belongs to the stream: both arrive with it (DSPI_MIGRATE_PAUSED: it
     // arrives paused); every source slot stays behind as a paused, frozen copy, its position frozen with it
@@ -1464,15 +1572,35 @@ int dspi_plan_grouping(dspi_ctx *c, dspi_stream_move *moves, uint32_t cap, uint3
 // ---- stream boots (dspi_boot.h: validation and the kernel's work items; dspi_boot.hip: the power-on kernel) ----
 int dspi_boot_streams(dspi_ctx *c, const uint32_t *streams, uint32_t n, const void *dump, size_t len, uint32_t flags, int *selection) {
     if (!c) return DSPI_E_INVAL;
-    if (flags & ~DSPI_BOOT_STREAMS_AS_IS) return fail(c, DSPI_E_INVAL, "dspi_boot_streams: undefined flag bits");
+    if (flags & ~(DSPI_BOOT_STREAMS_AS_IS | DSPI_BOOT_STREAMS_OWN_FLASH)) return fail(c, DSPI_E_INVAL, "dspi_boot_streams: undefined flag bits");
     // everything is validated before anything is written
     if (const char *why = boot_validate(streams, n, c->n_streams)) return fail(c, DSPI_E_INVAL, std::string("dspi_boot_streams: ") + why);
+    const bool own = (flags & DSPI_BOOT_STREAMS_OWN_FLASH) != 0;
+    if (own && !c->flash.on) return fail(c, DSPI_E_INVAL, "dspi_boot_streams: DSPI_BOOT_STREAMS_OWN_FLASH needs dspi_device_flash");
+    if (own && dump) return fail(c, DSPI_E_INVAL, "dspi_boot_streams: DSPI_BOOT_STREAMS_OWN_FLASH takes no dump");
     if (dump && len < kFlashDumpBytes) return fail(c, DSPI_E_SHORT, "dspi_boot_streams: dump shorter than DSPI_FLASH_DUMP_BYTES");
     // the device that has just been powered on: dspi_create's own, or one that boots from the dump's flash (first_boot = false, then
-    // boot(dump): Params::load_flash_dump's boot path; sample rate, UAC1 volume and mute stay at their power-on values)
-    auto p = std::make_unique<Params>(c->flavor, c->fma, dump ? false : !c->populated);
-    int sel = 48;
-    if (dump) sel = p->load_flash_dump(dump, len, true);
+    // boot(dump): Params::load_flash_dump's boot path; sample rate, UAC1 volume and mute stay at their power-on values).  With
+    // DSPI_BOOT_STREAMS_OWN_FLASH one such device per distinct flash object among the listed streams, booted from that flash.
+    struct Group { std::unique_ptr<Params> p; int32_t flash = -1; int sel = 48; std::vector<uint32_t> members; };
+    std::vector<Group> groups;
+    if (own) {
+        std::map<int32_t, size_t> of_flash;
+        for (uint32_t i = 0; i < n; i++) {
+            const auto it = of_flash.emplace(c->flash.index[streams[i]], groups.size());
+            if (it.second) { groups.emplace_back(); groups.back().flash = it.first->first; }
+            groups[it.first->second].members.push_back(streams[i]);
+        }
+        for (Group &g : groups) {
+            g.p = std::make_unique<Params>(c->flavor, c->fma, false);
+            g.sel = g.p->load_flash_dump(c->flash.objects[(size_t)g.flash]->bytes, kFlashDumpBytes, true);
+        }
+    } else {
+        groups.emplace_back();
+        groups[0].p = std::make_unique<Params>(c->flavor, c->fma, dump ? false : !c->populated);
+        if (dump) groups[0].sel = groups[0].p->load_flash_dump(dump, len, true);
+        groups[0].members.assign(streams, streams + n);
+    }
     // run-time state, on the context's stream, behind whatever it still has to do (the kernel reads the rows' residents' positions there)
     if (c->device != DSPI_DEVICE_NONE) {
         HIPCK(c, hipSetDevice(c->device));
@@ -1483,17 +1611,72 @@ int dspi_boot_streams(dspi_ctx *c, const uint32_t *streams, uint32_t n, const vo
         HIPCK(c, launch_boot(c->flavor, state_arrays(c), c->d_move, (uint32_t)items.size(), c->hs));
         if (bases) HIPCK(c, launch_pdm_base_scatter(c->d_pdm_base, c->d_move + items.size() * (sizeof(BootRowItem) / 4), n, c->n_streams, nullptr, c->hs));      // fade_base_pcm at power-on: 0
     }
-    // parameters: the listed streams leave their objects (whose pending state operations never reach them) and share ONE new one, whose
-    // own pending operations the next commit applies over the power-on state, as after dspi_create.  An object that lost its last stream
-    // is dropped, and a new object equal to one already here folded into it, by the fold-back pass (merge_images).
-    const int32_t slot = add_image(c, std::move(p));
-    for (uint32_t i = 0; i < n; i++) assign_image(c, streams[i], slot);
+    // the flash (dspi_device_flash): the dump with the boot's own writes, the flash a first boot leaves, or — own flash — the streams' flash
+    // with the boot's writes (in place when every holder is listed, else in a copy the listed holders share)
+    if (c->flash.on) {
+        for (Group &g : groups) {
+            std::unique_ptr<Flash> f;
+            if (own) {
+                if (c->flash.refs[(size_t)g.flash] == g.members.size()) { c->flash.objects[(size_t)g.flash]->boot_writes(c->flavor); continue; }
+                f = std::make_unique<Flash>(*c->flash.objects[(size_t)g.flash]);
+                f->boot_writes(c->flavor);
+            } else if (dump) {
+                f = std::make_unique<Flash>();
+                f->set_bytes(dump);
+                f->boot_writes(c->flavor);
+            } else f = Flash::first_boot(c->flavor, c->populated, nullptr);
+            g.flash = c->flash.add(std::move(f));
+            c->flash.boot(g.members.data(), (uint32_t)g.members.size(), g.flash);
+        }
+        for (Group &g : groups) flash_sync_mirrors(*c->flash.objects[(size_t)g.flash], *g.p);
+    }
+    // parameters: the listed streams leave their objects (whose pending state operations never reach them) and share ONE new one (own
+    // flash: one per distinct flash object), whose own pending operations the next commit applies over the power-on state, as after
+    // dspi_create.  An object that lost its last stream is dropped, and a new object equal to one already here folded into it, by the
+    // fold-back pass (merge_images).
+    for (Group &g : groups) {
+        const int32_t slot = add_image(c, std::move(g.p));
+        for (uint32_t s : g.members) assign_image(c, s, slot);
+    }
     c->launch_dirty = true; c->merge_hint = true;
     if (c->spdif_ps.on) c->spdif_ps.boot(streams, n, host_activity(c));      // a device that has just been powered on sends frame 0 of a block first
     c->pdm_life.boot(streams, n);      // ... and has never run its modulator
     c->pdm_fade.boot(streams, n);      // ... nor faded it
-    if (selection) *selection = sel;
+    if (selection) *selection = groups[0].sel;
     return (int)n;
+}
+
+// ---- the streams' own flashes (include/dspi.h "a stream's own flash"; dspi_flash.h) ----
+int dspi_device_flash(dspi_ctx *c, int enable) {
+    if (!c) return DSPI_E_INVAL;
+    if (enable < 0 || (enable != 0) == c->flash.on) return c->flash.on ? 1 : 0;
+    if (!enable) { c->flash.drop(); return 0; }
+    c->flash.enable(c->n_streams);
+    flash_first_boot_range(c, 0, c->n_streams);
+    return 1;
+}
+
+int dspi_flash_read(dspi_ctx *c, uint32_t stream, void *dump, size_t cap) {
+    if (!c || !dump) return DSPI_E_INVAL;
+    if (!c->flash.on) return fail(c, DSPI_E_INVAL, "dspi_flash_read: the streams own no flash (dspi_device_flash)");
+    if (stream >= c->n_streams) return fail(c, DSPI_E_INVAL, "dspi_flash_read: stream index out of range");
+    if (cap < kFlashDumpBytes) return fail(c, DSPI_E_SHORT, "dspi_flash_read: buffer shorter than DSPI_FLASH_DUMP_BYTES");
+    memcpy(dump, c->flash.readable(stream).bytes, kFlashDumpBytes);
+    return (int)kFlashDumpBytes;
+}
+
+int dspi_flash_write(dspi_ctx *c, uint32_t first, uint32_t count, const void *dump, size_t len) {
+    if (!c || !dump) return DSPI_E_INVAL;
+    // everything is validated before anything is written
+    if (!c->flash.on) return fail(c, DSPI_E_INVAL, "dspi_flash_write: the streams own no flash (dspi_device_flash)");
+    if (count == 0 || (uint64_t)first + count > c->n_streams) return fail(c, DSPI_E_INVAL, "dspi_flash_write: stream range out of bounds");
+    if (len < kFlashDumpBytes) return fail(c, DSPI_E_SHORT, "dspi_flash_write: dump shorter than DSPI_FLASH_DUMP_BYTES");
+    auto f = std::make_unique<Flash>();
+    f->set_bytes(dump);
+    const int32_t obj = c->flash.add(std::move(f));
+    for (uint32_t s = first; s < first + count; s++) c->flash.assign(s, obj);
+    flash_resync(c, first, count);      // the mirrors follow the new directory (without a valid one: the fresh directory every request would see)
+    return (int)count;
 }
 
 // ---- resizing (dspi_resize.h: validation, row arithmetic, the new slots' work items; dspi_boot.hip: the power-on kernel) ----
@@ -1542,6 +1725,10 @@ static void resize_books(dspi_ctx *c, uint32_t n_new, int32_t slot, bool arrive_
     }
     c->pdm_life.resize(n_new);      // (new slots: never ran)
     c->pdm_fade.resize(n_new);      // (... never faded)
+    if (c->flash.on) {              // (... and share the flash a first boot leaves; a shrink releases the cut slots')
+        c->flash.resize(n_new, n_new > n_old ? c->flash.add(Flash::first_boot(c->flavor, c->populated, nullptr)) : -1);
+        if (n_new > n_old) flash_resync(c, n_old, n_new - n_old);
+    }
     c->assignment_dirty = true; c->merge_hint = true;      // (an object may have lost its last stream, or the new one equal one already here: the fold-back pass)
     activity_changed(c);
 }

@@ -870,10 +870,28 @@ bool Params::slot_to_live(const void *image, int expect_slot) {
 
 int Params::load_slot(const void *image, size_t len, int expect_slot) {     // preset_load (flash_storage.c:794-849) under main.c:926-976
     if (len < (size_t)slot_size()) return 3;    // PRESET_ERR_CRC
+    return preset_apply(image, expect_slot, true);
+}
+
+uint32_t Params::flash_hold_samples() const {
+    const uint64_t hold = ((uint64_t)freq * 10u + 999u) / 1000u;
+    return hold < 512u ? 512u : (uint32_t)hold;
+}
+uint32_t Params::flash_premute_samples() const {
+    const uint64_t s = ((uint64_t)freq * 120u + 999u) / 1000u;
+    return s < kPresetMuteSamples ? kPresetMuteSamples : (uint32_t)s;
+}
+
+// preset_load (flash_storage.c:794-849): an occupied slot's image or, image == nullptr, the factory defaults of an unoccupied one.
+// main_loop: the bracket of the deferred REQ_PRESET_LOAD (main.c:926-976: prepare_pipeline_reset before, the type switch after);
+// without it the call is flash_load_params inside REQ_LOAD_PARAMS (usb_audio.c:2482-2489), which has neither.
+int Params::preset_apply(const void *image, int slot, bool main_loop) {
     FtzScope ftz;
-    pipeline_mute(kPresetMuteSamples);
+    if (main_loop) pipeline_mute(kPresetMuteSamples);
     uint8_t old_types[4]; memcpy(old_types, output_types, 4);
-    if (!slot_to_live(image, expect_slot)) { ops.mute_start = 0; ops.mute_cancel = 1; return 3; }    // preset_loading = false (:806)
+    if (image) {
+        if (!slot_to_live(image, slot)) { ops.mute_start = 0; ops.mute_cancel = 1; return 3; }    // preset_loading = false (:806)
+    } else apply_factory_defaults();                                                               // (:811-814)
 
     float fs = (float)freq;
     recalc_all_filters(fs); update_delay_samples(fs);
@@ -881,16 +899,24 @@ int Params::load_slot(const void *image, size_t len, int expect_slot) {     // p
     transition_core1();
     // preset_load ends by writing the directory (flash_storage.c:846-847) and every flash_write_sector re-arms the mute
     // for flash_mute_hold_samples() = max(10 ms, 512 samples) (:272-276, :347-348)
-    {
-        uint64_t hold = ((uint64_t)freq * 10u + 999u) / 1000u;
-        pipeline_mute(hold < 512u ? 512u : (uint32_t)hold);
-    }
+    pipeline_mute(flash_hold_samples());
     // a preset that changes an output slot's type goes through process_type_switches, which arms the mute once more
     // with PRESET_MUTE_SAMPLES (main.c:957-972, :279)
-    if (memcmp(old_types, output_types, (size_t)n_pairs) != 0) pipeline_mute(kPresetMuteSamples);
+    if (main_loop && memcmp(old_types, output_types, (size_t)n_pairs) != 0) pipeline_mute(kPresetMuteSamples);
     service();
     return 0;
 }
+
+void Params::preset_deleted_active() {     // flash_storage.c:882-904: no line zeroing here
+    FtzScope ftz;
+    pipeline_mute(kPresetMuteSamples);
+    apply_factory_defaults();
+    float fs = (float)freq;
+    recalc_all_filters(fs); update_delay_samples(fs);
+    transition_core1();
+}
+
+void Params::main_loop_pass() { FtzScope ftz; service(); }
 
 // ------------------------------------------------------------------------------------------
 // flash dump: directory sector, startup-slot selection, legacy migration (flash_storage.c:370-417, :997-1105)

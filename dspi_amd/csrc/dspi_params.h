@@ -68,6 +68,13 @@ public:
     void set_volume(int16_t v);
     void set_mute(bool m);
     int set_rate(uint32_t hz);
+    // the live half of the preset directory requests (dspi_flash.cpp runs them over a stream's own flash; no directory state lives here)
+    int preset_apply(const void *image, int slot, bool main_loop);      // preset_load: a validated-here slot image, or nullptr = factory defaults; main_loop: REQ_PRESET_LOAD's deferred bracket (main.c:926-976), else inside the request (REQ_LOAD_PARAMS)
+    void preset_deleted_active();                                       // preset_delete of the active slot: factory defaults under PRESET_MUTE_SAMPLES (flash_storage.c:882-904)
+    void main_loop_pass();                                              // the pending recomputations a serviced request leaves (main.c:867-894)
+    void flash_mute(uint32_t samples) { pipeline_mute(samples); }
+    uint32_t flash_hold_samples() const;                                // flash_mute_hold_samples(), flash_storage.c:272-276
+    uint32_t flash_premute_samples() const;                             // samples_for_duration_ms(freq, FLASH_WRITE_PREMUTE_MS), main.c:543-556
 
     void build_image(DevImage &img) const;
     int slot_size() const;

@@ -24,6 +24,8 @@ MIGRATE_AS_IS = 0x1
 MIGRATE_PAUSED = 0x2
 GROUP_ONE_WAY = 0x1
 BOOT_STREAMS_AS_IS = 0x1
+BOOT_STREAMS_OWN_FLASH = 0x2
+FLASH_DUMP_BYTES = 12 * 4096
 RESIZE_PAUSED = 0x1
 OUT_TILED = 0x2
 OUT_ENABLED_ONLY = 0x4
@@ -152,6 +154,10 @@ def lib() -> C.CDLL:
     if hasattr(L, "dspi_process_wire"):      # (ABI 8 + wire words per device: detected by symbol; with it dspi_wire_encode)
         L.dspi_process_wire.argtypes = [vp, vp, C.c_int, u32, u32, C.POINTER(_Out), vp, u32]
         L.dspi_wire_encode.argtypes = [vp, vp, u32, vp, vp, u32]
+    if hasattr(L, "dspi_device_flash"):      # (ABI 8 + a stream's own flash: detected by symbol; with it dspi_flash_read, dspi_flash_write, DSPI_BOOT_STREAMS_OWN_FLASH)
+        L.dspi_device_flash.argtypes = [vp, C.c_int]
+        L.dspi_flash_read.argtypes = [vp, u32, vp, C.c_size_t]
+        L.dspi_flash_write.argtypes = [vp, u32, u32, vp, C.c_size_t]
     _lib = L
     return L
 
@@ -669,14 +675,30 @@ class Dspi:
         return m
 
     # ---- stream boots (include/dspi.h: a slot is power-cycled inside its running context) ----
-    def boot_streams(self, streams, dump: bytes | None = None, as_is: bool = False) -> int:
+    def device_flash(self, enable: int = -1) -> int:
+        """dspi_device_flash: every stream owns a 48 KB preset area and the preset directory requests are served from it (enable < 0: only
+        read the mode).  Host memory only: no kernel, nothing per dspi_process call."""
+        return self._ck(self.L.dspi_device_flash(self.h, enable), "device_flash")
+
+    def flash_read(self, stream: int) -> bytes:
+        """dspi_flash_read: the stream's own flash (mode on only)"""
+        buf = C.create_string_buffer(FLASH_DUMP_BYTES)
+        self._ck(self.L.dspi_flash_read(self.h, stream, buf, FLASH_DUMP_BYTES), "flash_read")
+        return buf.raw
+
+    def flash_write(self, first: int, count: int, dump: bytes) -> int:
+        """dspi_flash_write: one image for [first, first + count) as one shared object; boots nothing"""
+        return self._ck(self.L.dspi_flash_write(self.h, first, count, dump, len(dump)), "flash_write")
+
+    def boot_streams(self, streams, dump: bytes | None = None, as_is: bool = False, own_flash: bool = False) -> int:
         """dspi_boot_streams: every listed slot becomes a device that has just been powered on — dspi_create's own (dump None) or one that
         boots from the 48 KB preset area `dump` — on its row's write positions (as_is: DSPI_BOOT_STREAMS_AS_IS, on the power-on positions).
+        own_flash: DSPI_BOOT_STREAMS_OWN_FLASH, every listed slot reboots from its own flash (dspi_device_flash).
         Returns preset_boot_load's selection (dspi_load_flash_dump's codes; 48 without a dump).  Works on host-only contexts."""
         s = np.ascontiguousarray(np.asarray(streams, dtype=np.uint32).reshape(-1))
         sel = C.c_int(-1)
         n = self._ck(self.L.dspi_boot_streams(self.h, s.ctypes.data if len(s) else None, len(s), dump, len(dump) if dump is not None else 0,
-                                              BOOT_STREAMS_AS_IS if as_is else 0, C.byref(sel)), "boot_streams")
+                                              (BOOT_STREAMS_AS_IS if as_is else 0) | (BOOT_STREAMS_OWN_FLASH if own_flash else 0), C.byref(sel)), "boot_streams")
         assert n == len(s)
         return sel.value
 

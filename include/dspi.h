@@ -77,7 +77,8 @@ extern "C" {
                               * 8 + grouping: detect by symbol (dspi_plan_grouping; with it DSPI_GROUP_ONE_WAY; additions only);
                               * 8 + PDM words from the call: detect by symbol (dspi_process_pdm; with it dspi_pdm_running; additions only);
                               * 8 + mixed input formats: detect by symbol (dspi_process_mixed; with it dspi_mixed_pcm_bytes; additions only);
-                              * 8 + wire words per device: detect by symbol (dspi_process_wire; with it dspi_wire_encode; additions only) */
+                              * 8 + wire words per device: detect by symbol (dspi_process_wire; with it dspi_wire_encode; additions only);
+                              * 8 + a stream's own flash: detect by symbol (dspi_device_flash; with it dspi_flash_read, dspi_flash_write, DSPI_BOOT_STREAMS_OWN_FLASH; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -542,8 +543,69 @@ int dspi_plan_grouping(dspi_ctx *ctx, dspi_stream_move *moves, uint32_t cap, uin
  *                       device that has just been powered on sends frame 0 of a block, preamble Z, first; see there.)
  * Not in scope: choosing which free slot an arrival takes. */
 #define DSPI_BOOT_STREAMS_AS_IS 0x1u   /* keep the power-on write positions (delay write index 0, ring position 0) */
+#define DSPI_BOOT_STREAMS_OWN_FLASH 0x2u   /* every listed slot reboots from its own flash (dspi_device_flash, below); the dump must be NULL */
 int dspi_boot_streams(dspi_ctx *ctx, const uint32_t *streams, uint32_t n,
                       const void *dump, size_t len, uint32_t flags, int *selection);
+
+/* ---- a stream's own flash: each stream owns its preset area, REQ_PRESET_* served ----------------------------------------------------------- */
+/* A DSPi device keeps ten presets, their names and its startup choice in 48 KB of flash, and its control application works through the
+ * preset directory requests: REQ_PRESET_SAVE / LOAD / DELETE (0x90-0x92), REQ_PRESET_GET_NAME / SET_NAME / GET_DIR (0x93-0x95),
+ * REQ_PRESET_SET_STARTUP / GET_STARTUP (0x96-0x97), REQ_PRESET_SET_INCLUDE_PINS / GET_INCLUDE_PINS (0x98-0x99), REQ_PRESET_GET_ACTIVE (0x9A)
+ * and the legacy REQ_SAVE_PARAMS / REQ_LOAD_PARAMS (0x51 / 0x52).  Without this mode a stream has no flash and those requests
+ * answer DSPI_E_UNSUPPORTED; with it every stream owns a preset area (DSPI_FLASH_DUMP_BYTES, laid out as for dspi_load_flash_dump), a device
+ * that is re-plugged or rebooted comes back with the presets its user saved, and all of it is held to the reference's own flash_storage.c,
+ * request handlers and main loop, byte for byte (tests/test_device_flash_cpu.py, tests/test_gpu_device_flash.py).
+ * There is NO NEW KERNEL in this mode and NO TIMING FIGURE: the audio side of these requests is mutes, delay-line zeroing and resets, which
+ * reach the streams as state operations at the next dspi_process commit like those of every other request.  The mode is consulted in
+ * request and maintenance calls only; dspi_process does no extra work per call.
+ *   the mode            belongs to the context, off after dspi_create.  dspi_device_flash(ctx, enable): enable < 0 only reads; returns the
+ *                       mode (0 / 1).  Off: every call behaves exactly as before, the requests above answer DSPI_E_UNSUPPORTED, and
+ *                       dspi_flash_read / dspi_flash_write / DSPI_BOOT_STREAMS_OWN_FLASH are refused (DSPI_E_INVAL).  Turning it on gives
+ *                       every stream the flash its boot left: the first-boot preset area (a version 2 directory in sector 0, name
+ *                       "Default", everything else erased; on a DSPI_BOOT_POPULATED_FLASH context an erased area), with the master-volume
+ *                       mode and the saved master volume of the stream's own parameters in the directory.  On a fresh default context that
+ *                       is byte for byte the flash of a firmware that has just been powered on.  The directory's include_pins is the
+ *                       first boot's 1, and load_bulk honours it from then on, as the device does.  Turning it off drops the flashes.
+ *   cost                48 KB of host memory per DISTINCT flash: streams share one object until one of them writes (clone on write, like
+ *                       the parameter objects).  65 536 distinct flashes are 3.2 GB.
+ *   requests            served through dspi_vendor_get / dspi_vendor_set in the direction and with the status bytes the firmware uses:
+ *                       SAVE / LOAD / DELETE / SAVE_PARAMS / LOAD_PARAMS answer on the IN side — PRESET_ERR_INVALID_SLOT (1) for a slot
+ *                       >= 10, else "accepted" (0); LOAD_PARAMS answers its result (0, or 3 for a slot that fails its CRC).  GET_NAME of a
+ *                       slot >= 10 stalls (DSPI_E_UNSUPPORTED).  SET_STARTUP with a bad mode or slot, SET_NAME of a slot >= 10 are
+ *                       accepted and ignored.  A SET without payload or with more than 64 bytes stalls, as the device's setup stage does.
+ *                       REQ_SET_MASTER_VOLUME_MODE and REQ_SAVE_MASTER_VOLUME write the directory sector.
+ *   the mute            what stands after each request is what the firmware leaves once its main loop has served it: every sector write
+ *                       re-arms max(10 ms, 512) samples at the stream's rate; deleting the active slot leaves 256 (and factory
+ *                       defaults); a load or delete that changes an output slot's type the type switch's 256; a setter that is ignored
+ *                       leaves the 120 ms pre-mute of the firmware's flash-write bracket.  The bracket's wall-clock waits pass no audio.
+ *   the directory       the firmware's cached one: read from sector 0 at boot, equal to it after every write; it differs from the sector
+ *                       only in last_active_slot between a boot that selected another slot and the next write, as on the device.
+ *   broadcast           a request addressed to DSPI_ALL_STREAMS is applied once per distinct (parameter object, flash object) pair; streams
+ *                       that shared both keep sharing both.  The answer is stream 0's.
+ *   dspi_flash_read     (ctx, stream, dump, cap): the stream's 48 KB.  Returns DSPI_FLASH_DUMP_BYTES; cap below it: DSPI_E_SHORT.
+ *   dspi_flash_write    (ctx, first, count, dump, len): one image for the whole range, as ONE shared object.  It replaces the bytes and boots
+ *                       nothing: the live parameters stay, except that their mirrors of the directory (master-volume mode, saved master
+ *                       volume, include_pins) are taken from the new directory (from the fresh one a device would see where the dump
+ *                       holds none).  Ranges and lengths are validated before anything is written.  This is how a flash is carried
+ *                       beside a snapshot, as dspi_spdif_stream_pos carries positions.
+ *   boots               dspi_load_flash_dump and dspi_boot_streams(dump) make the dump the streams' flash (one shared object) with the
+ *                       boot's own writes applied: a created directory, a version 1 directory persisted as version 2, a legacy sector
+ *                       migrated into slot 0.  dspi_boot_streams(NULL) gives the first-boot flash (DSPI_BOOT_POPULATED_FLASH: an erased one).
+ *                       DSPI_BOOT_STREAMS_OWN_FLASH (dump must be NULL): every listed slot reboots from its own flash — the device that
+ *                       was re-plugged; the listed streams share one new parameter object per distinct flash object among them, and
+ *                       `selection` receives the first listed stream's code.  Everything else is dspi_boot_streams as documented.
+ *   travel              dspi_move_streams: by reference, all entries at once; an open-end source keeps its flash.  dspi_migrate_streams:
+ *                       by value into the destination's book; the destination must have the mode if the source has (else DSPI_E_INVAL
+ *                       before either context is written); arrivals from a context without the mode get first-boot flashes.
+ *                       dspi_resize_streams: new slots share one first-boot flash, a shrink releases.  Pause, resume, realign, grouping
+ *                       and compaction plans do not touch it.  Snapshots do not carry it: an import leaves the slot's flash alone (the
+ *                       imported parameters' directory mirrors follow it); dspi_flash_read / dspi_flash_write carry it.
+ *   not touched         dspi_load_preset_slot, dspi_save_preset_slot, dspi_factory_defaults and dspi_load_bulk neither read nor write the
+ *                       flash (the firmware's factory reset leaves the directory alone too).
+ *   host-only contexts  everything here works on them. */
+int dspi_device_flash(dspi_ctx *ctx, int enable);
+int dspi_flash_read(dspi_ctx *ctx, uint32_t stream, void *dump, size_t cap);
+int dspi_flash_write(dspi_ctx *ctx, uint32_t first, uint32_t count, const void *dump, size_t len);
 
 /* ---- resizing: a context gains and gives back slots ----------------------------------------------------------------------------------- */
 /* n_streams is no constant of dspi_create.  A context that has drained (dspi_plan_compaction with DSPI_COMPACT_ONE_WAY, dspi_move_streams:
