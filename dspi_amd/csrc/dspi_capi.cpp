@@ -462,6 +462,14 @@ void for_paused_regions(dspi_ctx *c, const CallBuffer &b, F f) {
     if (runs.empty()) { f((size_t)0, b.bytes); return; }
     for_run_regions(c, b, runs, f);
 }
+// ... the tile of the tiled wire words (dspi_wire.h) that holds the columns behind the context's last stream — nothing, when the last tile
+// is full.  The tiled wire encoder writes no word there, so the host-buffer paths clear that tile ahead of the launches, as they clear
+// the paused streams' tiles: the ONE place where those columns become zeros.
+template <class F>
+void for_absent_columns(dspi_ctx *c, const CallBuffer &b, F f) {
+    const size_t row = (size_t)c->sm.row;
+    if (b.bytes && b.tile_cols && c->n_streams % row) f((size_t)(c->n_wg - 1) * row * b.per, row * b.per);
+}
 // ... of the PDM words that hold streams a dspi_process_pdm call does not list (nothing, while every stream is listed)
 template <class F>
 void for_unlisted_regions(dspi_ctx *c, const CallBuffer &b, const PdmWork &w, F f) {
@@ -1961,7 +1969,9 @@ static int launch_paths(dspi_ctx *c, KArgs &a, uint32_t r0, uint32_t r1) {
 // words, then the subframe encoder from there into a.pairs.  Paused streams: the chain leaves their words in the scratch stale, and the
 // ENCODER SKIPS them (SpdifRates::active) — the scratch is not zeroed —, so that in the caller's device buffer their subframes stay unwritten.
 // dspi_process_wire with an I2S slot in play (L.wire_encoder): the same route with the wire encoder (dspi_wire.hip) as the second pass; on the
-// host-buffer paths it also zeroes the I2S regions' second halves, which no word of the call reaches
+// host-buffer paths it also zeroes the I2S regions' second halves, which no word of the call reaches.
+// dspi_process_devices with DSPI_OUT_TILED (L.wire_tiled): the same route once more, the chain writing TILED pair words into the scratch and
+// the tiled wire encoder (dspi_wire_tiled.hip) reading them there
 static int launch_rows(dspi_ctx *c, KArgs a, const CallLayout &L, uint32_t r0, uint32_t r1) {
     if (!L.spdif_two_pass) return launch_paths(c, a, r0, r1);
     char *const subframes = reinterpret_cast<char *>(a.pairs);
@@ -1970,13 +1980,17 @@ static int launch_rows(dspi_ctx *c, KArgs a, const CallLayout &L, uint32_t r0, u
         const uint32_t q1 = std::min(r1, q0 + L.two_pass_rows);
         const size_t s0 = (size_t)q0 * row, s1 = std::min((size_t)q1 * row, (size_t)c->n_streams);
         a.pairs = c->d_spdif_words; a.pairs_stream0 = (uint32_t)s0;      // the kernels index by absolute stream: stream s0 lands at the scratch's start
+        // ... and tiled words by absolute row: row q0's tile lands at the scratch's start (rows below q0 are not launched, nothing below it is touched)
+        if (L.wire_tiled) { a.pairs = c->d_spdif_words - (size_t)q0 * row * c->sm.n_pairs * L.frames * 2; a.pairs_stream0 = 0u; }
         int rc = launch_paths(c, a, q0, q1);
         if (rc) return rc;
         uint32_t *const dst = reinterpret_cast<uint32_t *>(subframes + s0 * L.pairs.per);
         const uint32_t pos = c->spdif_ps.on ? c->spdif_ps.clock : c->spdif_pos;
         const SpdifRates rates{c->d_images, c->d_stream_image, (uint32_t)s0, activity(c)};
         const uint32_t *const stream_pos = c->spdif_ps.on ? c->d_spdif_ps : nullptr;
-        hipError_t e = L.wire_encoder ? launch_wire(c->d_spdif_words, dst, (uint32_t)(s1 - s0), (uint32_t)c->sm.n_pairs, (uint32_t)L.frames, pos, rates, L.mem != CallMem::Device,
+        hipError_t e = L.wire_tiled ? launch_wire_tiled(c->d_spdif_words, dst, (uint32_t)(s1 - s0), (uint32_t)c->sm.n_pairs, (uint32_t)L.frames, row, q1 - q0, pos, rates,
+                                                        L.mem != CallMem::Device, c->hs, stream_pos)
+                     : L.wire_encoder ? launch_wire(c->d_spdif_words, dst, (uint32_t)(s1 - s0), (uint32_t)c->sm.n_pairs, (uint32_t)L.frames, pos, rates, L.mem != CallMem::Device,
                                                     c->hs, stream_pos)
                                       : launch_spdif(false, c->d_spdif_words, dst, (uint32_t)(s1 - s0), (uint32_t)c->sm.n_pairs, (uint32_t)L.frames, row, q1 - q0, pos, 0u, rates,
                                                      c->hs, stream_pos);
@@ -2110,6 +2124,7 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
         if (out->sub && !(flags & DSPI_OUT_ENABLED_ONLY)) for_paused_regions(c, L.sub, [&](size_t at, size_t n) { memset(h + L.sub.off + at, 0, n); });
         if (out->peaks) for_paused_regions(c, L.peaks, [&](size_t at, size_t n) { memset(h + L.peaks.off + at, 0, n); });
     }
+    if (L.wire_tiled) for_absent_columns(c, L.pairs, [&](size_t at, size_t n) { memset(h + L.pairs.off + at, 0, n); });
     if ((L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, L.two_pass_bytes))) || (rc = launch_rows(c, a, L, 0, c->n_wg)) ||
         (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, reinterpret_cast<uint32_t *>(d + L.pdm_words.off), 0, c->n_streams))) ||
         (clip_out && (rc = gather_clip(c, reinterpret_cast<uint16_t *>(d + L.clip.off))))) return rc;
@@ -2194,6 +2209,11 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
         if (a.pairs && !(flags & DSPI_OUT_ENABLED_ONLY)) for_paused_regions(c, L.pairs, clear(a.pairs));
         if (a.sub && !(flags & DSPI_OUT_ENABLED_ONLY)) for_paused_regions(c, L.sub, clear(a.sub));
         if (a.peaks) for_paused_regions(c, L.peaks, clear(a.peaks));
+        HIPCK(c, me);
+    }
+    if (L.wire_tiled) {
+        hipError_t me = hipSuccess;
+        for_absent_columns(c, L.pairs, [&](size_t at, size_t n) { me = hipMemsetAsync(reinterpret_cast<char *>(a.pairs) + at, 0, n, c->hs); });
         HIPCK(c, me);
     }
     if (pc) {      // ... and for the words of the streams the call does not list
@@ -2295,7 +2315,8 @@ static bool wire_slots_in_play(const dspi_ctx *c) {
     for (size_t i = 0; i < c->images.size(); i++) if (c->images[i]) image_i2s[i] = wire_i2s_mask(c->images[i]->output_types, (uint32_t)c->sm.n_pairs);
     return wire_any_i2s(c->stream_image.data(), c->n_streams, host_activity(c), image_i2s.data());
 }
-// wire: dspi_process_wire (flags carry DSPI_OUT_SPDIF, which the wire layout implies): out->pairs in the wire layout
+// wire: dspi_process_wire and dspi_process_devices (flags carry DSPI_OUT_SPDIF, which the wire layout implies): out->pairs in the wire layout;
+// with DSPI_OUT_TILED beside it (dspi_process_devices alone; the callers have applied their own flag rule, dspi_wire.h) in the tiled wire layout
 static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags,
                         const MixedIn *mx = nullptr, bool wire = false) {
     if (!c || !pcm_in || !out) return DSPI_E_INVAL;
@@ -2315,12 +2336,14 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     in.n_pairs = (uint32_t)c->sm.n_pairs; in.n_blocks = n_blocks; in.block_len = block_len; in.bit_depth = (uint32_t)bit_depth; in.flags = flags;
     in.pairs = out->pairs; in.sub = out->sub; in.peaks = out->peaks; in.clip = clip_out; in.no_direct = c->no_direct;
     in.all_latency = c->flavor != 0; in.spdif_per_stream = c->spdif_ps.on; in.pdm_words = pdm_words != nullptr;
-    in.wire_slots = wire && wire_slots_in_play(c);      // none in play: the call IS the DSPI_OUT_SPDIF call, route and bytes
+    const bool tiled = flags & DSPI_OUT_TILED, spdif = flags & DSPI_OUT_SPDIF;
+    in.wire_tiled = wire && tiled;                                 // always two passes: there is no fused tiled encoder
+    in.wire_slots = wire && !tiled && wire_slots_in_play(c);      // none in play: the call IS the DSPI_OUT_SPDIF call, route and bytes
     for (const PathInfo &pi : kPaths)
         if (pi.group != PathGroup::Latency && !c->plan.items[(int)pi.path].empty()) in.all_latency = false;
     const CallLayout L = plan_call(in);
-    const bool tiled = flags & DSPI_OUT_TILED, spdif = flags & DSPI_OUT_SPDIF;
-    if ((rc = check_flag_combinations(c, flags))) return rc;
+    if (!wire && (rc = check_flag_combinations(c, flags))) return rc;
+    if (L.wire_tiled && L.frames > kWireTiledMaxFrames) return fail(c, DSPI_E_UNSUPPORTED, "dspi_process_devices: a tiled call carries at most 2 097 120 frames");
     if (L.spdif_two_pass && c->spdif_ps.on && (rc = upload_spdif_pos(c))) return rc;
     PdmCall pdm{pdm_words, nullptr};
     const PdmCall *const pc = pdm_words ? &pdm : nullptr;
@@ -2338,7 +2361,7 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     // (two-pass S/PDIF: the encoder reads the WHOLE scratch chunk, so the chain must write the silent pairs' zero words there as well)
     a.skip_silent = ((flags & DSPI_OUT_ENABLED_ONLY) && !L.spdif_two_pass) ? 1u : 0u;
     a.i2s_slots = (flags & DSPI_OUT_I2S_SLOTS) ? 1u : 0u;
-    if (spdif) { a.spdif = L.spdif_two_pass ? 0u : 1u; a.spdif_pos = c->spdif_pos; }
+    if (spdif && !in.wire_tiled) { a.spdif = L.spdif_two_pass ? 0u : 1u; a.spdif_pos = c->spdif_pos; }      // (the fused encoder is stream-major)
     if (c->flavor && !tiled) {      // stream-major layout, packed kernel: the mini lines of the outputs whose rows do not reach the emit wave through their delay line (dspi_chain_pk.inc)
         const size_t xb = (size_t)c->n_wg * 3 * kMaxOut * kChunk * c->sm.row * 4;
         if ((rc = ensure(c, c->d_xwords, xb))) return rc;
@@ -2418,15 +2441,17 @@ int dspi_mixed_pcm_bytes(const dspi_ctx *c, const uint8_t *bit_depths, uint32_t 
     return DSPI_OK;
 }
 
-int dspi_process_mixed(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
+// the one body of dspi_process_mixed and (wire: out->pairs in the wire layout, the flags already held to its own rule) dspi_process_devices
+static int mixed_call(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags,
+                      const char *who, bool wire) {
     if (!c || !pcm_in || !bit_depths || !out) return DSPI_E_INVAL;
-    int rc = mixed_check(c, bit_depths, n_blocks, block_len, "dspi_process_mixed");
+    int rc = mixed_check(c, bit_depths, n_blocks, block_len, who);
     if (rc) return rc;
-    // every entry equal: the call IS dspi_process / dspi_process_pdm at that depth (which refuses a bad flag bit and a host-only context itself)
-    if (const uint8_t depth = intake_uniform_depth(bit_depths, c->n_streams)) return process_call(c, pcm_in, depth, n_blocks, block_len, out, pdm_words, flags);
-    if ((rc = check_flag_bits(c, flags)) || (rc = check_flag_combinations(c, flags))) return rc;
+    // every entry equal: the call IS dspi_process / dspi_process_pdm / dspi_process_wire at that depth (which refuses a bad flag bit and a host-only context itself)
+    if (const uint8_t depth = intake_uniform_depth(bit_depths, c->n_streams)) return process_call(c, pcm_in, depth, n_blocks, block_len, out, pdm_words, flags, nullptr, wire);
+    if ((rc = check_flag_bits(c, flags)) || (!wire && (rc = check_flag_combinations(c, flags)))) return rc;
     MixedIn mx{bit_depths, std::vector<uint64_t>((size_t)c->n_streams + 1)};
-    if (!intake_offsets(bit_depths, c->n_streams, (uint64_t)n_blocks * block_len, nullptr, mx.offsets.data())) return fail(c, DSPI_E_INVAL, "dspi_process_mixed: the buffer's size overflows");
+    if (!intake_offsets(bit_depths, c->n_streams, (uint64_t)n_blocks * block_len, nullptr, mx.offsets.data())) return fail(c, DSPI_E_INVAL, std::string(who) + ": the buffer's size overflows");
     // the one case in which a 16-bit sample and its widened twin part ways (dspi_intake.h): refused, not approximated
     if (c->flavor)
         for (uint32_t s = 0; s < c->n_streams; s++) {
@@ -2434,10 +2459,55 @@ int dspi_process_mixed(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depth
             for (const float p : readable(c, (int32_t)s).preamp_linear) {
                 uint32_t w; memcpy(&w, &p, 4);
                 if (intake_preamp_breaks_widening(w))
-                    return fail(c, DSPI_E_UNSUPPORTED, "dspi_process_mixed: stream " + std::to_string(s) + " takes 16-bit input with a preamp below 2^-103, where widening to 24 bit is not exact");
+                    return fail(c, DSPI_E_UNSUPPORTED, std::string(who) + ": stream " + std::to_string(s) + " takes 16-bit input with a preamp below 2^-103, where widening to 24 bit is not exact");
             }
         }
-    return process_call(c, pcm_in, 24, n_blocks, block_len, out, pdm_words, flags, &mx);
+    return process_call(c, pcm_in, 24, n_blocks, block_len, out, pdm_words, flags, &mx, wire);
+}
+
+int dspi_process_mixed(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
+    return mixed_call(c, pcm_in, bit_depths, n_blocks, block_len, out, pdm_words, flags, "dspi_process_mixed", false);
+}
+
+// ---- every property of a device its host decides, in one call: depth vector, wire words, either layout (dspi_wire.h: the tiled wire layout
+// and the flag rule; dspi_wire_tiled.hip: its encoder) ----
+int dspi_process_devices(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    if (!devices_process_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_process_devices: the flags are DSPI_MEM_DEVICE, DSPI_OUT_TILED, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
+    return mixed_call(c, pcm_in, bit_depths, n_blocks, block_len, out, pdm_words, flags | DSPI_OUT_SPDIF, "dspi_process_devices", true);
+}
+
+int dspi_wire_encode_tiled(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos, uint32_t *wire, uint32_t flags) {
+    if (!c || !pairs || !wire || !block_pos || n_frames == 0) return DSPI_E_INVAL;
+    if (!wire_encode_tiled_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_wire_encode_tiled: the only flag is DSPI_MEM_DEVICE");
+    if (n_frames > kWireTiledMaxFrames) return fail(c, DSPI_E_INVAL, "dspi_wire_encode_tiled: at most 2 097 120 frames per call");
+    const bool dev = flags & DSPI_MEM_DEVICE;
+    // host positions are validated before anything is launched; device positions are the kernel's to reduce modulo 192
+    if (!dev) for (uint32_t s = 0; s < c->n_streams; s++) if (block_pos[s] >= kSpdifBlock) return fail(c, DSPI_E_INVAL, "dspi_wire_encode_tiled: a position is 0..191");
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    HIPCK(c, hipSetDevice(c->device));
+    const uint32_t row = (uint32_t)c->sm.row;
+    const size_t tile_in_b = (size_t)row * c->sm.n_pairs * n_frames * 8, in_b = c->n_wg * tile_in_b, out_b = in_b * 2, pos_b = (size_t)c->n_streams * 4;
+    const int32_t *d_in = pairs;
+    uint32_t *d_out = wire;
+    const uint32_t *d_pos = block_pos;
+    int rc;
+    if (!dev) {
+        if ((rc = ensure(c, c->d_spdif_in, in_b)) || (rc = ensure(c, c->d_spdif_out, out_b)) ||
+            (rc = ensure(c, c->d_spdif_vpos, pos_b))) return rc;
+        HIPCK(c, hipMemcpyAsync(c->d_spdif_in, pairs, in_b, hipMemcpyHostToDevice, c->hs));
+        HIPCK(c, hipMemcpyAsync(c->d_spdif_vpos, block_pos, pos_b, hipMemcpyHostToDevice, c->hs));
+        d_in = c->d_spdif_in; d_out = c->d_spdif_out; d_pos = c->d_spdif_vpos;
+        // (the staging buffer comes back whole: the encoder zeroes the I2S tails there, and the columns behind the last stream, which it
+        //  does not write, are cleared with their tile as the audio calls clear them)
+        hipError_t me = hipSuccess;
+        for_absent_columns(c, CallBuffer{out_b, (size_t)c->sm.n_pairs * n_frames * 16, true, 0}, [&](size_t at, size_t n) { me = hipMemsetAsync(reinterpret_cast<char *>(d_out) + at, 0, n, c->hs); });
+        HIPCK(c, me);
+    }
+    // every stream's types and rate are its own image's: committed first (unaware of pauses, like dspi_wire_encode)
+    if ((rc = commit_params(c))) return rc;
+    HIPCK(c, launch_wire_tiled(d_in, d_out, c->n_streams, (uint32_t)c->sm.n_pairs, n_frames, row, c->n_wg, 0u, SpdifRates{c->d_images, c->d_stream_image, 0u}, !dev, c->hs, d_pos));
+    return dev ? DSPI_OK : stage_down(c, wire, c->d_spdif_out, out_b);
 }
 
 // the prepass of a device-buffer mixed call alone, into the context's scratch: what tools/bench_mixed.py times (no chain, nothing advanced)

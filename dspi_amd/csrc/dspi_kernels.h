@@ -90,6 +90,13 @@ hipError_t launch_spdif(bool tiled, const int32_t *pairs, uint32_t *out, uint32_
 // zero_tails (the host-buffer paths): I2S lanes also store zeros over the second half of their region; else nothing writes it.
 hipError_t launch_wire(const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames, uint32_t block_pos, const SpdifRates &rates,
                        bool zero_tails, hipStream_t stream, const uint32_t *stream_pos = nullptr);
+// ---- the tiled wire encoder (dspi_wire_tiled.hip; dspi_wire.h: the tiled layout): launch_spdif's TILED form with the type of every pair taken
+// from the column's own image.  pairs = [tile][output][n_frames][row] as the chain writes them with KArgs::tiled_out, out = [tile][pair][4 *
+// n_frames][row]; n_streams columns from tile 0 on (n_streams <= n_tiles * row, the rest of the last tile holds nobody and is not touched);
+// row = 64 or 128.  rates, stream_pos, zero_tails as for launch_wire; zero_tails zeroes rows 2 F .. 4 F - 1 of an I2S column.
+constexpr uint32_t kWireTiledMaxFrames = 65535u * 32u;      // the frame slices ride on blockIdx.z
+hipError_t launch_wire_tiled(const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames, uint32_t row, uint32_t n_tiles, uint32_t block_pos,
+                             const SpdifRates &rates, bool zero_tails, hipStream_t stream, const uint32_t *stream_pos = nullptr);
 // I2S slots (audio_i2s_multi.c:217-226): words << 8 for the pairs in pair_mask; same layouts as the pair words themselves
 hipError_t launch_i2s(bool tiled, const int32_t *pairs, uint32_t *out, uint32_t n_streams, uint32_t n_pairs, uint32_t n_frames, uint32_t row,
                       uint32_t n_wg, uint32_t pair_mask, hipStream_t stream);

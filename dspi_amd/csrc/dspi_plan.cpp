@@ -321,12 +321,13 @@ LaunchPlan plan_launches(const PlanInput &in) {
 CallLayout plan_call(const CallInput &in) {
     CallLayout L;
     const size_t F = L.frames = (size_t)in.n_blocks * in.block_len;
-    const bool tiled = in.flags & DSPI_OUT_TILED, spdif = in.flags & DSPI_OUT_SPDIF;
+    // (the tiled wire layout is a tiled layout of subframe-sized regions, whatever the flags word says beside it)
+    const bool tiled = (in.flags & DSPI_OUT_TILED) || in.wire_tiled, spdif = (in.flags & DSPI_OUT_SPDIF) || in.wire_tiled;
     auto buffer = [&](bool passed, bool tile_cols, size_t per) {
         return CallBuffer{passed ? (tile_cols ? (size_t)in.n_wg * in.row : (size_t)in.n_streams) * per : 0, per, tile_cols, 0};
     };
     L.pcm = buffer(true, false, F * (in.bit_depth == 24 ? 6 : 4));
-    L.pairs = buffer(in.pairs, tiled, tiled ? (size_t)(in.n_out - 1) * F * 4 : (size_t)in.n_pairs * F * (spdif ? 16 : 8));
+    L.pairs = buffer(in.pairs, tiled, in.wire_tiled ? (size_t)in.n_pairs * F * 16 : tiled ? (size_t)(in.n_out - 1) * F * 4 : (size_t)in.n_pairs * F * (spdif ? 16 : 8));
     L.sub = buffer(in.sub, tiled, F * 4);
     L.peaks = buffer(in.peaks, false, (size_t)in.n_blocks * in.n_ch * 2);
     L.clip = buffer(in.clip, false, 2);
@@ -339,8 +340,11 @@ CallLayout plan_call(const CallInput &in) {
     // With per-stream block positions (dspi_spdif_per_stream) every flagged call goes this way, the latency layout's launches too: its
     // kernels write plain pair words into the scratch (KArgs::pairs_stream0) and the encoder alone knows the streams' positions.
     // dspi_process_wire with an I2S slot on an active stream (CallInput::wire_slots) goes this way for the same reason: the type is the stream's.
-    L.spdif_two_pass = spdif && in.pairs && (!in.all_latency || in.spdif_per_stream || in.wire_slots);
-    L.wire_encoder = L.spdif_two_pass && in.wire_slots;
+    // The tiled wire layout (CallInput::wire_tiled) always goes this way, I2S slot or not: there is no fused tiled encoder.  The chain writes
+    // TILED pair words into the scratch — a row of them is as large as a row of stream-major ones — and the tiled wire encoder runs from there.
+    L.spdif_two_pass = spdif && in.pairs && (!in.all_latency || in.spdif_per_stream || in.wire_slots || in.wire_tiled);
+    L.wire_encoder = L.spdif_two_pass && (in.wire_slots || in.wire_tiled);
+    L.wire_tiled = L.spdif_two_pass && in.wire_tiled;
     if (L.spdif_two_pass) {
         const size_t row_b = (size_t)in.row * in.n_pairs * F * 8;
         size_t rows = std::max<size_t>(1, ((size_t)1 << 30) / row_b);

@@ -119,6 +119,7 @@ struct CallInput {
     bool pdm_words = false;                           // dspi_process_pdm: the caller's PDM words, beside the outputs above
     bool spdif_per_stream = false;                    // dspi_spdif_per_stream is on: the latency layout's fused encoder knows one position per launch
     bool wire_slots = false;                          // dspi_process_wire while an active stream has an I2S slot (dspi_wire.h wire_any_i2s): the fused encoder knows one type
+    bool wire_tiled = false;                          // dspi_process_devices with DSPI_OUT_TILED: `pairs` is the wire layout, tiled (dspi_wire.h); sub and pdm_words tiled as ever
 };
 
 struct CallBuffer {
@@ -139,6 +140,7 @@ struct CallLayout {
     bool spdif_two_pass = false;                      // DSPI_OUT_SPDIF off the latency layout, or with per-stream positions: the chain's pair words, then the encoder
     uint32_t two_pass_rows = 0; size_t two_pass_bytes = 0;      // rows per pass, their scratch of pair words
     bool wire_encoder = false;                        // ... and the second pass is the wire encoder (CallInput::wire_slots), not the subframe encoder
+    bool wire_tiled = false;                          // ... its tiled form (CallInput::wire_tiled): the chain writes tiled pair words into the scratch
     CallMem mem = CallMem::Staged;
     size_t direct_bytes = 0;                          // the direct area: pcm, pairs, sub, peaks, clip, pdm_words at their `off`
     uint32_t n_chunks = 1, rows_per_chunk = 0;        // staged: chunk k = rows [k * rows_per_chunk, min(n_wg, (k + 1) * rows_per_chunk))

@@ -154,6 +154,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "dspi_process_wire"):      # (ABI 8 + wire words per device: detected by symbol; with it dspi_wire_encode)
         L.dspi_process_wire.argtypes = [vp, vp, C.c_int, u32, u32, C.POINTER(_Out), vp, u32]
         L.dspi_wire_encode.argtypes = [vp, vp, u32, vp, vp, u32]
+    if hasattr(L, "dspi_process_devices"):      # (ABI 8 + wire words on tiled and mixed-depth contexts: detected by symbol; with it dspi_wire_encode_tiled)
+        L.dspi_process_devices.argtypes = [vp, vp, vp, u32, u32, C.POINTER(_Out), vp, u32]
+        L.dspi_wire_encode_tiled.argtypes = [vp, vp, u32, vp, vp, u32]
     if hasattr(L, "dspi_device_flash"):      # (ABI 8 + a stream's own flash: detected by symbol; with it dspi_flash_read, dspi_flash_write, DSPI_BOOT_STREAMS_OWN_FLASH)
         L.dspi_device_flash.argtypes = [vp, C.c_int]
         L.dspi_flash_read.argtypes = [vp, u32, vp, C.c_size_t]
@@ -341,6 +344,32 @@ class Dspi:
             nt, F, R = sub_t.shape
             sub = sub_t.transpose(0, 2, 1).reshape(nt * R, F)[:S].copy()
         return pairs, sub
+
+    def untile_wire(self, wire_t: np.ndarray, types) -> np.ndarray:
+        """The tiled wire layout (include/dspi.h: dspi_process_devices) -> the stream-major wire layout, uint32 [S][P][F][4] (test helper).
+        wire_t: uint32 [tiles][P][F][4][R], i.e. per (tile, pair) a region of 4 F rows of R words; types: bool [S][P], slot p of stream s is
+        an I2S slot.  Stream s is column s % R of tile s // R.  An S/PDIF slot's subframe word j of frame f stands in row f * 4 + j; an I2S
+        slot's word of (side, frame f) in row side * F + f and goes to word 2 f + side of the stream-major region's first half; the rows
+        2 F .. 4 F - 1 of an I2S column (its tail) go to the second half as they are."""
+        nt, P, F, four, R = wire_t.shape
+        assert four == 4
+        S = self.n_streams
+        types = np.asarray(types, dtype=bool)
+        assert types.shape == (S, P) and nt * R >= S, (types.shape, wire_t.shape)
+        rows = wire_t.reshape(nt, P, 4 * F, R)
+        out = np.zeros((S, P, F, 4), dtype=np.uint32)
+        for s in range(S):
+            t, c = divmod(s, R)
+            for p in range(P):
+                col = rows[t, p, :, c]
+                if types[s, p]:
+                    flat = out[s, p].reshape(-1)
+                    flat[0:2 * F:2] = col[:F]              # side 0 (L) of frames 0 .. F - 1
+                    flat[1:2 * F:2] = col[F:2 * F]         # side 1 (R)
+                    flat[2 * F:] = col[2 * F:]             # the tail
+                else:
+                    out[s, p] = col.reshape(F, 4)
+        return out
 
     def process_device(self, pcm_ptr: int, n_blocks: int, block_len: int, bit_depth: int = 16,
                        pairs_ptr: int = 0, sub_ptr: int = 0, peaks_ptr: int = 0, tiled: bool = False, enabled_only: bool = False, i2s_slots: bool = False, spdif: bool = False,
@@ -561,6 +590,51 @@ class Dspi:
     def wire_encode_device(self, pairs_ptr: int, n_frames: int, block_pos_ptr: int, out_ptr: int):
         """dspi_wire_encode on device pointers (block_pos: uint32 [S] in device memory, taken modulo 192); asynchronous, see sync()."""
         self._ck(self.L.dspi_wire_encode(self.h, pairs_ptr, n_frames, block_pos_ptr, out_ptr, MEM_DEVICE), "wire_encode")
+
+    # ---- wire words on tiled and mixed-depth contexts (include/dspi.h: dspi_process_devices / dspi_wire_encode_tiled) ----
+    def process_devices_host(self, pcm: np.ndarray, bit_depths, n_blocks: int, block_len: int, want_sub=True, want_peaks=True, tiled=False, enabled_only=False,
+                             clip=False, pdm=False):
+        """dspi_process_devices on host arrays: pcm and bit_depths as for process_mixed_host; returns (wire, sub, peaks), with pdm=True
+        (wire, sub, peaks, words).  Stream-major: process_wire_host's arrays.  tiled=True: wire uint32 [tiles][P][F][4][R] in the tiled wire
+        layout (untile_wire), sub [tiles][F][R], words [tiles][F][8][R].  clip=True: self.last_clip as after process_host."""
+        S, F = self.n_streams, n_blocks * block_len
+        d = self._depths(bit_depths)
+        pcm = np.ascontiguousarray(pcm).view(np.uint8).reshape(-1)
+        if np.isin(d, (16, 24)).all(): assert pcm.nbytes == F * int(np.where(d == 24, 6, 4).sum()), (pcm.nbytes, S, F)      # (bad depths are the library's to refuse)
+        R = self.tile_streams(); nt = (S + R - 1) // R
+        wire = np.zeros((nt, self.P, F, 4, R) if tiled else (S, self.P, F, 4), dtype=np.uint32)
+        sub = np.zeros((nt, F, R) if tiled else (S, F), dtype=np.int32) if want_sub else None
+        peaks = np.zeros((S, n_blocks, self.C), dtype=np.uint16) if want_peaks else None
+        words = np.zeros((nt, F, 8, R) if tiled else (S, F, 8), dtype=np.uint32) if pdm else None
+        self.last_clip = np.zeros(S, dtype=np.uint16) if clip else None
+        out = _Out(wire.ctypes.data, sub.ctypes.data if want_sub else None, peaks.ctypes.data if want_peaks else None, self.last_clip.ctypes.data if clip else None)
+        self._ck(self.L.dspi_process_devices(self.h, pcm.ctypes.data, d.ctypes.data, n_blocks, block_len, C.byref(out), words.ctypes.data if pdm else None,
+                                             (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_CLIP_FLAGS if clip else 0)), "process_devices")
+        return (wire, sub, peaks, words) if pdm else (wire, sub, peaks)
+
+    def process_devices_device(self, pcm_ptr: int, bit_depths, n_blocks: int, block_len: int, wire_ptr: int, sub_ptr: int = 0, peaks_ptr: int = 0, words_ptr: int = 0,
+                               tiled: bool = False, enabled_only: bool = False, clip_ptr: int = 0):
+        """dspi_process_devices on raw device pointers (the depths stay a host array); what no word reaches is not written; asynchronous, see sync()."""
+        d = self._depths(bit_depths)
+        out = _Out(wire_ptr or None, sub_ptr or None, peaks_ptr or None, clip_ptr or None)
+        self._ck(self.L.dspi_process_devices(self.h, pcm_ptr, d.ctypes.data, n_blocks, block_len, C.byref(out), words_ptr or None,
+                                             MEM_DEVICE | (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_CLIP_FLAGS if clip_ptr else 0)), "process_devices")
+
+    def wire_encode_tiled_host(self, pairs_t: np.ndarray, block_pos) -> np.ndarray:
+        """dspi_wire_encode_tiled on host arrays: pairs_t int32 [tiles][2P][F][R] (process_host(tiled=True)), block_pos uint32 [S] (each 0..191)
+        -> uint32 [tiles][P][F][4][R] in the tiled wire layout (untile_wire), every stream's types and rate its own."""
+        pairs_t = np.ascontiguousarray(pairs_t, dtype=np.int32)
+        pos = np.ascontiguousarray(np.asarray(block_pos, dtype=np.uint32).reshape(-1))
+        assert len(pos) == self.n_streams, (len(pos), self.n_streams)
+        nt, O, F, R = pairs_t.shape
+        assert O == 2 * self.P and R == self.tile_streams() and nt == (self.n_streams + R - 1) // R, pairs_t.shape
+        out = np.zeros((nt, self.P, F, 4, R), dtype=np.uint32)
+        self._ck(self.L.dspi_wire_encode_tiled(self.h, pairs_t.ctypes.data, F, pos.ctypes.data, out.ctypes.data, 0), "wire_encode_tiled")
+        return out
+
+    def wire_encode_tiled_device(self, pairs_ptr: int, n_frames: int, block_pos_ptr: int, out_ptr: int):
+        """dspi_wire_encode_tiled on device pointers (block_pos: uint32 [S] in device memory, taken modulo 192); asynchronous, see sync()."""
+        self._ck(self.L.dspi_wire_encode_tiled(self.h, pairs_ptr, n_frames, block_pos_ptr, out_ptr, MEM_DEVICE), "wire_encode_tiled")
 
     def pdm_restart(self, stream: int = ALL):
         self._ck(self.L.dspi_pdm_restart(self.h, stream), "pdm_restart")

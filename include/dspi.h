@@ -78,7 +78,8 @@ extern "C" {
                               * 8 + PDM words from the call: detect by symbol (dspi_process_pdm; with it dspi_pdm_running; additions only);
                               * 8 + mixed input formats: detect by symbol (dspi_process_mixed; with it dspi_mixed_pcm_bytes; additions only);
                               * 8 + wire words per device: detect by symbol (dspi_process_wire; with it dspi_wire_encode; additions only);
-                              * 8 + a stream's own flash: detect by symbol (dspi_device_flash; with it dspi_flash_read, dspi_flash_write, DSPI_BOOT_STREAMS_OWN_FLASH; additions only) */
+                              * 8 + a stream's own flash: detect by symbol (dspi_device_flash; with it dspi_flash_read, dspi_flash_write, DSPI_BOOT_STREAMS_OWN_FLASH; additions only);
+                              * 8 + wire words on tiled and mixed-depth contexts: detect by symbol (dspi_process_devices; with it dspi_wire_encode_tiled; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -870,7 +871,8 @@ int dspi_spdif_encode_v(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, 
  *                 / DSPI_OUT_I2S_SLOTS, contiguous as a DMA buffer wants them.  The LAST 8 F bytes of the region are never written in a
  *                 caller's device buffer (DSPI_MEM_DEVICE) and come back as zeros in host buffers.
  *   paused stream the existing rule: its regions are untouched in device buffers and zero in host buffers.
- * A tiled wire layout is left out: both calls refuse DSPI_OUT_TILED.
+ * A tiled wire layout is left out: both calls refuse DSPI_OUT_TILED.  (Of THESE two calls that stays true; the tiled wire layout and the
+ * calls that take it, dspi_process_devices and dspi_wire_encode_tiled, have the section below.)
  *
  * dspi_process_wire is dspi_process (pdm_words NULL) or dspi_process_pdm (else, out->sub optional as there) with out->pairs in the wire
  * layout.  Flags: DSPI_MEM_DEVICE, DSPI_OUT_ENABLED_ONLY, DSPI_OUT_CLIP_FLAGS.  Refused with DSPI_E_INVAL before anything else is looked
@@ -894,6 +896,48 @@ int dspi_process_wire(dspi_ctx *ctx, const void *pcm_in, int bit_depth, uint32_t
                       const dspi_out *out, uint32_t *pdm_words /* may be NULL */, uint32_t flags);
 int dspi_wire_encode(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos,
                      uint32_t *wire, uint32_t flags);
+/* ---- wire words on tiled and mixed-depth contexts -------------------------------------------------------------------------------------- */
+/* What a device's HOST decides — its sample rate, its preset, its input format (usb_input_bit_depth) and the driver behind each output slot
+ * (output_types[]) — in ONE call, in either layout: dspi_process_devices has dspi_process_mixed's arguments (pcm_in, bit_depths: see there and
+ * dspi_mixed_pcm_bytes) and dspi_process_wire's out->pairs.
+ *
+ * Flags: DSPI_MEM_DEVICE, DSPI_OUT_TILED, DSPI_OUT_ENABLED_ONLY, DSPI_OUT_CLIP_FLAGS.  Without DSPI_OUT_TILED out->pairs is THE WIRE LAYOUT
+ * above.  With it out->pairs is THE TILED WIRE LAYOUT, and out->sub and pdm_words are tiled as in dspi_process_pdm.
+ *
+ * THE TILED WIRE LAYOUT has the size and the regions of dspi_spdif_encode_v's tiled subframes.  R = dspi_tile_streams, P = dspi_num_pairs,
+ * F = the call's frames; stream s stands in tile t = s / R at column c = s % R.  Pair p of tile t owns 16 F R bytes, 4 F rows of R words, at
+ * word offset ((t * P + p) * F) * 4 * R.  Column c of every row belongs to stream s, whose own type decides what stands there:
+ *   S/PDIF slot   uint32 [F][4][R] at column c, exactly the tiled subframes of dspi_spdif_encode_v: word (f * 4 + j) * R + c.  The block
+ *                 position is the context's, or the stream's own while dspi_spdif_per_stream is on; the sample-rate byte is the stream's own.
+ *   I2S slot      (output_types[p] == 1)  uint32 [2][F][R] (side, frame) at column c in the FIRST HALF of the region: word
+ *                 (side * F + f) * R + c, value word << 8 — for that column what dspi_i2s_encode with DSPI_OUT_TILED writes for outputs 2p
+ *                 and 2p + 1, the two planes back to back.  The column's words in the second half, rows 2 F .. 4 F - 1, are the tail.
+ *   no word reaches   an I2S column's tail, a paused stream's column and the columns past dspi_num_streams in the last tile: never written
+ *                 in a caller's device buffer (DSPI_MEM_DEVICE), zeros in host buffers.
+ * A consumer finds the words of stream s, pair p: region = ((s / R * P + p) * F) * 4 * R, column s % R, rows as above by the stream's type.
+ *
+ * A NULL ctx is refused first; then, before anything else is looked at, DSPI_OUT_SPDIF (it is implied), DSPI_OUT_I2S_SLOTS and every undefined
+ * bit give DSPI_E_INVAL; then the refusals of dspi_process_mixed in their order, the preamp refusal for 16-bit streams (DSPI_E_UNSUPPORTED)
+ * included.  A refused or failed call writes and advances nothing.  Block positions, per-stream positions, pauses, the PDM running byte and
+ * fade, and the clip flags behave as in dspi_process_wire and dspi_process_pdm.
+ *   stream-major, every depth equal                       the call IS dspi_process_wire at that depth: the same route, the same bytes.
+ *   stream-major, no active stream holds an I2S slot      the call IS dspi_process_mixed with DSPI_OUT_SPDIF.
+ *   tiled         every region holds, re-laid, the words of the stream-major call.  A tiled call ALWAYS runs in two passes, I2S slot or
+ *                 not — the chain's tiled pair words into a scratch, then the tiled wire encoder; there is no fused tiled encoder —, so with
+ *                 DSPI_OUT_ENABLED_ONLY its silent pairs carry silence in their own format, as on dspi_process_wire's two-pass route.
+ *                 At most 2 097 120 frames per tiled call (DSPI_E_UNSUPPORTED above).
+ *
+ * dspi_wire_encode_tiled is the stateless twin: dspi_wire_encode on tiled pair words, pairs = int32 [tile][output][n_frames][R] exactly as
+ * dspi_process wrote them with DSPI_OUT_TILED, wire = the tiled wire layout, block_pos = uint32 [dspi_num_streams], required, indexed by
+ * stream (block_pos[t * R + c]) as in dspi_spdif_encode_v; all three in host memory, or in device memory with DSPI_MEM_DEVICE, the only
+ * flag.  Host positions are validated (each < 192, else DSPI_E_INVAL) before anything is launched; device positions are taken modulo 192.
+ * Independent of the per-stream mode, unaware of pauses.  At most 2 097 120 frames per call (DSPI_E_INVAL above).  Returns DSPI_OK or a
+ * negative DSPI_E_*.
+ * The ABI stays 8: detect by symbol (dspi_process_devices; with it dspi_wire_encode_tiled; additions only). */
+int dspi_process_devices(dspi_ctx *ctx, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len,
+                         const dspi_out *out, uint32_t *pdm_words /* may be NULL */, uint32_t flags);
+int dspi_wire_encode_tiled(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos,
+                           uint32_t *wire, uint32_t flags);
 int dspi_i2s_encode(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, uint32_t pair_mask, uint32_t *words, uint32_t flags);
 /* the HIP stream (hipStream_t) the context launches on, for event timing by the caller */
 void *dspi_hip_stream(dspi_ctx *ctx);
