@@ -42,6 +42,7 @@
 #include "dspi_resize.h"
 #include "dspi_snapshot.h"
 #include "dspi_spdifpos.h"
+#include "dspi_spdifrx.h"
 #include "dspi_wire.h"
 
 using namespace dspi;
@@ -136,6 +137,11 @@ struct dspi_ctx {
     DevBuf<uint8_t> d_mixed_up{mem};
     DevBuf<uint64_t> d_mixed_tab{mem};
     std::vector<uint8_t> mixed_depths; uint64_t mixed_frames = 0;
+    // dspi_process_sources (dspi_spdifrx.h): a call with an S/PDIF source appends to the table the bitmap of the streams the INTAKE serves, the
+    // active PCM streams (mixed_mask: what the table holds of it; empty: none); the receiver kernel reads the sources and the context's own
+    // activity bitmap.  d_rx: the records of a host-memory call, on `hs` only, by calls that end synchronised (staged calls, dspi_spdif_decode)
+    std::vector<uint32_t> mixed_mask;
+    DevBuf<SpdifRx> d_rx{mem};
     DevBuf<int32_t> d_spdif_in{mem};
     DevBuf<uint32_t> d_spdif_out{mem};
     DevBuf<uint32_t> d_snap{mem};          // stream snapshots on host buffers: the records of one chunk of rows
@@ -2043,24 +2049,39 @@ static int pdm_sub_scratch(dspi_ctx *c, const CallLayout &L) { return ensure(c, 
 // ---- dspi_process_mixed: the call's layout (null in the three paths below: one depth for the call) ----
 // A mixed call is planned as the 24-bit call it becomes (plan_call knows nothing of it); only the way its `pcm` area is filled differs.
 struct MixedIn {
-    const uint8_t *depths;             // the caller's, validated
-    std::vector<uint64_t> offsets;     // [n_streams + 1] (dspi_intake.h)
+    const uint8_t *depths;             // the caller's, validated: 16 / 24, and in a dspi_process_sources call kSrcSpdif
+    std::vector<uint64_t> offsets;     // [n_streams + 1] (dspi_intake.h; with S/PDIF runs dspi_spdifrx.h)
+    SpdifRx *rx = nullptr;             // dspi_process_sources with an S/PDIF source: the caller's records [n_streams], in the call's memory; else null
 };
+static bool rx_stream(const dspi_ctx *c, const MixedIn &mx, uint32_t s) { return mx.depths[s] == kSrcSpdif && (!c->n_paused || c->active[s]); }
 // the path's scratch (d_mixed or d_mixed_up, `bytes`) and the device's table, before the first launch of the call (all-or-nothing: a call
 // that cannot have them runs nothing)
 static int intake_prepare(dspi_ctx *c, const MixedIn &mx, uint64_t frames, DevBuf<uint8_t> &scratch, size_t scratch_bytes) {
     int rc = ensure(c, scratch, scratch_bytes);
     if (rc) return rc;
     const size_t n = c->n_streams;
-    if (c->mixed_frames == frames && c->mixed_depths.size() == n && !memcmp(c->mixed_depths.data(), mx.depths, n)) return 0;
+    std::vector<uint32_t> mask;      // S/PDIF sources in the call: the intake's streams, behind the depths (padded to a word)
+    if (mx.rx) {
+        mask.assign((n + 31) / 32, 0u);
+        for (uint32_t s = 0; s < n; s++) if (mx.depths[s] != kSrcSpdif && (!c->n_paused || c->active[s])) mask[s >> 5] |= 1u << (s & 31u);
+    }
+    if (c->mixed_frames == frames && c->mixed_depths.size() == n && !memcmp(c->mixed_depths.data(), mx.depths, n) && c->mixed_mask == mask) return 0;
     c->mixed_frames = 0;
-    if ((rc = upload_via_move_area(c, c->d_mixed_tab, "hipHostMalloc failed (mixed input table)", {{mx.offsets.data(), (n + 1) * 8}, {mx.depths, n}}))) return rc;
-    c->mixed_depths.assign(mx.depths, mx.depths + n); c->mixed_frames = frames;
+    const uint32_t pad = 0;
+    if ((rc = upload_via_move_area(c, c->d_mixed_tab, "hipHostMalloc failed (mixed input table)",
+                                   {{mx.offsets.data(), (n + 1) * 8}, {mx.depths, n}, {&pad, (4 - n % 4) % 4}, {mask.data(), mask.size() * 4}}))) return rc;
+    c->mixed_depths.assign(mx.depths, mx.depths + n); c->mixed_frames = frames; c->mixed_mask.swap(mask);
     return 0;
 }
 // the intake launch for streams [s0, s1): `src` holds the caller's bytes at their offsets, `dst` is what the chain reads
-static int launch_intake_streams(dspi_ctx *c, uint64_t frames, const void *src, void *dst, size_t s0, size_t s1) {
-    hipError_t e = launch_intake(src, c->d_mixed_tab, reinterpret_cast<const uint8_t *>(c->d_mixed_tab + c->n_streams + 1), activity(c), dst, frames, (uint32_t)s0, (uint32_t)(s1 - s0), c->hs);
+// rx (a call with an S/PDIF source): the records in DEVICE memory; the intake then serves the PCM streams and the receiver kernel the others
+static int launch_intake_streams(dspi_ctx *c, uint64_t frames, const void *src, void *dst, size_t s0, size_t s1, SpdifRx *rx = nullptr) {
+    const uint8_t *const depths = reinterpret_cast<const uint8_t *>(c->d_mixed_tab + c->n_streams + 1);
+    const uint32_t *const pcm_streams = reinterpret_cast<const uint32_t *>(depths + ((size_t)c->n_streams + 3) / 4 * 4);
+    // (a call whose every active stream is an S/PDIF source has nothing for the intake)
+    const bool any_pcm = !rx || std::any_of(c->mixed_mask.begin(), c->mixed_mask.end(), [](uint32_t w) { return w != 0; });
+    hipError_t e = any_pcm ? launch_intake(src, c->d_mixed_tab, depths, rx ? pcm_streams : activity(c), dst, frames, (uint32_t)s0, (uint32_t)(s1 - s0), c->hs) : hipSuccess;
+    if (e == hipSuccess && rx) e = launch_spdifrx(true, src, c->d_mixed_tab, depths, activity(c), rx, dst, frames, (uint32_t)s0, (uint32_t)(s1 - s0), c->hs);
     return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("intake launch: ") + hipGetErrorString(e));
 }
 
@@ -2070,7 +2091,7 @@ static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     int rc = 0;
     if (pc && !out->sub) { if ((rc = pdm_sub_scratch(c, L))) return rc; a.sub = c->d_sub; }
     if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, L.two_pass_bytes))) return rc;
-    if (mx) { if ((rc = launch_intake_streams(c, L.frames, pcm_in, c->d_mixed, 0, c->n_streams))) return rc; a.pcm = c->d_mixed; }
+    if (mx) { if ((rc = launch_intake_streams(c, L.frames, pcm_in, c->d_mixed, 0, c->n_streams, mx->rx))) return rc; a.pcm = c->d_mixed; }
     if ((rc = launch_rows(c, a, L, 0, c->n_wg))) return rc;
     if (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, pc->words, 0, c->n_streams))) return rc;
     return clip_out ? gather_clip(c, clip_out) : DSPI_OK;
@@ -2104,10 +2125,17 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     int rc = direct_area(c, L.direct_bytes);
     if (rc) return rc;
     char *const h = c->h_direct, *const d = c->h_direct.device();
-    if (mx) {      // the copy widens as it copies (a paused stream's bytes are not read, and nobody reads its run of the area)
-        for (uint32_t s = 0; s < c->n_streams; s++)
-            if (!c->n_paused || c->active[s])
-                intake_widen_cpu(reinterpret_cast<uint8_t *>(h) + (size_t)s * L.pcm.per, static_cast<const uint8_t *>(pcm_in) + mx->offsets[s], mx->depths[s], L.frames);
+    std::vector<std::pair<uint32_t, SpdifRx>> rx_after;      // the records of the call's S/PDIF streams as the call leaves them: the caller's change when it succeeds
+    if (mx) {      // the copy widens, or decodes, as it copies (a paused stream's bytes are not read, and nobody reads its run of the area)
+        for (uint32_t s = 0; s < c->n_streams; s++) {
+            if (c->n_paused && !c->active[s]) continue;
+            uint8_t *const run = reinterpret_cast<uint8_t *>(h) + (size_t)s * L.pcm.per;
+            const uint8_t *const src = static_cast<const uint8_t *>(pcm_in) + mx->offsets[s];
+            if (mx->depths[s] == kSrcSpdif) {
+                rx_after.emplace_back(s, mx->rx[s]);
+                spdifrx_line_cpu(&rx_after.back().second, src, L.frames, nullptr, run);
+            } else intake_widen_cpu(run, src, mx->depths[s], L.frames);
+        }
     } else memcpy(h, pcm_in, L.pcm.bytes);
     a.pcm = d;
     if (out->pairs) a.pairs = reinterpret_cast<int32_t *>(d + L.pairs.off);
@@ -2177,6 +2205,7 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     if (out->peaks) memcpy(out->peaks, h + L.peaks.off, L.peaks.bytes);
     if (clip_out) memcpy(clip_out, h + L.clip.off, L.clip.bytes);
     if (pc) memcpy(pc->words, h + L.pdm_words.off, L.pdm_words.bytes);
+    for (const auto &r : rx_after) mx->rx[r.first] = r.second;
     return DSPI_OK;
 }
 
@@ -2222,6 +2251,15 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
         HIPCK(c, me);
     }
     if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, L.two_pass_bytes))) return rc;
+    // dspi_process_sources: the records of the call's S/PDIF streams go up ahead of the first launch and come down behind the last one (the
+    // other entries of the caller's array are neither read nor written: zeros go up in their place)
+    std::vector<SpdifRx> rx_stage;
+    if (mx && mx->rx) {
+        rx_stage.assign(c->n_streams, SpdifRx{});
+        for (uint32_t s = 0; s < c->n_streams; s++) if (rx_stream(c, *mx, s)) rx_stage[s] = mx->rx[s];
+        if ((rc = ensure(c, c->d_rx, rx_stage.size() * sizeof(SpdifRx)))) return rc;
+        HIPCK(c, hipMemcpyAsync(c->d_rx, rx_stage.data(), rx_stage.size() * sizeof(SpdifRx), hipMemcpyHostToDevice, c->hs));
+    }
     const uint32_t n_chunks = L.n_chunks, row = (uint32_t)c->sm.row;
     // the caller's buffers and the staging buffers: a row range is one contiguous piece of each (tiled words: whole tiles; else streams)
     // (dspi_process_mixed: the caller's PCM is as long as its depths make it, and a chunk's piece of it goes up to the same place of d_mixed_up)
@@ -2275,7 +2313,7 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
             if ((he = hipEventRecord(c->pipe_events[2 * ch], sin)) != hipSuccess || (he = hipStreamWaitEvent(c->hs, c->pipe_events[2 * ch], 0)) != hipSuccess) return fail_hip(he, "event");
         }
         if (pc && !out->sub) a.sub = c->d_sub - s0 * L.frames;      // (the chunk's first stream or tile stands at the scratch's start, in both layouts)
-        if (mx && (rc = launch_intake_streams(c, L.frames, c->d_mixed_up, c->d_in, s0, s1))) { unpin(); return rc; }
+        if (mx && (rc = launch_intake_streams(c, L.frames, c->d_mixed_up, c->d_in, s0, s1, mx->rx ? c->d_rx.get() : nullptr))) { unpin(); return rc; }
         if ((rc = launch_rows(c, a, L, r0, r1)) || (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, c->d_pdm_out, s0, s1)))) { unpin(); return rc; }
         if (n_chunks > 1) {
             if ((he = hipEventRecord(c->pipe_events[2 * ch + 1], c->hs)) != hipSuccess || (he = hipStreamWaitEvent(sout, c->pipe_events[2 * ch + 1], 0)) != hipSuccess) return fail_hip(he, "event");
@@ -2287,12 +2325,14 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
         if ((rc = gather_clip(c, c->d_clip))) { unpin(); return rc; }
         if ((he = hipMemcpyAsync(clip_out, c->d_clip, L.clip.bytes, hipMemcpyDeviceToHost, c->hs)) != hipSuccess) return fail_hip(he, "D2H clip flags");
     }
+    if (!rx_stage.empty() && (he = hipMemcpyAsync(rx_stage.data(), c->d_rx, rx_stage.size() * sizeof(SpdifRx), hipMemcpyDeviceToHost, c->hs)) != hipSuccess) return fail_hip(he, "D2H receiver records");
     if (n_chunks > 1) {
         if ((he = hipStreamSynchronize(c->hs_out)) != hipSuccess) return fail_hip(he, "sync");
         if ((he = hipStreamSynchronize(c->hs_in)) != hipSuccess) return fail_hip(he, "sync");
     }
     if ((he = hipStreamSynchronize(c->hs)) != hipSuccess) return fail_hip(he, "sync");
     unpin();
+    for (uint32_t s = 0; s < (uint32_t)rx_stage.size(); s++) if (rx_stream(c, *mx, s)) mx->rx[s] = rx_stage[s];
     return DSPI_OK;
 }
 
@@ -2426,8 +2466,10 @@ int dspi_wire_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, const
 
 // ---- 16- and 24-bit devices in one call (dspi_intake.h: the layout and why widening is exact; dspi_intake.hip: the kernel) ----
 // what both calls refuse about their arguments, in dspi_process's words
-static int mixed_check(dspi_ctx *c, const uint8_t *depths, uint32_t n_blocks, uint32_t block_len, const char *who) {
-    const uint32_t bad = intake_check_depths(depths, c->n_streams);
+// sources: the entries are those of dspi_process_sources (dspi_spdifrx.h), DSPI_SRC_SPDIF among them
+static int mixed_check(dspi_ctx *c, const uint8_t *depths, uint32_t n_blocks, uint32_t block_len, const char *who, bool sources = false) {
+    const uint32_t bad = sources ? sources_check(depths, c->n_streams) : intake_check_depths(depths, c->n_streams);
+    if (bad < c->n_streams && sources) return fail(c, DSPI_E_INVAL, std::string(who) + ": the source of stream " + std::to_string(bad) + " is none of DSPI_SRC_PCM16, DSPI_SRC_PCM24, DSPI_SRC_SPDIF");
     if (bad < c->n_streams) return fail(c, DSPI_E_INVAL, std::string(who) + ": the depth of stream " + std::to_string(bad) + " is neither 16 nor 24");
     if (n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN) return fail(c, DSPI_E_INVAL, std::string(who) + ": 1 <= block_len <= 192, n_blocks >= 1");
     return 0;
@@ -2441,17 +2483,30 @@ int dspi_mixed_pcm_bytes(const dspi_ctx *c, const uint8_t *bit_depths, uint32_t 
     return DSPI_OK;
 }
 
-// the one body of dspi_process_mixed and (wire: out->pairs in the wire layout, the flags already held to its own rule) dspi_process_devices
+// the one body of dspi_process_mixed, (wire: out->pairs in the wire layout, the flags already held to its own rule) dspi_process_devices and
+// (sources: bit_depths holds sources, rx the caller's records) dspi_process_sources, which without an S/PDIF entry is one of the two
 static int mixed_call(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags,
-                      const char *who, bool wire) {
+                      const char *who, bool wire, bool sources = false, dspi_spdif_rx *rx = nullptr) {
     if (!c || !pcm_in || !bit_depths || !out) return DSPI_E_INVAL;
-    int rc = mixed_check(c, bit_depths, n_blocks, block_len, who);
+    int rc = mixed_check(c, bit_depths, n_blocks, block_len, who, sources);
     if (rc) return rc;
+    const bool spdif_in = sources && sources_any_spdif(bit_depths, c->n_streams);
     // every entry equal: the call IS dspi_process / dspi_process_pdm / dspi_process_wire at that depth (which refuses a bad flag bit and a host-only context itself)
-    if (const uint8_t depth = intake_uniform_depth(bit_depths, c->n_streams)) return process_call(c, pcm_in, depth, n_blocks, block_len, out, pdm_words, flags, nullptr, wire);
+    if (const uint8_t depth = spdif_in ? 0 : intake_uniform_depth(bit_depths, c->n_streams)) return process_call(c, pcm_in, depth, n_blocks, block_len, out, pdm_words, flags, nullptr, wire);
     if ((rc = check_flag_bits(c, flags)) || (!wire && (rc = check_flag_combinations(c, flags)))) return rc;
     MixedIn mx{bit_depths, std::vector<uint64_t>((size_t)c->n_streams + 1)};
-    if (!intake_offsets(bit_depths, c->n_streams, (uint64_t)n_blocks * block_len, nullptr, mx.offsets.data())) return fail(c, DSPI_E_INVAL, std::string(who) + ": the buffer's size overflows");
+    if (spdif_in) {      // what an S/PDIF source asks of the call's arguments
+        if (!rx) return fail(c, DSPI_E_INVAL, std::string(who) + ": an S/PDIF source needs the receiver records (rx)");
+        mx.rx = reinterpret_cast<SpdifRx *>(rx);
+        if (flags & DSPI_MEM_DEVICE) {
+            if (reinterpret_cast<uintptr_t>(pcm_in) % 16u) return fail(c, DSPI_E_INVAL, std::string(who) + ": with an S/PDIF source a device input is 16-byte aligned");
+            if (reinterpret_cast<uintptr_t>(rx) % 4u) return fail(c, DSPI_E_INVAL, std::string(who) + ": device receiver records are 4-byte aligned");
+        } else
+            for (uint32_t s = 0; s < c->n_streams; s++)
+                if (rx_stream(c, mx, s) && mx.rx[s].sync > kRxBlock) return fail(c, DSPI_E_INVAL, std::string(who) + ": the record of stream " + std::to_string(s) + " has sync > 192");
+    }
+    if (!(sources ? sources_offsets(bit_depths, c->n_streams, (uint64_t)n_blocks * block_len, nullptr, mx.offsets.data())
+                  : intake_offsets(bit_depths, c->n_streams, (uint64_t)n_blocks * block_len, nullptr, mx.offsets.data()))) return fail(c, DSPI_E_INVAL, std::string(who) + ": the buffer's size overflows");
     // the one case in which a 16-bit sample and its widened twin part ways (dspi_intake.h): refused, not approximated
     if (c->flavor)
         for (uint32_t s = 0; s < c->n_streams; s++) {
@@ -2475,6 +2530,63 @@ int dspi_process_devices(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_dep
     if (!c) return DSPI_E_INVAL;
     if (!devices_process_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_process_devices: the flags are DSPI_MEM_DEVICE, DSPI_OUT_TILED, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
     return mixed_call(c, pcm_in, bit_depths, n_blocks, block_len, out, pdm_words, flags | DSPI_OUT_SPDIF, "dspi_process_devices", true);
+}
+
+// ---- S/PDIF input (dspi_spdifrx.h: the subframe, the record, the rule and the layout; dspi_spdifrx.hip: the receiver kernel) ----
+static_assert(sizeof(dspi_spdif_rx) == sizeof(SpdifRx) && offsetof(dspi_spdif_rx, c_bits) == offsetof(SpdifRx, c_bits) && offsetof(dspi_spdif_rx, hold) == offsetof(SpdifRx, hold) &&
+              offsetof(dspi_spdif_rx, sync) == offsetof(SpdifRx, sync) && offsetof(dspi_spdif_rx, coding_errors) == offsetof(SpdifRx, coding_errors), "include/dspi.h and dspi_spdifrx.h: one record");
+static_assert(DSPI_SRC_SPDIF == kSrcSpdif && DSPI_SRC_PCM16 == 16 && DSPI_SRC_PCM24 == 24, "include/dspi.h and dspi_spdifrx.h: one set of sources");
+
+int dspi_sources_bytes(const dspi_ctx *c, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len, uint64_t *total_bytes, uint64_t *offsets) {
+    if (!c || !sources) return DSPI_E_INVAL;
+    int rc = mixed_check(const_cast<dspi_ctx *>(c), sources, n_blocks, block_len, "dspi_sources_bytes", true);
+    if (rc) return rc;
+    if (!sources_offsets(sources, c->n_streams, (uint64_t)n_blocks * block_len, total_bytes, offsets)) return fail(const_cast<dspi_ctx *>(c), DSPI_E_INVAL, "dspi_sources_bytes: the buffer's size overflows");
+    return DSPI_OK;
+}
+
+int dspi_process_sources(dspi_ctx *c, const void *in, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, dspi_spdif_rx *rx, uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    const bool wire = flags & DSPI_OUT_WIRE;
+    flags &= ~DSPI_OUT_WIRE;
+    if (wire && !devices_process_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_process_sources: with DSPI_OUT_WIRE the flags are DSPI_MEM_DEVICE, DSPI_OUT_TILED, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
+    return mixed_call(c, in, sources, n_blocks, block_len, out, pdm_words, wire ? flags | DSPI_OUT_SPDIF : flags, "dspi_process_sources", wire, true, rx);
+}
+
+int dspi_spdif_decode(dspi_ctx *c, const uint32_t *subframes, uint32_t n_lines, uint32_t n_frames, dspi_spdif_rx *rx, int32_t *pairs, uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    if (!subframes || !rx || !pairs || n_lines == 0 || n_frames == 0) return fail(c, DSPI_E_INVAL, "dspi_spdif_decode: a NULL pointer or a zero count");
+    size_t in_b, rx_b;
+    if (n_lines > 0x7fffffffu || __builtin_mul_overflow((size_t)n_lines * kRxFrameBytes, (size_t)n_frames, &in_b) || __builtin_mul_overflow((size_t)n_lines, sizeof(SpdifRx), &rx_b))
+        return fail(c, DSPI_E_INVAL, "dspi_spdif_decode: the buffers' sizes overflow");
+    if (flags & ~DSPI_MEM_DEVICE) return fail(c, DSPI_E_INVAL, "dspi_spdif_decode: the only flag is DSPI_MEM_DEVICE");
+    const bool dev = flags & DSPI_MEM_DEVICE;
+    SpdifRx *const recs = reinterpret_cast<SpdifRx *>(rx);
+    if (dev) {
+        if (reinterpret_cast<uintptr_t>(subframes) % 16u || reinterpret_cast<uintptr_t>(rx) % 16u || reinterpret_cast<uintptr_t>(pairs) % 16u)
+            return fail(c, DSPI_E_INVAL, "dspi_spdif_decode: device pointers are 16-byte aligned");
+    } else
+        for (uint32_t l = 0; l < n_lines; l++) if (recs[l].sync > kRxBlock) return fail(c, DSPI_E_INVAL, "dspi_spdif_decode: the record of line " + std::to_string(l) + " has sync > 192");
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    HIPCK(c, hipSetDevice(c->device));
+    const size_t out_b = in_b / 2;
+    const void *d_in = subframes;
+    void *d_out = pairs, *d_rx = rx;
+    int rc;
+    if (!dev) {
+        if ((rc = ensure(c, c->d_spdif_out, in_b)) || (rc = ensure(c, c->d_spdif_in, out_b)) || (rc = ensure(c, c->d_rx, rx_b))) return rc;
+        HIPCK(c, hipMemcpyAsync(c->d_spdif_out, subframes, in_b, hipMemcpyHostToDevice, c->hs));
+        HIPCK(c, hipMemcpyAsync(c->d_rx, rx, rx_b, hipMemcpyHostToDevice, c->hs));
+        d_in = c->d_spdif_out; d_out = c->d_spdif_in; d_rx = c->d_rx;      // (the encoders' staging buffers the other way round: subframes in the larger one)
+    }
+    HIPCK(c, launch_spdifrx(false, d_in, nullptr, nullptr, nullptr, d_rx, d_out, n_frames, 0u, n_lines, c->hs));
+    if (dev) return DSPI_OK;
+    // the records come down into the library's own memory first: the caller's change only when every copy has succeeded
+    std::vector<SpdifRx> after(n_lines);
+    HIPCK(c, hipMemcpyAsync(after.data(), c->d_rx, rx_b, hipMemcpyDeviceToHost, c->hs));
+    if ((rc = stage_down(c, pairs, c->d_spdif_in, out_b))) return rc;
+    memcpy(recs, after.data(), rx_b);
+    return DSPI_OK;
 }
 
 int dspi_wire_encode_tiled(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos, uint32_t *wire, uint32_t flags) {
@@ -2525,6 +2637,25 @@ int dspi_debug_intake(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths
     if (c->n_paused && (rc = upload_activity(c))) return rc;
     if ((rc = intake_prepare(c, mx, frames, c->d_mixed, (size_t)out_bytes))) return rc;
     return launch_intake_streams(c, frames, pcm_in, c->d_mixed, 0, c->n_streams);
+}
+
+// ... of a dspi_process_sources call: the intake for the PCM streams and the receiver for the S/PDIF streams (tools/bench_spdif_in.py)
+int dspi_debug_sources_intake(dspi_ctx *c, const void *in, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len, dspi_spdif_rx *rx) {
+    if (!c || !in || !sources) return DSPI_E_INVAL;
+    int rc = mixed_check(c, sources, n_blocks, block_len, "dspi_debug_sources_intake", true);
+    if (rc) return rc;
+    const bool spdif_in = sources_any_spdif(sources, c->n_streams);
+    if (spdif_in && (!rx || reinterpret_cast<uintptr_t>(in) % 16u || reinterpret_cast<uintptr_t>(rx) % 4u)) return fail(c, DSPI_E_INVAL, "dspi_debug_sources_intake: rx is required and the input 16-byte aligned");
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no intake");
+    const uint64_t frames = (uint64_t)n_blocks * block_len;
+    MixedIn mx{sources, std::vector<uint64_t>((size_t)c->n_streams + 1), spdif_in ? reinterpret_cast<SpdifRx *>(rx) : nullptr};
+    uint64_t out_bytes = 0;
+    if (!sources_offsets(sources, c->n_streams, frames, nullptr, mx.offsets.data()) || __builtin_mul_overflow((uint64_t)c->n_streams * kIntakeOutFrame, frames, &out_bytes))
+        return fail(c, DSPI_E_INVAL, "dspi_debug_sources_intake: the buffer's size overflows");
+    HIPCK(c, hipSetDevice(c->device));
+    if (c->n_paused && (rc = upload_activity(c))) return rc;
+    if ((rc = intake_prepare(c, mx, frames, c->d_mixed, (size_t)out_bytes))) return rc;
+    return launch_intake_streams(c, frames, in, c->d_mixed, 0, c->n_streams, mx.rx);
 }
 
 int dspi_pdm_running(dspi_ctx *c, uint32_t first, uint32_t count, const uint8_t *set, uint8_t *get) {

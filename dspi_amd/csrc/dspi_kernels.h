@@ -155,4 +155,13 @@ hipError_t launch_boot(int flavor, const StateArrays &arr, const uint32_t *items
 hipError_t launch_intake(const void *src, const uint64_t *offsets, const uint8_t *depths, const uint32_t *active, void *dst, uint64_t frames,
                          uint32_t first, uint32_t count, hipStream_t stream);
 
+// ---- the S/PDIF receiver (dspi_spdifrx.h: the subframe, the record and the rule; dspi_spdifrx.hip: the kernel) ----
+// Lines [first, first + count) of subframes, `frames` frames of 16 bytes each, through their records rx[line] (40 bytes each, device memory,
+// read and written; a sync word above 192 is read as 0).  Line s stands at src + offsets[s] (offsets == nullptr: at src + 16 frames s), 16-byte
+// aligned.  packed: dst + 6 frames s takes the packed 24-bit run the chain reads (2-byte aligned), as launch_intake writes it; else dst is
+// int32 [line][frames][2], 8-byte aligned.  sources (null: every line): only lines whose entry is kSrcSpdif are served; active: the activity
+// bitmap or null.  A line that is not served is neither read nor written, and neither is its record.  All indexed by absolute line.
+hipError_t launch_spdifrx(bool packed, const void *src, const uint64_t *offsets, const uint8_t *sources, const uint32_t *active, void *rx, void *dst, uint64_t frames,
+                          uint32_t first, uint32_t count, hipStream_t stream);
+
 }  // namespace dspi

@@ -32,6 +32,11 @@ OUT_ENABLED_ONLY = 0x4
 OUT_I2S_SLOTS = 0x8
 OUT_SPDIF = 0x10
 OUT_CLIP_FLAGS = 0x20
+OUT_WIRE = 0x40      # dspi_process_sources only
+SRC_SPDIF, SRC_PCM16, SRC_PCM24 = 1, 16, 24
+# dspi_spdif_rx (include/dspi.h): 40 bytes, the first 20 the answer to REQ_GET_SPDIF_IN_STATUS
+SPDIF_RX = np.dtype([("state", "<u4"), ("sample_rate", "<u4"), ("parity_err_count", "<u4"), ("c_bits", "u1", (5,)), ("pad_", "u1", (3,)), ("hold", "<i4", (2,)),
+                     ("sync", "<u4"), ("held", "<u4"), ("coding_errors", "<u4")])
 E_INVAL = -10
 E_NODEVICE = -11
 E_UNSUPPORTED = -14
@@ -161,6 +166,11 @@ def lib() -> C.CDLL:
         L.dspi_device_flash.argtypes = [vp, C.c_int]
         L.dspi_flash_read.argtypes = [vp, u32, vp, C.c_size_t]
         L.dspi_flash_write.argtypes = [vp, u32, u32, vp, C.c_size_t]
+    if hasattr(L, "dspi_process_sources"):      # (ABI 8 + S/PDIF input: detected by symbol; with it dspi_spdif_decode, dspi_sources_bytes)
+        L.dspi_sources_bytes.argtypes = [vp, vp, u32, u32, C.POINTER(C.c_uint64), vp]
+        L.dspi_process_sources.argtypes = [vp, vp, vp, u32, u32, C.POINTER(_Out), vp, vp, u32]
+        L.dspi_spdif_decode.argtypes = [vp, vp, u32, u32, vp, vp, u32]
+        L.dspi_debug_sources_intake.argtypes = [vp, vp, vp, u32, u32, vp]
     _lib = L
     return L
 
@@ -635,6 +645,66 @@ class Dspi:
     def wire_encode_tiled_device(self, pairs_ptr: int, n_frames: int, block_pos_ptr: int, out_ptr: int):
         """dspi_wire_encode_tiled on device pointers (block_pos: uint32 [S] in device memory, taken modulo 192); asynchronous, see sync()."""
         self._ck(self.L.dspi_wire_encode_tiled(self.h, pairs_ptr, n_frames, block_pos_ptr, out_ptr, MEM_DEVICE), "wire_encode_tiled")
+
+    # ---- S/PDIF input (include/dspi.h: dspi_spdif_decode / dspi_process_sources) ----
+    def spdif_decode_host(self, subframes: np.ndarray, rx: np.ndarray) -> np.ndarray:
+        """dspi_spdif_decode on host arrays: subframes uint32 [lines][F][4], rx SPDIF_RX [lines] (updated in place) -> pairs int32 [lines][F][2]."""
+        sub = np.ascontiguousarray(subframes, dtype=np.uint32)
+        lines, F, _ = sub.shape
+        assert rx.dtype == SPDIF_RX and rx.flags.c_contiguous and rx.size == lines, (rx.dtype, rx.shape)
+        pairs = np.zeros((lines, F, 2), dtype=np.int32)
+        self._ck(self.L.dspi_spdif_decode(self.h, sub.ctypes.data, lines, F, rx.ctypes.data, pairs.ctypes.data, 0), "spdif_decode")
+        return pairs
+
+    def spdif_decode_device(self, sub_ptr: int, n_lines: int, n_frames: int, rx_ptr: int, pairs_ptr: int):
+        """dspi_spdif_decode on device pointers (16-byte aligned); asynchronous, see sync()."""
+        self._ck(self.L.dspi_spdif_decode(self.h, sub_ptr, n_lines, n_frames, rx_ptr, pairs_ptr, MEM_DEVICE), "spdif_decode")
+
+    def sources_bytes(self, sources, n_blocks: int, block_len: int):
+        """dspi_sources_bytes: (total bytes, offsets uint64 [n_streams + 1]) of the input of a dspi_process_sources call (sources uint8
+        [n_streams], each SRC_PCM16, SRC_PCM24 or SRC_SPDIF; an S/PDIF run starts at a multiple of 16).  Works on host-only contexts."""
+        d = self._depths(sources)
+        total, off = C.c_uint64(0), np.zeros(self.n_streams + 1, dtype=np.uint64)
+        self._ck(self.L.dspi_sources_bytes(self.h, d.ctypes.data, n_blocks, block_len, C.byref(total), off.ctypes.data), "sources_bytes")
+        return total.value, off
+
+    def process_sources_host(self, data: np.ndarray, sources, n_blocks: int, block_len: int, rx: np.ndarray | None = None, want_pairs=True, want_sub=True, want_peaks=True,
+                             tiled=False, enabled_only=False, spdif=False, wire=False, clip=False, pdm=False):
+        """dspi_process_sources on host arrays: data = one flat uint8 array laid out as sources_bytes says, rx = SPDIF_RX [n_streams] (updated in
+        place; may be None without an S/PDIF source).  Returns process_mixed_host's arrays; with wire=True (DSPI_OUT_WIRE) `pairs` is
+        process_devices_host's wire array."""
+        S, F = self.n_streams, n_blocks * block_len
+        d = self._depths(sources)
+        data = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        if rx is not None: assert rx.dtype == SPDIF_RX and rx.flags.c_contiguous and rx.size == S, (rx.dtype, rx.shape)
+        R = self.tile_streams(); nt = (S + R - 1) // R
+        if wire: pairs = np.zeros((nt, self.P, F, 4, R) if tiled else (S, self.P, F, 4), dtype=np.uint32)
+        elif tiled: pairs = np.zeros((nt, self.P * 2, F, R), dtype=np.int32) if want_pairs else None
+        else: pairs = (np.zeros((S, self.P, F, 4), dtype=np.uint32) if spdif else np.zeros((S, self.P, F, 2), dtype=np.int32)) if want_pairs else None
+        sub = np.zeros((nt, F, R) if tiled else (S, F), dtype=np.int32) if want_sub else None
+        peaks = np.zeros((S, n_blocks, self.C), dtype=np.uint16) if want_peaks else None
+        words = np.zeros((nt, F, 8, R) if tiled else (S, F, 8), dtype=np.uint32) if pdm else None
+        self.last_clip = np.zeros(S, dtype=np.uint16) if clip else None
+        out = _Out(pairs.ctypes.data if pairs is not None else None, sub.ctypes.data if want_sub else None, peaks.ctypes.data if want_peaks else None, self.last_clip.ctypes.data if clip else None)
+        self._ck(self.L.dspi_process_sources(self.h, data.ctypes.data, d.ctypes.data, n_blocks, block_len, C.byref(out), words.ctypes.data if pdm else None,
+                                             rx.ctypes.data if rx is not None else None,
+                                             (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_SPDIF if spdif else 0) | (OUT_WIRE if wire else 0) |
+                                             (OUT_CLIP_FLAGS if clip else 0)), "process_sources")
+        return (pairs, sub, peaks, words) if pdm else (pairs, sub, peaks)
+
+    def process_sources_device(self, in_ptr: int, sources, n_blocks: int, block_len: int, rx_ptr: int = 0, pairs_ptr: int = 0, sub_ptr: int = 0, peaks_ptr: int = 0,
+                               words_ptr: int = 0, tiled: bool = False, enabled_only: bool = False, spdif: bool = False, wire: bool = False, clip_ptr: int = 0):
+        """dspi_process_sources on raw device pointers (the sources stay a host array; rx: SPDIF_RX [n_streams] in device memory); asynchronous, see sync()."""
+        d = self._depths(sources)
+        out = _Out(pairs_ptr or None, sub_ptr or None, peaks_ptr or None, clip_ptr or None)
+        self._ck(self.L.dspi_process_sources(self.h, in_ptr, d.ctypes.data, n_blocks, block_len, C.byref(out), words_ptr or None, rx_ptr or None,
+                                             MEM_DEVICE | (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_SPDIF if spdif else 0) | (OUT_WIRE if wire else 0) |
+                                             (OUT_CLIP_FLAGS if clip_ptr else 0)), "process_sources")
+
+    def debug_sources_intake(self, in_ptr: int, sources, n_blocks: int, block_len: int, rx_ptr: int = 0):
+        """dspi_debug_sources_intake: the intake and the receiver of process_sources_device alone, into the context's scratch; asynchronous, see sync()."""
+        d = self._depths(sources)
+        self._ck(self.L.dspi_debug_sources_intake(self.h, in_ptr, d.ctypes.data, n_blocks, block_len, rx_ptr or None), "debug_sources_intake")
 
     def pdm_restart(self, stream: int = ALL):
         self._ck(self.L.dspi_pdm_restart(self.h, stream), "pdm_restart")

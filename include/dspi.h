@@ -79,7 +79,8 @@ extern "C" {
                               * 8 + mixed input formats: detect by symbol (dspi_process_mixed; with it dspi_mixed_pcm_bytes; additions only);
                               * 8 + wire words per device: detect by symbol (dspi_process_wire; with it dspi_wire_encode; additions only);
                               * 8 + a stream's own flash: detect by symbol (dspi_device_flash; with it dspi_flash_read, dspi_flash_write, DSPI_BOOT_STREAMS_OWN_FLASH; additions only);
-                              * 8 + wire words on tiled and mixed-depth contexts: detect by symbol (dspi_process_devices; with it dspi_wire_encode_tiled; additions only) */
+                              * 8 + wire words on tiled and mixed-depth contexts: detect by symbol (dspi_process_devices; with it dspi_wire_encode_tiled; additions only);
+                              * 8 + S/PDIF input: detect by symbol (dspi_process_sources; with it dspi_spdif_decode, dspi_sources_bytes, dspi_spdif_rx, DSPI_SRC_*, DSPI_OUT_WIRE; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -938,6 +939,94 @@ int dspi_process_devices(dspi_ctx *ctx, const void *pcm_in, const uint8_t *bit_d
                          const dspi_out *out, uint32_t *pdm_words /* may be NULL */, uint32_t flags);
 int dspi_wire_encode_tiled(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos,
                            uint32_t *wire, uint32_t flags);
+
+/* ---- S/PDIF input ------------------------------------------------------------------------------------------------------------------------ */
+/* A device takes its audio from an S/PDIF receiver instead of USB, through the identical pipeline (the reference's
+ * Documentation/Features/SPDIF_input_spec.md: 24-bit words, hold concealment on the validity bit, a 20-byte receiver status).  The firmware
+ * tree has no receiver code, so what is fixed here is: the subframe exactly as the firmware's own encoder writes it (what dspi_spdif_encode
+ * emits), the sample path (a decoded sample enters the chain as the 24-bit USB sample of the same value: "replaces USB audio at the entry
+ * point"), and the receiver rules below.
+ *
+ * THE SUBFRAME (pico_audio_spdif_multi: sample_encoding.h:27-47, audio_spdif.c:77-94, :101-113, :141-153).  A frame is four words {l, h} left,
+ * {l, h} right.  With cells = h:l (64 bits) time slot k owns bit 2k (the clock cell, 1 for k >= 4) and bit 2k + 1 (the data cell).
+ *   preamble     l & 0xff: Z 0x39, X 0xC9 (left), Y 0x69 (right)
+ *   sample       the data cells of slots 4..27, slot 4 = LSB, sign-extended from bit 23
+ *   status bits  V = slot 28 (h bit 25), U = slot 29 (bit 27), C = slot 30 (bit 29), P = slot 31 (bit 31)
+ *   parity       holds when the XOR of the data cells of slots 4..31 is 0
+ * A subframe is WELL-FORMED when its preamble byte is Z or X (left) or Y (right), and (l & 0x55555500) == 0x55555500 and
+ * (h & 0x55555555) == 0x55555555.
+ *
+ * THE RECEIVER: one record per stream, caller-owned, read and updated by every call.  A record of all zero bytes is a receiver just started.
+ * Its first 20 bytes are the answer to REQ_GET_SPDIF_IN_STATUS (the spec's "Response (20 bytes)").  For each frame, in order:
+ *   1. sync      left well-formed with Z: if sync != 1 this is a lock or re-lock and parity_err_count := 0; either way sync := 1.
+ *                Left well-formed with X while sync == 1 (Z expected): sync := 0, sample_rate := 0.  Left not well-formed: the same loss.
+ *                Then, right not well-formed: the same loss.
+ *   2. each side, left then right.  Not well-formed: coding_errors++, the output is hold[side], held++.  Well-formed: a parity failure does
+ *                parity_err_count++ and the sample still passes (the spec only counts).  Well-formed with V set: the output is hold[side],
+ *                held++.  Otherwise the output is the sample and hold[side] := the sample.
+ *   3. if sync != 0, with p = sync - 1: p < 40: bit p % 8 of c_bits[p / 8] := the left subframe's C; p == 31: sample_rate := 44100 / 48000 /
+ *                88200 / 96000 / 176400 / 192000 for byte 3 = 0x00 / 02 / 08 / 0A / 0C / 0E, else 0; then sync := 1 + (p + 1) % 192.
+ * At the end of the call state = 2 if sync != 0, else 1 if the call held any well-formed subframe, else 0.  Counters wrap.  A host-memory
+ * record with sync > 192 is DSPI_E_INVAL; a device-memory one is read as 0.
+ * Out of scope: lock timing and watchdogs, the mute during a source switch, TX clock tracking, running the chain at 88.2 / 176.4 / 192 kHz
+ * (reported, not settable), applying the detected rate (the caller calls dspi_set_sample_rate), I2S input, a tiled input, receiver state
+ * held by the context, serving 0x80-0x82 inside dspi_vendor_* (INTEGRATION.md says how a caller answers them). */
+typedef struct dspi_spdif_rx {      /* 40 bytes; the first 20 are REQ_GET_SPDIF_IN_STATUS's answer */
+    uint32_t state;                 /* 0 NO_SIGNAL, 1 ACQUIRING, 2 LOCKED: written at the end of every call */
+    uint32_t sample_rate;           /* Hz from channel status byte 3, or 0 */
+    uint32_t parity_err_count;      /* since the last lock */
+    uint8_t  c_bits[5], pad_[3];
+    int32_t  hold[2];               /* last good sample, left / right */
+    uint32_t sync;                  /* 0: not locked; 1 + p: the next frame is expected at block position p (0..191) */
+    uint32_t held;                  /* subframes concealed */
+    uint32_t coding_errors;         /* subframes that were not well-formed */
+} dspi_spdif_rx;
+#define DSPI_SPDIF_RX_NO_SIGNAL 0u
+#define DSPI_SPDIF_RX_ACQUIRING 1u
+#define DSPI_SPDIF_RX_LOCKED 2u
+
+/* dspi_spdif_decode: the inverse of dspi_spdif_encode, stateless per context (the state is the caller's records).
+ *   subframes  uint32 [line][n_frames][4]      a whole stream-major S/PDIF output buffer is dspi_num_streams * dspi_num_pairs lines
+ *   rx         dspi_spdif_rx [n_lines]         required, in/out
+ *   pairs      int32 [line][n_frames][2]       the words dspi_out.pairs holds
+ * All three in host memory, or in device memory with DSPI_MEM_DEVICE, the only flag (asynchronous on the context's stream then).
+ * DSPI_E_INVAL: a NULL pointer, a zero count, sizes that overflow, another flag, a device pointer that is not 16-byte aligned, a host record
+ * with sync > 192; then DSPI_E_NODEVICE on a host-only context.  A refused call writes nothing.  Returns DSPI_OK or a negative DSPI_E_*. */
+int dspi_spdif_decode(dspi_ctx *ctx, const uint32_t *subframes, uint32_t n_lines, uint32_t n_frames, dspi_spdif_rx *rx, int32_t *pairs, uint32_t flags);
+
+/* dspi_process_sources: dspi_process_mixed with one SOURCE per stream instead of one depth.
+ *   sources   uint8 [dspi_num_streams], HOST memory always: DSPI_SRC_PCM16, DSPI_SRC_PCM24 or DSPI_SRC_SPDIF (a paused stream's too: its
+ *             entry sizes its slot)
+ *   in        every stream's run of F = n_blocks * block_len frames at 4, 6 or 16 bytes per frame, back to back as in dspi_process_mixed,
+ *             except that an S/PDIF run starts at the next multiple of 16: offset[s] = offset[s - 1] + F * size[s - 1], rounded up to 16 when
+ *             sources[s] is DSPI_SRC_SPDIF.  An S/PDIF run holds the subframes uint32 [F][4] of ONE line (e.g. one pair of another context's
+ *             DSPI_OUT_SPDIF output).  A paused stream's bytes are never read.  dspi_sources_bytes gives the size (*total_bytes, may be
+ *             NULL) and the n_streams + 1 offsets (may be NULL); it works on host-only contexts.
+ *   rx        dspi_spdif_rx [dspi_num_streams], in host or device memory like the other pointers; required when any source is S/PDIF (else
+ *             it may be NULL).  Only the entries of ACTIVE S/PDIF streams are read or written.
+ * A decoded sample enters the chain as the 24-bit USB sample of the same value.  There is no preamp refusal for S/PDIF streams; 16-bit
+ * streams keep dspi_process_mixed's.
+ * Flags: dspi_process_mixed's, and DSPI_OUT_WIRE, defined for this call only: out->pairs is THE WIRE LAYOUT (with DSPI_OUT_TILED the tiled
+ * one) with the meaning and the flag refusals of dspi_process_devices.  Outputs, pauses, block positions, PDM bookkeeping and clip flags
+ * behave as in those calls.
+ * REFUSALS in dspi_process_mixed's order (with DSPI_OUT_WIRE: dspi_process_devices' flag rule first): DSPI_E_INVAL for a NULL pointer (ctx,
+ * in, sources, out), a source value that is none of the three, n_blocks / block_len / flag bits that dspi_process refuses, and — with an
+ * S/PDIF source present — a NULL rx, a host record of an active S/PDIF stream with sync > 192, a device `in` that is not 16-byte aligned, a
+ * device rx that is not 4-byte aligned, a size that overflows; then the preamp's DSPI_E_UNSUPPORTED; then DSPI_E_NODEVICE.  A refused or
+ * failed call writes nothing, and no host record changes.
+ * EQUIVALENCES: with no S/PDIF source the call IS dspi_process_mixed, with DSPI_OUT_WIRE dspi_process_devices (route, bytes and layout are
+ * the same); with uniform PCM sources it IS dspi_process.  Otherwise: device buffers take one more launch (dspi_spdifrx.hip) into the
+ * scratch the mixed path owns; small host calls decode on the CPU while copying into the pinned area; large host calls upload each
+ * chunk's bytes as they are and decode on the device.
+ * The ABI stays 8: detect by symbol (dspi_process_sources; with it dspi_spdif_decode, dspi_sources_bytes; additions only). */
+#define DSPI_SRC_SPDIF 1
+#define DSPI_SRC_PCM16 16
+#define DSPI_SRC_PCM24 24
+#define DSPI_OUT_WIRE 0x40u        /* dspi_process_sources only: out->pairs in the wire layout, as dspi_process_devices writes it */
+int dspi_sources_bytes(const dspi_ctx *ctx, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len,
+                       uint64_t *total_bytes, uint64_t *offsets /* [n_streams + 1] or NULL */);
+int dspi_process_sources(dspi_ctx *ctx, const void *in, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len,
+                         const dspi_out *out, uint32_t *pdm_words /* may be NULL */, dspi_spdif_rx *rx, uint32_t flags);
 int dspi_i2s_encode(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, uint32_t pair_mask, uint32_t *words, uint32_t flags);
 /* the HIP stream (hipStream_t) the context launches on, for event timing by the caller */
 void *dspi_hip_stream(dspi_ctx *ctx);
@@ -998,6 +1087,9 @@ int dspi_debug_eq_taps(dspi_ctx *ctx, int32_t stream, int channel, const float *
  * at; uniform depths are widened like any others.  For timing the pass (tools/bench_mixed.py); comes with dspi_process_mixed.
  * DSPI_E_INVAL as for that call's pointers, depths and lengths; DSPI_E_NODEVICE on a host-only context. */
 int dspi_debug_intake(dspi_ctx *ctx, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len);
+/* ... of a dspi_process_sources call on device buffers: the intake for its PCM streams and the receiver for its S/PDIF streams (rx: DEVICE
+ * memory, updated), the same way.  For timing (tools/bench_spdif_in.py); comes with dspi_process_sources. */
+int dspi_debug_sources_intake(dspi_ctx *ctx, const void *in, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len, dspi_spdif_rx *rx);
 
 #ifdef __cplusplus
 }
