@@ -34,6 +34,7 @@
 #include "dspi_flash.h"
 #include "dspi_group.h"
 #include "dspi_intake.h"
+#include "dspi_link.h"
 #include "dspi_migrate.h"
 #include "dspi_move.h"
 #include "dspi_pdmfade.h"
@@ -166,6 +167,8 @@ struct dspi_ctx {
     DevBuf<uint32_t> d_mig_pos{mem};
     PinnedBuf<char> h_mig{mem};
     hipEvent_t ev_mig = nullptr;
+    // dspi_process_linked: "the producer's stream has come this far": recorded on the PRODUCER's stream, waited for on this context's
+    hipEvent_t ev_link = nullptr;
     // dspi_device_flash (dspi_flash.h): while on, every stream holds a flash of its own (shared until written) and the preset directory requests
     // are served from it.  Host memory only; consulted in request and maintenance paths, never by dspi_process.
     FlashBook flash;
@@ -769,6 +772,7 @@ void dspi_destroy(dspi_ctx *c) {
         devmem_release(a, c->mem);      // every buffer and pinned area, here: with the context's device current and its streams still alive
         if (c->ev_move) (void)hipEventDestroy(c->ev_move);
         if (c->ev_mig) (void)hipEventDestroy(c->ev_mig);
+        if (c->ev_link) (void)hipEventDestroy(c->ev_link);
         for (hipEvent_t e : c->pipe_events) (void)hipEventDestroy(e);
         if (c->hs_in) (void)hipStreamDestroy(c->hs_in);
         if (c->hs_out) (void)hipStreamDestroy(c->hs_out);
@@ -2085,13 +2089,62 @@ static int launch_intake_streams(dspi_ctx *c, uint64_t frames, const void *src, 
     return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("intake launch: ") + hipGetErrorString(e));
 }
 
+// ---- dspi_process_linked / dspi_wire_decode (dspi_link.h): the call's links ----
+// Like a mixed call, a linked call is planned as the 24-bit call it becomes; its `pcm` area, d_mixed, is filled by the link receivers from
+// another call's wire buffer.  The device route only.
+struct LinkIn {
+    const WireView *view;      // validated; wire in device memory
+    const Link *links;         // [n], host memory, validated for the entries that are served
+    SpdifRx *rx;               // [n] in device memory, or null when no served link is S/PDIF
+    dspi_ctx *producer;        // whose stream writes view->wire (null, or the context itself: nothing to wait for)
+};
+// the device's table of a call's links: n + 1 offsets (what launch_spdifrx reads for the S/PDIF lines of a stream-major view), the n links, the n
+// kinds as bytes; an entry that is not served (a paused stream, a hole) has kind NONE there, so no kernel looks at its line.  It stands in the
+// mixed path's table, which then holds no mixed call's layout any more.
+struct LinkTab { const uint64_t *offsets; const Link *links; const uint8_t *kinds; bool any_spdif, any_i2s; };
+static int link_table(dspi_ctx *c, const WireView &v, const Link *links, uint32_t n, const uint8_t *active, LinkTab &t) {
+    std::vector<uint64_t> offsets((size_t)n + 1, 0u);
+    std::vector<Link> dl(n);
+    std::vector<uint8_t> kinds(((size_t)n + 7) / 8 * 8, 0u);
+    t.any_spdif = t.any_i2s = false;
+    for (uint32_t i = 0; i < n; i++) {
+        const bool on = (!active || active[i]) && links[i].kind != kLinkNone;
+        dl[i] = on ? links[i] : Link{0u, kLinkNone};
+        kinds[i] = (uint8_t)dl[i].kind;
+        if (on && !v.tile_streams) offsets[i] = link_region(links[i].line, v.n_frames) * 4u;
+        t.any_spdif = t.any_spdif || dl[i].kind == kLinkSpdif;
+        t.any_i2s = t.any_i2s || dl[i].kind == kLinkI2s;
+    }
+    c->mixed_frames = 0;
+    if (int rc = upload_via_move_area(c, c->d_mixed_tab, "hipHostMalloc failed (link table)", {{offsets.data(), offsets.size() * 8}, {dl.data(), (size_t)n * 8}, {kinds.data(), kinds.size()}})) return rc;
+    t.offsets = c->d_mixed_tab;
+    t.links = reinterpret_cast<const Link *>(c->d_mixed_tab + n + 1);
+    t.kinds = reinterpret_cast<const uint8_t *>(c->d_mixed_tab + 2 * (size_t)n + 1);
+    return 0;
+}
+// the link receivers of a dspi_process_linked call, into d_mixed, behind the producer's work where its stream is another one
+static int launch_links(dspi_ctx *c, const LinkIn &lk, uint64_t frames) {
+    LinkTab t;
+    int rc = link_table(c, *lk.view, lk.links, c->n_streams, host_activity(c), t);
+    if (rc) return rc;
+    if (lk.producer && lk.producer != c) {
+        if (!c->ev_link) HIPCK(c, hipEventCreateWithFlags(&c->ev_link, hipEventDisableTiming));
+        HIPCK(c, hipEventRecord(c->ev_link, lk.producer->hs));
+        HIPCK(c, hipStreamWaitEvent(c->hs, c->ev_link, 0));
+    }
+    const hipError_t e = launch_linkrx(true, lk.view->wire, t.links, t.offsets, t.kinds, nullptr, lk.rx, c->d_mixed, (uint32_t)frames, lk.view->n_pairs, lk.view->tile_streams, c->n_streams,
+                                       t.any_spdif, t.any_i2s, c->hs);
+    return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("link receiver launch: ") + hipGetErrorString(e));
+}
+
 // ---- device buffers: the caller's own, asynchronous on the context's stream ----
-static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, const PdmCall *pc, const MixedIn *mx) {
+static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, const PdmCall *pc, const MixedIn *mx, const LinkIn *lk = nullptr) {
     a.pcm = pcm_in; a.pairs = out->pairs; a.sub = out->sub; a.peaks = out->peaks;
     int rc = 0;
     if (pc && !out->sub) { if ((rc = pdm_sub_scratch(c, L))) return rc; a.sub = c->d_sub; }
     if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, L.two_pass_bytes))) return rc;
     if (mx) { if ((rc = launch_intake_streams(c, L.frames, pcm_in, c->d_mixed, 0, c->n_streams, mx->rx))) return rc; a.pcm = c->d_mixed; }
+    if (lk) { if ((rc = launch_links(c, *lk, L.frames))) return rc; a.pcm = c->d_mixed; }
     if ((rc = launch_rows(c, a, L, 0, c->n_wg))) return rc;
     if (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, pc->words, 0, c->n_streams))) return rc;
     return clip_out ? gather_clip(c, clip_out) : DSPI_OK;
@@ -2358,7 +2411,7 @@ static bool wire_slots_in_play(const dspi_ctx *c) {
 // wire: dspi_process_wire and dspi_process_devices (flags carry DSPI_OUT_SPDIF, which the wire layout implies): out->pairs in the wire layout;
 // with DSPI_OUT_TILED beside it (dspi_process_devices alone; the callers have applied their own flag rule, dspi_wire.h) in the tiled wire layout
 static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags,
-                        const MixedIn *mx = nullptr, bool wire = false) {
+                        const MixedIn *mx = nullptr, bool wire = false, const LinkIn *lk = nullptr) {
     if (!c || !pcm_in || !out) return DSPI_E_INVAL;
     int rc = check_flag_bits(c, flags);
     if (rc) return rc;
@@ -2390,6 +2443,7 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     if (pc && (rc = pdm_prepare(c, pdm))) return rc;
     if (mx && L.mem == CallMem::Device && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed, L.pcm.bytes))) return rc;
     if (mx && L.mem == CallMem::Staged && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed_up, (size_t)mx->offsets.back()))) return rc;
+    if (lk && (L.mem != CallMem::Device || (rc = ensure(c, c->d_mixed, L.pcm.bytes)))) return rc ? rc : fail(c, DSPI_E_INVAL, "dspi_process_linked: device memory only");
 
     KArgs a{};
     a.img = c->d_images; a.stream_image = c->d_stream_image; a.vals = c->d_vals;
@@ -2409,7 +2463,7 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     }
 
     switch (L.mem) {
-    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out, pc, mx); break;
+    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out, pc, mx, lk); break;
     case CallMem::Direct: rc = process_direct(c, L, a, pcm_in, out, clip_out, flags, call_t0, pc, mx); break;
     case CallMem::Staged: rc = process_staged(c, L, a, pcm_in, out, clip_out, flags, pc, mx); break;
     }
@@ -2587,6 +2641,113 @@ int dspi_spdif_decode(dspi_ctx *c, const uint32_t *subframes, uint32_t n_lines, 
     if ((rc = stage_down(c, pairs, c->d_spdif_in, out_b))) return rc;
     memcpy(recs, after.data(), rx_b);
     return DSPI_OK;
+}
+
+// ---- chained devices (dspi_link.h: views, links, the refusals and the reader on the CPU; dspi_linkrx.hip: the link receivers) ----
+static_assert(sizeof(dspi_wire_view) == sizeof(WireView) && offsetof(dspi_wire_view, wire) == offsetof(WireView, wire) && offsetof(dspi_wire_view, n_streams) == offsetof(WireView, n_streams) &&
+              offsetof(dspi_wire_view, n_pairs) == offsetof(WireView, n_pairs) && offsetof(dspi_wire_view, tile_streams) == offsetof(WireView, tile_streams) &&
+              offsetof(dspi_wire_view, n_frames) == offsetof(WireView, n_frames) && offsetof(dspi_wire_view, producer) == offsetof(WireView, producer), "include/dspi.h and dspi_link.h: one view");
+static_assert(sizeof(dspi_link) == sizeof(Link) && offsetof(dspi_link, kind) == offsetof(Link, kind), "include/dspi.h and dspi_link.h: one link");
+static_assert(DSPI_LINK_NONE == kLinkNone && DSPI_LINK_SPDIF == kLinkSpdif && DSPI_LINK_I2S == kLinkI2s && DSPI_LINK_SPDIF == DSPI_SRC_SPDIF, "include/dspi.h and dspi_link.h: one set of kinds");
+
+int dspi_wire_view_of(const dspi_ctx *p, const uint32_t *wire, uint32_t n_frames, uint32_t flags, dspi_wire_view *view) {
+    if (!p || !view) return DSPI_E_INVAL;
+    if (flags & ~DSPI_OUT_TILED) return fail(const_cast<dspi_ctx *>(p), DSPI_E_INVAL, "dspi_wire_view_of: the only flag is DSPI_OUT_TILED");
+    *view = dspi_wire_view{wire, p->n_streams, (uint32_t)p->sm.n_pairs, (flags & DSPI_OUT_TILED) ? (uint32_t)p->sm.row : 0u, n_frames, const_cast<dspi_ctx *>(p)};
+    return DSPI_OK;
+}
+
+int dspi_link_kinds(const dspi_ctx *p, dspi_link *links, uint32_t n) {
+    if (!p || (!links && n)) return DSPI_E_INVAL;
+    const uint32_t P = (uint32_t)p->sm.n_pairs;
+    for (uint32_t i = 0; i < n; i++)
+        if (links[i].line >= (uint64_t)p->n_streams * P) return fail(const_cast<dspi_ctx *>(p), DSPI_E_INVAL, "dspi_link_kinds: link " + std::to_string(i) + " names no line of the producer");
+    for (uint32_t i = 0; i < n; i++) links[i].kind = readable(p, (int32_t)(links[i].line / P)).output_types[links[i].line % P] == 1 ? DSPI_LINK_I2S : DSPI_LINK_SPDIF;
+    return DSPI_OK;
+}
+
+int dspi_wire_decode(dspi_ctx *c, const dspi_wire_view *view, const dspi_link *links, uint32_t n_links, dspi_spdif_rx *rx, int32_t *pairs, uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    if (!view || !links || !pairs || n_links == 0) return fail(c, DSPI_E_INVAL, "dspi_wire_decode: a NULL pointer or no link");
+    if (flags & ~DSPI_MEM_DEVICE) return fail(c, DSPI_E_INVAL, "dspi_wire_decode: the only flag is DSPI_MEM_DEVICE");
+    const bool dev = flags & DSPI_MEM_DEVICE;
+    const WireView &v = *reinterpret_cast<const WireView *>(view);
+    const Link *const lk = reinterpret_cast<const Link *>(links);
+    SpdifRx *const recs = reinterpret_cast<SpdifRx *>(rx);
+    if (const char *why = link_view_why(v, 0, dev)) return fail(c, DSPI_E_INVAL, std::string("dspi_wire_decode: ") + why);
+    const uint32_t bad = links_check(lk, n_links, link_view_lines(v), nullptr, true);
+    if (bad < n_links) return fail(c, DSPI_E_INVAL, "dspi_wire_decode: link " + std::to_string(bad) + " has a kind that is none of DSPI_LINK_*, or names no line of the view");
+    const bool any_spdif = links_any(lk, n_links, nullptr, kLinkSpdif);
+    const uint64_t F = v.n_frames;
+    size_t out_b, rx_b;
+    if (n_links > 0x7fffffffu || __builtin_mul_overflow((size_t)n_links * 8u, (size_t)F, &out_b) || __builtin_mul_overflow((size_t)n_links, sizeof(SpdifRx), &rx_b))
+        return fail(c, DSPI_E_INVAL, "dspi_wire_decode: the buffers' sizes overflow");
+    if (any_spdif && !rx) return fail(c, DSPI_E_INVAL, "dspi_wire_decode: an S/PDIF link needs the receiver records (rx)");
+    if (dev) {
+        if ((any_spdif && reinterpret_cast<uintptr_t>(rx) % 16u) || reinterpret_cast<uintptr_t>(pairs) % 16u) return fail(c, DSPI_E_INVAL, "dspi_wire_decode: device pointers are 16-byte aligned");
+    } else
+        for (uint32_t i = 0; i < n_links; i++)
+            if (lk[i].kind == kLinkSpdif && recs[i].sync > kRxBlock) return fail(c, DSPI_E_INVAL, "dspi_wire_decode: the record of link " + std::to_string(i) + " has sync > 192");
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    HIPCK(c, hipSetDevice(c->device));
+    WireView dv = v;
+    void *d_out = pairs, *d_rx = rx;
+    uint64_t words = 0;
+    int rc;
+    if (!dev) {
+        link_view_words(v, &words);
+        if ((rc = ensure(c, c->d_spdif_out, (size_t)words * 4)) || (rc = ensure(c, c->d_spdif_in, out_b)) || (any_spdif && (rc = ensure(c, c->d_rx, rx_b)))) return rc;
+        HIPCK(c, hipMemcpyAsync(c->d_spdif_out, v.wire, (size_t)words * 4, hipMemcpyHostToDevice, c->hs));
+        if (any_spdif) HIPCK(c, hipMemcpyAsync(c->d_rx, rx, rx_b, hipMemcpyHostToDevice, c->hs));
+        dv.wire = c->d_spdif_out; d_out = c->d_spdif_in; d_rx = any_spdif ? c->d_rx.get() : nullptr;
+    }
+    LinkTab t;
+    if ((rc = link_table(c, dv, lk, n_links, nullptr, t))) return rc;
+    HIPCK(c, launch_linkrx(false, dv.wire, t.links, t.offsets, t.kinds, nullptr, d_rx, d_out, v.n_frames, v.n_pairs, v.tile_streams, n_links, t.any_spdif, t.any_i2s, c->hs));
+    if (dev) return DSPI_OK;
+    // everything comes down into the library's own memory first: the caller's buffers change only when every copy has succeeded, and only
+    // where a link wrote (a hole's pair words and every record that is no S/PDIF link's stay the caller's)
+    std::vector<int32_t> got(out_b / 4);
+    std::vector<SpdifRx> after(any_spdif ? n_links : 0);
+    if (any_spdif) HIPCK(c, hipMemcpyAsync(after.data(), c->d_rx, rx_b, hipMemcpyDeviceToHost, c->hs));
+    if ((rc = stage_down(c, got.data(), c->d_spdif_in, out_b))) return rc;
+    for (uint32_t i = 0; i < n_links; i++) {
+        if (lk[i].kind == kLinkNone) continue;
+        memcpy(pairs + (size_t)i * 2 * F, got.data() + (size_t)i * 2 * F, (size_t)F * 8);
+        if (lk[i].kind == kLinkSpdif) recs[i] = after[i];
+    }
+    return DSPI_OK;
+}
+
+int dspi_process_linked(dspi_ctx *c, const dspi_wire_view *view, const dspi_link *links, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words,
+                        dspi_spdif_rx *rx, uint32_t flags) {
+    if (!c || !view || !links || !out) return DSPI_E_INVAL;
+    // 2. the flags
+    if (!(flags & DSPI_MEM_DEVICE)) return fail(c, DSPI_E_INVAL, "dspi_process_linked: DSPI_MEM_DEVICE is required");
+    const bool wire = flags & DSPI_OUT_WIRE;
+    flags &= ~DSPI_OUT_WIRE;
+    if (wire && !devices_process_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_process_linked: with DSPI_OUT_WIRE the flags are DSPI_MEM_DEVICE, DSPI_OUT_TILED, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
+    int rc;
+    if ((rc = check_flag_bits(c, flags)) || (!wire && (rc = check_flag_combinations(c, flags)))) return rc;
+    // 3. the lengths
+    if (n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN) return fail(c, DSPI_E_INVAL, "dspi_process_linked: 1 <= block_len <= 192, n_blocks >= 1");
+    // 4. the view
+    const WireView &v = *reinterpret_cast<const WireView *>(view);
+    const Link *const lk = reinterpret_cast<const Link *>(links);
+    const uint64_t F = (uint64_t)n_blocks * block_len;
+    if (F > 0xffffffffull) return fail(c, DSPI_E_INVAL, "dspi_process_linked: the view's n_frames is not n_blocks * block_len");
+    if (const char *why = link_view_why(v, F, true)) return fail(c, DSPI_E_INVAL, std::string("dspi_process_linked: ") + why);
+    // 5. the links of the active streams
+    const uint32_t bad = links_check(lk, c->n_streams, link_view_lines(v), host_activity(c), false);
+    if (bad < c->n_streams) return fail(c, DSPI_E_INVAL, "dspi_process_linked: the link of stream " + std::to_string(bad) + " is neither DSPI_LINK_SPDIF nor DSPI_LINK_I2S, or names no line of the view");
+    // 6. the records
+    const bool any_spdif = links_any(lk, c->n_streams, host_activity(c), kLinkSpdif);
+    if (any_spdif && !rx) return fail(c, DSPI_E_INVAL, "dspi_process_linked: an S/PDIF link needs the receiver records (rx)");
+    if (any_spdif && reinterpret_cast<uintptr_t>(rx) % 4u) return fail(c, DSPI_E_INVAL, "dspi_process_linked: device receiver records are 4-byte aligned");
+    // 7. the producer
+    if (view->producer && view->producer->device != DSPI_DEVICE_NONE && view->producer->device != c->device) return fail(c, DSPI_E_INVAL, "dspi_process_linked: the view's producer is on another HIP device");
+    LinkIn in{&v, lk, any_spdif ? reinterpret_cast<SpdifRx *>(rx) : nullptr, view->producer && view->producer->device != DSPI_DEVICE_NONE ? view->producer : nullptr};
+    return process_call(c, v.wire, 24, n_blocks, block_len, out, pdm_words, wire ? flags | DSPI_OUT_SPDIF : flags, nullptr, wire, &in);
 }
 
 int dspi_wire_encode_tiled(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos, uint32_t *wire, uint32_t flags) {

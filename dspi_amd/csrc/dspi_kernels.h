@@ -164,4 +164,13 @@ hipError_t launch_intake(const void *src, const uint64_t *offsets, const uint8_t
 hipError_t launch_spdifrx(bool packed, const void *src, const uint64_t *offsets, const uint8_t *sources, const uint32_t *active, void *rx, void *dst, uint64_t frames,
                           uint32_t first, uint32_t count, hipStream_t stream);
 
+// ---- the link receivers (dspi_link.h: views, links, where a link's words lie; dspi_linkrx.hip: the kernels) ----
+// Destinations [0, count): destination i takes links[i] (dspi::Link [count], device memory) of the wire buffer `wire` (n_pairs = 2 / 4, row = 0:
+// the wire layout, 64 / 128: the tiled one; the links are valid for it) through its record rx[i] (S/PDIF links only; as for launch_spdifrx) into
+// dst (packed: dst + 6 frames i, else int32 [count][frames][2]).  active: one bit per destination or null.  A destination whose link is
+// kLinkNone or whose bit is clear is neither read nor written.  Stream-major views also need, for launch_spdifrx: offsets[i] = the byte offset
+// of link i's region and kinds[i] = its kind as a byte (device memory).  any_spdif / any_i2s: what the links hold, as the host knows it.
+hipError_t launch_linkrx(bool packed, const uint32_t *wire, const void *links, const uint64_t *offsets, const uint8_t *kinds, const uint32_t *active, void *rx, void *dst,
+                         uint32_t frames, uint32_t n_pairs, uint32_t row, uint32_t count, bool any_spdif, bool any_i2s, hipStream_t stream);
+
 }  // namespace dspi

@@ -7,41 +7,22 @@ namespace dspi {
 
 void spdifrx_line_cpu(SpdifRx *rx, const void *words, uint64_t frames, int32_t *pairs, uint8_t *packed) {
     const uint8_t *in = static_cast<const uint8_t *>(words);
-    bool any_ok = false;
-    auto lose = [&]() { rx->sync = 0; rx->sample_rate = 0; };
+    RxRegs r{rx->sync, rx->sample_rate, rx->parity_err_count, rx->held, rx->coding_errors, 0, rx->hold[0], rx->hold[1], false};
+    memcpy(&r.cbits, rx->c_bits, 8);      // (the five status bytes and the padding behind them, which is kept)
     for (uint64_t f = 0; f < frames; f++) {
         uint32_t w[4];
         memcpy(w, in + f * kRxFrameBytes, sizeof w);
-        const bool ok[2] = {rx_left_ok(w[0], w[1]), rx_right_ok(w[2], w[3])};
-        const uint32_t data[2] = {rx_data(w[0], w[1]), rx_data(w[2], w[3])};
-        any_ok = any_ok || ok[0] || ok[1];
-        // 1. sync
-        if (ok[0] && (w[0] & 0xffu) == kPreZ) {
-            if (rx->sync != 1) rx->parity_err_count = 0;      // a lock or a re-lock
-            rx->sync = 1;
-        } else if (!ok[0] || rx->sync == 1) lose();            // malformed, or X where Z is expected
-        if (!ok[1]) lose();
-        // 2. each side
-        int32_t out[2];
-        for (int side = 0; side < 2; side++) {
-            if (!ok[side]) rx->coding_errors++;
-            else if (rx_parity_fails(data[side])) rx->parity_err_count++;      // counted only: the sample passes
-            if (!ok[side] || rx_v(data[side])) { out[side] = rx->hold[side]; rx->held++; }
-            else out[side] = rx->hold[side] = rx_sample(data[side]);
-        }
-        // 3. the channel status
-        if (rx->sync) {
-            const uint32_t p = rx->sync - 1;
-            if (p < kRxStatusBits) rx->c_bits[p / 8] = (uint8_t)((rx->c_bits[p / 8] & ~(1u << p % 8)) | (uint32_t)rx_c(data[0]) << p % 8);
-            if (p == 31) rx->sample_rate = rx_rate(rx->c_bits[3]);
-            rx->sync = 1 + (p + 1) % kRxBlock;
-        }
+        int32_t out[2] = {0, 0};
+        rx_frame(r, w[0], w[1], w[2], w[3], out[0], out[1]);
         if (pairs) { pairs[2 * f] = out[0]; pairs[2 * f + 1] = out[1]; }
         if (packed)
             for (int side = 0; side < 2; side++)
                 for (int b = 0; b < 3; b++) packed[6 * f + 3 * side + b] = (uint8_t)((uint32_t)out[side] >> 8 * b);
     }
-    rx->state = rx->sync ? 2u : any_ok ? 1u : 0u;
+    rx->sync = r.sync; rx->sample_rate = r.rate; rx->parity_err_count = r.parity; rx->held = r.held; rx->coding_errors = r.coding;
+    memcpy(rx->c_bits, &r.cbits, 8);
+    rx->hold[0] = r.hold_l; rx->hold[1] = r.hold_r;
+    rx->state = r.sync ? 2u : r.any_ok ? 1u : 0u;
 }
 
 uint32_t sources_check(const uint8_t *sources, uint32_t n) {

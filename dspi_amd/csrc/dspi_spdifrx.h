@@ -56,6 +56,46 @@ constexpr uint32_t rx_rate(uint32_t byte3) {
     return byte3 == 0x00 ? 44100u : byte3 == 0x02 ? 48000u : byte3 == 0x08 ? 88200u : byte3 == 0x0A ? 96000u : byte3 == 0x0C ? 176400u : byte3 == 0x0E ? 192000u : 0u;
 }
 
+// ---- one frame by the rule itself, steps 1-3 of include/dspi.h, on the record as registers hold it (constexpr: spdifrx_line_cpu runs it frame
+// after frame, and so does every lane of dspi_linkrx.hip's tiled kernel: one text for the sequential rule) ----
+struct RxRegs {
+    uint32_t sync, rate, parity, held, coding;      // the record's sync (<= 192), sample_rate, parity_err_count, held, coding_errors
+    uint64_t cbits;                                 // c_bits[0..4] in bits 0..39; above them the record's padding, kept
+    int32_t hold_l, hold_r;
+    bool any_ok;                                    // a well-formed subframe since the call began: what `state` is written from
+};
+constexpr void rx_lose(RxRegs &r) { r.sync = 0; r.rate = 0; }
+constexpr int32_t rx_side(RxRegs &r, bool ok, uint32_t data, int32_t &hold) {
+    // (sums and selects, no branch: the counters stay in registers on the device)
+    const bool good = ok && !rx_v(data);
+    r.coding += ok ? 0u : 1u;
+    r.parity += ok && rx_parity_fails(data) ? 1u : 0u;      // counted only: the sample passes
+    r.held += good ? 0u : 1u;
+    hold = good ? rx_sample(data) : hold;
+    return hold;
+}
+constexpr void rx_frame(RxRegs &r, uint32_t l0, uint32_t h0, uint32_t l1, uint32_t h1, int32_t &out_l, int32_t &out_r) {
+    const bool ok_l = rx_left_ok(l0, h0), ok_r = rx_right_ok(l1, h1);
+    const uint32_t data_l = rx_data(l0, h0), data_r = rx_data(l1, h1);
+    r.any_ok = r.any_ok || ok_l || ok_r;
+    // 1. sync
+    if (ok_l && (l0 & 0xffu) == kPreZ) {
+        if (r.sync != 1) r.parity = 0;      // a lock or a re-lock
+        r.sync = 1;
+    } else if (!ok_l || r.sync == 1) rx_lose(r);      // malformed, or X where Z is expected
+    if (!ok_r) rx_lose(r);
+    // 2. each side
+    out_l = rx_side(r, ok_l, data_l, r.hold_l);
+    out_r = rx_side(r, ok_r, data_r, r.hold_r);
+    // 3. the channel status
+    if (r.sync) {
+        const uint32_t p = r.sync - 1;
+        if (p < kRxStatusBits) r.cbits = (r.cbits & ~(1ull << p)) | (uint64_t)rx_c(data_l) << p;
+        if (p == 31) r.rate = rx_rate((uint32_t)(r.cbits >> 24) & 0xffu);
+        r.sync = 1 + (p + 1) % kRxBlock;
+    }
+}
+
 // ---- the sync machine over up to 64 consecutive frames given as bit masks, bit i = frame i (the kernel's ballots; constexpr: the kernel
 // and tests/spdifrx_driver.cpp run this one text).  Only three kinds of frame change the machine by more than a step: a left Z, a malformed
 // subframe, and a left X where the position is 0; between two of them the position advances by one per frame.  So the walk goes from event

@@ -37,6 +37,10 @@ SRC_SPDIF, SRC_PCM16, SRC_PCM24 = 1, 16, 24
 # dspi_spdif_rx (include/dspi.h): 40 bytes, the first 20 the answer to REQ_GET_SPDIF_IN_STATUS
 SPDIF_RX = np.dtype([("state", "<u4"), ("sample_rate", "<u4"), ("parity_err_count", "<u4"), ("c_bits", "u1", (5,)), ("pad_", "u1", (3,)), ("hold", "<i4", (2,)),
                      ("sync", "<u4"), ("held", "<u4"), ("coding_errors", "<u4")])
+# dspi_link / dspi_wire_view (include/dspi.h, chained devices): a line of a producer's wire buffer and the buffer itself
+LINK_NONE, LINK_SPDIF, LINK_I2S = 0, 1, 2
+LINK = np.dtype([("line", "<u4"), ("kind", "<u4")])
+WIRE_VIEW = np.dtype([("wire", "<u8"), ("n_streams", "<u4"), ("n_pairs", "<u4"), ("tile_streams", "<u4"), ("n_frames", "<u4"), ("producer", "<u8")])
 E_INVAL = -10
 E_NODEVICE = -11
 E_UNSUPPORTED = -14
@@ -171,6 +175,11 @@ def lib() -> C.CDLL:
         L.dspi_process_sources.argtypes = [vp, vp, vp, u32, u32, C.POINTER(_Out), vp, vp, u32]
         L.dspi_spdif_decode.argtypes = [vp, vp, u32, u32, vp, vp, u32]
         L.dspi_debug_sources_intake.argtypes = [vp, vp, vp, u32, u32, vp]
+    if hasattr(L, "dspi_process_linked"):      # (ABI 8 + chained devices: detected by symbol; with it dspi_wire_decode, dspi_wire_view_of, dspi_link_kinds)
+        L.dspi_wire_view_of.argtypes = [vp, vp, u32, u32, vp]
+        L.dspi_link_kinds.argtypes = [vp, vp, u32]
+        L.dspi_wire_decode.argtypes = [vp, vp, vp, u32, vp, vp, u32]
+        L.dspi_process_linked.argtypes = [vp, vp, vp, u32, u32, C.POINTER(_Out), vp, vp, u32]
     _lib = L
     return L
 
@@ -705,6 +714,57 @@ class Dspi:
         """dspi_debug_sources_intake: the intake and the receiver of process_sources_device alone, into the context's scratch; asynchronous, see sync()."""
         d = self._depths(sources)
         self._ck(self.L.dspi_debug_sources_intake(self.h, in_ptr, d.ctypes.data, n_blocks, block_len, rx_ptr or None), "debug_sources_intake")
+
+    # ---- chained devices (include/dspi.h: dspi_wire_decode / dspi_process_linked) ----
+    def wire_view_of(self, wire_ptr: int, n_frames: int, tiled: bool = False) -> np.ndarray:
+        """dspi_wire_view_of: a WIRE_VIEW record (0-d array) of a buffer THIS context wrote, or will write, in the wire layout (tiled: the tiled
+        one); producer = this context.  Bookkeeping only: works on host-only contexts, wire_ptr may be a host or a device address."""
+        v = np.zeros((), dtype=WIRE_VIEW)
+        self._ck(self.L.dspi_wire_view_of(self.h, wire_ptr or None, n_frames, OUT_TILED if tiled else 0, v.ctypes.data), "wire_view_of")
+        return v
+
+    def link_kinds(self, lines) -> np.ndarray:
+        """dspi_link_kinds: LINK [n] naming `lines` (stream * pairs + pair of THIS context), each kind from its stream's current output type."""
+        links = np.zeros(len(lines), dtype=LINK)
+        links["line"] = lines
+        self._ck(self.L.dspi_link_kinds(self.h, links.ctypes.data, len(links)), "link_kinds")
+        return links
+
+    @staticmethod
+    def _links(links) -> np.ndarray:
+        links = np.ascontiguousarray(links)
+        assert links.dtype == LINK and links.ndim == 1, (links.dtype, links.shape)
+        return links
+
+    def wire_decode_host(self, view: np.ndarray, wire: np.ndarray, links, rx: np.ndarray | None, pairs: np.ndarray | None = None) -> np.ndarray:
+        """dspi_wire_decode on host arrays: `wire` = the buffer `view` describes (its address is put into a copy of the view), links LINK [n],
+        rx SPDIF_RX [n] (updated in place; may be None without an S/PDIF link) -> pairs int32 [n][F][2] (given: only the links' entries are written)."""
+        links = self._links(links)
+        wire = np.ascontiguousarray(wire, dtype=np.uint32)
+        v = view.copy(); v["wire"] = wire.ctypes.data
+        F = int(v["n_frames"])
+        if rx is not None: assert rx.dtype == SPDIF_RX and rx.flags.c_contiguous and rx.size == len(links), (rx.dtype, rx.shape)
+        if pairs is None: pairs = np.zeros((len(links), F, 2), dtype=np.int32)
+        assert pairs.dtype == np.int32 and pairs.flags.c_contiguous and pairs.shape == (len(links), F, 2), pairs.shape
+        self._ck(self.L.dspi_wire_decode(self.h, v.ctypes.data, links.ctypes.data, len(links), rx.ctypes.data if rx is not None else None, pairs.ctypes.data, 0), "wire_decode")
+        return pairs
+
+    def wire_decode_device(self, view: np.ndarray, links, rx_ptr: int, pairs_ptr: int):
+        """dspi_wire_decode on device pointers (view["wire"], rx and pairs 16-byte aligned; the links stay a host array); asynchronous, see sync()."""
+        links = self._links(links)
+        self._ck(self.L.dspi_wire_decode(self.h, view.ctypes.data, links.ctypes.data, len(links), rx_ptr or None, pairs_ptr, MEM_DEVICE), "wire_decode")
+
+    def process_linked_device(self, view: np.ndarray, links, n_blocks: int, block_len: int, rx_ptr: int = 0, pairs_ptr: int = 0, sub_ptr: int = 0, peaks_ptr: int = 0,
+                              words_ptr: int = 0, tiled: bool = False, enabled_only: bool = False, spdif: bool = False, wire: bool = False, clip_ptr: int = 0):
+        """dspi_process_linked on raw device pointers: stream s of this context takes its frames from links[s] (LINK [n_streams], a host array) of
+        the device buffer `view` describes; rx: SPDIF_RX [n_streams] in device memory.  With view["producer"] set the call waits for the
+        producer's stream itself.  Asynchronous, see sync()."""
+        links = self._links(links)
+        assert len(links) == self.n_streams, (len(links), self.n_streams)
+        out = _Out(pairs_ptr or None, sub_ptr or None, peaks_ptr or None, clip_ptr or None)
+        self._ck(self.L.dspi_process_linked(self.h, view.ctypes.data, links.ctypes.data, n_blocks, block_len, C.byref(out), words_ptr or None, rx_ptr or None,
+                                            MEM_DEVICE | (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_SPDIF if spdif else 0) | (OUT_WIRE if wire else 0) |
+                                            (OUT_CLIP_FLAGS if clip_ptr else 0)), "process_linked")
 
     def pdm_restart(self, stream: int = ALL):
         self._ck(self.L.dspi_pdm_restart(self.h, stream), "pdm_restart")

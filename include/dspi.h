@@ -80,7 +80,8 @@ extern "C" {
                               * 8 + wire words per device: detect by symbol (dspi_process_wire; with it dspi_wire_encode; additions only);
                               * 8 + a stream's own flash: detect by symbol (dspi_device_flash; with it dspi_flash_read, dspi_flash_write, DSPI_BOOT_STREAMS_OWN_FLASH; additions only);
                               * 8 + wire words on tiled and mixed-depth contexts: detect by symbol (dspi_process_devices; with it dspi_wire_encode_tiled; additions only);
-                              * 8 + S/PDIF input: detect by symbol (dspi_process_sources; with it dspi_spdif_decode, dspi_sources_bytes, dspi_spdif_rx, DSPI_SRC_*, DSPI_OUT_WIRE; additions only) */
+                              * 8 + S/PDIF input: detect by symbol (dspi_process_sources; with it dspi_spdif_decode, dspi_sources_bytes, dspi_spdif_rx, DSPI_SRC_*, DSPI_OUT_WIRE; additions only);
+                              * 8 + chained devices: detect by symbol (dspi_process_linked; with it dspi_wire_decode, dspi_wire_view_of, dspi_link_kinds, dspi_wire_view, dspi_link, DSPI_LINK_*; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -969,7 +970,7 @@ int dspi_wire_encode_tiled(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frame
  * At the end of the call state = 2 if sync != 0, else 1 if the call held any well-formed subframe, else 0.  Counters wrap.  A host-memory
  * record with sync > 192 is DSPI_E_INVAL; a device-memory one is read as 0.
  * Out of scope: lock timing and watchdogs, the mute during a source switch, TX clock tracking, running the chain at 88.2 / 176.4 / 192 kHz
- * (reported, not settable), applying the detected rate (the caller calls dspi_set_sample_rate), I2S input, a tiled input, receiver state
+ * (reported, not settable), applying the detected rate (the caller calls dspi_set_sample_rate), receiver state
  * held by the context, serving 0x80-0x82 inside dspi_vendor_* (INTEGRATION.md says how a caller answers them). */
 typedef struct dspi_spdif_rx {      /* 40 bytes; the first 20 are REQ_GET_SPDIF_IN_STATUS's answer */
     uint32_t state;                 /* 0 NO_SIGNAL, 1 ACQUIRING, 2 LOCKED: written at the end of every call */
@@ -1027,6 +1028,82 @@ int dspi_sources_bytes(const dspi_ctx *ctx, const uint8_t *sources, uint32_t n_b
                        uint64_t *total_bytes, uint64_t *offsets /* [n_streams + 1] or NULL */);
 int dspi_process_sources(dspi_ctx *ctx, const void *in, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len,
                          const dspi_out *out, uint32_t *pdm_words /* may be NULL */, dspi_spdif_rx *rx, uint32_t flags);
+/* ---- chained devices: input from another context's wire words ------------------------------------------------------------------------------ */
+/* A context's input may be another call's OUTPUT, read where it lies: a VIEW names a buffer some call wrote through out->pairs in THE WIRE LAYOUT
+ * (tile_streams == 0) or THE TILED WIRE LAYOUT (above), and a LINK names one line of it, pair p of producer stream s, and says which of the two
+ * word formats its region holds.  No copy, no gather in front of the call: dspi_process_devices(A, ...); dspi_process_linked(B, ...);
+ *
+ * THE WORDS OF A LINK.  L = the link's line, s = L / P, p = L % P, P = view->n_pairs, F = view->n_frames, R = view->tile_streams.
+ *   stream-major   the region starts at word (L * F) * 4.
+ *                  S/PDIF: frame f, word j (of {l, h} left, {l, h} right) is at + f * 4 + j.     I2S: frame f, side k is at + f * 2 + k.
+ *   tiled          the region starts at word ((s / R * P + p) * F) * 4 * R, the column is c = s % R.
+ *                  S/PDIF: word (f * 4 + j) * R + c.                                            I2S: word (k * F + f) * R + c.
+ * These are the two layouts above, read backwards.  An I2S word decodes to (int32_t)word >> 8, an arithmetic shift; the low byte is ignored;
+ * no record is read or written.  An S/PDIF line goes through THE RECEIVER (S/PDIF input, above), unchanged, with the caller's record for that
+ * link.  A decoded sample enters the chain as the 24-bit USB sample of the same value.
+ *
+ * dspi_wire_view_of fills *view from a producer context: n_streams, n_pairs, tile_streams (0, or dspi_tile_streams with flags = DSPI_OUT_TILED; any
+ * other flag is DSPI_E_INVAL), n_frames and wire as given, producer = the context itself.  dspi_link_kinds sets links[i].kind for i < n from the
+ * producer's CURRENT output_types[] of the line links[i].line: DSPI_LINK_I2S where the slot's type is 1, else DSPI_LINK_SPDIF (a line that is
+ * not the producer's: DSPI_E_INVAL, nothing written).  Both are bookkeeping only and work on host-only contexts.
+ *
+ * dspi_wire_decode is the stateless inverse of dspi_wire_encode / dspi_wire_encode_tiled.
+ *   links     dspi_link [n_links], HOST memory always.  An entry of kind DSPI_LINK_NONE is skipped: its pair words and its record are untouched.
+ *             Several links may name one line (a splitter); each has its own record.
+ *   rx        dspi_spdif_rx [n_links], in/out; required only if a link is S/PDIF.  Only S/PDIF links' entries are read or written.
+ *   pairs     int32 [n_links][F][2]
+ * view->wire, rx and pairs in host memory, or in device memory with DSPI_MEM_DEVICE, the only flag (asynchronous on the context's stream then;
+ * view->producer is not looked at: the caller orders the work).  DSPI_E_INVAL, in this order: a NULL ctx, view, links or pairs or n_links == 0;
+ * another flag; the view (as in dspi_process_linked, n_frames != 0 in place of its F); a link whose kind is none of the three or, unless its
+ * kind is NONE, whose line >= n_streams * n_pairs; a NULL rx where a link is S/PDIF; with DSPI_MEM_DEVICE an rx or pairs that is not 16-byte
+ * aligned; a host record of an S/PDIF link with sync > 192; then DSPI_E_NODEVICE on a host-only context.  A refused call writes nothing.
+ *
+ * dspi_process_linked is dspi_process_sources in which stream s' of ctx takes its F = n_blocks * block_len frames from links[s'] in *view
+ * instead of from a run in `in`.
+ *   flags     DSPI_MEM_DEVICE is REQUIRED: the view, rx and everything in *out are device memory (a chained context's input is another
+ *             context's output buffer).  Beyond that exactly the flags of dspi_process_sources, DSPI_OUT_WIRE and DSPI_OUT_TILED included, so
+ *             ctx can be someone else's producer.
+ *   links     dspi_link [dspi_num_streams], HOST memory always.  Every ACTIVE stream needs a link of kind S/PDIF or I2S; a paused stream's entry
+ *             is ignored: nothing of a paused stream is read or written, and its record is untouched.
+ *   rx        dspi_spdif_rx [dspi_num_streams], required if an active stream's link is S/PDIF; only those entries are read or written (a
+ *             record with sync > 192 is read as 0).
+ *   view      view->n_frames == F; view->wire must not overlap out->pairs of the same call.
+ * Outputs, pauses, block positions, PDM bookkeeping and clip flags behave as in dspi_process_sources.  No preamp refusal: no stream is 16-bit.
+ * No state is added to the context: records and links are the caller's; snapshots, moves, migrations and resizes know nothing of them.
+ * REFUSALS, in this order (a refused call writes nothing):
+ *   1. DSPI_E_INVAL   a NULL ctx, view, links or out
+ *   2. DSPI_E_INVAL   DSPI_MEM_DEVICE missing; then dspi_process_sources' own flag rule
+ *   3. DSPI_E_INVAL   n_blocks / block_len as dspi_process refuses them
+ *   4. DSPI_E_INVAL   the view: a NULL wire or one that is not 16-byte aligned, n_pairs not 2 or 4, tile_streams not 0 / 64 / 128,
+ *                     n_streams == 0, n_frames != F, a size that overflows 64 bits
+ *   5. DSPI_E_INVAL   a link of an active stream whose kind is neither S/PDIF nor I2S, or whose line >= n_streams * n_pairs
+ *   6. DSPI_E_INVAL   rx NULL, or not 4-byte aligned, where an active stream's link is S/PDIF
+ *   7. DSPI_E_INVAL   view->producer on another HIP device than ctx (a host-only producer has none)
+ *   8. DSPI_E_NODEVICE on a host-only context
+ * ORDERING.  With view->producer set and != ctx the call records an event on the producer's HIP stream and makes its own stream wait for it
+ * before the first kernel that reads view->wire: a chain needs no dspi_sync between the producer's call and this one.  The event is created
+ * once per context and destroyed with it.  With producer == ctx, or NULL, nothing is recorded: the stream is the same, or the caller orders
+ * the work itself.
+ * The ABI stays 8: detect by symbol (dspi_process_linked; with it dspi_wire_decode, dspi_wire_view_of, dspi_link_kinds; additions only). */
+#define DSPI_LINK_NONE  0u
+#define DSPI_LINK_SPDIF 1u      /* == DSPI_SRC_SPDIF: the region holds subframes */
+#define DSPI_LINK_I2S   2u      /* the region holds I2S slot words, word << 8, in its first half */
+typedef struct dspi_wire_view {     /* a buffer some call wrote through out->pairs in a wire layout */
+    const uint32_t *wire;           /* THE WIRE LAYOUT (tile_streams == 0) or THE TILED WIRE LAYOUT; 16-byte aligned when in device memory */
+    uint32_t n_streams;             /* the producer's dspi_num_streams at that call */
+    uint32_t n_pairs;               /* its dspi_num_pairs: 4 / 2 */
+    uint32_t tile_streams;          /* 0, or its dspi_tile_streams: 128 / 64 */
+    uint32_t n_frames;              /* F of that call */
+    dspi_ctx *producer;             /* NULL, or the context on whose HIP stream `wire` is being written: ORDERING above */
+} dspi_wire_view;
+typedef struct dspi_link { uint32_t line; uint32_t kind; } dspi_link;   /* line = producer stream * n_pairs + pair */
+int dspi_wire_view_of(const dspi_ctx *producer, const uint32_t *wire, uint32_t n_frames, uint32_t flags /* 0 or DSPI_OUT_TILED */, dspi_wire_view *view);
+int dspi_link_kinds(const dspi_ctx *producer, dspi_link *links, uint32_t n);
+int dspi_wire_decode(dspi_ctx *ctx, const dspi_wire_view *view, const dspi_link *links, uint32_t n_links,
+                     dspi_spdif_rx *rx, int32_t *pairs, uint32_t flags);
+int dspi_process_linked(dspi_ctx *ctx, const dspi_wire_view *view, const dspi_link *links /* [dspi_num_streams], HOST memory always */,
+                        uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words /* may be NULL */,
+                        dspi_spdif_rx *rx, uint32_t flags);
 int dspi_i2s_encode(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, uint32_t pair_mask, uint32_t *words, uint32_t flags);
 /* the HIP stream (hipStream_t) the context launches on, for event timing by the caller */
 void *dspi_hip_stream(dspi_ctx *ctx);
