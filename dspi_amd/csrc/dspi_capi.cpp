@@ -37,6 +37,7 @@
 #include "dspi_link.h"
 #include "dspi_migrate.h"
 #include "dspi_move.h"
+#include "dspi_patch.h"
 #include "dspi_pdmfade.h"
 #include "dspi_pdmlife.h"
 #include "dspi_plan.h"
@@ -2137,14 +2138,61 @@ static int launch_links(dspi_ctx *c, const LinkIn &lk, uint64_t frames) {
     return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("link receiver launch: ") + hipGetErrorString(e));
 }
 
+// ---- dspi_process_patched (dspi_patch.h): the call's plan ----
+// The union of the two: planned as the 24-bit call it becomes, d_mixed filled by the intake and the receiver from `in`, by the link receivers
+// from the stream-major views and by the patch receiver from every tiled view.  The device route only.
+struct PatchIn {
+    const void *in;             // device memory, or null when no active stream has a run
+    const WireView *views;      // [n_views], validated where an active LINK stream names them
+    const dspi_wire_view *cviews;      // the same, for the producers
+    uint32_t n_views;
+    SpdifRx *rx;                // [n] in device memory, or null when nothing served is S/PDIF
+    const PatchPlan *plan;
+};
+// the front end of a patched call, into d_mixed: at most one intake launch, one receiver launch over `in`, two launches per stream-major view
+// and one for all tiled views; each view's kernels behind its producer's work where that runs on another stream.  The plan's table stands in
+// the mixed path's table, which then holds no mixed call's layout any more.
+static int launch_patched(dspi_ctx *c, const PatchIn &pi, uint64_t frames) {
+    const PatchPlan &p = *pi.plan;
+    c->mixed_frames = 0;
+    if (int rc = upload_via_move_area(c, c->d_mixed_tab, "hipHostMalloc failed (patch table)", {{p.table.data(), p.table.size() * 8}})) return rc;
+    const uint64_t *const tab = c->d_mixed_tab;
+    const uint8_t *const in_kinds = reinterpret_cast<const uint8_t *>(tab + p.in_kinds);
+    hipError_t e = hipSuccess;
+    if (p.any_pcm) e = launch_intake(pi.in, tab + p.in_offsets, in_kinds, reinterpret_cast<const uint32_t *>(tab + p.pcm_mask), c->d_mixed, frames, 0u, c->n_streams, c->hs);
+    if (e == hipSuccess && p.any_spdif_in) e = launch_spdifrx(true, pi.in, tab + p.in_offsets, in_kinds, nullptr, pi.rx, c->d_mixed, frames, 0u, c->n_streams, c->hs);
+    if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string("intake launch: ") + hipGetErrorString(e));
+    // one wait per DISTINCT producer that an active LINK stream's view names, all of them before the first kernel that reads a view
+    for (uint32_t v = 0; v < pi.n_views; v++) {
+        dspi_ctx *const prod = p.view[v].used ? pi.cviews[v].producer : nullptr;
+        if (!prod || prod == c || prod->device == DSPI_DEVICE_NONE) continue;
+        bool seen = false;
+        for (uint32_t u = 0; u < v; u++) seen = seen || (p.view[u].used && pi.cviews[u].producer == prod);
+        if (seen) continue;
+        if (!c->ev_link) HIPCK(c, hipEventCreateWithFlags(&c->ev_link, hipEventDisableTiming));
+        HIPCK(c, hipEventRecord(c->ev_link, prod->hs));
+        HIPCK(c, hipStreamWaitEvent(c->hs, c->ev_link, 0));
+    }
+    for (uint32_t v = 0; v < pi.n_views && e == hipSuccess; v++) {
+        const PatchPlan::View &pv = p.view[v];
+        if (!pv.used || pi.views[v].tile_streams) continue;
+        e = launch_linkrx(true, pi.views[v].wire, tab + pv.links, tab + pv.offsets, reinterpret_cast<const uint8_t *>(tab + pv.kinds), nullptr, pi.rx, c->d_mixed, (uint32_t)frames,
+                          pi.views[v].n_pairs, 0u, c->n_streams, pv.any_spdif, pv.any_i2s, c->hs);
+    }
+    if (e == hipSuccess && p.any_tiled) e = launch_patchrx(tab + p.cols, pi.rx, c->d_mixed, (uint32_t)frames, c->n_streams, p.tiled_spdif, c->hs);
+    return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("patch receiver launch: ") + hipGetErrorString(e));
+}
+
 // ---- device buffers: the caller's own, asynchronous on the context's stream ----
-static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, const PdmCall *pc, const MixedIn *mx, const LinkIn *lk = nullptr) {
+static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, const PdmCall *pc, const MixedIn *mx, const LinkIn *lk = nullptr,
+                          const PatchIn *pt = nullptr) {
     a.pcm = pcm_in; a.pairs = out->pairs; a.sub = out->sub; a.peaks = out->peaks;
     int rc = 0;
     if (pc && !out->sub) { if ((rc = pdm_sub_scratch(c, L))) return rc; a.sub = c->d_sub; }
     if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, L.two_pass_bytes))) return rc;
     if (mx) { if ((rc = launch_intake_streams(c, L.frames, pcm_in, c->d_mixed, 0, c->n_streams, mx->rx))) return rc; a.pcm = c->d_mixed; }
     if (lk) { if ((rc = launch_links(c, *lk, L.frames))) return rc; a.pcm = c->d_mixed; }
+    if (pt) { if ((rc = launch_patched(c, *pt, L.frames))) return rc; a.pcm = c->d_mixed; }
     if ((rc = launch_rows(c, a, L, 0, c->n_wg))) return rc;
     if (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, pc->words, 0, c->n_streams))) return rc;
     return clip_out ? gather_clip(c, clip_out) : DSPI_OK;
@@ -2411,7 +2459,7 @@ static bool wire_slots_in_play(const dspi_ctx *c) {
 // wire: dspi_process_wire and dspi_process_devices (flags carry DSPI_OUT_SPDIF, which the wire layout implies): out->pairs in the wire layout;
 // with DSPI_OUT_TILED beside it (dspi_process_devices alone; the callers have applied their own flag rule, dspi_wire.h) in the tiled wire layout
 static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags,
-                        const MixedIn *mx = nullptr, bool wire = false, const LinkIn *lk = nullptr) {
+                        const MixedIn *mx = nullptr, bool wire = false, const LinkIn *lk = nullptr, const PatchIn *pt = nullptr) {
     if (!c || !pcm_in || !out) return DSPI_E_INVAL;
     int rc = check_flag_bits(c, flags);
     if (rc) return rc;
@@ -2444,6 +2492,7 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     if (mx && L.mem == CallMem::Device && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed, L.pcm.bytes))) return rc;
     if (mx && L.mem == CallMem::Staged && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed_up, (size_t)mx->offsets.back()))) return rc;
     if (lk && (L.mem != CallMem::Device || (rc = ensure(c, c->d_mixed, L.pcm.bytes)))) return rc ? rc : fail(c, DSPI_E_INVAL, "dspi_process_linked: device memory only");
+    if (pt && (L.mem != CallMem::Device || (rc = ensure(c, c->d_mixed, L.pcm.bytes)))) return rc ? rc : fail(c, DSPI_E_INVAL, "dspi_process_patched: device memory only");
 
     KArgs a{};
     a.img = c->d_images; a.stream_image = c->d_stream_image; a.vals = c->d_vals;
@@ -2463,7 +2512,7 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     }
 
     switch (L.mem) {
-    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out, pc, mx, lk); break;
+    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out, pc, mx, lk, pt); break;
     case CallMem::Direct: rc = process_direct(c, L, a, pcm_in, out, clip_out, flags, call_t0, pc, mx); break;
     case CallMem::Staged: rc = process_staged(c, L, a, pcm_in, out, clip_out, flags, pc, mx); break;
     }
@@ -2750,6 +2799,80 @@ int dspi_process_linked(dspi_ctx *c, const dspi_wire_view *view, const dspi_link
     return process_call(c, v.wire, 24, n_blocks, block_len, out, pdm_words, wire ? flags | DSPI_OUT_SPDIF : flags, nullptr, wire, &in);
 }
 
+// ---- the patch bay (dspi_patch.h: the layout, the refusals and the plan; dspi_patchrx.hip: the tiled receiver) ----
+static_assert(sizeof(dspi_patch) == sizeof(Patch) && offsetof(dspi_patch, line) == offsetof(Patch, line) && offsetof(dspi_patch, kind) == offsetof(Patch, kind), "include/dspi.h and dspi_patch.h: one patch");
+static_assert(DSPI_SRC_LINK == kSrcLink && DSPI_MAX_VIEWS == kPatchMaxViews, "include/dspi.h and dspi_patch.h: one set of sources");
+
+int dspi_patched_bytes(const dspi_ctx *c, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len, uint64_t *total_bytes, uint64_t *offsets) {
+    if (!c || !sources) return DSPI_E_INVAL;
+    dspi_ctx *const m = const_cast<dspi_ctx *>(c);
+    uint32_t at = 0;
+    if (const char *why = patch_sources_why(sources, c->n_streams, &at)) return fail(m, DSPI_E_INVAL, "dspi_patched_bytes: stream " + std::to_string(at) + ": " + why);
+    if (n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN) return fail(m, DSPI_E_INVAL, "dspi_patched_bytes: 1 <= block_len <= 192, n_blocks >= 1");
+    if (!patch_offsets(sources, c->n_streams, (uint64_t)n_blocks * block_len, total_bytes, offsets)) return fail(m, DSPI_E_INVAL, "dspi_patched_bytes: the buffer's size overflows");
+    return DSPI_OK;
+}
+
+// refusals 3 to 10 of dspi_process_patched, in their order (dspi_debug_patched_intake shares them); *rx_needed: an active stream is an S/PDIF run or link
+static int patched_check(dspi_ctx *c, const char *who, const void *in, const uint8_t *sources, const dspi_wire_view *views, uint32_t n_views, const dspi_patch *patches,
+                         uint32_t n_blocks, uint32_t block_len, const dspi_spdif_rx *rx, bool *rx_needed) {
+    const std::string w = std::string(who) + ": ";
+    const uint32_t n = c->n_streams;
+    const uint8_t *const act = host_activity(c);
+    const WireView *const vs = reinterpret_cast<const WireView *>(views);
+    const Patch *const ps = reinterpret_cast<const Patch *>(patches);
+    uint32_t at = 0;
+    if (n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN) return fail(c, DSPI_E_INVAL, w + "1 <= block_len <= 192, n_blocks >= 1");
+    const uint64_t F = (uint64_t)n_blocks * block_len;
+    if (const char *why = patch_sources_why(sources, n, &at)) return fail(c, DSPI_E_INVAL, w + "stream " + std::to_string(at) + ": " + why);
+    const bool any_link = patch_any(sources, n, act, kSrcLink);
+    if (any_link)
+        if (const char *why = patch_views_why(sources, n, act, vs, n_views, ps, F, &at)) return fail(c, DSPI_E_INVAL, w + why + " (view or stream " + std::to_string(at) + ")");
+    if (const char *why = patch_in_why(in, sources, n, act)) return fail(c, DSPI_E_INVAL, w + why);
+    if (const char *why = patch_rx_why(rx, sources, n, act, ps)) return fail(c, DSPI_E_INVAL, w + why);
+    *rx_needed = patch_needs_rx(sources, n, act, ps);
+    uint64_t out_bytes = 0;
+    if (!patch_offsets(sources, n, F, nullptr, nullptr) || __builtin_mul_overflow((uint64_t)n * kIntakeOutFrame, F, &out_bytes)) return fail(c, DSPI_E_INVAL, w + "the buffer's size overflows");
+    // the one case in which a 16-bit sample and its widened twin part ways (dspi_intake.h): refused, not approximated
+    if (c->flavor)
+        for (uint32_t s = 0; s < n; s++) {
+            if (sources[s] != 16 || (act && !act[s])) continue;
+            for (const float p : readable(c, (int32_t)s).preamp_linear) {
+                uint32_t bits; memcpy(&bits, &p, 4);
+                if (intake_preamp_breaks_widening(bits))
+                    return fail(c, DSPI_E_UNSUPPORTED, w + "stream " + std::to_string(s) + " takes 16-bit input with a preamp below 2^-103, where widening to 24 bit is not exact");
+            }
+        }
+    if (any_link)
+        for (uint32_t s = 0; s < n; s++) {
+            if (sources[s] != kSrcLink || (act && !act[s])) continue;
+            const dspi_ctx *const prod = views[ps[s].view].producer;
+            if (prod && prod->device != DSPI_DEVICE_NONE && prod->device != c->device) return fail(c, DSPI_E_INVAL, w + "the producer of view " + std::to_string(ps[s].view) + " is on another HIP device");
+        }
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    return 0;
+}
+
+int dspi_process_patched(dspi_ctx *c, const void *in, const uint8_t *sources, const dspi_wire_view *views, uint32_t n_views, const dspi_patch *patches, uint32_t n_blocks, uint32_t block_len,
+                         const dspi_out *out, uint32_t *pdm_words, dspi_spdif_rx *rx, uint32_t flags) {
+    if (!c || !sources || !out) return DSPI_E_INVAL;
+    // 2. the flags
+    if (!(flags & DSPI_MEM_DEVICE)) return fail(c, DSPI_E_INVAL, "dspi_process_patched: DSPI_MEM_DEVICE is required");
+    const bool wire = flags & DSPI_OUT_WIRE;
+    flags &= ~DSPI_OUT_WIRE;
+    if (wire && !devices_process_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_process_patched: with DSPI_OUT_WIRE the flags are DSPI_MEM_DEVICE, DSPI_OUT_TILED, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
+    int rc;
+    if ((rc = check_flag_bits(c, flags)) || (!wire && (rc = check_flag_combinations(c, flags)))) return rc;
+    // 3. to 11.
+    bool rx_needed = false;
+    if ((rc = patched_check(c, "dspi_process_patched", in, sources, views, n_views, patches, n_blocks, block_len, rx, &rx_needed))) return rc;
+    PatchPlan plan;
+    patch_plan(sources, c->n_streams, host_activity(c), reinterpret_cast<const WireView *>(views), n_views, reinterpret_cast<const Patch *>(patches), (uint64_t)n_blocks * block_len, plan);
+    const PatchIn pi{in, reinterpret_cast<const WireView *>(views), views, n_views, rx_needed ? reinterpret_cast<SpdifRx *>(rx) : nullptr, &plan};
+    // (process_call wants an input pointer; a call of LINK streams has none, and nothing reads it: the chain reads d_mixed)
+    return process_call(c, in ? in : static_cast<const void *>(out), 24, n_blocks, block_len, out, pdm_words, wire ? flags | DSPI_OUT_SPDIF : flags, nullptr, wire, nullptr, &pi);
+}
+
 int dspi_wire_encode_tiled(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos, uint32_t *wire, uint32_t flags) {
     if (!c || !pairs || !wire || !block_pos || n_frames == 0) return DSPI_E_INVAL;
     if (!wire_encode_tiled_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_wire_encode_tiled: the only flag is DSPI_MEM_DEVICE");
@@ -2817,6 +2940,22 @@ int dspi_debug_sources_intake(dspi_ctx *c, const void *in, const uint8_t *source
     if (c->n_paused && (rc = upload_activity(c))) return rc;
     if ((rc = intake_prepare(c, mx, frames, c->d_mixed, (size_t)out_bytes))) return rc;
     return launch_intake_streams(c, frames, in, c->d_mixed, 0, c->n_streams, mx.rx);
+}
+
+// ... of a dspi_process_patched call: the intake, the receiver over `in`, the link receivers and the patch receiver (tools/bench_patched.py)
+int dspi_debug_patched_intake(dspi_ctx *c, const void *in, const uint8_t *sources, const dspi_wire_view *views, uint32_t n_views, const dspi_patch *patches, uint32_t n_blocks, uint32_t block_len,
+                              dspi_spdif_rx *rx) {
+    if (!c || !sources) return DSPI_E_INVAL;
+    bool rx_needed = false;
+    int rc = patched_check(c, "dspi_debug_patched_intake", in, sources, views, n_views, patches, n_blocks, block_len, rx, &rx_needed);
+    if (rc) return rc;
+    const uint64_t frames = (uint64_t)n_blocks * block_len;
+    HIPCK(c, hipSetDevice(c->device));
+    if ((rc = ensure(c, c->d_mixed, (size_t)(c->n_streams * kIntakeOutFrame * frames)))) return rc;
+    PatchPlan plan;
+    patch_plan(sources, c->n_streams, host_activity(c), reinterpret_cast<const WireView *>(views), n_views, reinterpret_cast<const Patch *>(patches), frames, plan);
+    const PatchIn pi{in, reinterpret_cast<const WireView *>(views), views, n_views, rx_needed ? reinterpret_cast<SpdifRx *>(rx) : nullptr, &plan};
+    return launch_patched(c, pi, frames);
 }
 
 int dspi_pdm_running(dspi_ctx *c, uint32_t first, uint32_t count, const uint8_t *set, uint8_t *get) {

@@ -173,4 +173,10 @@ hipError_t launch_spdifrx(bool packed, const void *src, const uint64_t *offsets,
 hipError_t launch_linkrx(bool packed, const uint32_t *wire, const void *links, const uint64_t *offsets, const uint8_t *kinds, const uint32_t *active, void *rx, void *dst,
                          uint32_t frames, uint32_t n_pairs, uint32_t row, uint32_t count, bool any_spdif, bool any_i2s, hipStream_t stream);
 
+// ---- the tiled receiver of dspi_process_patched (dspi_patch.h: the plan; dspi_patchrx.hip: the kernel) ----
+// Destinations [0, count): destination i takes cols[i] (dspi::PatchCol [count], device memory, 16-byte aligned: the column of its line in whichever
+// tiled view, resolved by the host) through its record rx[i] (S/PDIF patches only) into dst + 6 frames i, packed 24 bit.  A destination whose
+// kind is kLinkNone is neither read nor written.  any_spdif: what the patches hold, as the host knows it.
+hipError_t launch_patchrx(const void *cols, void *rx, void *dst, uint32_t frames, uint32_t count, bool any_spdif, hipStream_t stream);
+
 }  // namespace dspi

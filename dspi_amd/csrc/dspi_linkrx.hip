@@ -4,7 +4,7 @@
 // nothing, its record included.
 //
 //   tiled view          one LANE per destination, 64 destinations per workgroup (one wave), the kind per lane — dspi_wire_tiled.hip read
-//                       backwards.  A lane walks its link's column frame by frame.  An S/PDIF lane carries its record in registers, runs
+//                       backwards.  A lane walks its link's column frame by frame (dspi_colwalk.h: the walk, shared with dspi_patchrx.hip).  An S/PDIF lane carries its record in registers, runs
 //                       rx_frame (dspi_spdifrx.h, the sequential rule itself) per frame and writes the record back once; an I2S lane has
 //                       none.  The row loads of a wave coalesce where neighbouring destinations link neighbouring columns of one region;
 //                       any other map is as correct and slower.  At 65 536 destinations this is one wave per SIMD, so a lane keeps a GROUP
@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dspi_colwalk.h"
 #include "dspi_intake.h"
 #include "dspi_kernels.h"
 #include "dspi_link.h"
@@ -24,9 +25,6 @@
 namespace dspi {
 
 namespace {
-
-constexpr uint32_t kLinkLanes = 64;
-constexpr uint32_t kGroup = 8;      // frames a lane requests at once: 32 (S/PDIF) or 16 (I2S) row loads in flight while it walks the group before
 
 struct LinkArgs {
     const uint32_t *wire;
@@ -40,87 +38,13 @@ struct LinkArgs {
 __device__ inline bool served(const LinkArgs &a, uint32_t i) { return !a.active || (a.active[i >> 5] >> (i & 31u) & 1u); }
 
 template <bool kPacked>
-__device__ inline void put(void *dst, uint32_t i, uint32_t frames, uint64_t f, int32_t l, int32_t r) {
-    if (kPacked) {
-        uint16_t *const d = reinterpret_cast<uint16_t *>(static_cast<uint8_t *>(dst) + (uint64_t)i * kIntakeOutFrame * frames) + 3u * f;
-        d[0] = (uint16_t)l;
-        d[1] = (uint16_t)(((uint32_t)l >> 16 & 0xffu) | ((uint32_t)r & 0xffu) << 8);
-        d[2] = (uint16_t)((uint32_t)r >> 8);
-    } else {
-        reinterpret_cast<int2 *>(dst)[(uint64_t)i * frames + f] = make_int2(l, r);
-    }
-}
-
-// the row loads of the kGroup frames from `base` of a column, all of them inside the line (w: registers, every index a constant)
-__device__ inline void load_spdif(uint32_t (&w)[kGroup][4], const uint32_t *col, uint64_t base, uint32_t row) {
-#pragma unroll
-    for (uint32_t g = 0; g < kGroup; g++)
-#pragma unroll
-        for (uint32_t j = 0; j < 4; j++) w[g][j] = col[link_spdif_word_tiled(base + g, j, row, 0u)];
-}
-__device__ inline void load_i2s(uint32_t (&w)[kGroup][2], const uint32_t *col, uint64_t base, uint32_t frames, uint32_t row) {
-#pragma unroll
-    for (uint32_t g = 0; g < kGroup; g++)
-#pragma unroll
-        for (uint32_t side = 0; side < 2; side++) w[g][side] = col[link_i2s_word_tiled(base + g, side, frames, row, 0u)];
-}
-
-template <bool kPacked>
 __global__ __launch_bounds__(kLinkLanes) void linkrx_tiled_kernel(const LinkArgs a) {
     const uint32_t i = blockIdx.x * kLinkLanes + threadIdx.x;
     if (i >= a.count) return;
     const Link lk = a.links[i];
     if ((lk.kind != kLinkSpdif && lk.kind != kLinkI2s) || !served(a, i)) return;
-    const uint32_t F = a.frames, R = a.row;
-    const uint64_t whole = F - F % kGroup;      // the frames of whole groups; the rest, fewer than kGroup, go one by one
-    const uint32_t *const col = a.wire + link_region_tiled(lk.line, a.n_pairs, R, F) + link_column(lk.line, a.n_pairs, R);
-
-    if (lk.kind == kLinkSpdif) {
-        uint32_t *const rec = a.rx + (size_t)i * kRxWords;
-        RxRegs r{rec[7], rec[1], rec[2], rec[8], rec[9], (uint64_t)rec[4] << 32 | rec[3], (int32_t)rec[5], (int32_t)rec[6], false};
-        if (r.sync > kRxBlock) r.sync = 0;
-        uint32_t cur[kGroup][4], nxt[kGroup][4];
-        if (whole) load_spdif(cur, col, 0u, R);
-        for (uint64_t base = 0; base < whole; base += kGroup) {
-            const bool more = base + kGroup < whole;
-            if (more) load_spdif(nxt, col, base + kGroup, R);      // in flight during the walk
-#pragma unroll
-            for (uint32_t g = 0; g < kGroup; g++) {
-                int32_t out_l = 0, out_r = 0;
-                rx_frame(r, cur[g][0], cur[g][1], cur[g][2], cur[g][3], out_l, out_r);
-                put<kPacked>(a.dst, i, F, base + g, out_l, out_r);
-            }
-            if (more) {
-#pragma unroll
-                for (uint32_t g = 0; g < kGroup; g++)
-#pragma unroll
-                    for (uint32_t j = 0; j < 4; j++) cur[g][j] = nxt[g][j];
-            }
-        }
-        for (uint64_t f = whole; f < F; f++) {
-            int32_t out_l = 0, out_r = 0;
-            rx_frame(r, col[link_spdif_word_tiled(f, 0, R, 0u)], col[link_spdif_word_tiled(f, 1, R, 0u)], col[link_spdif_word_tiled(f, 2, R, 0u)], col[link_spdif_word_tiled(f, 3, R, 0u)], out_l, out_r);
-            put<kPacked>(a.dst, i, F, f, out_l, out_r);
-        }
-        rec[0] = r.sync ? 2u : r.any_ok ? 1u : 0u;
-        rec[1] = r.rate; rec[2] = r.parity; rec[3] = (uint32_t)r.cbits; rec[4] = (uint32_t)(r.cbits >> 32);
-        rec[5] = (uint32_t)r.hold_l; rec[6] = (uint32_t)r.hold_r; rec[7] = r.sync; rec[8] = r.held; rec[9] = r.coding;
-    } else {
-        uint32_t cur[kGroup][2], nxt[kGroup][2];
-        if (whole) load_i2s(cur, col, 0u, F, R);
-        for (uint64_t base = 0; base < whole; base += kGroup) {
-            const bool more = base + kGroup < whole;
-            if (more) load_i2s(nxt, col, base + kGroup, F, R);
-#pragma unroll
-            for (uint32_t g = 0; g < kGroup; g++) put<kPacked>(a.dst, i, F, base + g, link_i2s_sample(cur[g][0]), link_i2s_sample(cur[g][1]));
-            if (more) {
-#pragma unroll
-                for (uint32_t g = 0; g < kGroup; g++) { cur[g][0] = nxt[g][0]; cur[g][1] = nxt[g][1]; }
-            }
-        }
-        for (uint64_t f = whole; f < F; f++)
-            put<kPacked>(a.dst, i, F, f, link_i2s_sample(col[link_i2s_word_tiled(f, 0, F, R, 0u)]), link_i2s_sample(col[link_i2s_word_tiled(f, 1, F, R, 0u)]));
-    }
+    const uint32_t *const col = a.wire + link_region_tiled(lk.line, a.n_pairs, a.row, a.frames) + link_column(lk.line, a.n_pairs, a.row);
+    walk_column<kPacked>(col, lk.kind, a.row, a.frames, a.rx + (size_t)i * kRxWords, a.dst, i);
 }
 
 // a frame's two slot words are one 8-byte word of the region's first half

@@ -34,12 +34,15 @@ OUT_SPDIF = 0x10
 OUT_CLIP_FLAGS = 0x20
 OUT_WIRE = 0x40      # dspi_process_sources only
 SRC_SPDIF, SRC_PCM16, SRC_PCM24 = 1, 16, 24
+SRC_LINK = 2         # dspi_process_patched / dspi_patched_bytes only
+MAX_VIEWS = 8
 # dspi_spdif_rx (include/dspi.h): 40 bytes, the first 20 the answer to REQ_GET_SPDIF_IN_STATUS
 SPDIF_RX = np.dtype([("state", "<u4"), ("sample_rate", "<u4"), ("parity_err_count", "<u4"), ("c_bits", "u1", (5,)), ("pad_", "u1", (3,)), ("hold", "<i4", (2,)),
                      ("sync", "<u4"), ("held", "<u4"), ("coding_errors", "<u4")])
 # dspi_link / dspi_wire_view (include/dspi.h, chained devices): a line of a producer's wire buffer and the buffer itself
 LINK_NONE, LINK_SPDIF, LINK_I2S = 0, 1, 2
 LINK = np.dtype([("line", "<u4"), ("kind", "<u4")])
+PATCH = np.dtype([("view", "<u4"), ("line", "<u4"), ("kind", "<u4")])
 WIRE_VIEW = np.dtype([("wire", "<u8"), ("n_streams", "<u4"), ("n_pairs", "<u4"), ("tile_streams", "<u4"), ("n_frames", "<u4"), ("producer", "<u8")])
 E_INVAL = -10
 E_NODEVICE = -11
@@ -180,6 +183,10 @@ def lib() -> C.CDLL:
         L.dspi_link_kinds.argtypes = [vp, vp, u32]
         L.dspi_wire_decode.argtypes = [vp, vp, vp, u32, vp, vp, u32]
         L.dspi_process_linked.argtypes = [vp, vp, vp, u32, u32, C.POINTER(_Out), vp, vp, u32]
+    if hasattr(L, "dspi_process_patched"):      # (ABI 8 + the patch bay: detected by symbol; with it dspi_patched_bytes)
+        L.dspi_patched_bytes.argtypes = [vp, vp, u32, u32, C.POINTER(C.c_uint64), vp]
+        L.dspi_process_patched.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, C.POINTER(_Out), vp, vp, u32]
+        L.dspi_debug_patched_intake.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, vp]
     _lib = L
     return L
 
@@ -765,6 +772,42 @@ class Dspi:
         self._ck(self.L.dspi_process_linked(self.h, view.ctypes.data, links.ctypes.data, n_blocks, block_len, C.byref(out), words_ptr or None, rx_ptr or None,
                                             MEM_DEVICE | (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_SPDIF if spdif else 0) | (OUT_WIRE if wire else 0) |
                                             (OUT_CLIP_FLAGS if clip_ptr else 0)), "process_linked")
+
+    # ---- the patch bay (include/dspi.h: dspi_process_patched) ----
+    def patched_bytes(self, sources, n_blocks: int, block_len: int):
+        """dspi_patched_bytes: (total bytes, offsets uint64 [n_streams + 1]) of `in` of a dspi_process_patched call: sources_bytes in which a
+        SRC_LINK stream occupies no bytes.  Works on host-only contexts."""
+        d = self._depths(sources)
+        total, off = C.c_uint64(0), np.zeros(self.n_streams + 1, dtype=np.uint64)
+        self._ck(self.L.dspi_patched_bytes(self.h, d.ctypes.data, n_blocks, block_len, C.byref(total), off.ctypes.data), "patched_bytes")
+        return total.value, off
+
+    def _patch_args(self, sources, views, patches):
+        d = self._depths(sources)
+        views = np.ascontiguousarray(views).reshape(-1) if views is not None else None
+        patches = np.ascontiguousarray(patches) if patches is not None else None
+        if views is not None: assert views.dtype == WIRE_VIEW, views.dtype
+        if patches is not None: assert patches.dtype == PATCH and patches.shape == (self.n_streams,), (patches.dtype, patches.shape)
+        return d, views, patches
+
+    def process_patched_device(self, in_ptr: int, sources, views, patches, n_blocks: int, block_len: int, rx_ptr: int = 0, pairs_ptr: int = 0, sub_ptr: int = 0, peaks_ptr: int = 0,
+                               words_ptr: int = 0, tiled: bool = False, enabled_only: bool = False, spdif: bool = False, wire: bool = False, clip_ptr: int = 0):
+        """dspi_process_patched on raw device pointers: stream s takes its frames from its run of `in` (sources[s] = SRC_PCM16 / SRC_PCM24 /
+        SRC_SPDIF, laid out as patched_bytes says) or, sources[s] = SRC_LINK, from line patches[s]["line"] of views[patches[s]["view"]] (WIRE_VIEW
+        [n_views] and PATCH [n_streams], host arrays; both may be None without a LINK stream); rx: SPDIF_RX [n_streams] in device memory.  The
+        call waits for the views' producers itself.  Asynchronous, see sync()."""
+        d, views, patches = self._patch_args(sources, views, patches)
+        out = _Out(pairs_ptr or None, sub_ptr or None, peaks_ptr or None, clip_ptr or None)
+        self._ck(self.L.dspi_process_patched(self.h, in_ptr or None, d.ctypes.data, views.ctypes.data if views is not None else None, len(views) if views is not None else 0,
+                                             patches.ctypes.data if patches is not None else None, n_blocks, block_len, C.byref(out), words_ptr or None, rx_ptr or None,
+                                             MEM_DEVICE | (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_SPDIF if spdif else 0) | (OUT_WIRE if wire else 0) |
+                                             (OUT_CLIP_FLAGS if clip_ptr else 0)), "process_patched")
+
+    def debug_patched_intake(self, in_ptr: int, sources, views, patches, n_blocks: int, block_len: int, rx_ptr: int = 0):
+        """dspi_debug_patched_intake: everything process_patched_device runs in front of the chain, into the context's scratch; asynchronous, see sync()."""
+        d, views, patches = self._patch_args(sources, views, patches)
+        self._ck(self.L.dspi_debug_patched_intake(self.h, in_ptr or None, d.ctypes.data, views.ctypes.data if views is not None else None, len(views) if views is not None else 0,
+                                                  patches.ctypes.data if patches is not None else None, n_blocks, block_len, rx_ptr or None), "debug_patched_intake")
 
     def pdm_restart(self, stream: int = ALL):
         self._ck(self.L.dspi_pdm_restart(self.h, stream), "pdm_restart")

@@ -81,7 +81,8 @@ extern "C" {
                               * 8 + a stream's own flash: detect by symbol (dspi_device_flash; with it dspi_flash_read, dspi_flash_write, DSPI_BOOT_STREAMS_OWN_FLASH; additions only);
                               * 8 + wire words on tiled and mixed-depth contexts: detect by symbol (dspi_process_devices; with it dspi_wire_encode_tiled; additions only);
                               * 8 + S/PDIF input: detect by symbol (dspi_process_sources; with it dspi_spdif_decode, dspi_sources_bytes, dspi_spdif_rx, DSPI_SRC_*, DSPI_OUT_WIRE; additions only);
-                              * 8 + chained devices: detect by symbol (dspi_process_linked; with it dspi_wire_decode, dspi_wire_view_of, dspi_link_kinds, dspi_wire_view, dspi_link, DSPI_LINK_*; additions only) */
+                              * 8 + chained devices: detect by symbol (dspi_process_linked; with it dspi_wire_decode, dspi_wire_view_of, dspi_link_kinds, dspi_wire_view, dspi_link, DSPI_LINK_*; additions only);
+                              * 8 + the patch bay: detect by symbol (dspi_process_patched; with it dspi_patched_bytes, dspi_patch, DSPI_SRC_LINK, DSPI_MAX_VIEWS; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -1104,6 +1105,59 @@ int dspi_wire_decode(dspi_ctx *ctx, const dspi_wire_view *view, const dspi_link 
 int dspi_process_linked(dspi_ctx *ctx, const dspi_wire_view *view, const dspi_link *links /* [dspi_num_streams], HOST memory always */,
                         uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words /* may be NULL */,
                         dspi_spdif_rx *rx, uint32_t flags);
+/* ---- the patch bay: USB, S/PDIF and linked inputs in one call --------------------------------------------------------------------------------- */
+/* dspi_process_patched is the union of dspi_process_sources and dspi_process_linked: every stream takes its F = n_blocks * block_len frames from
+ * wherever it is plugged in — a run of `in`, or one line of one of up to DSPI_MAX_VIEWS views — in one call.
+ *   sources   uint8 [dspi_num_streams], HOST memory always: DSPI_SRC_PCM16, DSPI_SRC_PCM24, DSPI_SRC_SPDIF or DSPI_SRC_LINK.  The first three
+ *             mean exactly what they mean in dspi_process_sources.  DSPI_SRC_LINK: the stream's words are in somebody's wire buffer.
+ *             dspi_sources_bytes and dspi_process_sources keep refusing the value 2.
+ *   in        the runs of dspi_process_sources, except that a LINK stream occupies ZERO bytes of `in`: offset[s] = offset[s - 1] + F * size[s - 1]
+ *             with size 4, 6, 16 or 0, rounded up to 16 when sources[s] is DSPI_SRC_SPDIF.  dspi_patched_bytes is dspi_sources_bytes with that
+ *             one extra rule (*total_bytes and the n_streams + 1 offsets, either may be NULL); it works on host-only contexts.  A paused
+ *             stream's entry still sizes its slot; its bytes are never read.  `in` may be NULL when no active stream has a run.
+ *   views     dspi_wire_view [n_views], HOST memory always, 1 <= n_views <= DSPI_MAX_VIEWS, each as in dspi_process_linked, of either layout
+ *             and any tile size, mixed freely.  A view that no active LINK stream names is not looked at beyond its validation.
+ *   patches   dspi_patch [dspi_num_streams], HOST memory always.  patches[s] is read only for an ACTIVE stream whose source is DSPI_SRC_LINK:
+ *             views[patches[s].view] is its view, line and kind are dspi_link's, and the words of the link lie where THE WORDS OF A LINK puts
+ *             them.  An S/PDIF link goes through THE RECEIVER with rx[s]; an I2S link is word >> 8 with no record.  Any map and any fan-out is
+ *             allowed, across views too.  views and patches may be NULL when no active stream is a LINK stream.
+ *   rx        dspi_spdif_rx [dspi_num_streams], device memory; required when any active stream is an S/PDIF run or an S/PDIF link.  Only those
+ *             streams' entries are read or written (a record with sync > 192 is read as 0).
+ *   flags     DSPI_MEM_DEVICE is REQUIRED, as on dspi_process_linked: in, the views, rx and everything in *out are device memory.  Beyond that
+ *             exactly the flags of dspi_process_sources, DSPI_OUT_WIRE and DSPI_OUT_TILED included.
+ * Outputs, pauses, block positions, PDM bookkeeping and clip flags behave as in dspi_process_sources.  The preamp refusal applies to PCM16
+ * streams.  No state is added to the context: records, views and patches are the caller's.
+ * ORDERING.  For every DISTINCT views[v].producer that is non-NULL, is not ctx, and is named by an active LINK stream, the call records an event
+ * on that producer's HIP stream and makes its own stream wait for it before the first kernel that reads that view.  With producer == ctx or
+ * NULL nothing is recorded: with producer == ctx stream s may eat what another stream of ctx put on its wire in the PREVIOUS call (two wire
+ * buffers, used alternately).  No view's wire may overlap out->pairs of the same call.
+ * REFUSALS, in this order (a refused call writes nothing, and no record changes):
+ *   1. DSPI_E_INVAL   a NULL ctx, sources or out
+ *   2. DSPI_E_INVAL   DSPI_MEM_DEVICE missing; then dspi_process_sources' own flag rule
+ *   3. DSPI_E_INVAL   n_blocks / block_len as dspi_process refuses them
+ *   4. DSPI_E_INVAL   a source value that is none of the four
+ *   5. DSPI_E_INVAL   when an active stream is a LINK stream: views or patches NULL, n_views == 0 or n_views > DSPI_MAX_VIEWS; then EVERY view
+ *                     among the n_views by dspi_process_linked's rule 4, lowest index first; then each such stream, lowest first: view >=
+ *                     n_views, a kind that is neither S/PDIF nor I2S, line >= n_streams * n_pairs of its view
+ *   6. DSPI_E_INVAL   in NULL, or not 16-byte aligned, where an active stream has a run
+ *   7. DSPI_E_INVAL   rx NULL, or not 4-byte aligned, where it is required
+ *   8. DSPI_E_INVAL   a size that overflows 64 bits
+ *   9. DSPI_E_UNSUPPORTED   the preamp's refusal (dspi_process_mixed)
+ *  10. DSPI_E_INVAL   the producer of a view that an active LINK stream names is on another HIP device than ctx
+ *  11. DSPI_E_NODEVICE on a host-only context
+ * EQUIVALENCES, for outputs and records alike, byte for byte: with no active LINK stream the call IS dspi_process_sources on device buffers;
+ * with every active stream a LINK stream and one view it IS dspi_process_linked.  Otherwise a call costs at most one intake launch, one receiver
+ * launch over `in`, two launches per stream-major view and ONE launch for all tiled views (dspi_patchrx.hip) in front of the 24-bit chain.
+ * The ABI stays 8: detect by symbol (dspi_process_patched; with it dspi_patched_bytes; additions only). */
+#define DSPI_SRC_LINK 2            /* dspi_process_patched / dspi_patched_bytes only */
+#define DSPI_MAX_VIEWS 8
+typedef struct dspi_patch { uint32_t view; uint32_t line; uint32_t kind; } dspi_patch;   /* 12 bytes; line and kind as in dspi_link, view < n_views */
+int dspi_patched_bytes(const dspi_ctx *ctx, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len,
+                       uint64_t *total_bytes, uint64_t *offsets /* [n_streams + 1] or NULL */);
+int dspi_process_patched(dspi_ctx *ctx, const void *in, const uint8_t *sources,
+                         const dspi_wire_view *views, uint32_t n_views, const dspi_patch *patches /* [dspi_num_streams], HOST memory always */,
+                         uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words /* may be NULL */,
+                         dspi_spdif_rx *rx, uint32_t flags);
 int dspi_i2s_encode(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, uint32_t pair_mask, uint32_t *words, uint32_t flags);
 /* the HIP stream (hipStream_t) the context launches on, for event timing by the caller */
 void *dspi_hip_stream(dspi_ctx *ctx);
@@ -1167,6 +1221,10 @@ int dspi_debug_intake(dspi_ctx *ctx, const void *pcm_in, const uint8_t *bit_dept
 /* ... of a dspi_process_sources call on device buffers: the intake for its PCM streams and the receiver for its S/PDIF streams (rx: DEVICE
  * memory, updated), the same way.  For timing (tools/bench_spdif_in.py); comes with dspi_process_sources. */
 int dspi_debug_sources_intake(dspi_ctx *ctx, const void *in, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len, dspi_spdif_rx *rx);
+/* ... of a dspi_process_patched call: everything in front of the chain (the intake, the receiver over `in`, the link receivers and the one
+ * launch for all tiled views), with the call's refusals 3 to 11.  For timing (tools/bench_patched.py); comes with dspi_process_patched. */
+int dspi_debug_patched_intake(dspi_ctx *ctx, const void *in, const uint8_t *sources, const dspi_wire_view *views, uint32_t n_views,
+                              const dspi_patch *patches, uint32_t n_blocks, uint32_t block_len, dspi_spdif_rx *rx);
 
 #ifdef __cplusplus
 }
