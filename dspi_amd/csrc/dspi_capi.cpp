@@ -35,6 +35,7 @@
 #include "dspi_group.h"
 #include "dspi_intake.h"
 #include "dspi_link.h"
+#include "dspi_meters.h"
 #include "dspi_migrate.h"
 #include "dspi_move.h"
 #include "dspi_patch.h"
@@ -173,6 +174,12 @@ struct dspi_ctx {
     // dspi_device_flash (dspi_flash.h): while on, every stream holds a flash of its own (shared until written) and the preset directory requests
     // are served from it.  Host memory only; consulted in request and maintenance paths, never by dspi_process.
     FlashBook flash;
+    // the meter bridge (dspi_meters.h): no state of its own — the meters are the caller's.  Scratch on `hs` only: the alarm kernels' counts and
+    // offsets, the uploaded list of dspi_clear_clips_list (through h_move, behind ev_move), and what a host-memory call brings down (every
+    // stream's clip word, or the status blocks of a range) before it ends synchronised
+    DevBuf<uint32_t> d_meter_scan{mem};
+    DevBuf<uint32_t> d_meter_list{mem};
+    DevBuf<uint8_t> d_meter_down{mem};
     std::string err;
 };
 
@@ -2995,6 +3002,84 @@ int dspi_pdm_fade_state(dspi_ctx *c, uint32_t first, uint32_t count, const uint3
     } else if (get) HIPCK(c, hipMemcpy(base.data(), c->d_pdm_base + first, (size_t)count * 4, hipMemcpyDeviceToHost));
     if (get) for (uint32_t k = 0; k < count; k++) get[k] = (uint32_t)c->pdm_fade.pos[first + k] | (uint32_t)(uint16_t)base[k] << 16;
     return (int)count;
+}
+
+// ---- the meter bridge (dspi_meters.h: the words, the rules and the CPU paths; dspi_meterbridge.hip: the kernels) ----
+static_assert(DSPI_MEM_DEVICE == kMeterMemDevice, "include/dspi.h and dspi_meters.h: one flag");
+
+int dspi_meters_update(dspi_ctx *c, const uint16_t *peaks, uint32_t n_blocks, uint32_t hold_packets, uint32_t decay_q15, uint32_t *meters, uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    if (const char *why = meters_update_why(peaks, n_blocks, hold_packets, decay_q15, meters, flags, c->n_streams, c->sm.n_ch)) return fail(c, DSPI_E_INVAL, std::string("dspi_meters_update: ") + why);
+    if (!(flags & DSPI_MEM_DEVICE)) {      // the activity is the context's at the time of the call, on either path
+        meters_update_cpu(peaks, c->n_streams, n_blocks, c->sm.n_ch, hold_packets, decay_q15, meters, host_activity(c));
+        return DSPI_OK;
+    }
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "dspi_meters_update: a host-only context has no device memory");
+    HIPCK(c, hipSetDevice(c->device));
+    if (c->n_paused) { int rc = upload_activity(c); if (rc) return rc; }
+    HIPCK(c, launch_meters_update(c->sm.n_ch, peaks, c->n_streams, n_blocks, hold_packets, decay_q15, meters, activity(c), c->hs));
+    return DSPI_OK;
+}
+
+int dspi_meters_alarms(dspi_ctx *c, const uint32_t *meters, uint32_t level_q15, uint32_t *streams, uint32_t *info, uint32_t cap, uint32_t *total, uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    if (const char *why = meters_alarms_why(meters, level_q15, streams, info, cap, total, flags)) return fail(c, DSPI_E_INVAL, std::string("dspi_meters_alarms: ") + why);
+    const bool dev = flags & DSPI_MEM_DEVICE;
+    if (c->device == DSPI_DEVICE_NONE) {
+        if (dev) return fail(c, DSPI_E_NODEVICE, "dspi_meters_alarms: a host-only context has no device memory");
+        return (int)meters_alarms_cpu(meters, nullptr, c->n_streams, c->sm.n_ch, level_q15, streams, info, cap, total);      // no chain has run: no clip bit
+    }
+    HIPCK(c, hipSetDevice(c->device));
+    const uint32_t row = (uint32_t)c->sm.row, n_slots = (uint32_t)c->sm.n_slots, clip_slot = (uint32_t)c->sm.clip;
+    int rc;
+    if (dev) {
+        if ((rc = ensure(c, c->d_meter_scan, (size_t)meters_alarm_workgroups(c->n_streams) * 2u * 4u))) return rc;
+        HIPCK(c, launch_meters_alarms(c->sm.n_ch, c->d_state, c->n_streams, row, n_slots, clip_slot, meters, level_q15, c->d_meter_scan, streams, info, cap, total, c->hs));
+        return DSPI_OK;
+    }
+    // host memory: every stream's clip word comes down (one launch, one copy), the scan runs on the CPU
+    std::vector<uint16_t> clip(c->n_streams);
+    if ((rc = ensure(c, c->d_meter_down, (size_t)c->n_streams * 2u))) return rc;
+    HIPCK(c, launch_clip_gather(c->d_state, c->n_streams, row, n_slots, clip_slot, reinterpret_cast<uint16_t *>(c->d_meter_down.p), c->hs));
+    if ((rc = stage_down(c, clip.data(), c->d_meter_down.p, (size_t)c->n_streams * 2u))) return rc;
+    return (int)meters_alarms_cpu(meters, clip.data(), c->n_streams, c->sm.n_ch, level_q15, streams, info, cap, total);
+}
+
+int dspi_status_all(dspi_ctx *c, uint32_t first, uint32_t count, void *buf, size_t cap, uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    if (const char *why = status_all_why(first, count, buf, flags, c->n_streams)) return fail(c, DSPI_E_INVAL, std::string("dspi_status_all: ") + why);
+    const size_t block = status_block_bytes(c->sm.n_ch), bytes = (size_t)count * block;
+    if (cap < bytes) return fail(c, DSPI_E_SHORT, "dspi_status_all: the buffer is too small");
+    const bool dev = flags & DSPI_MEM_DEVICE;
+    if (c->device == DSPI_DEVICE_NONE) {
+        if (dev) return fail(c, DSPI_E_NODEVICE, "dspi_status_all: a host-only context has no device memory");
+        const uint16_t no_peaks[kMaxCh] = {};      // (as fetch_status answers there)
+        for (uint32_t i = 0; i < count; i++) status_pack(no_peaks, 0, c->sm.n_ch, static_cast<uint8_t *>(buf) + i * block);
+        return (int)count;
+    }
+    HIPCK(c, hipSetDevice(c->device));
+    void *dst = buf;
+    int rc;
+    if (!dev) {
+        if ((rc = ensure(c, c->d_meter_down, bytes))) return rc;
+        dst = c->d_meter_down.p;
+    }
+    HIPCK(c, launch_status_gather(c->sm.n_ch, c->d_state, first, count, (uint32_t)c->sm.row, (uint32_t)c->sm.n_slots, (uint32_t)c->sm.peaks, (uint32_t)c->sm.clip, dst, c->hs));
+    if (!dev && (rc = stage_down(c, buf, dst, bytes))) return rc;
+    return (int)count;
+}
+
+int dspi_clear_clips_list(dspi_ctx *c, const uint32_t *streams, uint32_t n) {
+    if (!c) return DSPI_E_INVAL;
+    if (!streams && n) return fail(c, DSPI_E_INVAL, "dspi_clear_clips_list: a NULL list");
+    const uint32_t bad = clear_list_check(streams, n, c->n_streams);
+    if (bad < n) return fail(c, DSPI_E_INVAL, "dspi_clear_clips_list: entry " + std::to_string(bad) + " names no stream of the context");
+    if (c->device == DSPI_DEVICE_NONE || n == 0) return (int)n;      // (host-only: no chain has run, nothing to clear)
+    HIPCK(c, hipSetDevice(c->device));
+    int rc = upload_via_move_area(c, c->d_meter_list, "hipHostMalloc failed (clip clear list)", {{streams, (size_t)n * 4u}});
+    if (rc) return rc;
+    HIPCK(c, launch_clip_clear(c->d_state, c->d_meter_list, n, (uint32_t)c->sm.row, (uint32_t)c->sm.n_slots, (uint32_t)c->sm.clip, c->hs));
+    return (int)n;
 }
 
 }  // extern "C"

@@ -105,6 +105,21 @@ hipError_t launch_i2s(bool tiled, const int32_t *pairs, uint32_t *out, uint32_t 
 hipError_t launch_detmath(int which, const float *a, const float *b, uint32_t n, float *out, hipStream_t stream);      // dspi_status.hip
 hipError_t launch_clip_gather(const uint32_t *state, uint32_t n_streams, uint32_t row, uint32_t n_slots, uint32_t clip_slot, uint16_t *out, hipStream_t stream);
 
+// ---- the meter bridge (dspi_meters.h: the words and the rules; dspi_meterbridge.hip: the kernels).  n_ch = 7 or 11; state / row / n_slots /
+// clip_slot as for launch_clip_gather; everything else in device memory, 4-byte aligned.
+// meters [n][n_ch] through the packets of peaks [n][n_blocks][n_ch], kMeterStagePackets (dspi_meters.h) of them in LDS at once; active: the activity bitmap or null = every stream (a paused stream's
+// words and peaks are not touched)
+hipError_t launch_meters_update(int n_ch, const uint16_t *peaks, uint32_t n, uint32_t n_blocks, uint32_t hold, uint32_t decay, uint32_t *meters, const uint32_t *active, hipStream_t stream);
+// the alarm list of streams [0, n): three launches.  meters and info may be null; scratch: 2 * meters_alarm_workgroups(n) words.
+constexpr uint32_t meters_alarm_workgroups(uint32_t n) { return (n + 255u) / 256u; }
+hipError_t launch_meters_alarms(int n_ch, const uint32_t *state, uint32_t n, uint32_t row, uint32_t n_slots, uint32_t clip_slot, const uint32_t *meters, uint32_t level,
+                                uint32_t *scratch, uint32_t *streams, uint32_t *info, uint32_t cap, uint32_t *total, hipStream_t stream);
+// the status blocks (2 n_ch + 4 bytes each) of streams [first, first + count), back to back, into out (any alignment)
+hipError_t launch_status_gather(int n_ch, const uint32_t *state, uint32_t first, uint32_t count, uint32_t row, uint32_t n_slots, uint32_t peaks_slot, uint32_t clip_slot, void *out,
+                                hipStream_t stream);
+// zero into the four clip slots of every listed stream (each < the context's streams; any order, duplicates allowed)
+hipError_t launch_clip_clear(uint32_t *state, const uint32_t *list, uint32_t n_list, uint32_t row, uint32_t n_slots, uint32_t clip_slot, hipStream_t stream);
+
 // ---- the context's four per-stream arrays, [W][position][R] each (dspi_snapshot.hip's and dspi_boot.hip's launchers take them as one) ----
 struct StateArrays { uint32_t *state, *dlines, *ring, *pdm; };
 // the one flavour ladder of their launchers (dspi_snapshot.hip, dspi_boot.hip; no chain file uses it): f(the flavour's row width as a

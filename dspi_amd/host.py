@@ -187,6 +187,11 @@ def lib() -> C.CDLL:
         L.dspi_patched_bytes.argtypes = [vp, vp, u32, u32, C.POINTER(C.c_uint64), vp]
         L.dspi_process_patched.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, C.POINTER(_Out), vp, vp, u32]
         L.dspi_debug_patched_intake.argtypes = [vp, vp, vp, vp, u32, vp, u32, u32, vp]
+    if hasattr(L, "dspi_meters_update"):      # (ABI 8 + the meter bridge: detected by symbol; with it dspi_meters_alarms, dspi_status_all, dspi_clear_clips_list)
+        L.dspi_meters_update.argtypes = [vp, vp, u32, u32, u32, vp, u32]
+        L.dspi_meters_alarms.argtypes = [vp, vp, u32, vp, vp, u32, vp, u32]
+        L.dspi_status_all.argtypes = [vp, u32, u32, vp, C.c_size_t, u32]
+        L.dspi_clear_clips_list.argtypes = [vp, vp, u32]
     _lib = L
     return L
 
@@ -964,6 +969,51 @@ class Dspi:
     def stream_capacity(self) -> int:
         """dspi_stream_capacity: the streams the context's arrays have room for (rows x tile_streams())."""
         return int(self.L.dspi_stream_capacity(self.h))
+
+    # ---- the meter bridge (include/dspi.h: meter ballistics, alarms and status for every stream of a context) ----
+    def meters_update_host(self, peaks: np.ndarray, meters: np.ndarray, hold_packets: int, decay_q15: int) -> np.ndarray:
+        """dspi_meters_update on host arrays (the CPU path): peaks uint16 [S][blocks][C] as a process call returned them, meters uint32 [S][C]
+        (level | count << 16), updated in place and returned."""
+        S = self.n_streams
+        assert peaks.dtype == np.uint16 and peaks.flags.c_contiguous and peaks.ndim == 3 and peaks.shape[0] == S and peaks.shape[2] == self.C, peaks.shape
+        assert meters.dtype == np.uint32 and meters.flags.c_contiguous and meters.shape == (S, self.C), meters.shape
+        self._ck(self.L.dspi_meters_update(self.h, peaks.ctypes.data, peaks.shape[1], hold_packets, decay_q15, meters.ctypes.data, 0), "meters_update")
+        return meters
+
+    def meters_update_device(self, peaks_ptr: int, n_blocks: int, meters_ptr: int, hold_packets: int, decay_q15: int):
+        """dspi_meters_update on device pointers: asynchronous on the context's stream, behind the process call that wrote the peaks"""
+        self._ck(self.L.dspi_meters_update(self.h, peaks_ptr, n_blocks, hold_packets, decay_q15, meters_ptr, MEM_DEVICE), "meters_update")
+
+    def meters_alarms_host(self, meters: np.ndarray | None, level_q15: int, cap: int | None = None, want_info: bool = True):
+        """dspi_meters_alarms on host arrays: (streams uint32 [written], info uint32 [written] or None, total).  meters None: clip-only alarms;
+        cap: the list's room (default: every stream)."""
+        cap = self.n_streams if cap is None else cap
+        streams, info, total = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32) if want_info else None, C.c_uint32(0)
+        if meters is not None: assert meters.dtype == np.uint32 and meters.flags.c_contiguous and meters.shape == (self.n_streams, self.C), meters.shape
+        n = self._ck(self.L.dspi_meters_alarms(self.h, meters.ctypes.data if meters is not None else None, level_q15, streams.ctypes.data,
+                                               info.ctypes.data if want_info else None, cap, C.byref(total), 0), "meters_alarms")
+        return streams[:n], info[:n] if want_info else None, total.value
+
+    def meters_alarms_device(self, meters_ptr: int, level_q15: int, streams_ptr: int, info_ptr: int, cap: int, total_ptr: int):
+        """dspi_meters_alarms on device pointers (meters_ptr / info_ptr 0: not given): asynchronous; *total lands on the device"""
+        self._ck(self.L.dspi_meters_alarms(self.h, meters_ptr or None, level_q15, streams_ptr, info_ptr or None, cap, total_ptr, MEM_DEVICE), "meters_alarms")
+
+    def status_all(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """dspi_status_all into host memory: uint8 [count][2 C + 4], row i what status(first + i) answers"""
+        count = self.n_streams - first if count is None else count
+        buf = np.zeros((count, self.C * 2 + 4), dtype=np.uint8)
+        self._ck(self.L.dspi_status_all(self.h, first, count, buf.ctypes.data, buf.nbytes, 0), "status_all")
+        return buf
+
+    def status_all_device(self, buf_ptr: int, cap: int, first: int = 0, count: int | None = None) -> int:
+        """dspi_status_all into device memory (cap bytes at buf_ptr): asynchronous"""
+        count = self.n_streams - first if count is None else count
+        return self._ck(self.L.dspi_status_all(self.h, first, count, buf_ptr, cap, MEM_DEVICE), "status_all")
+
+    def clear_clips_list(self, streams) -> int:
+        """dspi_clear_clips_list: REQ_CLEAR_CLIPS for the listed streams (any order, duplicates allowed), one launch on the context's stream"""
+        s = np.ascontiguousarray(np.asarray(streams, dtype=np.uint32).reshape(-1))
+        return self._ck(self.L.dspi_clear_clips_list(self.h, s.ctypes.data if len(s) else None, len(s)), "clear_clips_list")
 
     def sync(self):
         self._ck(self.L.dspi_sync(self.h), "sync")

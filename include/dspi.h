@@ -82,7 +82,8 @@ extern "C" {
                               * 8 + wire words on tiled and mixed-depth contexts: detect by symbol (dspi_process_devices; with it dspi_wire_encode_tiled; additions only);
                               * 8 + S/PDIF input: detect by symbol (dspi_process_sources; with it dspi_spdif_decode, dspi_sources_bytes, dspi_spdif_rx, DSPI_SRC_*, DSPI_OUT_WIRE; additions only);
                               * 8 + chained devices: detect by symbol (dspi_process_linked; with it dspi_wire_decode, dspi_wire_view_of, dspi_link_kinds, dspi_wire_view, dspi_link, DSPI_LINK_*; additions only);
-                              * 8 + the patch bay: detect by symbol (dspi_process_patched; with it dspi_patched_bytes, dspi_patch, DSPI_SRC_LINK, DSPI_MAX_VIEWS; additions only) */
+                              * 8 + the patch bay: detect by symbol (dspi_process_patched; with it dspi_patched_bytes, dspi_patch, DSPI_SRC_LINK, DSPI_MAX_VIEWS; additions only);
+                              * 8 + the meter bridge: detect by symbol (dspi_meters_update; with it dspi_meters_alarms, dspi_status_all, dspi_clear_clips_list; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -1167,6 +1168,66 @@ void *dspi_hip_stream(dspi_ctx *ctx);
 int dspi_get_status(dspi_ctx *ctx, int32_t stream, void *buf, size_t cap);
 /* REQ_CLEAR_CLIPS: returns the flags that were set (DSPI_ALL_STREAMS: clears every stream, returns stream 0's flags) */
 int dspi_clear_clips(dspi_ctx *ctx, int32_t stream);
+
+/* ---- the meter bridge: meter ballistics, alarms and status for every stream of a context ----------------------------------------------- */
+/* The peaks a process-family call writes through out->peaks are instantaneous block peaks, one per packet and channel: no decay, no hold —
+ * ballistics are the host application's (the firmware's metering spec), and the two calls above serve one device at a time.  These four
+ * calls are that host's side for a whole context: they consume the words the chain leaves (out->peaks, the sticky clip bits, the status
+ * block) and touch no sample arithmetic.  C = dspi_num_channels, n = dspi_num_streams.
+ * METER STATE IS THE CALLER'S, like the S/PDIF receiver records: uint32 [n][C], one word = level | count << 16 (level: a block peak's scale,
+ * 0..65535; count: the packets its hold has left); an all-zero word is a meter at rest.  The calls keep nothing in the context, so moves,
+ * migrations, boots, resizes and snapshots need no new book — the caller relocates its meter words by the same lists as its other
+ * per-stream buffers.  Meters that the context owns and that travel with a stream are not part of this interface.
+ *
+ * dspi_meters_update(ctx, peaks, n_blocks, hold_packets, decay_q15, meters, flags)
+ *     peaks = uint16 [n][n_blocks][C], exactly what a process-family call wrote through out->peaks; meters in and out.  For every stream that
+ *     is ACTIVE in the context at the time of this call, every channel, and packets k = 0 .. n_blocks - 1 in order, p = peaks[s][k][c]:
+ *         if (p >= level)      { level = p; count = hold_packets; }
+ *         else if (count > 0)  { count--; }
+ *         else                 { level = max(p, (level * decay_q15) >> 15); }      (32-bit unsigned product)
+ *     hold_packets 0..65535; decay_q15 0..32768: 32768 never decays (level is the running maximum), 0 drops to p once the hold has run out.
+ *     A packet is the unit of time (1 ms of audio at the firmware's packetisation).  Integer arithmetic: the result is defined bit for bit,
+ *     and one call over K packets equals calls over any split of them.
+ *     PAUSED STREAMS: a paused stream's words are neither read nor written — the meter freezes, as the firmware's peak words do between
+ *     packets — and its region of peaks is never read.  The activity used is the context's AT THE TIME OF THIS CALL, not at the time of the
+ *     process call that wrote the peaks: update before changing pauses.
+ *     flags 0: both buffers in host memory; the call runs on the CPU and works on host-only contexts.  DSPI_MEM_DEVICE: both are device
+ *     pointers and the call is asynchronous on the context's stream, behind the process call that wrote peaks: no dspi_sync between them.
+ *     REFUSALS, in this order, nothing written: DSPI_E_INVAL for a NULL pointer, n_blocks == 0, hold_packets or decay_q15 out of range,
+ *     another flag bit, a size that overflows, a device pointer that is not 4-byte aligned; then DSPI_E_NODEVICE for DSPI_MEM_DEVICE on a
+ *     host-only context.  Returns DSPI_OK.
+ *
+ * dspi_meters_alarms(ctx, meters, level_q15, streams, info, cap, total, flags)
+ *     Stream s in [0, n) is IN ALARM when the context's sticky clip bits for s are non-zero (the word DSPI_OUT_CLIP_FLAGS and dspi_get_status
+ *     report, read from the context itself), or when meters (may be NULL: clip-only alarms) is given and some channel's level >= level_q15
+ *     (0..65535; 0 lists every stream).  Paused streams count, with their frozen state.  streams [cap] receives the alarmed streams in
+ *     ASCENDING order, the lowest min(*total, cap) of them; info [cap] (may be NULL), beside each, mask of the channels at or above the level
+ *     | clip bits << 16; *total = the number found, which may exceed cap.  The order is deterministic (counts per workgroup, a scan, ordered
+ *     writes; no atomic cursor).
+ *     flags 0: host memory; returns the number written; on a host-only context the clip bits are 0.  DSPI_MEM_DEVICE: all four pointers are
+ *     device pointers, the call is asynchronous on the context's stream, returns DSPI_OK, and *total lands on the device.
+ *     REFUSALS: DSPI_E_INVAL for NULL streams or total, cap == 0, level_q15 > 65535, another flag bit, a device pointer that is not 4-byte
+ *     aligned; then DSPI_E_NODEVICE as above.
+ *
+ * dspi_status_all(ctx, first, count, buf, cap, flags)
+ *     The REQ_GET_STATUS wValue-9 block of every stream of [first, first + count), packed back to back: 2 C + 4 bytes each (26 / 18), both
+ *     CPU-load bytes 0; each block byte for byte what dspi_get_status(ctx, s, ..) answers, paused streams included.  One launch and at most
+ *     one copy.  Host memory, or device memory (any alignment) with DSPI_MEM_DEVICE, asynchronous then.  Host-only context: blocks of zero
+ *     peaks and flags.  Returns count.  DSPI_E_INVAL for a NULL buf, count == 0, a range past n, another flag bit; DSPI_E_SHORT when
+ *     cap < count * (2 C + 4); then DSPI_E_NODEVICE as above.
+ *
+ * dspi_clear_clips_list(ctx, streams, n)
+ *     REQ_CLEAR_CLIPS for a list in HOST memory, any order, duplicates allowed: the clip bits of every listed stream are cleared in one launch
+ *     on the context's stream — ordered behind earlier process calls without dspi_clear_clips' per-stream synchronisation —, no other
+ *     stream's are touched.  An entry >= n is DSPI_E_INVAL and clears nothing.  Host-only: nothing to clear.  Returns n.  After it
+ *     dspi_get_status, DSPI_OUT_CLIP_FLAGS and the next launch see the bits cleared, exactly as after dspi_clear_clips on each entry.
+ * The ABI stays 8: detect by symbol (dspi_meters_update; with it dspi_meters_alarms, dspi_status_all, dspi_clear_clips_list; additions only). */
+int dspi_meters_update(dspi_ctx *ctx, const uint16_t *peaks, uint32_t n_blocks, uint32_t hold_packets, uint32_t decay_q15,
+                       uint32_t *meters, uint32_t flags);
+int dspi_meters_alarms(dspi_ctx *ctx, const uint32_t *meters /* may be NULL */, uint32_t level_q15,
+                       uint32_t *streams, uint32_t *info /* may be NULL */, uint32_t cap, uint32_t *total, uint32_t flags);
+int dspi_status_all(dspi_ctx *ctx, uint32_t first, uint32_t count, void *buf, size_t cap, uint32_t flags);
+int dspi_clear_clips_list(dspi_ctx *ctx, const uint32_t *streams, uint32_t n);
 
 /* ---- introspection for tests (host-side derived parameter image of a stream) ------------ */
 /* Copies the packed device parameter image; returns its size.  Layout is internal (csrc/dspi_image.h). */
