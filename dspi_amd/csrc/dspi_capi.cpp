@@ -38,6 +38,7 @@
 #include "dspi_meters.h"
 #include "dspi_migrate.h"
 #include "dspi_move.h"
+#include "dspi_packets.h"
 #include "dspi_patch.h"
 #include "dspi_pdmfade.h"
 #include "dspi_pdmlife.h"
@@ -2190,9 +2191,28 @@ static int launch_patched(dspi_ctx *c, const PatchIn &pi, uint64_t frames) {
     return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("patch receiver launch: ") + hipGetErrorString(e));
 }
 
+// ---- dspi_process_packets (dspi_packets.h): the call's table ----
+// Planned as the 24-bit call it becomes, d_mixed filled by the packet receiver from the caller's arena.  The device route only.
+struct PacketIn {
+    const void *arena;          // device memory
+    const uint8_t *depths;      // [n], host memory, validated
+    const uint64_t *table;      // [n][n_blocks], host memory, validated for the active streams
+    uint32_t n_blocks, block_len;
+};
+// the front end of a packet call, into d_mixed: the table and the depths go up through the pinned move area (the caller may reuse its table
+// when the call returns), then one launch.  They stand in the mixed path's table, which then holds no mixed call's layout any more.
+static int launch_packets(dspi_ctx *c, const PacketIn &pk) {
+    const size_t entries = (size_t)c->n_streams * pk.n_blocks;
+    c->mixed_frames = 0;
+    if (int rc = upload_via_move_area(c, c->d_mixed_tab, "hipHostMalloc failed (packet table)", {{pk.table, entries * 8}, {pk.depths, c->n_streams}})) return rc;
+    const uint64_t *const tab = c->d_mixed_tab;
+    const hipError_t e = launch_packetrx(pk.arena, tab, reinterpret_cast<const uint8_t *>(tab + entries), activity(c), c->d_mixed, c->n_streams, pk.n_blocks, pk.block_len, c->hs);
+    return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("packet receiver launch: ") + hipGetErrorString(e));
+}
+
 // ---- device buffers: the caller's own, asynchronous on the context's stream ----
 static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, const PdmCall *pc, const MixedIn *mx, const LinkIn *lk = nullptr,
-                          const PatchIn *pt = nullptr) {
+                          const PatchIn *pt = nullptr, const PacketIn *pk = nullptr) {
     a.pcm = pcm_in; a.pairs = out->pairs; a.sub = out->sub; a.peaks = out->peaks;
     int rc = 0;
     if (pc && !out->sub) { if ((rc = pdm_sub_scratch(c, L))) return rc; a.sub = c->d_sub; }
@@ -2200,6 +2220,7 @@ static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     if (mx) { if ((rc = launch_intake_streams(c, L.frames, pcm_in, c->d_mixed, 0, c->n_streams, mx->rx))) return rc; a.pcm = c->d_mixed; }
     if (lk) { if ((rc = launch_links(c, *lk, L.frames))) return rc; a.pcm = c->d_mixed; }
     if (pt) { if ((rc = launch_patched(c, *pt, L.frames))) return rc; a.pcm = c->d_mixed; }
+    if (pk) { if ((rc = launch_packets(c, *pk))) return rc; a.pcm = c->d_mixed; }
     if ((rc = launch_rows(c, a, L, 0, c->n_wg))) return rc;
     if (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, pc->words, 0, c->n_streams))) return rc;
     return clip_out ? gather_clip(c, clip_out) : DSPI_OK;
@@ -2466,7 +2487,7 @@ static bool wire_slots_in_play(const dspi_ctx *c) {
 // wire: dspi_process_wire and dspi_process_devices (flags carry DSPI_OUT_SPDIF, which the wire layout implies): out->pairs in the wire layout;
 // with DSPI_OUT_TILED beside it (dspi_process_devices alone; the callers have applied their own flag rule, dspi_wire.h) in the tiled wire layout
 static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags,
-                        const MixedIn *mx = nullptr, bool wire = false, const LinkIn *lk = nullptr, const PatchIn *pt = nullptr) {
+                        const MixedIn *mx = nullptr, bool wire = false, const LinkIn *lk = nullptr, const PatchIn *pt = nullptr, const PacketIn *pk = nullptr) {
     if (!c || !pcm_in || !out) return DSPI_E_INVAL;
     int rc = check_flag_bits(c, flags);
     if (rc) return rc;
@@ -2500,6 +2521,7 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     if (mx && L.mem == CallMem::Staged && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed_up, (size_t)mx->offsets.back()))) return rc;
     if (lk && (L.mem != CallMem::Device || (rc = ensure(c, c->d_mixed, L.pcm.bytes)))) return rc ? rc : fail(c, DSPI_E_INVAL, "dspi_process_linked: device memory only");
     if (pt && (L.mem != CallMem::Device || (rc = ensure(c, c->d_mixed, L.pcm.bytes)))) return rc ? rc : fail(c, DSPI_E_INVAL, "dspi_process_patched: device memory only");
+    if (pk && (L.mem != CallMem::Device || (rc = ensure(c, c->d_mixed, L.pcm.bytes)))) return rc ? rc : fail(c, DSPI_E_INVAL, "dspi_process_packets: device memory only");
 
     KArgs a{};
     a.img = c->d_images; a.stream_image = c->d_stream_image; a.vals = c->d_vals;
@@ -2519,7 +2541,7 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     }
 
     switch (L.mem) {
-    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out, pc, mx, lk, pt); break;
+    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out, pc, mx, lk, pt, pk); break;
     case CallMem::Direct: rc = process_direct(c, L, a, pcm_in, out, clip_out, flags, call_t0, pc, mx); break;
     case CallMem::Staged: rc = process_staged(c, L, a, pcm_in, out, clip_out, flags, pc, mx); break;
     }
@@ -2963,6 +2985,68 @@ int dspi_debug_patched_intake(dspi_ctx *c, const void *in, const uint8_t *source
     patch_plan(sources, c->n_streams, host_activity(c), reinterpret_cast<const WireView *>(views), n_views, reinterpret_cast<const Patch *>(patches), frames, plan);
     const PatchIn pi{in, reinterpret_cast<const WireView *>(views), views, n_views, rx_needed ? reinterpret_cast<SpdifRx *>(rx) : nullptr, &plan};
     return launch_patched(c, pi, frames);
+}
+
+// ---- input from a packet table (dspi_packets.h: the entry rule, the check and the address arithmetic; dspi_packetrx.hip: the kernel) ----
+// refusals 2 to 5 of dspi_process_packets behind the pointers, in their order (dspi_packets_check and dspi_debug_packets_intake share them)
+static int packets_refusals(dspi_ctx *c, const char *who, const uint8_t *depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes, uint64_t *bad_entry) {
+    const std::string w = std::string(who) + ": ";
+    uint64_t at = 0;
+    switch (packets_check(depths, table, c->n_streams, n_blocks, block_len, DSPI_MAX_BLOCK_LEN, arena_bytes, host_activity(c), &at)) {
+    case PacketsBad::Ok: return 0;
+    case PacketsBad::Lengths: return fail(c, DSPI_E_INVAL, w + "1 <= block_len <= 192, n_blocks >= 1");
+    case PacketsBad::Depth: return fail(c, DSPI_E_INVAL, w + "the depth of stream " + std::to_string(at) + " is neither 16 nor 24");
+    case PacketsBad::Overflow: return fail(c, DSPI_E_INVAL, w + "the table has more than 2^31 - 1 entries");
+    case PacketsBad::Entry: break;
+    }
+    if (bad_entry) *bad_entry = at;
+    return fail(c, DSPI_E_INVAL, w + "entry " + std::to_string(at) + " (stream " + std::to_string(at / n_blocks) + ", packet " + std::to_string(at % n_blocks) + ") is odd or its packet does not end inside the arena");
+}
+
+int dspi_packets_check(const dspi_ctx *c, const uint8_t *bit_depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes, uint64_t *bad_entry) {
+    if (!c || !table || !bit_depths) return DSPI_E_INVAL;
+    return packets_refusals(const_cast<dspi_ctx *>(c), "dspi_packets_check", bit_depths, table, n_blocks, block_len, arena_bytes, bad_entry);
+}
+
+int dspi_process_packets(dspi_ctx *c, const void *arena, uint64_t arena_bytes, const uint8_t *bit_depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, const dspi_out *out,
+                         uint32_t *pdm_words, uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    // 1. the flags
+    if (!(flags & DSPI_MEM_DEVICE)) return fail(c, DSPI_E_INVAL, "dspi_process_packets: DSPI_MEM_DEVICE is required");
+    const bool wire = flags & DSPI_OUT_WIRE;
+    flags &= ~DSPI_OUT_WIRE;
+    if (wire && !devices_process_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_process_packets: with DSPI_OUT_WIRE the flags are DSPI_MEM_DEVICE, DSPI_OUT_TILED, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
+    int rc;
+    if ((rc = check_flag_bits(c, flags)) || (!wire && (rc = check_flag_combinations(c, flags)))) return rc;
+    // 2. to 5.
+    if (!arena || !table || !bit_depths || !out) return fail(c, DSPI_E_INVAL, "dspi_process_packets: arena, table, bit_depths and out are required");
+    if ((rc = packets_refusals(c, "dspi_process_packets", bit_depths, table, n_blocks, block_len, arena_bytes, nullptr))) return rc;
+    // 6. the one case in which a 16-bit sample and its widened twin part ways (dspi_intake.h): refused, not approximated
+    if (c->flavor)
+        for (uint32_t s = 0; s < c->n_streams; s++) {
+            if (bit_depths[s] != 16 || (c->n_paused && !c->active[s])) continue;
+            for (const float p : readable(c, (int32_t)s).preamp_linear) {
+                uint32_t w; memcpy(&w, &p, 4);
+                if (intake_preamp_breaks_widening(w))
+                    return fail(c, DSPI_E_UNSUPPORTED, "dspi_process_packets: stream " + std::to_string(s) + " takes 16-bit input with a preamp below 2^-103, where widening to 24 bit is not exact");
+            }
+        }
+    // 7. (process_call refuses the host-only context)
+    const PacketIn pk{arena, bit_depths, table, n_blocks, block_len};
+    return process_call(c, arena, 24, n_blocks, block_len, out, pdm_words, wire ? flags | DSPI_OUT_SPDIF : flags, nullptr, wire, nullptr, nullptr, &pk);
+}
+
+// the front end of a dspi_process_packets call alone, into the context's scratch: what tools/bench_packets.py times (no chain, nothing advanced)
+int dspi_debug_packets_intake(dspi_ctx *c, const void *arena, uint64_t arena_bytes, const uint8_t *bit_depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len) {
+    if (!c || !arena || !table || !bit_depths) return DSPI_E_INVAL;
+    int rc = packets_refusals(c, "dspi_debug_packets_intake", bit_depths, table, n_blocks, block_len, arena_bytes, nullptr);
+    if (rc) return rc;
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no intake");
+    HIPCK(c, hipSetDevice(c->device));
+    if (c->n_paused && (rc = upload_activity(c))) return rc;
+    if ((rc = ensure(c, c->d_mixed, (size_t)c->n_streams * kIntakeOutFrame * n_blocks * block_len))) return rc;
+    const PacketIn pk{arena, bit_depths, table, n_blocks, block_len};
+    return launch_packets(c, pk);
 }
 
 int dspi_pdm_running(dspi_ctx *c, uint32_t first, uint32_t count, const uint8_t *set, uint8_t *get) {

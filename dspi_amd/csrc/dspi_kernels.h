@@ -194,4 +194,12 @@ hipError_t launch_linkrx(bool packed, const uint32_t *wire, const void *links, c
 // kind is kLinkNone is neither read nor written.  any_spdif: what the patches hold, as the host knows it.
 hipError_t launch_patchrx(const void *cols, void *rx, void *dst, uint32_t frames, uint32_t count, bool any_spdif, hipStream_t stream);
 
+// ---- the front end of dspi_process_packets (dspi_packets.h: the table and the address arithmetic; dspi_packetrx.hip: the kernel) ----
+// Streams [0, n_streams): packet k of stream s (block_len frames at depths[s] = 16 or 24) from arena + table[s * n_blocks + k] into
+// dst + 6 block_len (n_blocks s + k), packed 24 bit.  table [n_streams][n_blocks] and depths [n_streams] in device memory, the entries legal
+// for the arena (dspi_packets.h) wherever `active`, the activity bitmap or null, has the stream's bit: a paused stream is neither read nor
+// written, and neither are its entries.  arena and dst are 2-byte aligned.
+hipError_t launch_packetrx(const void *arena, const uint64_t *table, const uint8_t *depths, const uint32_t *active, void *dst, uint32_t n_streams, uint32_t n_blocks,
+                           uint32_t block_len, hipStream_t stream);
+
 }  // namespace dspi

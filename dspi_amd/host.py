@@ -192,6 +192,10 @@ def lib() -> C.CDLL:
         L.dspi_meters_alarms.argtypes = [vp, vp, u32, vp, vp, u32, vp, u32]
         L.dspi_status_all.argtypes = [vp, u32, u32, vp, C.c_size_t, u32]
         L.dspi_clear_clips_list.argtypes = [vp, vp, u32]
+    if hasattr(L, "dspi_process_packets"):      # (ABI 8 + input from a packet table: detected by symbol; with it dspi_packets_check)
+        L.dspi_packets_check.argtypes = [vp, vp, vp, u32, u32, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.dspi_process_packets.argtypes = [vp, vp, C.c_uint64, vp, vp, u32, u32, C.POINTER(_Out), vp, u32]
+        L.dspi_debug_packets_intake.argtypes = [vp, vp, C.c_uint64, vp, vp, u32, u32]
     _lib = L
     return L
 
@@ -813,6 +817,38 @@ class Dspi:
         d, views, patches = self._patch_args(sources, views, patches)
         self._ck(self.L.dspi_debug_patched_intake(self.h, in_ptr or None, d.ctypes.data, views.ctypes.data if views is not None else None, len(views) if views is not None else 0,
                                                   patches.ctypes.data if patches is not None else None, n_blocks, block_len, rx_ptr or None), "debug_patched_intake")
+
+    # ---- input from a packet table (include/dspi.h: dspi_process_packets) ----
+    def _packet_table(self, table, n_blocks: int) -> np.ndarray:
+        t = np.ascontiguousarray(table, dtype=np.uint64)
+        assert t.size == self.n_streams * n_blocks, (t.shape, self.n_streams, n_blocks)
+        return t
+
+    def packets_check(self, bit_depths, table, n_blocks: int, block_len: int, arena_bytes: int):
+        """dspi_packets_check: None when a dspi_process_packets call would accept this table (uint64 [n_streams][n_blocks], byte offsets in an arena
+        of arena_bytes) and these depths; raises DspiError otherwise, after setting self.bad_entry to s * n_blocks + k of the entry refused (None
+        when the refusal is not about an entry).  Works on host-only contexts."""
+        d, t = self._depths(bit_depths), self._packet_table(table, n_blocks)
+        bad = C.c_uint64(2 ** 64 - 1)
+        rc = self.L.dspi_packets_check(self.h, d.ctypes.data, t.ctypes.data, n_blocks, block_len, arena_bytes, C.byref(bad))
+        self.bad_entry = None if rc == 0 or bad.value == 2 ** 64 - 1 else bad.value
+        self._ck(rc, "packets_check")
+
+    def process_packets_device(self, arena_ptr: int, arena_bytes: int, bit_depths, table, n_blocks: int, block_len: int, pairs_ptr: int = 0, sub_ptr: int = 0, peaks_ptr: int = 0,
+                               words_ptr: int = 0, tiled: bool = False, enabled_only: bool = False, spdif: bool = False, wire: bool = False, clip_ptr: int = 0):
+        """dspi_process_packets on raw device pointers: packet k of stream s is block_len frames at bit_depths[s] at arena_ptr + table[s][k] (the
+        depths and the table stay host arrays; the table may be reused when this returns).  Otherwise process_mixed_device; wire=True
+        (DSPI_OUT_WIRE): pairs in the wire layout, with tiled=True the tiled one.  Asynchronous, see sync()."""
+        d, t = self._depths(bit_depths), self._packet_table(table, n_blocks)
+        out = _Out(pairs_ptr or None, sub_ptr or None, peaks_ptr or None, clip_ptr or None)
+        self._ck(self.L.dspi_process_packets(self.h, arena_ptr, arena_bytes, d.ctypes.data, t.ctypes.data, n_blocks, block_len, C.byref(out), words_ptr or None,
+                                             MEM_DEVICE | (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_SPDIF if spdif else 0) | (OUT_WIRE if wire else 0) |
+                                             (OUT_CLIP_FLAGS if clip_ptr else 0)), "process_packets")
+
+    def debug_packets_intake(self, arena_ptr: int, arena_bytes: int, bit_depths, table, n_blocks: int, block_len: int):
+        """dspi_debug_packets_intake: what process_packets_device runs in front of the chain, into the context's scratch; asynchronous, see sync()."""
+        d, t = self._depths(bit_depths), self._packet_table(table, n_blocks)
+        self._ck(self.L.dspi_debug_packets_intake(self.h, arena_ptr, arena_bytes, d.ctypes.data, t.ctypes.data, n_blocks, block_len), "debug_packets_intake")
 
     def pdm_restart(self, stream: int = ALL):
         self._ck(self.L.dspi_pdm_restart(self.h, stream), "pdm_restart")

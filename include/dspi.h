@@ -83,7 +83,8 @@ extern "C" {
                               * 8 + S/PDIF input: detect by symbol (dspi_process_sources; with it dspi_spdif_decode, dspi_sources_bytes, dspi_spdif_rx, DSPI_SRC_*, DSPI_OUT_WIRE; additions only);
                               * 8 + chained devices: detect by symbol (dspi_process_linked; with it dspi_wire_decode, dspi_wire_view_of, dspi_link_kinds, dspi_wire_view, dspi_link, DSPI_LINK_*; additions only);
                               * 8 + the patch bay: detect by symbol (dspi_process_patched; with it dspi_patched_bytes, dspi_patch, DSPI_SRC_LINK, DSPI_MAX_VIEWS; additions only);
-                              * 8 + the meter bridge: detect by symbol (dspi_meters_update; with it dspi_meters_alarms, dspi_status_all, dspi_clear_clips_list; additions only) */
+                              * 8 + the meter bridge: detect by symbol (dspi_meters_update; with it dspi_meters_alarms, dspi_status_all, dspi_clear_clips_list; additions only);
+                              * 8 + input from a packet table: detect by symbol (dspi_process_packets; with it dspi_packets_check; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -1159,6 +1160,41 @@ int dspi_process_patched(dspi_ctx *ctx, const void *in, const uint8_t *sources,
                          const dspi_wire_view *views, uint32_t n_views, const dspi_patch *patches /* [dspi_num_streams], HOST memory always */,
                          uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words /* may be NULL */,
                          dspi_spdif_rx *rx, uint32_t flags);
+/* ---- input from a packet table, in arrival order ------------------------------------------------------------------------------------------- */
+/* dspi_process_packets is dspi_process_mixed with each stream's frames taken packet by packet from where a table points: the packets stay
+ * in the arena they were received into, and the library gathers them as it widens them.
+ *   arena     DEVICE memory, arena_bytes long, 2-byte aligned: the received packets, anywhere, in any order, with anything in between.
+ *   table     uint64 [dspi_num_streams][n_blocks], HOST memory always (like bit_depths and links).  table[s * n_blocks + k] is the byte offset in
+ *             arena of packet k of stream s: block_len frames of 4 bytes (bit_depths[s] == 16) or 6 (24), interleaved LE stereo.  The table goes
+ *             up with the call, through the context's pinned area: the caller may reuse its table when the call returns.
+ *   flags     DSPI_MEM_DEVICE is REQUIRED: arena and everything in *out are device memory; table and bit_depths are host memory.  The call is
+ *             asynchronous on the context's stream like every device call.  Beyond that exactly the flags of dspi_process_sources: with
+ *             DSPI_OUT_WIRE, under dspi_process_devices' flag rule, out->pairs is the wire layout, with DSPI_OUT_TILED the tiled one.
+ * AN ENTRY IS LEGAL when it is even and offset + block_len * frame bytes <= arena_bytes.  Entries may be equal and may overlap in any way:
+ * one programme to many devices (every stream's entries name the same packets), a packet repeated to conceal a lost one, a sliding window.
+ * Entries of PAUSED streams are neither read nor checked: they may hold anything.  Nothing outside [offset, offset + length) of an active
+ * stream's entries is read from the arena: neighbouring bytes may lie outside the caller's allocation.
+ * Outputs, pdm_words, the clip flags, pauses, block positions and the state all behave as in dspi_process_mixed: the call IS
+ * dspi_process_mixed on the input that the table describes, byte for byte (uniform depths included).  No state is added to the context:
+ * snapshots, moves, migrations and resizes are unaffected.
+ * REFUSALS, in this order (a refused call writes nothing and changes nothing):
+ *   1. DSPI_E_INVAL   a NULL ctx; DSPI_MEM_DEVICE missing; then dspi_process_sources' own flag rule
+ *   2. DSPI_E_INVAL   a NULL arena, table, bit_depths or out; n_blocks == 0 or block_len == 0; block_len > DSPI_MAX_BLOCK_LEN, as
+ *                     dspi_process_mixed refuses it
+ *   3. DSPI_E_INVAL   a depth that is neither 16 nor 24 (any stream, paused or not, lowest first)
+ *   4. DSPI_E_INVAL   a table of more than 2^31 - 1 entries: dspi_num_streams * n_blocks
+ *   5. DSPI_E_INVAL   the first illegal entry of an active stream, in table order; the message names its index s * n_blocks + k
+ *   6. DSPI_E_UNSUPPORTED   the preamp's refusal for active 16-bit streams, exactly as in dspi_process_mixed
+ *   7. DSPI_E_NODEVICE on a host-only context
+ * dspi_packets_check applies refusals 2 to 5 (no arena, no out) and works on host-only contexts; at refusal 5 *bad_entry, when not NULL, takes
+ * s * n_blocks + k of the entry refused, and is not written otherwise.
+ * LEFT OUT: arenas in host memory; tables in device memory; S/PDIF and linked sources in the same call (the patch bay keeps those); a
+ * packet-table OUTPUT (a packetiser); per-packet lengths (block_len is one number per call); an option of dspi_host.
+ * The ABI stays 8: detect by symbol (dspi_process_packets; with it dspi_packets_check; additions only). */
+int dspi_packets_check(const dspi_ctx *ctx, const uint8_t *bit_depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len,
+                       uint64_t arena_bytes, uint64_t *bad_entry /* may be NULL: s * n_blocks + k of the first entry refused */);
+int dspi_process_packets(dspi_ctx *ctx, const void *arena, uint64_t arena_bytes, const uint8_t *bit_depths, const uint64_t *table,
+                         uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words /* may be NULL */, uint32_t flags);
 int dspi_i2s_encode(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_frames, uint32_t pair_mask, uint32_t *words, uint32_t flags);
 /* the HIP stream (hipStream_t) the context launches on, for event timing by the caller */
 void *dspi_hip_stream(dspi_ctx *ctx);
@@ -1286,6 +1322,10 @@ int dspi_debug_sources_intake(dspi_ctx *ctx, const void *in, const uint8_t *sour
  * launch for all tiled views), with the call's refusals 3 to 11.  For timing (tools/bench_patched.py); comes with dspi_process_patched. */
 int dspi_debug_patched_intake(dspi_ctx *ctx, const void *in, const uint8_t *sources, const dspi_wire_view *views, uint32_t n_views,
                               const dspi_patch *patches, uint32_t n_blocks, uint32_t block_len, dspi_spdif_rx *rx);
+/* ... of a dspi_process_packets call: the table's upload and the one launch of dspi_packetrx.hip, with the call's refusals 2 to 5 and then
+ * DSPI_E_NODEVICE.  For timing (tools/bench_packets.py); comes with dspi_process_packets. */
+int dspi_debug_packets_intake(dspi_ctx *ctx, const void *arena, uint64_t arena_bytes, const uint8_t *bit_depths, const uint64_t *table,
+                              uint32_t n_blocks, uint32_t block_len);
 
 #ifdef __cplusplus
 }
