@@ -39,6 +39,7 @@
 #include "dspi_migrate.h"
 #include "dspi_move.h"
 #include "dspi_packets.h"
+#include "dspi_packets_out.h"
 #include "dspi_patch.h"
 #include "dspi_pdmfade.h"
 #include "dspi_pdmlife.h"
@@ -181,6 +182,9 @@ struct dspi_ctx {
     DevBuf<uint32_t> d_meter_scan{mem};
     DevBuf<uint32_t> d_meter_list{mem};
     DevBuf<uint8_t> d_meter_down{mem};
+    // dspi_packets_emit (dspi_packets_out.h): no state — the device's copy of the call's table with the formats behind it, on `hs` only (it goes
+    // up through h_move, behind ev_move).  Not d_mixed_tab: a process call's table stays what that call left.
+    DevBuf<uint64_t> d_emit_tab{mem};
     std::string err;
 };
 
@@ -3047,6 +3051,79 @@ int dspi_debug_packets_intake(dspi_ctx *c, const void *arena, uint64_t arena_byt
     if ((rc = ensure(c, c->d_mixed, (size_t)c->n_streams * kIntakeOutFrame * n_blocks * block_len))) return rc;
     const PacketIn pk{arena, bit_depths, table, n_blocks, block_len};
     return launch_packets(c, pk);
+}
+
+// ---- outputs to a packet table (dspi_packets_out.h: the entry rule, the checks, the CPU path and the address arithmetic; dspi_packettx.hip: the kernels) ----
+static_assert(DSPI_PACKET_SKIP == kPacketSkip && DSPI_EMIT_CHECK_OVERLAP == kEmitCheckOverlap, "include/dspi.h and dspi_packets_out.h: one skip word, one flag");
+// refusals 2 to 5 of dspi_packets_emit behind the pointers, in their order, and the overlap rule when asked (dspi_packets_emit_check shares them)
+static int emit_refusals(dspi_ctx *c, const char *who, const uint8_t *formats, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes, bool overlap,
+                         uint64_t *bad_entry) {
+    const std::string w = std::string(who) + ": ";
+    uint64_t at = 0;
+    const EmitBad bad = packets_emit_check(formats, table, c->n_streams, (uint32_t)c->sm.n_pairs, n_blocks, block_len, DSPI_MAX_BLOCK_LEN, arena_bytes, host_activity(c), overlap, &at);
+    switch (bad) {
+    case EmitBad::Ok: return 0;
+    case EmitBad::Lengths: return fail(c, DSPI_E_INVAL, w + "1 <= block_len <= 192, n_blocks >= 1");
+    case EmitBad::Format: return fail(c, DSPI_E_INVAL, w + "the format of stream " + std::to_string(at) + " is neither 24 nor 32");
+    case EmitBad::Overflow: return fail(c, DSPI_E_INVAL, w + "the table has more than 2^31 - 1 entries");
+    case EmitBad::Entry: case EmitBad::Overlap: break;
+    }
+    if (bad_entry) *bad_entry = at;
+    const uint64_t per = (uint64_t)c->sm.n_pairs * n_blocks;
+    const std::string which = "entry " + std::to_string(at) + " (stream " + std::to_string(at / per) + ", pair " + std::to_string(at % per / n_blocks) + ", packet " + std::to_string(at % n_blocks) + ")";
+    return fail(c, DSPI_E_INVAL, w + which + (bad == EmitBad::Entry ? " is odd or its packet does not end inside the arena" : " overlaps another entry"));
+}
+
+int dspi_packets_emit_check(const dspi_ctx *c, const uint8_t *formats, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes, uint32_t check_flags,
+                            uint64_t *bad_entry) {
+    if (!c) return DSPI_E_INVAL;
+    dspi_ctx *const m = const_cast<dspi_ctx *>(c);
+    if (check_flags & ~DSPI_EMIT_CHECK_OVERLAP) return fail(m, DSPI_E_INVAL, "dspi_packets_emit_check: check_flags is 0 or DSPI_EMIT_CHECK_OVERLAP");
+    if (!formats || !table) return fail(m, DSPI_E_INVAL, "dspi_packets_emit_check: formats and table are required");
+    return emit_refusals(m, "dspi_packets_emit_check", formats, table, n_blocks, block_len, arena_bytes, check_flags & DSPI_EMIT_CHECK_OVERLAP, bad_entry);
+}
+
+int dspi_packets_emit(dspi_ctx *c, const int32_t *pairs, uint32_t n_blocks, uint32_t block_len, const uint8_t *formats, const uint64_t *table, void *arena, uint64_t arena_bytes,
+                      uint32_t flags) {
+    if (!c) return DSPI_E_INVAL;
+    // 1. the flags
+    if (flags & ~(DSPI_MEM_DEVICE | DSPI_OUT_TILED)) return fail(c, DSPI_E_INVAL, "dspi_packets_emit: the flags are DSPI_MEM_DEVICE and DSPI_OUT_TILED");
+    // 2. to 5.
+    if (!pairs || !formats || !table || !arena) return fail(c, DSPI_E_INVAL, "dspi_packets_emit: pairs, formats, table and arena are required");
+    int rc = emit_refusals(c, "dspi_packets_emit", formats, table, n_blocks, block_len, arena_bytes, false, nullptr);
+    if (rc) return rc;
+    const uint32_t P = (uint32_t)c->sm.n_pairs, R = (flags & DSPI_OUT_TILED) ? (uint32_t)c->sm.row : 0u;
+    if (!(flags & DSPI_MEM_DEVICE)) {      // the CPU path: the activity is the context's at the time of the call, as on the device
+        const uint8_t *const act = host_activity(c);
+        for (uint32_t s = 0; s < c->n_streams; s++)
+            if (!act || act[s]) packets_emit_cpu(static_cast<uint8_t *>(arena), pairs, table + (uint64_t)s * P * n_blocks, formats[s], s, P, n_blocks, block_len, R);
+        return DSPI_OK;
+    }
+    // 6.
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "dspi_packets_emit: a host-only context has no device memory");
+    if ((reinterpret_cast<uintptr_t>(pairs) & 15u) || (reinterpret_cast<uintptr_t>(arena) & 1u))
+        return fail(c, DSPI_E_INVAL, "dspi_packets_emit: device pairs are 16-byte aligned (every hipMalloc is) and the arena 2-byte");
+    if (R && emit_tiled_workgroups(c->n_streams, R, P, n_blocks, block_len) > 0x7fffffffull) return fail(c, DSPI_E_INVAL, "dspi_packets_emit: more than 2^31 - 1 workgroups");
+    HIPCK(c, hipSetDevice(c->device));
+    if (c->n_paused && (rc = upload_activity(c))) return rc;
+    const size_t entries = (size_t)c->n_streams * P * n_blocks;
+    if ((rc = upload_via_move_area(c, c->d_emit_tab, "hipHostMalloc failed (emit table)", {{table, entries * 8}, {formats, c->n_streams}}))) return rc;
+    const uint64_t *const tab = c->d_emit_tab;
+    const hipError_t e = launch_packettx(pairs, R, tab, reinterpret_cast<const uint8_t *>(tab + entries), activity(c), arena, c->n_streams, P, n_blocks, block_len, c->hs);
+    return e == hipSuccess ? DSPI_OK : fail(c, DSPI_E_HIP, std::string("packetiser launch: ") + hipGetErrorString(e));
+}
+
+// the one launch of a dspi_packets_emit call alone, the table and the formats already in device memory: what tools/bench_packets_out.py times
+// (no upload; NOTHING is checked but the pointers and the lengths — the table must be one that dspi_packets_emit_check accepts)
+int dspi_debug_packets_emit_launch(dspi_ctx *c, const int32_t *pairs, uint32_t n_blocks, uint32_t block_len, const uint8_t *formats, const uint64_t *table, void *arena, uint32_t flags) {
+    if (!c || !pairs || !formats || !table || !arena || !n_blocks || !block_len || block_len > DSPI_MAX_BLOCK_LEN || (flags & ~(DSPI_MEM_DEVICE | DSPI_OUT_TILED)) || !(flags & DSPI_MEM_DEVICE) ||
+        (reinterpret_cast<uintptr_t>(pairs) & 15u) || (reinterpret_cast<uintptr_t>(arena) & 1u))
+        return DSPI_E_INVAL;
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no packetiser");
+    HIPCK(c, hipSetDevice(c->device));
+    if (c->n_paused) { int rc = upload_activity(c); if (rc) return rc; }
+    const hipError_t e = launch_packettx(pairs, (flags & DSPI_OUT_TILED) ? (uint32_t)c->sm.row : 0u, table, formats, activity(c), arena, c->n_streams, (uint32_t)c->sm.n_pairs, n_blocks, block_len, c->hs);
+    return e == hipSuccess ? DSPI_OK : fail(c, DSPI_E_HIP, std::string("packetiser launch: ") + hipGetErrorString(e));
 }
 
 int dspi_pdm_running(dspi_ctx *c, uint32_t first, uint32_t count, const uint8_t *set, uint8_t *get) {

@@ -33,6 +33,8 @@ OUT_I2S_SLOTS = 0x8
 OUT_SPDIF = 0x10
 OUT_CLIP_FLAGS = 0x20
 OUT_WIRE = 0x40      # dspi_process_sources only
+PACKET_SKIP = 2 ** 64 - 1      # dspi_packets_emit: a table entry that emits nothing
+EMIT_CHECK_OVERLAP = 0x1       # dspi_packets_emit_check only
 SRC_SPDIF, SRC_PCM16, SRC_PCM24 = 1, 16, 24
 SRC_LINK = 2         # dspi_process_patched / dspi_patched_bytes only
 MAX_VIEWS = 8
@@ -196,6 +198,10 @@ def lib() -> C.CDLL:
         L.dspi_packets_check.argtypes = [vp, vp, vp, u32, u32, C.c_uint64, C.POINTER(C.c_uint64)]
         L.dspi_process_packets.argtypes = [vp, vp, C.c_uint64, vp, vp, u32, u32, C.POINTER(_Out), vp, u32]
         L.dspi_debug_packets_intake.argtypes = [vp, vp, C.c_uint64, vp, vp, u32, u32]
+    if hasattr(L, "dspi_packets_emit"):      # (ABI 8 + outputs to a packet table: detected by symbol; with it dspi_packets_emit_check)
+        L.dspi_packets_emit_check.argtypes = [vp, vp, vp, u32, u32, C.c_uint64, u32, C.POINTER(C.c_uint64)]
+        L.dspi_packets_emit.argtypes = [vp, vp, u32, u32, vp, vp, vp, C.c_uint64, u32]
+        L.dspi_debug_packets_emit_launch.argtypes = [vp, vp, u32, u32, vp, vp, vp, u32]
     _lib = L
     return L
 
@@ -849,6 +855,49 @@ class Dspi:
         """dspi_debug_packets_intake: what process_packets_device runs in front of the chain, into the context's scratch; asynchronous, see sync()."""
         d, t = self._depths(bit_depths), self._packet_table(table, n_blocks)
         self._ck(self.L.dspi_debug_packets_intake(self.h, arena_ptr, arena_bytes, d.ctypes.data, t.ctypes.data, n_blocks, block_len), "debug_packets_intake")
+
+    # ---- outputs to a packet table (include/dspi.h: dspi_packets_emit) ----
+    def _formats(self, formats) -> np.ndarray:
+        f = np.ascontiguousarray(np.asarray(formats, dtype=np.uint8).reshape(-1))
+        assert f.size == self.n_streams, (f.size, self.n_streams)
+        return f
+
+    def _emit_table(self, table, n_blocks: int) -> np.ndarray:
+        t = np.ascontiguousarray(table, dtype=np.uint64)
+        assert t.size == self.n_streams * self.P * n_blocks, (t.shape, self.n_streams, self.P, n_blocks)
+        return t
+
+    def packets_emit_check(self, formats, table, n_blocks: int, block_len: int, arena_bytes: int, overlap: bool = False):
+        """dspi_packets_emit_check: None when a dspi_packets_emit call would accept this table (uint64 [n_streams][n_pairs][n_blocks], byte offsets
+        in an arena of arena_bytes, or PACKET_SKIP) and these formats (24 or 32 per stream), and, overlap=True, no two entries share a byte; raises
+        DspiError otherwise, after setting self.bad_entry to the index of the entry refused (None when the refusal is not about an entry).
+        Works on host-only contexts."""
+        f, t = self._formats(formats), self._emit_table(table, n_blocks)
+        bad = C.c_uint64(2 ** 64 - 1)
+        rc = self.L.dspi_packets_emit_check(self.h, f.ctypes.data, t.ctypes.data, n_blocks, block_len, arena_bytes, EMIT_CHECK_OVERLAP if overlap else 0, C.byref(bad))
+        self.bad_entry = None if rc == 0 or bad.value == 2 ** 64 - 1 else bad.value
+        self._ck(rc, "packets_emit_check")
+
+    def packets_emit_host(self, pairs: np.ndarray, n_blocks: int, block_len: int, formats, table, arena: np.ndarray, tiled: bool = False) -> np.ndarray:
+        """dspi_packets_emit on host arrays (the CPU path; works on host-only contexts): pairs int32 as a process call returned them
+        ([S][P][F][2], tiled=True: [tiles][2 P][F][R]); arena uint8, written in place where the table's entries point, and returned."""
+        f, t = self._formats(formats), self._emit_table(table, n_blocks)
+        F, R = n_blocks * block_len, self.tile_streams()
+        shape = ((self.n_streams + R - 1) // R, 2 * self.P, F, R) if tiled else (self.n_streams, self.P, F, 2)
+        assert pairs.dtype == np.int32 and pairs.flags.c_contiguous and pairs.shape == shape, (pairs.shape, shape)
+        assert arena.dtype == np.uint8 and arena.flags.c_contiguous and arena.ndim == 1
+        self._ck(self.L.dspi_packets_emit(self.h, pairs.ctypes.data, n_blocks, block_len, f.ctypes.data, t.ctypes.data, arena.ctypes.data, arena.size, OUT_TILED if tiled else 0), "packets_emit")
+        return arena
+
+    def packets_emit_device(self, pairs_ptr: int, n_blocks: int, block_len: int, formats, table, arena_ptr: int, arena_bytes: int, tiled: bool = False):
+        """dspi_packets_emit on raw device pointers (the formats and the table stay host arrays; the table may be reused when this returns).
+        Asynchronous on the context's stream, behind the process call that wrote the pairs; see sync()."""
+        f, t = self._formats(formats), self._emit_table(table, n_blocks)
+        self._ck(self.L.dspi_packets_emit(self.h, pairs_ptr, n_blocks, block_len, f.ctypes.data, t.ctypes.data, arena_ptr, arena_bytes, MEM_DEVICE | (OUT_TILED if tiled else 0)), "packets_emit")
+
+    def debug_packets_emit_launch(self, pairs_ptr: int, n_blocks: int, block_len: int, formats_ptr: int, table_ptr: int, arena_ptr: int, tiled: bool = False):
+        """dspi_debug_packets_emit_launch: the one launch of packets_emit_device, formats and table already in DEVICE memory and unchecked; asynchronous"""
+        self._ck(self.L.dspi_debug_packets_emit_launch(self.h, pairs_ptr, n_blocks, block_len, formats_ptr, table_ptr, arena_ptr, MEM_DEVICE | (OUT_TILED if tiled else 0)), "debug_packets_emit_launch")
 
     def pdm_restart(self, stream: int = ALL):
         self._ck(self.L.dspi_pdm_restart(self.h, stream), "pdm_restart")

@@ -1327,6 +1327,57 @@ int dspi_debug_patched_intake(dspi_ctx *ctx, const void *in, const uint8_t *sour
 int dspi_debug_packets_intake(dspi_ctx *ctx, const void *arena, uint64_t arena_bytes, const uint8_t *bit_depths, const uint64_t *table,
                               uint32_t n_blocks, uint32_t block_len);
 
+/* ---- outputs to a packet table, in departure order ------------------------------------------------------------------------------------------ */
+/* dspi_packets_emit is the packetiser that the packet-table section above leaves out: it takes the plain pair words that a process call wrote
+ * for this context and writes one packet per stream, pair and block into an arena, each where a table points, in the wire format of a USB
+ * audio packet or as the words stand.  It is stateless and runs behind any process call; no chain kernel is involved.
+ *   pairs     the SOURCE, only read: plain pair words as a process call wrote them for this context without DSPI_OUT_SPDIF, DSPI_OUT_I2S_SLOTS or
+ *             DSPI_OUT_WIRE.  With F = n_blocks * block_len: int32 [stream][pair][F][2], or with DSPI_OUT_TILED in flags
+ *             int32 [tile][output][F][R], R = dspi_tile_streams(), left = output 2p, right = output 2p + 1.
+ *   formats   uint8 [dspi_num_streams], HOST memory always, one value per stream.  32: a packet is block_len frames of the two int32 LE words as
+ *             they stand, 8 bytes per frame.  24: a packet is the low three bytes of each word, LE, L then R, 6 bytes per frame: byte for byte
+ *             a 24-bit USB packet, the very bytes dspi_process_packets reads at depth 24.
+ *   table     uint64 [dspi_num_streams][dspi_num_pairs][n_blocks], HOST memory always.  table[(s * n_pairs + p) * n_blocks + k] is the byte
+ *             offset in arena where packet k of pair p of stream s goes, or DSPI_PACKET_SKIP: that packet is not emitted.  The table goes up
+ *             with the call, through the context's pinned area: the caller may reuse its emit table when the call returns.
+ *   flags     DSPI_MEM_DEVICE: pairs and arena are device memory (pairs 16-byte aligned, as every allocation is; arena 2-byte) and the call is
+ *             asynchronous on the context's stream, behind the call that wrote pairs: no dspi_sync between them.  Without it both are host
+ *             memory, the call runs on the CPU, synchronously, and works on host-only contexts.  DSPI_OUT_TILED: the source layout, as above.
+ *             Every other bit is refused.
+ * AN EMIT ENTRY IS LEGAL when it is DSPI_PACKET_SKIP, or when it is even and offset + block_len * frame bytes <= arena_bytes.
+ * Entries of one call must not overlap each other or the source; the call does not check this.  Where two entries overlap, every byte of the
+ * overlap holds that byte of one of them, unspecified which.  In every case nothing outside the union of the entries is written:
+ * neighbouring bytes of the arena are never touched, not even by a read-modify-write, and may belong to someone else.
+ * Rows of PAUSED streams are neither read nor checked, their source columns are not read, and nothing is written for them.
+ * AN EMIT TABLE CAN BE THE NEXT CONTEXT'S INPUT TABLE: with format 24, the rows of context A's emit table for one pair, handed unchanged to
+ * dspi_process_packets on context B with every depth 24 and the same arena, feed B what A wrote; when A and B launch on one HIP stream no
+ * synchronisation is needed between the two calls, otherwise B's stream waits for A's (an event, or dspi_sync on A).
+ * REFUSALS of dspi_packets_emit, in this order (a refused call writes nothing):
+ *   1. DSPI_E_INVAL   a NULL ctx; a flag bit other than DSPI_MEM_DEVICE and DSPI_OUT_TILED
+ *   2. DSPI_E_INVAL   a NULL pairs, formats, table or arena; n_blocks == 0 or block_len == 0; block_len > DSPI_MAX_BLOCK_LEN
+ *   3. DSPI_E_INVAL   a format that is neither 24 nor 32 (any stream, paused or not, lowest first)
+ *   4. DSPI_E_INVAL   an emit table of more than 2^31 - 1 entries: dspi_num_streams * dspi_num_pairs * n_blocks
+ *   5. DSPI_E_INVAL   the first illegal emit entry of an active stream, in table order; the message names its index
+ *   6. DSPI_E_NODEVICE   DSPI_MEM_DEVICE on a host-only context (then DSPI_E_INVAL for a misaligned device pointer)
+ * dspi_packets_emit_check applies refusals 2 to 5 (no pairs, no arena) and works on host-only contexts.  With DSPI_EMIT_CHECK_OVERLAP in
+ * check_flags (any other bit: DSPI_E_INVAL) it then refuses the first entry, in table order, that shares a byte with another entry of an
+ * active stream; it finds it by sorting, on the CPU, and is the caller's choice.  At refusal 5 and at an overlap *bad_entry, when not NULL,
+ * takes the index of the entry refused, and is not written otherwise.
+ * LEFT OUT of the packetiser: the sub channel; wire-layout and S/PDIF sources; 16-bit packets; per-packet lengths; tables in device memory; a
+ * fused process-and-emit call; an option of dspi_host.
+ * The ABI stays 8: detect by symbol (dspi_packets_emit; with it dspi_packets_emit_check; additions only). */
+#define DSPI_PACKET_SKIP UINT64_MAX        /* a table entry that emits nothing */
+#define DSPI_EMIT_CHECK_OVERLAP 0x1u       /* dspi_packets_emit_check only */
+int dspi_packets_emit_check(const dspi_ctx *ctx, const uint8_t *formats, const uint64_t *table, uint32_t n_blocks, uint32_t block_len,
+                            uint64_t arena_bytes, uint32_t check_flags, uint64_t *bad_entry /* may be NULL */);
+int dspi_packets_emit(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_blocks, uint32_t block_len, const uint8_t *formats,
+                      const uint64_t *table, void *arena, uint64_t arena_bytes, uint32_t flags);
+/* The one launch of a dspi_packets_emit call on device buffers, alone: formats and table are DEVICE memory here, already uploaded, and are not
+ * checked — the table must be one that dspi_packets_emit_check accepts for this context.  flags as for the call, DSPI_MEM_DEVICE required.
+ * Asynchronous on the context's stream.  For timing (tools/bench_packets_out.py); comes with dspi_packets_emit. */
+int dspi_debug_packets_emit_launch(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_blocks, uint32_t block_len, const uint8_t *formats,
+                                   const uint64_t *table, void *arena, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif
