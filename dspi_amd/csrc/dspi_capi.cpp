@@ -131,13 +131,15 @@ struct dspi_ctx {
     DevBuf<int32_t> d_pdm_pack{mem};
     // the arrays that follow the row capacity cap_wg, in the order of their table (dspi_devmem.h kPersist): dspi_create, pdm_state, dspi_pdm_fade and the resizes walk it
     MemNode *const persist[kNumPersist] = {&d_state, &d_dlines, &d_ring, &d_pdm, &d_pdm_base};
-    // dspi_process_mixed (dspi_intake.h).  d_mixed: device buffers only — a scratch of n_streams * 6F bytes that the intake kernel writes and the
-    // chain reads, both on `hs`, asynchronously.  d_mixed_up: staged host buffers only — where a chunk's bytes go up as they are (on hs_in when
-    // the call has several chunks), the intake then writes d_in.  THE RULE: whatever a stream other than `hs` touches (hs_in: d_in, d_mixed_up)
-    // belongs to the staged path alone, which ends synchronised; nothing that an asynchronous call leaves in flight on `hs` is touched from
-    // another stream.  That is why the two paths do not share one scratch.  d_mixed_tab: the device's table of the call's layout, (n + 1) uint64
-    // offsets with the n depths behind them, read and written on `hs` only; it goes up through h_move, behind ev_move, and stays while the
-    // depths and the frame count repeat: mixed_depths / mixed_frames say what it holds (0 frames: nothing)
+    // The audio calls' front end (CallFront).  d_mixed: device buffers only — a scratch of n_streams * 6F bytes that the front end's kernels
+    // (the intake, the receivers: every kind but Pcm) write and the chain reads, both on `hs`, asynchronously.  d_mixed_up: staged host buffers
+    // only, mixed calls only — where a chunk's bytes go up as they are (on hs_in when the call has several chunks), the intake then writes
+    // d_in.  THE RULE: whatever a stream other than `hs` touches (hs_in: d_in, d_mixed_up) belongs to the staged path alone, which ends
+    // synchronised; nothing that an asynchronous call leaves in flight on `hs` is touched from another stream.  That is why the two paths do
+    // not share one scratch.  d_mixed_tab: the device's table of the call's front end, whichever kind (a mixed call's: (n + 1) uint64 offsets
+    // with the n depths behind them), read and written on `hs` only.  ONE owner: it goes up through upload_front_table alone (through h_move,
+    // behind ev_move), which forgets what the table held.  A mixed call's table stays while the depths and the frame count repeat:
+    // mixed_depths / mixed_frames say what it holds (0 frames: no mixed call's layout), and only intake_prepare sets them
     DevBuf<uint8_t> d_mixed{mem};
     DevBuf<uint8_t> d_mixed_up{mem};
     DevBuf<uint64_t> d_mixed_tab{mem};
@@ -191,6 +193,9 @@ struct dspi_ctx {
 namespace {
 
 int fail(dspi_ctx *c, int code, const std::string &msg) { if (c) c->err = msg; return code; }
+// two refusals that many calls share, each text once: a call that needs the GPU on a context without one, and a call's lengths (`who`: the public call)
+int refuse_host_only(dspi_ctx *c) { return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path"); }
+int refuse_lengths(dspi_ctx *c, const char *who) { return fail(c, DSPI_E_INVAL, std::string(who) + ": 1 <= block_len <= 192, n_blocks >= 1"); }
 
 #define HIPCK(c, call)                                                                                   \
     do {                                                                                                 \
@@ -962,7 +967,7 @@ int dspi_debug_image_count(dspi_ctx *c) {
 int dspi_debug_eq_taps(dspi_ctx *c, int32_t stream, int channel, const float *x, uint32_t n, float *taps, float *other) {
     if (!c || !x || !taps || !other || n == 0 || n > (1u << 20) || !valid_stream(c, stream) || stream < 0) return DSPI_E_INVAL;
     if (c->flavor != DSPI_FLAVOR_RP2350_F32 || channel < 0 || channel >= c->sm.n_ch) return DSPI_E_INVAL;
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if (c->device == DSPI_DEVICE_NONE) return refuse_host_only(c);
     HIPCK(c, hipSetDevice(c->device));
     DevImage img;
     readable(c, stream).build_image(img);
@@ -980,7 +985,7 @@ int dspi_debug_eq_taps(dspi_ctx *c, int32_t stream, int channel, const float *x,
 
 int dspi_debug_detmath(dspi_ctx *c, int which, const float *a, const float *b, uint32_t n, float *out) {
     if (!c || !a || !out || ((which == 1 || which == 4) && !b) || n == 0 || n > (1u << 24) || which < 0 || which > 4) return DSPI_E_INVAL;
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if (c->device == DSPI_DEVICE_NONE) return refuse_host_only(c);
     HIPCK(c, hipSetDevice(c->device));
     DevMem mem; DevBuf<float> d_a{mem}, d_b{mem}, d_o{mem}; ReleaseOnReturn scratch{mem};
     HipAlloc al;
@@ -1012,7 +1017,7 @@ static int stage_down(dspi_ctx *c, void *host, const void *staged, size_t bytes)
 
 int dspi_pdm_modulate(dspi_ctx *c, const int32_t *sub, uint32_t n_frames, uint32_t *words, uint32_t flags) {
     if (!c || !sub || !words || n_frames == 0) return DSPI_E_INVAL;
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if (c->device == DSPI_DEVICE_NONE) return refuse_host_only(c);
     HIPCK(c, hipSetDevice(c->device));
     int rc = pdm_state(c);
     if (rc) return rc;
@@ -1846,7 +1851,7 @@ static int spdif_rates(dspi_ctx *c, uint32_t &fs, SpdifRates &rates) {
 
 int dspi_spdif_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, uint32_t block_pos, uint32_t *subframes, uint32_t flags) {
     if (!c || !pairs || !subframes || n_frames == 0 || block_pos >= 192) return DSPI_E_INVAL;
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if (c->device == DSPI_DEVICE_NONE) return refuse_host_only(c);
     HIPCK(c, hipSetDevice(c->device));
     const bool tiled = flags & DSPI_OUT_TILED, dev = flags & DSPI_MEM_DEVICE;
     const size_t cols = tiled ? (size_t)c->n_wg * c->sm.row : (size_t)c->n_streams;
@@ -1870,7 +1875,7 @@ int dspi_spdif_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, uint
 // ---- I2S slots: pico_audio_i2s_multi/audio_i2s_multi.c:217-226 (dspi_spdif.hip) ----
 int dspi_i2s_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, uint32_t pair_mask, uint32_t *words, uint32_t flags) {
     if (!c || !pairs || !words || n_frames == 0 || (pair_mask >> c->sm.n_pairs) != 0) return DSPI_E_INVAL;
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if (c->device == DSPI_DEVICE_NONE) return refuse_host_only(c);
     HIPCK(c, hipSetDevice(c->device));
     if (pair_mask == DSPI_I2S_PAIRS_BY_TYPE) {          // the slots whose output type is I2S (output_types[], REQ_SET_OUTPUT_TYPE)
         const Params &p = readable(c, DSPI_ALL_STREAMS);
@@ -1922,7 +1927,7 @@ int dspi_spdif_stream_pos(dspi_ctx *c, uint32_t first, uint32_t count, const uin
 int dspi_spdif_encode_v(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos, uint32_t *subframes, uint32_t flags) {
     if (!c || !pairs || !subframes || !block_pos || n_frames == 0) return DSPI_E_INVAL;
     if (flags & ~(DSPI_MEM_DEVICE | DSPI_OUT_TILED)) return fail(c, DSPI_E_INVAL, "dspi_spdif_encode_v: undefined flag bits");
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if (c->device == DSPI_DEVICE_NONE) return refuse_host_only(c);
     const bool tiled = flags & DSPI_OUT_TILED, dev = flags & DSPI_MEM_DEVICE;
     // host positions are validated before anything is launched; device positions are the kernels' to reduce modulo 192
     if (!dev) for (uint32_t s = 0; s < c->n_streams; s++) if (block_pos[s] >= kSpdifBlock) return fail(c, DSPI_E_INVAL, "dspi_spdif_encode_v: a position is 0..191");
@@ -2063,36 +2068,51 @@ static int launch_pdm_streams(dspi_ctx *c, const PdmCall &pc, const CallLayout &
 // where the chain leaves the Q28 sub words of a dspi_process_pdm call whose caller passed no `sub`: the library's scratch (device memory)
 static int pdm_sub_scratch(dspi_ctx *c, const CallLayout &L) { return ensure(c, c->d_sub, L.sub_scratch.bytes); }
 
-// ---- dspi_process_mixed: the call's layout (null in the three paths below: one depth for the call) ----
-// A mixed call is planned as the 24-bit call it becomes (plan_call knows nothing of it); only the way its `pcm` area is filled differs.
-struct MixedIn {
-    const uint8_t *depths;             // the caller's, validated: 16 / 24, and in a dspi_process_sources call kSrcSpdif
-    std::vector<uint64_t> offsets;     // [n_streams + 1] (dspi_intake.h; with S/PDIF runs dspi_spdifrx.h)
-    SpdifRx *rx = nullptr;             // dspi_process_sources with an S/PDIF source: the caller's records [n_streams], in the call's memory; else null
+// ---- where the chain's input comes from: the front end of an audio call, built on the public call's stack ----
+// Whatever the kind, the call is planned as the PCM call it becomes (24 bit; plan_call knows nothing of the kinds); only the way its `pcm` area
+// is filled differs.  Pcm: the caller's buffer as it stands.  Every other kind fills d_mixed on the device route; Mixed alone has host routes too.
+struct CallFront {
+    enum Kind : uint8_t { Pcm, Mixed, Linked, Patched, Packets };
+    Kind kind = Pcm;
+    bool wire = false;                     // out->pairs in the wire layout (process_call)
+    const char *who = "dspi_process";      // the public call, for messages
+    SpdifRx *rx = nullptr;                 // the records of the S/PDIF streams [n_streams], or null when none is served.  Mixed: in the call's memory; Linked, Patched: device memory
+    const uint8_t *depths = nullptr;       // Mixed: 16 / 24, and in a dspi_process_sources call kSrcSpdif; Packets: 16 / 24.  The caller's, validated, like all that follows
+    const uint64_t *offsets = nullptr;     // Mixed: [n_streams + 1] (dspi_intake.h; with S/PDIF runs dspi_spdifrx.h)
+    const WireView *views = nullptr; uint32_t n_views = 0;      // Linked: the one view; Patched: [n_views], validated where an active LINK stream names them.  Wire words in device memory
+    const Link *links = nullptr;           // Linked: [n_streams], host memory, validated for the entries that are served
+    const PatchPlan *plan = nullptr;       // Patched (dspi_patch.h)
+    const uint64_t *table = nullptr; uint32_t n_blocks = 0, block_len = 0;      // Packets: [n_streams][n_blocks], host memory, validated for the active streams
+    bool host_capable() const { return kind == Pcm || kind == Mixed; }      // the others: the device route only
+    bool reads_pcm_in() const { return kind != Linked && kind != Patched; }      // (Patched: `in` may be null, when no active stream has a run; Packets: the arena)
 };
-static bool rx_stream(const dspi_ctx *c, const MixedIn &mx, uint32_t s) { return mx.depths[s] == kSrcSpdif && (!c->n_paused || c->active[s]); }
-// the path's scratch (d_mixed or d_mixed_up, `bytes`) and the device's table, before the first launch of the call (all-or-nothing: a call
-// that cannot have them runs nothing)
-static int intake_prepare(dspi_ctx *c, const MixedIn &mx, uint64_t frames, DevBuf<uint8_t> &scratch, size_t scratch_bytes) {
+static bool rx_stream(const dspi_ctx *c, const CallFront &f, uint32_t s) { return f.depths[s] == kSrcSpdif && (!c->n_paused || c->active[s]); }
+
+// THE owner of d_mixed_tab: every front end's table goes up here (through the pinned move area: the caller may reuse its own when the call
+// returns), and what goes up is no mixed call's layout until intake_prepare, the one other writer of the cache's key, says that it is
+static int upload_front_table(dspi_ctx *c, const char *why, std::initializer_list<std::pair<const void *, size_t>> parts) {
+    c->mixed_frames = 0;
+    return upload_via_move_area(c, c->d_mixed_tab, why, parts);
+}
+// Mixed: the path's scratch (d_mixed or d_mixed_up) and the device's table, which stays while the depths, the frame count and the intake's streams repeat
+static int intake_prepare(dspi_ctx *c, const CallFront &f, uint64_t frames, DevBuf<uint8_t> &scratch, size_t scratch_bytes) {
     int rc = ensure(c, scratch, scratch_bytes);
     if (rc) return rc;
     const size_t n = c->n_streams;
     std::vector<uint32_t> mask;      // S/PDIF sources in the call: the intake's streams, behind the depths (padded to a word)
-    if (mx.rx) {
+    if (f.rx) {
         mask.assign((n + 31) / 32, 0u);
-        for (uint32_t s = 0; s < n; s++) if (mx.depths[s] != kSrcSpdif && (!c->n_paused || c->active[s])) mask[s >> 5] |= 1u << (s & 31u);
+        for (uint32_t s = 0; s < n; s++) if (f.depths[s] != kSrcSpdif && (!c->n_paused || c->active[s])) mask[s >> 5] |= 1u << (s & 31u);
     }
-    if (c->mixed_frames == frames && c->mixed_depths.size() == n && !memcmp(c->mixed_depths.data(), mx.depths, n) && c->mixed_mask == mask) return 0;
-    c->mixed_frames = 0;
+    if (c->mixed_frames == frames && c->mixed_depths.size() == n && !memcmp(c->mixed_depths.data(), f.depths, n) && c->mixed_mask == mask) return 0;
     const uint32_t pad = 0;
-    if ((rc = upload_via_move_area(c, c->d_mixed_tab, "hipHostMalloc failed (mixed input table)",
-                                   {{mx.offsets.data(), (n + 1) * 8}, {mx.depths, n}, {&pad, (4 - n % 4) % 4}, {mask.data(), mask.size() * 4}}))) return rc;
-    c->mixed_depths.assign(mx.depths, mx.depths + n); c->mixed_frames = frames; c->mixed_mask.swap(mask);
+    if ((rc = upload_front_table(c, "hipHostMalloc failed (mixed input table)", {{f.offsets, (n + 1) * 8}, {f.depths, n}, {&pad, (4 - n % 4) % 4}, {mask.data(), mask.size() * 4}}))) return rc;
+    c->mixed_depths.assign(f.depths, f.depths + n); c->mixed_frames = frames; c->mixed_mask.swap(mask);
     return 0;
 }
 // the intake launch for streams [s0, s1): `src` holds the caller's bytes at their offsets, `dst` is what the chain reads
 // rx (a call with an S/PDIF source): the records in DEVICE memory; the intake then serves the PCM streams and the receiver kernel the others
-static int launch_intake_streams(dspi_ctx *c, uint64_t frames, const void *src, void *dst, size_t s0, size_t s1, SpdifRx *rx = nullptr) {
+static int launch_intake_streams(dspi_ctx *c, uint64_t frames, const void *src, void *dst, size_t s0, size_t s1, SpdifRx *rx) {
     const uint8_t *const depths = reinterpret_cast<const uint8_t *>(c->d_mixed_tab + c->n_streams + 1);
     const uint32_t *const pcm_streams = reinterpret_cast<const uint32_t *>(depths + ((size_t)c->n_streams + 3) / 4 * 4);
     // (a call whose every active stream is an S/PDIF source has nothing for the intake)
@@ -2102,18 +2122,9 @@ static int launch_intake_streams(dspi_ctx *c, uint64_t frames, const void *src, 
     return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("intake launch: ") + hipGetErrorString(e));
 }
 
-// ---- dspi_process_linked / dspi_wire_decode (dspi_link.h): the call's links ----
-// Like a mixed call, a linked call is planned as the 24-bit call it becomes; its `pcm` area, d_mixed, is filled by the link receivers from
-// another call's wire buffer.  The device route only.
-struct LinkIn {
-    const WireView *view;      // validated; wire in device memory
-    const Link *links;         // [n], host memory, validated for the entries that are served
-    SpdifRx *rx;               // [n] in device memory, or null when no served link is S/PDIF
-    dspi_ctx *producer;        // whose stream writes view->wire (null, or the context itself: nothing to wait for)
-};
+// ---- Linked, and dspi_wire_decode (dspi_link.h): the call's links ----
 // the device's table of a call's links: n + 1 offsets (what launch_spdifrx reads for the S/PDIF lines of a stream-major view), the n links, the n
-// kinds as bytes; an entry that is not served (a paused stream, a hole) has kind NONE there, so no kernel looks at its line.  It stands in the
-// mixed path's table, which then holds no mixed call's layout any more.
+// kinds as bytes; an entry that is not served (a paused stream, a hole) has kind NONE there, so no kernel looks at its line
 struct LinkTab { const uint64_t *offsets; const Link *links; const uint8_t *kinds; bool any_spdif, any_i2s; };
 static int link_table(dspi_ctx *c, const WireView &v, const Link *links, uint32_t n, const uint8_t *active, LinkTab &t) {
     std::vector<uint64_t> offsets((size_t)n + 1, 0u);
@@ -2128,104 +2139,97 @@ static int link_table(dspi_ctx *c, const WireView &v, const Link *links, uint32_
         t.any_spdif = t.any_spdif || dl[i].kind == kLinkSpdif;
         t.any_i2s = t.any_i2s || dl[i].kind == kLinkI2s;
     }
-    c->mixed_frames = 0;
-    if (int rc = upload_via_move_area(c, c->d_mixed_tab, "hipHostMalloc failed (link table)", {{offsets.data(), offsets.size() * 8}, {dl.data(), (size_t)n * 8}, {kinds.data(), kinds.size()}})) return rc;
+    if (int rc = upload_front_table(c, "hipHostMalloc failed (link table)", {{offsets.data(), offsets.size() * 8}, {dl.data(), (size_t)n * 8}, {kinds.data(), kinds.size()}})) return rc;
     t.offsets = c->d_mixed_tab;
     t.links = reinterpret_cast<const Link *>(c->d_mixed_tab + n + 1);
     t.kinds = reinterpret_cast<const uint8_t *>(c->d_mixed_tab + 2 * (size_t)n + 1);
     return 0;
 }
-// the link receivers of a dspi_process_linked call, into d_mixed, behind the producer's work where its stream is another one
-static int launch_links(dspi_ctx *c, const LinkIn &lk, uint64_t frames) {
+// what this context's stream does from here on runs behind what the producer of a view has queued so far (a view without one, the context's
+// own, a host-only producer: nothing to wait for).  "The producer's stream has come this far": recorded there, waited for here
+static int wait_for_producer(dspi_ctx *c, const WireView &v) {
+    dspi_ctx *const prod = static_cast<dspi_ctx *>(v.producer);
+    if (!prod || prod == c || prod->device == DSPI_DEVICE_NONE) return 0;
+    if (!c->ev_link) HIPCK(c, hipEventCreateWithFlags(&c->ev_link, hipEventDisableTiming));
+    HIPCK(c, hipEventRecord(c->ev_link, prod->hs));
+    HIPCK(c, hipStreamWaitEvent(c->hs, c->ev_link, 0));
+    return 0;
+}
+// Linked: the link receivers from another call's wire buffer, behind the producer's work
+static int launch_links(dspi_ctx *c, const CallFront &f, uint64_t frames) {
+    const WireView &v = *f.views;
     LinkTab t;
-    int rc = link_table(c, *lk.view, lk.links, c->n_streams, host_activity(c), t);
-    if (rc) return rc;
-    if (lk.producer && lk.producer != c) {
-        if (!c->ev_link) HIPCK(c, hipEventCreateWithFlags(&c->ev_link, hipEventDisableTiming));
-        HIPCK(c, hipEventRecord(c->ev_link, lk.producer->hs));
-        HIPCK(c, hipStreamWaitEvent(c->hs, c->ev_link, 0));
-    }
-    const hipError_t e = launch_linkrx(true, lk.view->wire, t.links, t.offsets, t.kinds, nullptr, lk.rx, c->d_mixed, (uint32_t)frames, lk.view->n_pairs, lk.view->tile_streams, c->n_streams,
-                                       t.any_spdif, t.any_i2s, c->hs);
+    int rc = link_table(c, v, f.links, c->n_streams, host_activity(c), t);
+    if (rc || (rc = wait_for_producer(c, v))) return rc;
+    const hipError_t e = launch_linkrx(true, v.wire, t.links, t.offsets, t.kinds, nullptr, f.rx, c->d_mixed, (uint32_t)frames, v.n_pairs, v.tile_streams, c->n_streams, t.any_spdif, t.any_i2s, c->hs);
     return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("link receiver launch: ") + hipGetErrorString(e));
 }
 
-// ---- dspi_process_patched (dspi_patch.h): the call's plan ----
-// The union of the two: planned as the 24-bit call it becomes, d_mixed filled by the intake and the receiver from `in`, by the link receivers
-// from the stream-major views and by the patch receiver from every tiled view.  The device route only.
-struct PatchIn {
-    const void *in;             // device memory, or null when no active stream has a run
-    const WireView *views;      // [n_views], validated where an active LINK stream names them
-    const dspi_wire_view *cviews;      // the same, for the producers
-    uint32_t n_views;
-    SpdifRx *rx;                // [n] in device memory, or null when nothing served is S/PDIF
-    const PatchPlan *plan;
-};
-// the front end of a patched call, into d_mixed: at most one intake launch, one receiver launch over `in`, two launches per stream-major view
-// and one for all tiled views; each view's kernels behind its producer's work where that runs on another stream.  The plan's table stands in
-// the mixed path's table, which then holds no mixed call's layout any more.
-static int launch_patched(dspi_ctx *c, const PatchIn &pi, uint64_t frames) {
-    const PatchPlan &p = *pi.plan;
-    c->mixed_frames = 0;
-    if (int rc = upload_via_move_area(c, c->d_mixed_tab, "hipHostMalloc failed (patch table)", {{p.table.data(), p.table.size() * 8}})) return rc;
+// Patched (dspi_patch.h), the union of the two: at most one intake launch, one receiver launch over `in` (device memory, or null when no active
+// stream has a run), two launches per stream-major view and one for all tiled views; each view's kernels behind its producer's work
+static int launch_patched(dspi_ctx *c, const CallFront &f, const void *in, uint64_t frames) {
+    const PatchPlan &p = *f.plan;
+    int rc = upload_front_table(c, "hipHostMalloc failed (patch table)", {{p.table.data(), p.table.size() * 8}});
+    if (rc) return rc;
     const uint64_t *const tab = c->d_mixed_tab;
     const uint8_t *const in_kinds = reinterpret_cast<const uint8_t *>(tab + p.in_kinds);
     hipError_t e = hipSuccess;
-    if (p.any_pcm) e = launch_intake(pi.in, tab + p.in_offsets, in_kinds, reinterpret_cast<const uint32_t *>(tab + p.pcm_mask), c->d_mixed, frames, 0u, c->n_streams, c->hs);
-    if (e == hipSuccess && p.any_spdif_in) e = launch_spdifrx(true, pi.in, tab + p.in_offsets, in_kinds, nullptr, pi.rx, c->d_mixed, frames, 0u, c->n_streams, c->hs);
+    if (p.any_pcm) e = launch_intake(in, tab + p.in_offsets, in_kinds, reinterpret_cast<const uint32_t *>(tab + p.pcm_mask), c->d_mixed, frames, 0u, c->n_streams, c->hs);
+    if (e == hipSuccess && p.any_spdif_in) e = launch_spdifrx(true, in, tab + p.in_offsets, in_kinds, nullptr, f.rx, c->d_mixed, frames, 0u, c->n_streams, c->hs);
     if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string("intake launch: ") + hipGetErrorString(e));
     // one wait per DISTINCT producer that an active LINK stream's view names, all of them before the first kernel that reads a view
-    for (uint32_t v = 0; v < pi.n_views; v++) {
-        dspi_ctx *const prod = p.view[v].used ? pi.cviews[v].producer : nullptr;
-        if (!prod || prod == c || prod->device == DSPI_DEVICE_NONE) continue;
-        bool seen = false;
-        for (uint32_t u = 0; u < v; u++) seen = seen || (p.view[u].used && pi.cviews[u].producer == prod);
-        if (seen) continue;
-        if (!c->ev_link) HIPCK(c, hipEventCreateWithFlags(&c->ev_link, hipEventDisableTiming));
-        HIPCK(c, hipEventRecord(c->ev_link, prod->hs));
-        HIPCK(c, hipStreamWaitEvent(c->hs, c->ev_link, 0));
+    for (uint32_t v = 0; v < f.n_views; v++) {
+        bool seen = !p.view[v].used;      // (an unused view's producer is nobody's business)
+        for (uint32_t u = 0; u < v; u++) seen = seen || (p.view[u].used && f.views[u].producer == f.views[v].producer);
+        if (!seen && (rc = wait_for_producer(c, f.views[v]))) return rc;
     }
-    for (uint32_t v = 0; v < pi.n_views && e == hipSuccess; v++) {
+    for (uint32_t v = 0; v < f.n_views && e == hipSuccess; v++) {
         const PatchPlan::View &pv = p.view[v];
-        if (!pv.used || pi.views[v].tile_streams) continue;
-        e = launch_linkrx(true, pi.views[v].wire, tab + pv.links, tab + pv.offsets, reinterpret_cast<const uint8_t *>(tab + pv.kinds), nullptr, pi.rx, c->d_mixed, (uint32_t)frames,
-                          pi.views[v].n_pairs, 0u, c->n_streams, pv.any_spdif, pv.any_i2s, c->hs);
+        if (!pv.used || f.views[v].tile_streams) continue;
+        e = launch_linkrx(true, f.views[v].wire, tab + pv.links, tab + pv.offsets, reinterpret_cast<const uint8_t *>(tab + pv.kinds), nullptr, f.rx, c->d_mixed, (uint32_t)frames,
+                          f.views[v].n_pairs, 0u, c->n_streams, pv.any_spdif, pv.any_i2s, c->hs);
     }
-    if (e == hipSuccess && p.any_tiled) e = launch_patchrx(tab + p.cols, pi.rx, c->d_mixed, (uint32_t)frames, c->n_streams, p.tiled_spdif, c->hs);
+    if (e == hipSuccess && p.any_tiled) e = launch_patchrx(tab + p.cols, f.rx, c->d_mixed, (uint32_t)frames, c->n_streams, p.tiled_spdif, c->hs);
     return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("patch receiver launch: ") + hipGetErrorString(e));
 }
 
-// ---- dspi_process_packets (dspi_packets.h): the call's table ----
-// Planned as the 24-bit call it becomes, d_mixed filled by the packet receiver from the caller's arena.  The device route only.
-struct PacketIn {
-    const void *arena;          // device memory
-    const uint8_t *depths;      // [n], host memory, validated
-    const uint64_t *table;      // [n][n_blocks], host memory, validated for the active streams
-    uint32_t n_blocks, block_len;
-};
-// the front end of a packet call, into d_mixed: the table and the depths go up through the pinned move area (the caller may reuse its table
-// when the call returns), then one launch.  They stand in the mixed path's table, which then holds no mixed call's layout any more.
-static int launch_packets(dspi_ctx *c, const PacketIn &pk) {
-    const size_t entries = (size_t)c->n_streams * pk.n_blocks;
-    c->mixed_frames = 0;
-    if (int rc = upload_via_move_area(c, c->d_mixed_tab, "hipHostMalloc failed (packet table)", {{pk.table, entries * 8}, {pk.depths, c->n_streams}})) return rc;
+// Packets (dspi_packets.h): the table with the depths behind it, then the packet receiver over the caller's arena (device memory)
+static int launch_packets(dspi_ctx *c, const CallFront &f, const void *arena) {
+    const size_t entries = (size_t)c->n_streams * f.n_blocks;
+    if (int rc = upload_front_table(c, "hipHostMalloc failed (packet table)", {{f.table, entries * 8}, {f.depths, c->n_streams}})) return rc;
     const uint64_t *const tab = c->d_mixed_tab;
-    const hipError_t e = launch_packetrx(pk.arena, tab, reinterpret_cast<const uint8_t *>(tab + entries), activity(c), c->d_mixed, c->n_streams, pk.n_blocks, pk.block_len, c->hs);
+    const hipError_t e = launch_packetrx(arena, tab, reinterpret_cast<const uint8_t *>(tab + entries), activity(c), c->d_mixed, c->n_streams, f.n_blocks, f.block_len, c->hs);
     return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("packet receiver launch: ") + hipGetErrorString(e));
 }
 
+// ---- the device route's front end, in two steps (process_call and process_device; the dspi_debug_*_intake calls run the same two) ----
+// what must exist before the first launch, so that a call which cannot have it runs nothing: Mixed, the path's scratch and the table (on the
+// direct path the CPU widens into the pinned area: nothing); the other kinds, the scratch their receivers write
+static int front_prepare(dspi_ctx *c, const CallFront &f, CallMem mem, uint64_t frames, size_t pcm_bytes) {
+    if (f.kind == CallFront::Pcm || mem == CallMem::Direct) return 0;
+    if (f.kind != CallFront::Mixed) return ensure(c, c->d_mixed, pcm_bytes);
+    return mem == CallMem::Device ? intake_prepare(c, f, frames, c->d_mixed, pcm_bytes) : intake_prepare(c, f, frames, c->d_mixed_up, (size_t)f.offsets[c->n_streams]);
+}
+// the launches that fill d_mixed from `pcm_in` (Pcm: none); *chain_pcm: what the chain then reads
+static int front_launch(dspi_ctx *c, const CallFront &f, const void *pcm_in, uint64_t frames, const void **chain_pcm) {
+    *chain_pcm = f.kind == CallFront::Pcm ? pcm_in : c->d_mixed.get();
+    switch (f.kind) {
+    case CallFront::Pcm: break;
+    case CallFront::Mixed: return launch_intake_streams(c, frames, pcm_in, c->d_mixed, 0, c->n_streams, f.rx);
+    case CallFront::Linked: return launch_links(c, f, frames);
+    case CallFront::Patched: return launch_patched(c, f, pcm_in, frames);
+    case CallFront::Packets: return launch_packets(c, f, pcm_in);
+    }
+    return 0;
+}
+
 // ---- device buffers: the caller's own, asynchronous on the context's stream ----
-static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, const PdmCall *pc, const MixedIn *mx, const LinkIn *lk = nullptr,
-                          const PatchIn *pt = nullptr, const PacketIn *pk = nullptr) {
-    a.pcm = pcm_in; a.pairs = out->pairs; a.sub = out->sub; a.peaks = out->peaks;
+static int process_device(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, const PdmCall *pc, const CallFront &front) {
+    a.pairs = out->pairs; a.sub = out->sub; a.peaks = out->peaks;
     int rc = 0;
     if (pc && !out->sub) { if ((rc = pdm_sub_scratch(c, L))) return rc; a.sub = c->d_sub; }
     if (L.spdif_two_pass && (rc = ensure(c, c->d_spdif_words, L.two_pass_bytes))) return rc;
-    if (mx) { if ((rc = launch_intake_streams(c, L.frames, pcm_in, c->d_mixed, 0, c->n_streams, mx->rx))) return rc; a.pcm = c->d_mixed; }
-    if (lk) { if ((rc = launch_links(c, *lk, L.frames))) return rc; a.pcm = c->d_mixed; }
-    if (pt) { if ((rc = launch_patched(c, *pt, L.frames))) return rc; a.pcm = c->d_mixed; }
-    if (pk) { if ((rc = launch_packets(c, *pk))) return rc; a.pcm = c->d_mixed; }
-    if ((rc = launch_rows(c, a, L, 0, c->n_wg))) return rc;
+    if ((rc = front_launch(c, front, pcm_in, L.frames, &a.pcm)) || (rc = launch_rows(c, a, L, 0, c->n_wg))) return rc;
     if (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, pc->words, 0, c->n_streams))) return rc;
     return clip_out ? gather_clip(c, clip_out) : DSPI_OK;
 }
@@ -2254,20 +2258,20 @@ static void completion_word(dspi_ctx *c) {
 }
 
 static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags,
-                          std::chrono::steady_clock::time_point call_t0, const PdmCall *pc, const MixedIn *mx) {
+                          std::chrono::steady_clock::time_point call_t0, const PdmCall *pc, const CallFront &front) {
     int rc = direct_area(c, L.direct_bytes);
     if (rc) return rc;
     char *const h = c->h_direct, *const d = c->h_direct.device();
     std::vector<std::pair<uint32_t, SpdifRx>> rx_after;      // the records of the call's S/PDIF streams as the call leaves them: the caller's change when it succeeds
-    if (mx) {      // the copy widens, or decodes, as it copies (a paused stream's bytes are not read, and nobody reads its run of the area)
+    if (front.kind == CallFront::Mixed) {      // the copy widens, or decodes, as it copies (a paused stream's bytes are not read, and nobody reads its run of the area)
         for (uint32_t s = 0; s < c->n_streams; s++) {
             if (c->n_paused && !c->active[s]) continue;
             uint8_t *const run = reinterpret_cast<uint8_t *>(h) + (size_t)s * L.pcm.per;
-            const uint8_t *const src = static_cast<const uint8_t *>(pcm_in) + mx->offsets[s];
-            if (mx->depths[s] == kSrcSpdif) {
-                rx_after.emplace_back(s, mx->rx[s]);
+            const uint8_t *const src = static_cast<const uint8_t *>(pcm_in) + front.offsets[s];
+            if (front.depths[s] == kSrcSpdif) {
+                rx_after.emplace_back(s, front.rx[s]);
                 spdifrx_line_cpu(&rx_after.back().second, src, L.frames, nullptr, run);
-            } else intake_widen_cpu(run, src, mx->depths[s], L.frames);
+            } else intake_widen_cpu(run, src, front.depths[s], L.frames);
         }
     } else memcpy(h, pcm_in, L.pcm.bytes);
     a.pcm = d;
@@ -2338,7 +2342,7 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     if (out->peaks) memcpy(out->peaks, h + L.peaks.off, L.peaks.bytes);
     if (clip_out) memcpy(clip_out, h + L.clip.off, L.clip.bytes);
     if (pc) memcpy(pc->words, h + L.pdm_words.off, L.pdm_words.bytes);
-    for (const auto &r : rx_after) mx->rx[r.first] = r.second;
+    for (const auto &r : rx_after) front.rx[r.first] = r.second;
     return DSPI_OK;
 }
 
@@ -2347,7 +2351,8 @@ static int process_direct(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
 // cut into chunks and chunk i's D2H runs while chunk i+1 computes and chunk i+2 uploads (three streams, events).  The caller's
 // buffers are pinned for the duration of the call (hipHostRegister: ~8 ms per GiB) so that the copies are asynchronous DMA; when
 // that is refused (already registered, read-only mapping ...) the copies still work, just synchronously. ----
-static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags, const PdmCall *pc, const MixedIn *mx) {
+static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void *pcm_in, const dspi_out *out, uint16_t *clip_out, uint32_t flags, const PdmCall *pc, const CallFront &front) {
+    const bool mixed = front.kind == CallFront::Mixed;
     int rc;
     if ((rc = ensure(c, c->d_in, L.pcm.bytes))) return rc;
     a.pcm = c->d_in;
@@ -2387,9 +2392,9 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     // dspi_process_sources: the records of the call's S/PDIF streams go up ahead of the first launch and come down behind the last one (the
     // other entries of the caller's array are neither read nor written: zeros go up in their place)
     std::vector<SpdifRx> rx_stage;
-    if (mx && mx->rx) {
+    if (mixed && front.rx) {
         rx_stage.assign(c->n_streams, SpdifRx{});
-        for (uint32_t s = 0; s < c->n_streams; s++) if (rx_stream(c, *mx, s)) rx_stage[s] = mx->rx[s];
+        for (uint32_t s = 0; s < c->n_streams; s++) if (rx_stream(c, front, s)) rx_stage[s] = front.rx[s];
         if ((rc = ensure(c, c->d_rx, rx_stage.size() * sizeof(SpdifRx)))) return rc;
         HIPCK(c, hipMemcpyAsync(c->d_rx, rx_stage.data(), rx_stage.size() * sizeof(SpdifRx), hipMemcpyHostToDevice, c->hs));
     }
@@ -2397,9 +2402,9 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     // the caller's buffers and the staging buffers: a row range is one contiguous piece of each (tiled words: whole tiles; else streams)
     // (dspi_process_mixed: the caller's PCM is as long as its depths make it, and a chunk's piece of it goes up to the same place of d_mixed_up)
     CallBuffer pcm_b = L.pcm;
-    if (mx) pcm_b.bytes = (size_t)mx->offsets.back();
+    if (mixed) pcm_b.bytes = (size_t)front.offsets[c->n_streams];
     struct Buf { void *host; void *dev; const CallBuffer &b; const char *what; bool pinned; };
-    Buf bufs[5] = {{const_cast<void *>(pcm_in), mx ? (void *)c->d_mixed_up : c->d_in, pcm_b, "H2D", false}, {out->pairs, a.pairs, L.pairs, "D2H pairs", false},
+    Buf bufs[5] = {{const_cast<void *>(pcm_in), mixed ? (void *)c->d_mixed_up : c->d_in, pcm_b, "H2D", false}, {out->pairs, a.pairs, L.pairs, "D2H pairs", false},
                    {out->sub, a.sub, L.sub, "D2H sub", false}, {out->peaks, a.peaks, L.peaks, "D2H peaks", false},
                    {pc ? pc->words : nullptr, c->d_pdm_out, L.pdm_words, "D2H pdm words", false}};
     if (n_chunks > 1)
@@ -2436,9 +2441,9 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
             return kind == hipMemcpyHostToDevice ? hipMemcpyAsync(d, h, n, kind, s) : hipMemcpyAsync(h, d, n, kind, s);
         };
         hipStream_t sin = n_chunks > 1 ? c->hs_in : c->hs, sout = n_chunks > 1 ? c->hs_out : c->hs;
-        if (mx) {
+        if (mixed) {
             uint64_t b0, b1;
-            intake_row_range(mx->offsets.data(), c->n_streams, row, r0, r1, &b0, &b1);
+            intake_row_range(front.offsets, c->n_streams, row, r0, r1, &b0, &b1);
             he = hipMemcpyAsync(c->d_mixed_up + b0, static_cast<const char *>(pcm_in) + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, sin);
         } else he = copy(bufs[0], hipMemcpyHostToDevice, sin);
         if (he != hipSuccess) return fail_hip(he, bufs[0].what);
@@ -2446,7 +2451,7 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
             if ((he = hipEventRecord(c->pipe_events[2 * ch], sin)) != hipSuccess || (he = hipStreamWaitEvent(c->hs, c->pipe_events[2 * ch], 0)) != hipSuccess) return fail_hip(he, "event");
         }
         if (pc && !out->sub) a.sub = c->d_sub - s0 * L.frames;      // (the chunk's first stream or tile stands at the scratch's start, in both layouts)
-        if (mx && (rc = launch_intake_streams(c, L.frames, c->d_mixed_up, c->d_in, s0, s1, mx->rx ? c->d_rx.get() : nullptr))) { unpin(); return rc; }
+        if (mixed && (rc = launch_intake_streams(c, L.frames, c->d_mixed_up, c->d_in, s0, s1, front.rx ? c->d_rx.get() : nullptr))) { unpin(); return rc; }
         if ((rc = launch_rows(c, a, L, r0, r1)) || (pc && (rc = launch_pdm_streams(c, *pc, L, a.tiled_out != 0, a.sub, c->d_pdm_out, s0, s1)))) { unpin(); return rc; }
         if (n_chunks > 1) {
             if ((he = hipEventRecord(c->pipe_events[2 * ch + 1], c->hs)) != hipSuccess || (he = hipStreamWaitEvent(sout, c->pipe_events[2 * ch + 1], 0)) != hipSuccess) return fail_hip(he, "event");
@@ -2465,14 +2470,15 @@ static int process_staged(dspi_ctx *c, const CallLayout &L, KArgs &a, const void
     }
     if ((he = hipStreamSynchronize(c->hs)) != hipSuccess) return fail_hip(he, "sync");
     unpin();
-    for (uint32_t s = 0; s < (uint32_t)rx_stage.size(); s++) if (rx_stream(c, *mx, s)) mx->rx[s] = rx_stage[s];
+    for (uint32_t s = 0; s < (uint32_t)rx_stage.size(); s++) if (rx_stream(c, front, s)) front.rx[s] = rx_stage[s];
     return DSPI_OK;
 }
 
-// the one body of dspi_process (pdm_words == nullptr), dspi_process_pdm and (mx: its layout) dspi_process_mixed on depths that differ
-// What the audio calls refuse about their flags: the two rules, each in one place.  process_call applies them where dspi_process always
-// has (the bits first of all, the combinations behind the host-only context's refusal: tests/test_capi.py pins that order);
-// dspi_process_mixed applies both ahead of its own refusals, as its contract orders them.  A new flag rule goes INTO one of the two.
+// ---- what the audio calls refuse, each rule in one place.  The rules are building blocks: every public call applies them in the order its
+// own contract in include/dspi.h numbers, which the CPU tests pin ----
+// The flags, two rules.  process_call applies them where dspi_process always has (the bits first of all, the combinations behind the
+// host-only context's refusal: tests/test_capi.py pins that order); dspi_process_mixed applies both ahead of its own refusals, as its
+// contract orders them.  A new flag rule goes INTO one of the two.
 static int check_flag_bits(dspi_ctx *c, uint32_t flags) {
     // undefined flag bits are refused, not ignored: a later ABI may give them a meaning that reads further members of dspi_out
     constexpr uint32_t kKnownFlags = DSPI_MEM_DEVICE | DSPI_OUT_TILED | DSPI_OUT_ENABLED_ONLY | DSPI_OUT_I2S_SLOTS | DSPI_OUT_SPDIF | DSPI_OUT_CLIP_FLAGS;
@@ -2488,14 +2494,50 @@ static bool wire_slots_in_play(const dspi_ctx *c) {
     for (size_t i = 0; i < c->images.size(); i++) if (c->images[i]) image_i2s[i] = wire_i2s_mask(c->images[i]->output_types, (uint32_t)c->sm.n_pairs);
     return wire_any_i2s(c->stream_image.data(), c->n_streams, host_activity(c), image_i2s.data());
 }
-// wire: dspi_process_wire and dspi_process_devices (flags carry DSPI_OUT_SPDIF, which the wire layout implies): out->pairs in the wire layout;
-// with DSPI_OUT_TILED beside it (dspi_process_devices alone; the callers have applied their own flag rule, dspi_wire.h) in the tiled wire layout
-static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags,
-                        const MixedIn *mx = nullptr, bool wire = false, const LinkIn *lk = nullptr, const PatchIn *pt = nullptr, const PacketIn *pk = nullptr) {
-    if (!c || !pcm_in || !out) return DSPI_E_INVAL;
+// The flag preamble of the calls that take DSPI_OUT_WIRE as a flag: *wire and the flags process_call gets (DSPI_OUT_WIRE stripped; with it
+// DSPI_OUT_SPDIF, which the wire layout implies, and the flags held to dspi_process_devices' rule).  device_only (dspi_process_linked,
+// _patched, _packets): DSPI_MEM_DEVICE is required, refused first of all, and the two rules above follow at once.  dspi_process_sources takes
+// host memory too, and leaves the two rules to mixed_call, which applies them behind its own argument refusals
+static int front_flags(dspi_ctx *c, const char *who, uint32_t *flags, bool *wire, bool device_only) {
+    if (device_only && !(*flags & DSPI_MEM_DEVICE)) return fail(c, DSPI_E_INVAL, std::string(who) + ": DSPI_MEM_DEVICE is required");
+    *wire = *flags & DSPI_OUT_WIRE;
+    *flags &= ~DSPI_OUT_WIRE;
+    if (*wire && !devices_process_flags_ok(*flags))
+        return fail(c, DSPI_E_INVAL, std::string(who) + ": with DSPI_OUT_WIRE the flags are DSPI_MEM_DEVICE, DSPI_OUT_TILED, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
+    int rc;
+    if (device_only && ((rc = check_flag_bits(c, *flags)) || (!*wire && (rc = check_flag_combinations(c, *flags))))) return rc;
+    if (*wire) *flags |= DSPI_OUT_SPDIF;
+    return 0;
+}
+// The lengths of a call
+static int check_lengths(dspi_ctx *c, const char *who, uint32_t n_blocks, uint32_t block_len) {
+    return (n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN) ? refuse_lengths(c, who) : 0;
+}
+// The one case in which a 16-bit sample and its widened twin part ways (dspi_intake.h), refused, not approximated: an active stream whose
+// entry of `kinds` is 16 with a preamp below 2^-103 on the float chain
+static int check_widening(dspi_ctx *c, const char *who, const uint8_t *kinds, const uint8_t *active) {
+    if (!c->flavor) return 0;
+    for (uint32_t s = 0; s < c->n_streams; s++) {
+        if (kinds[s] != 16 || (active && !active[s])) continue;
+        for (const float p : readable(c, (int32_t)s).preamp_linear) {
+            uint32_t w; memcpy(&w, &p, 4);
+            if (intake_preamp_breaks_widening(w))
+                return fail(c, DSPI_E_UNSUPPORTED, std::string(who) + ": stream " + std::to_string(s) + " takes 16-bit input with a preamp below 2^-103, where widening to 24 bit is not exact");
+        }
+    }
+    return 0;
+}
+
+// ---- the one body of every audio call ----
+// pcm_in: what the front end reads (front.reads_pcm_in(): required exactly then), at bit_depth where the front is Pcm; every other kind is the
+// 24-bit call it becomes.  pdm_words: dspi_process_pdm's words, or null.  front: where the chain's input comes from (CallFront; its public call
+// has refused what it refuses about its own arguments) and front.wire: out->pairs in the wire layout, the flags carrying DSPI_OUT_SPDIF, which
+// that layout implies; with DSPI_OUT_TILED beside it (the callers have applied their own flag rule, dspi_wire.h) in the tiled wire layout
+static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags, const CallFront &front) {
+    if (!c || !out || (!pcm_in && front.reads_pcm_in())) return DSPI_E_INVAL;
     int rc = check_flag_bits(c, flags);
     if (rc) return rc;
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if (c->device == DSPI_DEVICE_NONE) return refuse_host_only(c);
     if ((bit_depth != 16 && bit_depth != 24) || n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN)
         return fail(c, DSPI_E_INVAL, "bit_depth must be 16/24, 1 <= block_len <= 192, n_blocks >= 1");
     const auto call_t0 = std::chrono::steady_clock::now();
@@ -2510,22 +2552,19 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     in.pairs = out->pairs; in.sub = out->sub; in.peaks = out->peaks; in.clip = clip_out; in.no_direct = c->no_direct;
     in.all_latency = c->flavor != 0; in.spdif_per_stream = c->spdif_ps.on; in.pdm_words = pdm_words != nullptr;
     const bool tiled = flags & DSPI_OUT_TILED, spdif = flags & DSPI_OUT_SPDIF;
-    in.wire_tiled = wire && tiled;                                 // always two passes: there is no fused tiled encoder
-    in.wire_slots = wire && !tiled && wire_slots_in_play(c);      // none in play: the call IS the DSPI_OUT_SPDIF call, route and bytes
+    in.wire_tiled = front.wire && tiled;                           // always two passes: there is no fused tiled encoder
+    in.wire_slots = front.wire && !tiled && wire_slots_in_play(c);      // none in play: the call IS the DSPI_OUT_SPDIF call, route and bytes
     for (const PathInfo &pi : kPaths)
         if (pi.group != PathGroup::Latency && !c->plan.items[(int)pi.path].empty()) in.all_latency = false;
     const CallLayout L = plan_call(in);
-    if (!wire && (rc = check_flag_combinations(c, flags))) return rc;
+    if (!front.wire && (rc = check_flag_combinations(c, flags))) return rc;
     if (L.wire_tiled && L.frames > kWireTiledMaxFrames) return fail(c, DSPI_E_UNSUPPORTED, "dspi_process_devices: a tiled call carries at most 2 097 120 frames");
     if (L.spdif_two_pass && c->spdif_ps.on && (rc = upload_spdif_pos(c))) return rc;
     PdmCall pdm{pdm_words, nullptr};
     const PdmCall *const pc = pdm_words ? &pdm : nullptr;
     if (pc && (rc = pdm_prepare(c, pdm))) return rc;
-    if (mx && L.mem == CallMem::Device && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed, L.pcm.bytes))) return rc;
-    if (mx && L.mem == CallMem::Staged && (rc = intake_prepare(c, *mx, L.frames, c->d_mixed_up, (size_t)mx->offsets.back()))) return rc;
-    if (lk && (L.mem != CallMem::Device || (rc = ensure(c, c->d_mixed, L.pcm.bytes)))) return rc ? rc : fail(c, DSPI_E_INVAL, "dspi_process_linked: device memory only");
-    if (pt && (L.mem != CallMem::Device || (rc = ensure(c, c->d_mixed, L.pcm.bytes)))) return rc ? rc : fail(c, DSPI_E_INVAL, "dspi_process_patched: device memory only");
-    if (pk && (L.mem != CallMem::Device || (rc = ensure(c, c->d_mixed, L.pcm.bytes)))) return rc ? rc : fail(c, DSPI_E_INVAL, "dspi_process_packets: device memory only");
+    if (L.mem != CallMem::Device && !front.host_capable()) return fail(c, DSPI_E_INVAL, std::string(front.who) + ": device memory only");
+    if ((rc = front_prepare(c, front, L.mem, L.frames, L.pcm.bytes))) return rc;
 
     KArgs a{};
     a.img = c->d_images; a.stream_image = c->d_stream_image; a.vals = c->d_vals;
@@ -2545,9 +2584,9 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
     }
 
     switch (L.mem) {
-    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out, pc, mx, lk, pt, pk); break;
-    case CallMem::Direct: rc = process_direct(c, L, a, pcm_in, out, clip_out, flags, call_t0, pc, mx); break;
-    case CallMem::Staged: rc = process_staged(c, L, a, pcm_in, out, clip_out, flags, pc, mx); break;
+    case CallMem::Device: rc = process_device(c, L, a, pcm_in, out, clip_out, pc, front); break;
+    case CallMem::Direct: rc = process_direct(c, L, a, pcm_in, out, clip_out, flags, call_t0, pc, front); break;
+    case CallMem::Staged: rc = process_staged(c, L, a, pcm_in, out, clip_out, flags, pc, front); break;
     }
     if (rc == DSPI_OK && pc) { c->pdm_life.commit(); c->pdm_fade.commit(c->pdm_life, (uint32_t)L.frames); }      // a failed call leaves the running bytes and the fade positions alone
     if (rc == DSPI_OK && spdif) {      // a failed call leaves the block positions alone
@@ -2558,19 +2597,19 @@ static int process_call(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t
 }
 
 int dspi_process(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t flags) {
-    return process_call(c, pcm_in, bit_depth, n_blocks, block_len, out, nullptr, flags);
+    return process_call(c, pcm_in, bit_depth, n_blocks, block_len, out, nullptr, flags, CallFront{});
 }
 
 int dspi_process_pdm(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
     if (!c || !pdm_words) return DSPI_E_INVAL;
-    return process_call(c, pcm_in, bit_depth, n_blocks, block_len, out, pdm_words, flags);
+    return process_call(c, pcm_in, bit_depth, n_blocks, block_len, out, pdm_words, flags, CallFront{});
 }
 
 // ---- S/PDIF and I2S slots in one call, per device (dspi_wire.h: the layout and the rules; dspi_wire.hip: the encoder) ----
 int dspi_process_wire(dspi_ctx *c, const void *pcm_in, int bit_depth, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
     if (!c) return DSPI_E_INVAL;
     if (!wire_process_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_process_wire: the flags are DSPI_MEM_DEVICE, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
-    return process_call(c, pcm_in, bit_depth, n_blocks, block_len, out, pdm_words, flags | DSPI_OUT_SPDIF, nullptr, true);
+    return process_call(c, pcm_in, bit_depth, n_blocks, block_len, out, pdm_words, flags | DSPI_OUT_SPDIF, CallFront{CallFront::Pcm, true});
 }
 
 int dspi_wire_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos, uint32_t *wire, uint32_t flags) {
@@ -2579,7 +2618,7 @@ int dspi_wire_encode(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, const
     const bool dev = flags & DSPI_MEM_DEVICE;
     // host positions are validated before anything is launched; device positions are the kernel's to reduce modulo 192
     if (!dev) for (uint32_t s = 0; s < c->n_streams; s++) if (block_pos[s] >= kSpdifBlock) return fail(c, DSPI_E_INVAL, "dspi_wire_encode: a position is 0..191");
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if (c->device == DSPI_DEVICE_NONE) return refuse_host_only(c);
     HIPCK(c, hipSetDevice(c->device));
     const size_t in_b = (size_t)c->n_streams * c->sm.n_pairs * n_frames * 8, out_b = in_b * 2, pos_b = (size_t)c->n_streams * 4;
     const int32_t *d_in = pairs;
@@ -2607,8 +2646,7 @@ static int mixed_check(dspi_ctx *c, const uint8_t *depths, uint32_t n_blocks, ui
     const uint32_t bad = sources ? sources_check(depths, c->n_streams) : intake_check_depths(depths, c->n_streams);
     if (bad < c->n_streams && sources) return fail(c, DSPI_E_INVAL, std::string(who) + ": the source of stream " + std::to_string(bad) + " is none of DSPI_SRC_PCM16, DSPI_SRC_PCM24, DSPI_SRC_SPDIF");
     if (bad < c->n_streams) return fail(c, DSPI_E_INVAL, std::string(who) + ": the depth of stream " + std::to_string(bad) + " is neither 16 nor 24");
-    if (n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN) return fail(c, DSPI_E_INVAL, std::string(who) + ": 1 <= block_len <= 192, n_blocks >= 1");
-    return 0;
+    return check_lengths(c, who, n_blocks, block_len);
 }
 
 int dspi_mixed_pcm_bytes(const dspi_ctx *c, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len, uint64_t *total_bytes, uint64_t *offsets) {
@@ -2628,9 +2666,11 @@ static int mixed_call(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths
     if (rc) return rc;
     const bool spdif_in = sources && sources_any_spdif(bit_depths, c->n_streams);
     // every entry equal: the call IS dspi_process / dspi_process_pdm / dspi_process_wire at that depth (which refuses a bad flag bit and a host-only context itself)
-    if (const uint8_t depth = spdif_in ? 0 : intake_uniform_depth(bit_depths, c->n_streams)) return process_call(c, pcm_in, depth, n_blocks, block_len, out, pdm_words, flags, nullptr, wire);
+    if (const uint8_t depth = spdif_in ? 0 : intake_uniform_depth(bit_depths, c->n_streams))
+        return process_call(c, pcm_in, depth, n_blocks, block_len, out, pdm_words, flags, CallFront{CallFront::Pcm, wire});
     if ((rc = check_flag_bits(c, flags)) || (!wire && (rc = check_flag_combinations(c, flags)))) return rc;
-    MixedIn mx{bit_depths, std::vector<uint64_t>((size_t)c->n_streams + 1)};
+    std::vector<uint64_t> offsets((size_t)c->n_streams + 1);
+    CallFront mx{CallFront::Mixed, wire, who, nullptr, bit_depths, offsets.data()};
     if (spdif_in) {      // what an S/PDIF source asks of the call's arguments
         if (!rx) return fail(c, DSPI_E_INVAL, std::string(who) + ": an S/PDIF source needs the receiver records (rx)");
         mx.rx = reinterpret_cast<SpdifRx *>(rx);
@@ -2641,19 +2681,10 @@ static int mixed_call(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths
             for (uint32_t s = 0; s < c->n_streams; s++)
                 if (rx_stream(c, mx, s) && mx.rx[s].sync > kRxBlock) return fail(c, DSPI_E_INVAL, std::string(who) + ": the record of stream " + std::to_string(s) + " has sync > 192");
     }
-    if (!(sources ? sources_offsets(bit_depths, c->n_streams, (uint64_t)n_blocks * block_len, nullptr, mx.offsets.data())
-                  : intake_offsets(bit_depths, c->n_streams, (uint64_t)n_blocks * block_len, nullptr, mx.offsets.data()))) return fail(c, DSPI_E_INVAL, std::string(who) + ": the buffer's size overflows");
-    // the one case in which a 16-bit sample and its widened twin part ways (dspi_intake.h): refused, not approximated
-    if (c->flavor)
-        for (uint32_t s = 0; s < c->n_streams; s++) {
-            if (bit_depths[s] != 16 || (c->n_paused && !c->active[s])) continue;
-            for (const float p : readable(c, (int32_t)s).preamp_linear) {
-                uint32_t w; memcpy(&w, &p, 4);
-                if (intake_preamp_breaks_widening(w))
-                    return fail(c, DSPI_E_UNSUPPORTED, std::string(who) + ": stream " + std::to_string(s) + " takes 16-bit input with a preamp below 2^-103, where widening to 24 bit is not exact");
-            }
-        }
-    return process_call(c, pcm_in, 24, n_blocks, block_len, out, pdm_words, flags, &mx, wire);
+    if (!(sources ? sources_offsets(bit_depths, c->n_streams, (uint64_t)n_blocks * block_len, nullptr, offsets.data())
+                  : intake_offsets(bit_depths, c->n_streams, (uint64_t)n_blocks * block_len, nullptr, offsets.data()))) return fail(c, DSPI_E_INVAL, std::string(who) + ": the buffer's size overflows");
+    if ((rc = check_widening(c, who, bit_depths, host_activity(c)))) return rc;
+    return process_call(c, pcm_in, 24, n_blocks, block_len, out, pdm_words, flags, mx);
 }
 
 int dspi_process_mixed(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, uint32_t flags) {
@@ -2683,10 +2714,9 @@ int dspi_sources_bytes(const dspi_ctx *c, const uint8_t *sources, uint32_t n_blo
 
 int dspi_process_sources(dspi_ctx *c, const void *in, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len, const dspi_out *out, uint32_t *pdm_words, dspi_spdif_rx *rx, uint32_t flags) {
     if (!c) return DSPI_E_INVAL;
-    const bool wire = flags & DSPI_OUT_WIRE;
-    flags &= ~DSPI_OUT_WIRE;
-    if (wire && !devices_process_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_process_sources: with DSPI_OUT_WIRE the flags are DSPI_MEM_DEVICE, DSPI_OUT_TILED, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
-    return mixed_call(c, in, sources, n_blocks, block_len, out, pdm_words, wire ? flags | DSPI_OUT_SPDIF : flags, "dspi_process_sources", wire, true, rx);
+    bool wire;
+    if (int rc = front_flags(c, "dspi_process_sources", &flags, &wire, false)) return rc;
+    return mixed_call(c, in, sources, n_blocks, block_len, out, pdm_words, flags, "dspi_process_sources", wire, true, rx);
 }
 
 int dspi_spdif_decode(dspi_ctx *c, const uint32_t *subframes, uint32_t n_lines, uint32_t n_frames, dspi_spdif_rx *rx, int32_t *pairs, uint32_t flags) {
@@ -2703,7 +2733,7 @@ int dspi_spdif_decode(dspi_ctx *c, const uint32_t *subframes, uint32_t n_lines, 
             return fail(c, DSPI_E_INVAL, "dspi_spdif_decode: device pointers are 16-byte aligned");
     } else
         for (uint32_t l = 0; l < n_lines; l++) if (recs[l].sync > kRxBlock) return fail(c, DSPI_E_INVAL, "dspi_spdif_decode: the record of line " + std::to_string(l) + " has sync > 192");
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if (c->device == DSPI_DEVICE_NONE) return refuse_host_only(c);
     HIPCK(c, hipSetDevice(c->device));
     const size_t out_b = in_b / 2;
     const void *d_in = subframes;
@@ -2770,7 +2800,7 @@ int dspi_wire_decode(dspi_ctx *c, const dspi_wire_view *view, const dspi_link *l
     } else
         for (uint32_t i = 0; i < n_links; i++)
             if (lk[i].kind == kLinkSpdif && recs[i].sync > kRxBlock) return fail(c, DSPI_E_INVAL, "dspi_wire_decode: the record of link " + std::to_string(i) + " has sync > 192");
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if (c->device == DSPI_DEVICE_NONE) return refuse_host_only(c);
     HIPCK(c, hipSetDevice(c->device));
     WireView dv = v;
     void *d_out = pairs, *d_rx = rx;
@@ -2805,14 +2835,10 @@ int dspi_process_linked(dspi_ctx *c, const dspi_wire_view *view, const dspi_link
                         dspi_spdif_rx *rx, uint32_t flags) {
     if (!c || !view || !links || !out) return DSPI_E_INVAL;
     // 2. the flags
-    if (!(flags & DSPI_MEM_DEVICE)) return fail(c, DSPI_E_INVAL, "dspi_process_linked: DSPI_MEM_DEVICE is required");
-    const bool wire = flags & DSPI_OUT_WIRE;
-    flags &= ~DSPI_OUT_WIRE;
-    if (wire && !devices_process_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_process_linked: with DSPI_OUT_WIRE the flags are DSPI_MEM_DEVICE, DSPI_OUT_TILED, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
-    int rc;
-    if ((rc = check_flag_bits(c, flags)) || (!wire && (rc = check_flag_combinations(c, flags)))) return rc;
+    bool wire;
+    int rc = front_flags(c, "dspi_process_linked", &flags, &wire, true);
     // 3. the lengths
-    if (n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN) return fail(c, DSPI_E_INVAL, "dspi_process_linked: 1 <= block_len <= 192, n_blocks >= 1");
+    if (rc || (rc = check_lengths(c, "dspi_process_linked", n_blocks, block_len))) return rc;
     // 4. the view
     const WireView &v = *reinterpret_cast<const WireView *>(view);
     const Link *const lk = reinterpret_cast<const Link *>(links);
@@ -2828,8 +2854,9 @@ int dspi_process_linked(dspi_ctx *c, const dspi_wire_view *view, const dspi_link
     if (any_spdif && reinterpret_cast<uintptr_t>(rx) % 4u) return fail(c, DSPI_E_INVAL, "dspi_process_linked: device receiver records are 4-byte aligned");
     // 7. the producer
     if (view->producer && view->producer->device != DSPI_DEVICE_NONE && view->producer->device != c->device) return fail(c, DSPI_E_INVAL, "dspi_process_linked: the view's producer is on another HIP device");
-    LinkIn in{&v, lk, any_spdif ? reinterpret_cast<SpdifRx *>(rx) : nullptr, view->producer && view->producer->device != DSPI_DEVICE_NONE ? view->producer : nullptr};
-    return process_call(c, v.wire, 24, n_blocks, block_len, out, pdm_words, wire ? flags | DSPI_OUT_SPDIF : flags, nullptr, wire, &in);
+    CallFront in{CallFront::Linked, wire, "dspi_process_linked", any_spdif ? reinterpret_cast<SpdifRx *>(rx) : nullptr};
+    in.views = &v; in.n_views = 1; in.links = lk;
+    return process_call(c, nullptr, 24, n_blocks, block_len, out, pdm_words, flags, in);
 }
 
 // ---- the patch bay (dspi_patch.h: the layout, the refusals and the plan; dspi_patchrx.hip: the tiled receiver) ----
@@ -2841,21 +2868,23 @@ int dspi_patched_bytes(const dspi_ctx *c, const uint8_t *sources, uint32_t n_blo
     dspi_ctx *const m = const_cast<dspi_ctx *>(c);
     uint32_t at = 0;
     if (const char *why = patch_sources_why(sources, c->n_streams, &at)) return fail(m, DSPI_E_INVAL, "dspi_patched_bytes: stream " + std::to_string(at) + ": " + why);
-    if (n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN) return fail(m, DSPI_E_INVAL, "dspi_patched_bytes: 1 <= block_len <= 192, n_blocks >= 1");
+    if (int rc = check_lengths(m, "dspi_patched_bytes", n_blocks, block_len)) return rc;
     if (!patch_offsets(sources, c->n_streams, (uint64_t)n_blocks * block_len, total_bytes, offsets)) return fail(m, DSPI_E_INVAL, "dspi_patched_bytes: the buffer's size overflows");
     return DSPI_OK;
 }
 
-// refusals 3 to 10 of dspi_process_patched, in their order (dspi_debug_patched_intake shares them); *rx_needed: an active stream is an S/PDIF run or link
-static int patched_check(dspi_ctx *c, const char *who, const void *in, const uint8_t *sources, const dspi_wire_view *views, uint32_t n_views, const dspi_patch *patches,
-                         uint32_t n_blocks, uint32_t block_len, const dspi_spdif_rx *rx, bool *rx_needed) {
-    const std::string w = std::string(who) + ": ";
+// refusals 3 to 10 of dspi_process_patched, in their order (dspi_debug_patched_intake shares them), for f.who; and for a call that has passed
+// them its plan, with the descriptor's members that name it (f.rx: null unless an active stream is an S/PDIF run or link)
+static int patched_front(dspi_ctx *c, CallFront &f, PatchPlan &plan, const void *in, const uint8_t *sources, const dspi_wire_view *views, uint32_t n_views, const dspi_patch *patches,
+                         uint32_t n_blocks, uint32_t block_len, dspi_spdif_rx *rx) {
+    const std::string w = std::string(f.who) + ": ";
     const uint32_t n = c->n_streams;
     const uint8_t *const act = host_activity(c);
     const WireView *const vs = reinterpret_cast<const WireView *>(views);
     const Patch *const ps = reinterpret_cast<const Patch *>(patches);
     uint32_t at = 0;
-    if (n_blocks == 0 || block_len == 0 || block_len > DSPI_MAX_BLOCK_LEN) return fail(c, DSPI_E_INVAL, w + "1 <= block_len <= 192, n_blocks >= 1");
+    int rc = check_lengths(c, f.who, n_blocks, block_len);
+    if (rc) return rc;
     const uint64_t F = (uint64_t)n_blocks * block_len;
     if (const char *why = patch_sources_why(sources, n, &at)) return fail(c, DSPI_E_INVAL, w + "stream " + std::to_string(at) + ": " + why);
     const bool any_link = patch_any(sources, n, act, kSrcLink);
@@ -2863,26 +2892,18 @@ static int patched_check(dspi_ctx *c, const char *who, const void *in, const uin
         if (const char *why = patch_views_why(sources, n, act, vs, n_views, ps, F, &at)) return fail(c, DSPI_E_INVAL, w + why + " (view or stream " + std::to_string(at) + ")");
     if (const char *why = patch_in_why(in, sources, n, act)) return fail(c, DSPI_E_INVAL, w + why);
     if (const char *why = patch_rx_why(rx, sources, n, act, ps)) return fail(c, DSPI_E_INVAL, w + why);
-    *rx_needed = patch_needs_rx(sources, n, act, ps);
     uint64_t out_bytes = 0;
     if (!patch_offsets(sources, n, F, nullptr, nullptr) || __builtin_mul_overflow((uint64_t)n * kIntakeOutFrame, F, &out_bytes)) return fail(c, DSPI_E_INVAL, w + "the buffer's size overflows");
-    // the one case in which a 16-bit sample and its widened twin part ways (dspi_intake.h): refused, not approximated
-    if (c->flavor)
-        for (uint32_t s = 0; s < n; s++) {
-            if (sources[s] != 16 || (act && !act[s])) continue;
-            for (const float p : readable(c, (int32_t)s).preamp_linear) {
-                uint32_t bits; memcpy(&bits, &p, 4);
-                if (intake_preamp_breaks_widening(bits))
-                    return fail(c, DSPI_E_UNSUPPORTED, w + "stream " + std::to_string(s) + " takes 16-bit input with a preamp below 2^-103, where widening to 24 bit is not exact");
-            }
-        }
+    if ((rc = check_widening(c, f.who, sources, act))) return rc;
     if (any_link)
         for (uint32_t s = 0; s < n; s++) {
             if (sources[s] != kSrcLink || (act && !act[s])) continue;
             const dspi_ctx *const prod = views[ps[s].view].producer;
             if (prod && prod->device != DSPI_DEVICE_NONE && prod->device != c->device) return fail(c, DSPI_E_INVAL, w + "the producer of view " + std::to_string(ps[s].view) + " is on another HIP device");
         }
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if (c->device == DSPI_DEVICE_NONE) return refuse_host_only(c);
+    f.views = vs; f.n_views = n_views; f.plan = &plan; f.rx = patch_needs_rx(sources, n, act, ps) ? reinterpret_cast<SpdifRx *>(rx) : nullptr;
+    patch_plan(sources, n, act, vs, n_views, ps, F, plan);
     return 0;
 }
 
@@ -2890,20 +2911,13 @@ int dspi_process_patched(dspi_ctx *c, const void *in, const uint8_t *sources, co
                          const dspi_out *out, uint32_t *pdm_words, dspi_spdif_rx *rx, uint32_t flags) {
     if (!c || !sources || !out) return DSPI_E_INVAL;
     // 2. the flags
-    if (!(flags & DSPI_MEM_DEVICE)) return fail(c, DSPI_E_INVAL, "dspi_process_patched: DSPI_MEM_DEVICE is required");
-    const bool wire = flags & DSPI_OUT_WIRE;
-    flags &= ~DSPI_OUT_WIRE;
-    if (wire && !devices_process_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_process_patched: with DSPI_OUT_WIRE the flags are DSPI_MEM_DEVICE, DSPI_OUT_TILED, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
-    int rc;
-    if ((rc = check_flag_bits(c, flags)) || (!wire && (rc = check_flag_combinations(c, flags)))) return rc;
+    bool wire;
+    int rc = front_flags(c, "dspi_process_patched", &flags, &wire, true);
     // 3. to 11.
-    bool rx_needed = false;
-    if ((rc = patched_check(c, "dspi_process_patched", in, sources, views, n_views, patches, n_blocks, block_len, rx, &rx_needed))) return rc;
     PatchPlan plan;
-    patch_plan(sources, c->n_streams, host_activity(c), reinterpret_cast<const WireView *>(views), n_views, reinterpret_cast<const Patch *>(patches), (uint64_t)n_blocks * block_len, plan);
-    const PatchIn pi{in, reinterpret_cast<const WireView *>(views), views, n_views, rx_needed ? reinterpret_cast<SpdifRx *>(rx) : nullptr, &plan};
-    // (process_call wants an input pointer; a call of LINK streams has none, and nothing reads it: the chain reads d_mixed)
-    return process_call(c, in ? in : static_cast<const void *>(out), 24, n_blocks, block_len, out, pdm_words, wire ? flags | DSPI_OUT_SPDIF : flags, nullptr, wire, nullptr, &pi);
+    CallFront pt{CallFront::Patched, wire, "dspi_process_patched"};
+    if (rc || (rc = patched_front(c, pt, plan, in, sources, views, n_views, patches, n_blocks, block_len, rx))) return rc;
+    return process_call(c, in, 24, n_blocks, block_len, out, pdm_words, flags, pt);
 }
 
 int dspi_wire_encode_tiled(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames, const uint32_t *block_pos, uint32_t *wire, uint32_t flags) {
@@ -2913,7 +2927,7 @@ int dspi_wire_encode_tiled(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames,
     const bool dev = flags & DSPI_MEM_DEVICE;
     // host positions are validated before anything is launched; device positions are the kernel's to reduce modulo 192
     if (!dev) for (uint32_t s = 0; s < c->n_streams; s++) if (block_pos[s] >= kSpdifBlock) return fail(c, DSPI_E_INVAL, "dspi_wire_encode_tiled: a position is 0..191");
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: the HIP path is the only audio path");
+    if (c->device == DSPI_DEVICE_NONE) return refuse_host_only(c);
     HIPCK(c, hipSetDevice(c->device));
     const uint32_t row = (uint32_t)c->sm.row;
     const size_t tile_in_b = (size_t)row * c->sm.n_pairs * n_frames * 8, in_b = c->n_wg * tile_in_b, out_b = in_b * 2, pos_b = (size_t)c->n_streams * 4;
@@ -2939,56 +2953,47 @@ int dspi_wire_encode_tiled(dspi_ctx *c, const int32_t *pairs, uint32_t n_frames,
     return dev ? DSPI_OK : stage_down(c, wire, c->d_spdif_out, out_b);
 }
 
-// the prepass of a device-buffer mixed call alone, into the context's scratch: what tools/bench_mixed.py times (no chain, nothing advanced)
-int dspi_debug_intake(dspi_ctx *c, const void *pcm_in, const uint8_t *bit_depths, uint32_t n_blocks, uint32_t block_len) {
-    if (!c || !pcm_in || !bit_depths) return DSPI_E_INVAL;
-    int rc = mixed_check(c, bit_depths, n_blocks, block_len, "dspi_debug_intake");
-    if (rc) return rc;
-    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no intake");
-    const uint64_t frames = (uint64_t)n_blocks * block_len;
-    MixedIn mx{bit_depths, std::vector<uint64_t>((size_t)c->n_streams + 1)};
-    uint64_t out_bytes = 0;
-    if (!intake_offsets(bit_depths, c->n_streams, frames, nullptr, mx.offsets.data()) || __builtin_mul_overflow((uint64_t)c->n_streams * kIntakeOutFrame, frames, &out_bytes))
-        return fail(c, DSPI_E_INVAL, "dspi_debug_intake: the buffer's size overflows");
+// ---- the front end of a device-buffer call alone, into the context's scratch: what the tools/bench_* of the input calls time (no chain, nothing
+// advanced).  Each call's own argument checks, then the route's own two steps on the call's descriptor.  (upload_pauses: the activity bitmap goes
+// up as commit_params sends it up in the real call; a patched call's kernels read the plan's masks, built from the host's record, instead) ----
+static int debug_front(dspi_ctx *c, const CallFront &f, const void *in, uint64_t frames, bool upload_pauses = true) {
     HIPCK(c, hipSetDevice(c->device));
-    if (c->n_paused && (rc = upload_activity(c))) return rc;
-    if ((rc = intake_prepare(c, mx, frames, c->d_mixed, (size_t)out_bytes))) return rc;
-    return launch_intake_streams(c, frames, pcm_in, c->d_mixed, 0, c->n_streams);
+    int rc;
+    if (upload_pauses && c->n_paused && (rc = upload_activity(c))) return rc;
+    if ((rc = front_prepare(c, f, CallMem::Device, frames, (size_t)c->n_streams * kIntakeOutFrame * frames))) return rc;
+    const void *chain_pcm;
+    return front_launch(c, f, in, frames, &chain_pcm);
 }
 
-// ... of a dspi_process_sources call: the intake for the PCM streams and the receiver for the S/PDIF streams (tools/bench_spdif_in.py)
-int dspi_debug_sources_intake(dspi_ctx *c, const void *in, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len, dspi_spdif_rx *rx) {
-    if (!c || !in || !sources) return DSPI_E_INVAL;
-    int rc = mixed_check(c, sources, n_blocks, block_len, "dspi_debug_sources_intake", true);
+// ... of a dspi_process_mixed call, the intake (tools/bench_mixed.py), and (sources) of a dspi_process_sources call, the intake for the PCM
+// streams and the receiver for the S/PDIF streams (tools/bench_spdif_in.py)
+static int debug_mixed_intake(dspi_ctx *c, const char *who, const void *in, const uint8_t *kinds, uint32_t n_blocks, uint32_t block_len, bool sources, dspi_spdif_rx *rx) {
+    if (!c || !in || !kinds) return DSPI_E_INVAL;
+    int rc = mixed_check(c, kinds, n_blocks, block_len, who, sources);
     if (rc) return rc;
-    const bool spdif_in = sources_any_spdif(sources, c->n_streams);
-    if (spdif_in && (!rx || reinterpret_cast<uintptr_t>(in) % 16u || reinterpret_cast<uintptr_t>(rx) % 4u)) return fail(c, DSPI_E_INVAL, "dspi_debug_sources_intake: rx is required and the input 16-byte aligned");
+    const bool spdif_in = sources && sources_any_spdif(kinds, c->n_streams);
+    if (spdif_in && (!rx || reinterpret_cast<uintptr_t>(in) % 16u || reinterpret_cast<uintptr_t>(rx) % 4u)) return fail(c, DSPI_E_INVAL, std::string(who) + ": rx is required and the input 16-byte aligned");
     if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no intake");
     const uint64_t frames = (uint64_t)n_blocks * block_len;
-    MixedIn mx{sources, std::vector<uint64_t>((size_t)c->n_streams + 1), spdif_in ? reinterpret_cast<SpdifRx *>(rx) : nullptr};
+    std::vector<uint64_t> offsets((size_t)c->n_streams + 1);
     uint64_t out_bytes = 0;
-    if (!sources_offsets(sources, c->n_streams, frames, nullptr, mx.offsets.data()) || __builtin_mul_overflow((uint64_t)c->n_streams * kIntakeOutFrame, frames, &out_bytes))
-        return fail(c, DSPI_E_INVAL, "dspi_debug_sources_intake: the buffer's size overflows");
-    HIPCK(c, hipSetDevice(c->device));
-    if (c->n_paused && (rc = upload_activity(c))) return rc;
-    if ((rc = intake_prepare(c, mx, frames, c->d_mixed, (size_t)out_bytes))) return rc;
-    return launch_intake_streams(c, frames, in, c->d_mixed, 0, c->n_streams, mx.rx);
+    if (!(sources ? sources_offsets(kinds, c->n_streams, frames, nullptr, offsets.data()) : intake_offsets(kinds, c->n_streams, frames, nullptr, offsets.data())) ||
+        __builtin_mul_overflow((uint64_t)c->n_streams * kIntakeOutFrame, frames, &out_bytes)) return fail(c, DSPI_E_INVAL, std::string(who) + ": the buffer's size overflows");
+    return debug_front(c, CallFront{CallFront::Mixed, false, who, spdif_in ? reinterpret_cast<SpdifRx *>(rx) : nullptr, kinds, offsets.data()}, in, frames);
+}
+int dspi_debug_intake(dspi_ctx *c, const void *in, const uint8_t *depths, uint32_t n_blocks, uint32_t block_len) { return debug_mixed_intake(c, "dspi_debug_intake", in, depths, n_blocks, block_len, false, nullptr); }
+int dspi_debug_sources_intake(dspi_ctx *c, const void *in, const uint8_t *sources, uint32_t n_blocks, uint32_t block_len, dspi_spdif_rx *rx) {
+    return debug_mixed_intake(c, "dspi_debug_sources_intake", in, sources, n_blocks, block_len, true, rx);
 }
 
 // ... of a dspi_process_patched call: the intake, the receiver over `in`, the link receivers and the patch receiver (tools/bench_patched.py)
 int dspi_debug_patched_intake(dspi_ctx *c, const void *in, const uint8_t *sources, const dspi_wire_view *views, uint32_t n_views, const dspi_patch *patches, uint32_t n_blocks, uint32_t block_len,
                               dspi_spdif_rx *rx) {
     if (!c || !sources) return DSPI_E_INVAL;
-    bool rx_needed = false;
-    int rc = patched_check(c, "dspi_debug_patched_intake", in, sources, views, n_views, patches, n_blocks, block_len, rx, &rx_needed);
-    if (rc) return rc;
-    const uint64_t frames = (uint64_t)n_blocks * block_len;
-    HIPCK(c, hipSetDevice(c->device));
-    if ((rc = ensure(c, c->d_mixed, (size_t)(c->n_streams * kIntakeOutFrame * frames)))) return rc;
     PatchPlan plan;
-    patch_plan(sources, c->n_streams, host_activity(c), reinterpret_cast<const WireView *>(views), n_views, reinterpret_cast<const Patch *>(patches), frames, plan);
-    const PatchIn pi{in, reinterpret_cast<const WireView *>(views), views, n_views, rx_needed ? reinterpret_cast<SpdifRx *>(rx) : nullptr, &plan};
-    return launch_patched(c, pi, frames);
+    CallFront pt{CallFront::Patched, false, "dspi_debug_patched_intake"};
+    if (int rc = patched_front(c, pt, plan, in, sources, views, n_views, patches, n_blocks, block_len, rx)) return rc;
+    return debug_front(c, pt, in, (uint64_t)n_blocks * block_len, false);
 }
 
 // ---- input from a packet table (dspi_packets.h: the entry rule, the check and the address arithmetic; dspi_packetrx.hip: the kernel) ----
@@ -2998,13 +3003,19 @@ static int packets_refusals(dspi_ctx *c, const char *who, const uint8_t *depths,
     uint64_t at = 0;
     switch (packets_check(depths, table, c->n_streams, n_blocks, block_len, DSPI_MAX_BLOCK_LEN, arena_bytes, host_activity(c), &at)) {
     case PacketsBad::Ok: return 0;
-    case PacketsBad::Lengths: return fail(c, DSPI_E_INVAL, w + "1 <= block_len <= 192, n_blocks >= 1");
+    case PacketsBad::Lengths: return refuse_lengths(c, who);
     case PacketsBad::Depth: return fail(c, DSPI_E_INVAL, w + "the depth of stream " + std::to_string(at) + " is neither 16 nor 24");
     case PacketsBad::Overflow: return fail(c, DSPI_E_INVAL, w + "the table has more than 2^31 - 1 entries");
     case PacketsBad::Entry: break;
     }
     if (bad_entry) *bad_entry = at;
     return fail(c, DSPI_E_INVAL, w + "entry " + std::to_string(at) + " (stream " + std::to_string(at / n_blocks) + ", packet " + std::to_string(at % n_blocks) + ") is odd or its packet does not end inside the arena");
+}
+
+static CallFront packets_front(const char *who, bool wire, const uint8_t *depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len) {
+    CallFront pk{CallFront::Packets, wire, who};
+    pk.depths = depths; pk.table = table; pk.n_blocks = n_blocks; pk.block_len = block_len;
+    return pk;
 }
 
 int dspi_packets_check(const dspi_ctx *c, const uint8_t *bit_depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes, uint64_t *bad_entry) {
@@ -3016,28 +3027,16 @@ int dspi_process_packets(dspi_ctx *c, const void *arena, uint64_t arena_bytes, c
                          uint32_t *pdm_words, uint32_t flags) {
     if (!c) return DSPI_E_INVAL;
     // 1. the flags
-    if (!(flags & DSPI_MEM_DEVICE)) return fail(c, DSPI_E_INVAL, "dspi_process_packets: DSPI_MEM_DEVICE is required");
-    const bool wire = flags & DSPI_OUT_WIRE;
-    flags &= ~DSPI_OUT_WIRE;
-    if (wire && !devices_process_flags_ok(flags)) return fail(c, DSPI_E_INVAL, "dspi_process_packets: with DSPI_OUT_WIRE the flags are DSPI_MEM_DEVICE, DSPI_OUT_TILED, DSPI_OUT_ENABLED_ONLY and DSPI_OUT_CLIP_FLAGS");
-    int rc;
-    if ((rc = check_flag_bits(c, flags)) || (!wire && (rc = check_flag_combinations(c, flags)))) return rc;
+    bool wire;
+    int rc = front_flags(c, "dspi_process_packets", &flags, &wire, true);
+    if (rc) return rc;
     // 2. to 5.
     if (!arena || !table || !bit_depths || !out) return fail(c, DSPI_E_INVAL, "dspi_process_packets: arena, table, bit_depths and out are required");
     if ((rc = packets_refusals(c, "dspi_process_packets", bit_depths, table, n_blocks, block_len, arena_bytes, nullptr))) return rc;
-    // 6. the one case in which a 16-bit sample and its widened twin part ways (dspi_intake.h): refused, not approximated
-    if (c->flavor)
-        for (uint32_t s = 0; s < c->n_streams; s++) {
-            if (bit_depths[s] != 16 || (c->n_paused && !c->active[s])) continue;
-            for (const float p : readable(c, (int32_t)s).preamp_linear) {
-                uint32_t w; memcpy(&w, &p, 4);
-                if (intake_preamp_breaks_widening(w))
-                    return fail(c, DSPI_E_UNSUPPORTED, "dspi_process_packets: stream " + std::to_string(s) + " takes 16-bit input with a preamp below 2^-103, where widening to 24 bit is not exact");
-            }
-        }
+    // 6. the preamp rule
+    if ((rc = check_widening(c, "dspi_process_packets", bit_depths, host_activity(c)))) return rc;
     // 7. (process_call refuses the host-only context)
-    const PacketIn pk{arena, bit_depths, table, n_blocks, block_len};
-    return process_call(c, arena, 24, n_blocks, block_len, out, pdm_words, wire ? flags | DSPI_OUT_SPDIF : flags, nullptr, wire, nullptr, nullptr, &pk);
+    return process_call(c, arena, 24, n_blocks, block_len, out, pdm_words, flags, packets_front("dspi_process_packets", wire, bit_depths, table, n_blocks, block_len));
 }
 
 // the front end of a dspi_process_packets call alone, into the context's scratch: what tools/bench_packets.py times (no chain, nothing advanced)
@@ -3046,11 +3045,7 @@ int dspi_debug_packets_intake(dspi_ctx *c, const void *arena, uint64_t arena_byt
     int rc = packets_refusals(c, "dspi_debug_packets_intake", bit_depths, table, n_blocks, block_len, arena_bytes, nullptr);
     if (rc) return rc;
     if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no intake");
-    HIPCK(c, hipSetDevice(c->device));
-    if (c->n_paused && (rc = upload_activity(c))) return rc;
-    if ((rc = ensure(c, c->d_mixed, (size_t)c->n_streams * kIntakeOutFrame * n_blocks * block_len))) return rc;
-    const PacketIn pk{arena, bit_depths, table, n_blocks, block_len};
-    return launch_packets(c, pk);
+    return debug_front(c, packets_front("dspi_debug_packets_intake", false, bit_depths, table, n_blocks, block_len), arena, (uint64_t)n_blocks * block_len);
 }
 
 // ---- outputs to a packet table (dspi_packets_out.h: the entry rule, the checks, the CPU path and the address arithmetic; dspi_packettx.hip: the kernels) ----
@@ -3063,7 +3058,7 @@ static int emit_refusals(dspi_ctx *c, const char *who, const uint8_t *formats, c
     const EmitBad bad = packets_emit_check(formats, table, c->n_streams, (uint32_t)c->sm.n_pairs, n_blocks, block_len, DSPI_MAX_BLOCK_LEN, arena_bytes, host_activity(c), overlap, &at);
     switch (bad) {
     case EmitBad::Ok: return 0;
-    case EmitBad::Lengths: return fail(c, DSPI_E_INVAL, w + "1 <= block_len <= 192, n_blocks >= 1");
+    case EmitBad::Lengths: return refuse_lengths(c, who);
     case EmitBad::Format: return fail(c, DSPI_E_INVAL, w + "the format of stream " + std::to_string(at) + " is neither 24 nor 32");
     case EmitBad::Overflow: return fail(c, DSPI_E_INVAL, w + "the table has more than 2^31 - 1 entries");
     case EmitBad::Entry: case EmitBad::Overlap: break;

@@ -361,6 +361,43 @@ def test_after_a_grow(flavor):
     x.close()
 
 
+# ---- 7b. other front ends in between ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("flavor", (W.F32_FMA, 0), ids=fid)
+def test_table_survives_other_front_ends(flavor):
+    """The device's table of a call's front end is one buffer for every kind of call, and a mixed call keeps its own there while the depths
+    and the frame count repeat.  mixed, packets, mixed, patched, mixed on one context, device buffers, the same depths and 2 x 48 frames every
+    time: each mixed call would find its table cached unless the call in between had said that the table is no longer a mixed call's.  The
+    packet table describes the mixed layout itself, the patched call takes the depths as its sources (no LINK stream, no view).  A twin makes
+    five plain mixed calls on the same bytes: pairs, sub, peaks and clip flags are equal after every call.  One full row and 3 streams."""
+    from test_gpu_packets import Outs, Source, contiguous, run_mixed, run_packets, same, to_dev
+    n, Bk = 2, 48
+    blob = WL.full_chain_blob(int(flavor))
+    probe = context(flavor, 1, FS, blob)
+    S = probe.tile_streams() + 3
+    probe.close()
+    d, t = context(flavor, S, FS, blob), context(flavor, S, FS, blob)
+    depths = pattern("alternating", S).astype(np.uint8)
+    src = Source(S, Bk, 5 * n)
+    _, at = d.mixed_pcm_bytes(depths, n, Bk)
+
+    def run_patched(buf):
+        total, off = d.patched_bytes(depths, n, Bk)
+        pin = np.full(max(total, 16), FILL, dtype=np.uint8)
+        for s in range(S): pin[int(off[s]):int(off[s]) + int(at[s + 1] - at[s])] = buf[int(at[s]):int(at[s + 1])]
+        a, o = to_dev(pin), Outs(d, n, Bk)
+        d.process_patched_device(a.data_ptr(), depths, None, None, n, Bk, pairs_ptr=o.pairs.data_ptr(), **o.ptrs())
+        d.sync()
+        return o.fetch()
+
+    for k, kind in enumerate(("mixed", "packets", "mixed", "patched", "mixed")):
+        buf, table = contiguous(lambda s, p: src.packet(s, depths[s], k * n + p), depths, n)
+        assert buf.size == at[-1]
+        want = run_mixed(t, buf, depths, n, Bk)
+        got = run_packets(d, buf, depths, table, n, Bk) if kind == "packets" else run_patched(buf) if kind == "patched" else run_mixed(d, buf, depths, n, Bk)
+        same(got, want, f"call {k} ({kind})")
+    d.close(); t.close()
+
+
 # ---- 8. the refusal -------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("flavor", FLAVORS_WITH_KERNEL, ids=fid)
 def test_preamp_refusal(flavor):
