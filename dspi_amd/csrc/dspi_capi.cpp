@@ -48,6 +48,7 @@
 #include "dspi_snapshot.h"
 #include "dspi_spdifpos.h"
 #include "dspi_spdifrx.h"
+#include "dspi_tablecheck.h"
 #include "dspi_wire.h"
 
 using namespace dspi;
@@ -187,6 +188,9 @@ struct dspi_ctx {
     // dspi_packets_emit (dspi_packets_out.h): no state — the device's copy of the call's table with the formats behind it, on `hs` only (it goes
     // up through h_move, behind ev_move).  Not d_mixed_tab: a process call's table stays what that call left.
     DevBuf<uint64_t> d_emit_tab{mem};
+    // the resident packet tables' entry check (dspi_tablecheck.h): no state — the answer word, with the call's n depth / format bytes behind it
+    // (they go up through h_move, behind ev_move), on `hs` only.  Not d_mixed_tab: a check leaves the front end's table what it was.
+    DevBuf<uint64_t> d_tabcheck{mem};
     std::string err;
 };
 
@@ -2083,6 +2087,7 @@ struct CallFront {
     const Link *links = nullptr;           // Linked: [n_streams], host memory, validated for the entries that are served
     const PatchPlan *plan = nullptr;       // Patched (dspi_patch.h)
     const uint64_t *table = nullptr; uint32_t n_blocks = 0, block_len = 0;      // Packets: [n_streams][n_blocks], host memory, validated for the active streams
+    bool table_on_device = false;          // Packets: the table is DEVICE memory (dspi_process_packets_resident), checked there or warranted by the caller
     bool host_capable() const { return kind == Pcm || kind == Mixed; }      // the others: the device route only
     bool reads_pcm_in() const { return kind != Linked && kind != Patched; }      // (Patched: `in` may be null, when no active stream has a run; Packets: the arena)
 };
@@ -2195,10 +2200,11 @@ static int launch_patched(dspi_ctx *c, const CallFront &f, const void *in, uint6
 
 // Packets (dspi_packets.h): the table with the depths behind it, then the packet receiver over the caller's arena (device memory)
 static int launch_packets(dspi_ctx *c, const CallFront &f, const void *arena) {
-    const size_t entries = (size_t)c->n_streams * f.n_blocks;
-    if (int rc = upload_front_table(c, "hipHostMalloc failed (packet table)", {{f.table, entries * 8}, {f.depths, c->n_streams}})) return rc;
+    // (a table on the device stays where it lies: only the depths go up)
+    const size_t entries = (size_t)c->n_streams * f.n_blocks, up = f.table_on_device ? 0 : entries;
+    if (int rc = upload_front_table(c, "hipHostMalloc failed (packet table)", {{f.table, up * 8}, {f.depths, c->n_streams}})) return rc;
     const uint64_t *const tab = c->d_mixed_tab;
-    const hipError_t e = launch_packetrx(arena, tab, reinterpret_cast<const uint8_t *>(tab + entries), activity(c), c->d_mixed, c->n_streams, f.n_blocks, f.block_len, c->hs);
+    const hipError_t e = launch_packetrx(arena, f.table_on_device ? f.table : tab, reinterpret_cast<const uint8_t *>(tab + up), activity(c), c->d_mixed, c->n_streams, f.n_blocks, f.block_len, c->hs);
     return e == hipSuccess ? 0 : fail(c, DSPI_E_HIP, std::string("packet receiver launch: ") + hipGetErrorString(e));
 }
 
@@ -2997,19 +3003,27 @@ int dspi_debug_patched_intake(dspi_ctx *c, const void *in, const uint8_t *source
 }
 
 // ---- input from a packet table (dspi_packets.h: the entry rule, the check and the address arithmetic; dspi_packetrx.hip: the kernel) ----
-// refusals 2 to 5 of dspi_process_packets behind the pointers, in their order (dspi_packets_check and dspi_debug_packets_intake share them)
-static int packets_refusals(dspi_ctx *c, const char *who, const uint8_t *depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes, uint64_t *bad_entry) {
+// refusal 5's code and text (the host check's and the device check's)
+static int refuse_packet_entry(dspi_ctx *c, const char *who, uint64_t at, uint32_t n_blocks, uint64_t *bad_entry) {
+    if (bad_entry) *bad_entry = at;
+    return fail(c, DSPI_E_INVAL, std::string(who) + ": entry " + std::to_string(at) + " (stream " + std::to_string(at / n_blocks) + ", packet " + std::to_string(at % n_blocks) + ") is odd or its packet does not end inside the arena");
+}
+// refusals 2 to 5 of dspi_process_packets behind the pointers, in their order (dspi_packets_check and dspi_debug_packets_intake share them).
+// host_table false (the resident calls): the table is device memory, so every stream counts as paused here and no entry is looked at:
+// refusals 2 to 4 alone, the table pointer never dereferenced
+static int packets_refusals(dspi_ctx *c, const char *who, const uint8_t *depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes, uint64_t *bad_entry,
+                            bool host_table = true) {
     const std::string w = std::string(who) + ": ";
     uint64_t at = 0;
-    switch (packets_check(depths, table, c->n_streams, n_blocks, block_len, DSPI_MAX_BLOCK_LEN, arena_bytes, host_activity(c), &at)) {
+    const std::vector<uint8_t> nobody(host_table ? 0 : c->n_streams, 0u);
+    switch (packets_check(depths, table, c->n_streams, n_blocks, block_len, DSPI_MAX_BLOCK_LEN, arena_bytes, host_table ? host_activity(c) : nobody.data(), &at)) {
     case PacketsBad::Ok: return 0;
     case PacketsBad::Lengths: return refuse_lengths(c, who);
     case PacketsBad::Depth: return fail(c, DSPI_E_INVAL, w + "the depth of stream " + std::to_string(at) + " is neither 16 nor 24");
     case PacketsBad::Overflow: return fail(c, DSPI_E_INVAL, w + "the table has more than 2^31 - 1 entries");
     case PacketsBad::Entry: break;
     }
-    if (bad_entry) *bad_entry = at;
-    return fail(c, DSPI_E_INVAL, w + "entry " + std::to_string(at) + " (stream " + std::to_string(at / n_blocks) + ", packet " + std::to_string(at % n_blocks) + ") is odd or its packet does not end inside the arena");
+    return refuse_packet_entry(c, who, at, n_blocks, bad_entry);
 }
 
 static CallFront packets_front(const char *who, bool wire, const uint8_t *depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len) {
@@ -3050,12 +3064,22 @@ int dspi_debug_packets_intake(dspi_ctx *c, const void *arena, uint64_t arena_byt
 
 // ---- outputs to a packet table (dspi_packets_out.h: the entry rule, the checks, the CPU path and the address arithmetic; dspi_packettx.hip: the kernels) ----
 static_assert(DSPI_PACKET_SKIP == kPacketSkip && DSPI_EMIT_CHECK_OVERLAP == kEmitCheckOverlap, "include/dspi.h and dspi_packets_out.h: one skip word, one flag");
-// refusals 2 to 5 of dspi_packets_emit behind the pointers, in their order, and the overlap rule when asked (dspi_packets_emit_check shares them)
+// refusal 5's code and text, and the overlap's (the host check's and the device check's)
+static int refuse_emit_entry(dspi_ctx *c, const char *who, uint64_t at, uint32_t n_blocks, bool overlaps, uint64_t *bad_entry) {
+    if (bad_entry) *bad_entry = at;
+    const uint64_t per = (uint64_t)c->sm.n_pairs * n_blocks;
+    const std::string which = "entry " + std::to_string(at) + " (stream " + std::to_string(at / per) + ", pair " + std::to_string(at % per / n_blocks) + ", packet " + std::to_string(at % n_blocks) + ")";
+    return fail(c, DSPI_E_INVAL, std::string(who) + ": " + which + (overlaps ? " overlaps another entry" : " is odd or its packet does not end inside the arena"));
+}
+// refusals 2 to 5 of dspi_packets_emit behind the pointers, in their order, and the overlap rule when asked (dspi_packets_emit_check shares them).
+// host_table false: as in packets_refusals
 static int emit_refusals(dspi_ctx *c, const char *who, const uint8_t *formats, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes, bool overlap,
-                         uint64_t *bad_entry) {
+                         uint64_t *bad_entry, bool host_table = true) {
     const std::string w = std::string(who) + ": ";
     uint64_t at = 0;
-    const EmitBad bad = packets_emit_check(formats, table, c->n_streams, (uint32_t)c->sm.n_pairs, n_blocks, block_len, DSPI_MAX_BLOCK_LEN, arena_bytes, host_activity(c), overlap, &at);
+    const std::vector<uint8_t> nobody(host_table ? 0 : c->n_streams, 0u);
+    const EmitBad bad = packets_emit_check(formats, table, c->n_streams, (uint32_t)c->sm.n_pairs, n_blocks, block_len, DSPI_MAX_BLOCK_LEN, arena_bytes,
+                                           host_table ? host_activity(c) : nobody.data(), overlap, &at);
     switch (bad) {
     case EmitBad::Ok: return 0;
     case EmitBad::Lengths: return refuse_lengths(c, who);
@@ -3063,10 +3087,7 @@ static int emit_refusals(dspi_ctx *c, const char *who, const uint8_t *formats, c
     case EmitBad::Overflow: return fail(c, DSPI_E_INVAL, w + "the table has more than 2^31 - 1 entries");
     case EmitBad::Entry: case EmitBad::Overlap: break;
     }
-    if (bad_entry) *bad_entry = at;
-    const uint64_t per = (uint64_t)c->sm.n_pairs * n_blocks;
-    const std::string which = "entry " + std::to_string(at) + " (stream " + std::to_string(at / per) + ", pair " + std::to_string(at % per / n_blocks) + ", packet " + std::to_string(at % n_blocks) + ")";
-    return fail(c, DSPI_E_INVAL, w + which + (bad == EmitBad::Entry ? " is odd or its packet does not end inside the arena" : " overlaps another entry"));
+    return refuse_emit_entry(c, who, at, n_blocks, bad == EmitBad::Overlap, bad_entry);
 }
 
 int dspi_packets_emit_check(const dspi_ctx *c, const uint8_t *formats, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes, uint32_t check_flags,
@@ -3119,6 +3140,128 @@ int dspi_debug_packets_emit_launch(dspi_ctx *c, const int32_t *pairs, uint32_t n
     if (c->n_paused) { int rc = upload_activity(c); if (rc) return rc; }
     const hipError_t e = launch_packettx(pairs, (flags & DSPI_OUT_TILED) ? (uint32_t)c->sm.row : 0u, table, formats, activity(c), arena, c->n_streams, (uint32_t)c->sm.n_pairs, n_blocks, block_len, c->hs);
     return e == hipSuccess ? DSPI_OK : fail(c, DSPI_E_HIP, std::string("packetiser launch: ") + hipGetErrorString(e));
+}
+
+// ---- resident packet tables: both packet calls on a table that lies in DEVICE memory (dspi_tablecheck.h: the checker's arithmetic;
+// dspi_tablecheck.hip: its kernel).  Only the table moves: the depths / formats stay host memory, refusals 2 to 4 and the preamp rule stay on the
+// host, and refusal 5 is the checker's answer, waited for — or the caller's warrant (DSPI_TABLE_CHECKED), and then nothing waits ----
+static_assert(DSPI_TABLE_CHECKED == 0x1u, "include/dspi.h");
+static TableCheck resident_table(const dspi_ctx *c, uint32_t kind, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes) {
+    const uint32_t per = kind == kTableEmit ? (uint32_t)c->sm.n_pairs * n_blocks : n_blocks;      // (refusal 4 came first: no overflow)
+    return TableCheck{(uint64_t)c->n_streams * per, arena_bytes, per, block_len, kind};
+}
+// what stands between refusal 4 and refusal 5 in all four calls (audio: the text every audio call refuses a host-only context with)
+static int resident_device_refusals(dspi_ctx *c, const char *who, const uint64_t *table, bool audio = false) {
+    if (c->device == DSPI_DEVICE_NONE) return audio ? refuse_host_only(c) : fail(c, DSPI_E_NODEVICE, std::string(who) + ": a host-only context has no device memory");
+    if (reinterpret_cast<uintptr_t>(table) & 15u) return fail(c, DSPI_E_INVAL, std::string(who) + ": a device table is 16-byte aligned (every hipMalloc is)");
+    return 0;
+}
+// The checker on the context's stream, waited for: the answer word with the n kind bytes behind it goes up through the pinned area, the one
+// launch follows, and the 8 bytes come back.  *answer: the lowest refused index of an active stream, or kTableCheckNone.
+static int resident_check(dspi_ctx *c, const TableCheck &t, const uint8_t *kinds, const uint64_t *table, uint64_t *answer) {
+    HIPCK(c, hipSetDevice(c->device));
+    int rc;
+    if (c->n_paused && (rc = upload_activity(c))) return rc;
+    const uint64_t none = kTableCheckNone;
+    if ((rc = upload_via_move_area(c, c->d_tabcheck, "hipHostMalloc failed (table check)", {{&none, 8}, {kinds, c->n_streams}}))) return rc;
+    const hipError_t e = launch_tablecheck(t, table, reinterpret_cast<const uint8_t *>(c->d_tabcheck + 1), activity(c), c->d_tabcheck, 0u, c->hs);
+    if (e != hipSuccess) return fail(c, DSPI_E_HIP, std::string("table check launch: ") + hipGetErrorString(e));
+    HIPCK(c, hipMemcpyAsync(answer, c->d_tabcheck, 8, hipMemcpyDeviceToHost, c->hs));
+    HIPCK(c, hipStreamSynchronize(c->hs));
+    return 0;
+}
+// refusals 2 to 4, the device's two, then 5 unless the caller warrants it (`checked`), of the input kind ...
+static int resident_packets_refusals(dspi_ctx *c, const char *who, const uint8_t *depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes, bool audio,
+                                     bool checked, uint64_t *bad_entry) {
+    int rc = packets_refusals(c, who, depths, table, n_blocks, block_len, arena_bytes, nullptr, false);
+    if (rc || (rc = resident_device_refusals(c, who, table, audio)) || checked) return rc;
+    uint64_t at = kTableCheckNone;
+    if ((rc = resident_check(c, resident_table(c, kTableInput, n_blocks, block_len, arena_bytes), depths, table, &at))) return rc;
+    return at == kTableCheckNone ? 0 : refuse_packet_entry(c, who, at, n_blocks, bad_entry);
+}
+// ... and 2 to 5 of the emit kind, as the check call applies them (dspi_packets_emit_resident has its pointers' alignments in between)
+static int resident_emit_refusals(dspi_ctx *c, const char *who, const uint8_t *formats, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes,
+                                  uint64_t *bad_entry) {
+    int rc = emit_refusals(c, who, formats, table, n_blocks, block_len, arena_bytes, false, nullptr, false);
+    if (rc || (rc = resident_device_refusals(c, who, table))) return rc;
+    uint64_t at = kTableCheckNone;
+    if ((rc = resident_check(c, resident_table(c, kTableEmit, n_blocks, block_len, arena_bytes), formats, table, &at))) return rc;
+    return at == kTableCheckNone ? 0 : refuse_emit_entry(c, who, at, n_blocks, false, bad_entry);
+}
+
+int dspi_packets_check_resident(dspi_ctx *c, const uint8_t *bit_depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes, uint64_t *bad_entry) {
+    if (!c || !table || !bit_depths) return DSPI_E_INVAL;
+    return resident_packets_refusals(c, "dspi_packets_check_resident", bit_depths, table, n_blocks, block_len, arena_bytes, false, false, bad_entry);
+}
+
+int dspi_packets_emit_check_resident(dspi_ctx *c, const uint8_t *formats, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes, uint32_t check_flags,
+                                     uint64_t *bad_entry) {
+    if (!c) return DSPI_E_INVAL;
+    if (check_flags) return fail(c, DSPI_E_INVAL, "dspi_packets_emit_check_resident: check_flags is 0 (overlap detection stays with host tables)");
+    if (!formats || !table) return fail(c, DSPI_E_INVAL, "dspi_packets_emit_check_resident: formats and table are required");
+    return resident_emit_refusals(c, "dspi_packets_emit_check_resident", formats, table, n_blocks, block_len, arena_bytes, bad_entry);
+}
+
+int dspi_process_packets_resident(dspi_ctx *c, const void *arena, uint64_t arena_bytes, const uint8_t *bit_depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len,
+                                  const dspi_out *out, uint32_t *pdm_words, uint32_t flags, uint32_t table_flags) {
+    static const char who[] = "dspi_process_packets_resident";
+    if (!c) return DSPI_E_INVAL;
+    // 1. the flags
+    bool wire;
+    int rc = front_flags(c, who, &flags, &wire, true);
+    if (rc) return rc;
+    if (table_flags & ~DSPI_TABLE_CHECKED) return fail(c, DSPI_E_INVAL, std::string(who) + ": table_flags is 0 or DSPI_TABLE_CHECKED");
+    // 2. to 4., the device's two, 5. on the device
+    if (!arena || !table || !bit_depths || !out) return fail(c, DSPI_E_INVAL, std::string(who) + ": arena, table, bit_depths and out are required");
+    if ((rc = resident_packets_refusals(c, who, bit_depths, table, n_blocks, block_len, arena_bytes, true, table_flags & DSPI_TABLE_CHECKED, nullptr))) return rc;
+    // 6. the preamp rule
+    if ((rc = check_widening(c, who, bit_depths, host_activity(c)))) return rc;
+    CallFront pk = packets_front(who, wire, bit_depths, table, n_blocks, block_len);
+    pk.table_on_device = true;
+    return process_call(c, arena, 24, n_blocks, block_len, out, pdm_words, flags, pk);
+}
+
+int dspi_packets_emit_resident(dspi_ctx *c, const int32_t *pairs, uint32_t n_blocks, uint32_t block_len, const uint8_t *formats, const uint64_t *table, void *arena, uint64_t arena_bytes,
+                               uint32_t flags, uint32_t table_flags) {
+    static const char who[] = "dspi_packets_emit_resident";
+    if (!c) return DSPI_E_INVAL;
+    // 1. the flags
+    if (flags & ~(DSPI_MEM_DEVICE | DSPI_OUT_TILED)) return fail(c, DSPI_E_INVAL, std::string(who) + ": the flags are DSPI_MEM_DEVICE and DSPI_OUT_TILED");
+    if (!(flags & DSPI_MEM_DEVICE)) return fail(c, DSPI_E_INVAL, std::string(who) + ": DSPI_MEM_DEVICE is required");
+    if (table_flags & ~DSPI_TABLE_CHECKED) return fail(c, DSPI_E_INVAL, std::string(who) + ": table_flags is 0 or DSPI_TABLE_CHECKED");
+    // 2. to 4.
+    if (!pairs || !formats || !table || !arena) return fail(c, DSPI_E_INVAL, std::string(who) + ": pairs, formats, table and arena are required");
+    int rc = emit_refusals(c, who, formats, table, n_blocks, block_len, arena_bytes, false, nullptr, false);
+    if (rc || (rc = resident_device_refusals(c, who, table))) return rc;
+    const uint32_t P = (uint32_t)c->sm.n_pairs, R = (flags & DSPI_OUT_TILED) ? (uint32_t)c->sm.row : 0u;
+    if ((reinterpret_cast<uintptr_t>(pairs) & 15u) || (reinterpret_cast<uintptr_t>(arena) & 1u))
+        return fail(c, DSPI_E_INVAL, std::string(who) + ": device pairs are 16-byte aligned (every hipMalloc is) and the arena 2-byte");
+    if (R && emit_tiled_workgroups(c->n_streams, R, P, n_blocks, block_len) > 0x7fffffffull) return fail(c, DSPI_E_INVAL, std::string(who) + ": more than 2^31 - 1 workgroups");
+    // 5. on the device
+    if (!(table_flags & DSPI_TABLE_CHECKED)) {
+        uint64_t at = kTableCheckNone;
+        if ((rc = resident_check(c, resident_table(c, kTableEmit, n_blocks, block_len, arena_bytes), formats, table, &at))) return rc;
+        if (at != kTableCheckNone) return refuse_emit_entry(c, who, at, n_blocks, false, nullptr);
+    }
+    HIPCK(c, hipSetDevice(c->device));
+    if (c->n_paused && (rc = upload_activity(c))) return rc;
+    // (the table stays where it lies: only the formats go up)
+    if ((rc = upload_via_move_area(c, c->d_emit_tab, "hipHostMalloc failed (emit formats)", {{formats, c->n_streams}}))) return rc;
+    const hipError_t e = launch_packettx(pairs, R, table, reinterpret_cast<const uint8_t *>(c->d_emit_tab.get()), activity(c), arena, c->n_streams, P, n_blocks, block_len, c->hs);
+    return e == hipSuccess ? DSPI_OK : fail(c, DSPI_E_HIP, std::string("packetiser launch: ") + hipGetErrorString(e));
+}
+
+// the checker's one launch alone, asynchronous on the context's stream, the answer left in the context's word and not read: what
+// tools/bench_packets_resident.py times.  kind 0: an input table, 1: an emit table; kinds (the depths / formats) and table are DEVICE memory
+int dspi_debug_table_check_launch(dspi_ctx *c, uint32_t kind, const uint8_t *kinds, const uint64_t *table, uint32_t n_blocks, uint32_t block_len, uint64_t arena_bytes) {
+    if (!c || kind > kTableEmit || !kinds || !table || !n_blocks || !block_len || block_len > DSPI_MAX_BLOCK_LEN || (reinterpret_cast<uintptr_t>(table) & 15u)) return DSPI_E_INVAL;
+    if ((uint64_t)c->n_streams * (kind == kTableEmit ? (uint64_t)c->sm.n_pairs : 1u) * n_blocks > kPacketMaxEntries) return DSPI_E_INVAL;
+    if (c->device == DSPI_DEVICE_NONE) return fail(c, DSPI_E_NODEVICE, "host-only context: no table check");
+    HIPCK(c, hipSetDevice(c->device));
+    int rc;
+    if ((c->n_paused && (rc = upload_activity(c))) || (rc = ensure(c, c->d_tabcheck, 8))) return rc;
+    const hipError_t e = launch_tablecheck(resident_table(c, kind, n_blocks, block_len, arena_bytes), table, kinds, activity(c), c->d_tabcheck, 0u, c->hs);
+    return e == hipSuccess ? DSPI_OK : fail(c, DSPI_E_HIP, std::string("table check launch: ") + hipGetErrorString(e));
 }
 
 int dspi_pdm_running(dspi_ctx *c, uint32_t first, uint32_t count, const uint8_t *set, uint8_t *get) {

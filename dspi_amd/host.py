@@ -35,6 +35,7 @@ OUT_CLIP_FLAGS = 0x20
 OUT_WIRE = 0x40      # dspi_process_sources only
 PACKET_SKIP = 2 ** 64 - 1      # dspi_packets_emit: a table entry that emits nothing
 EMIT_CHECK_OVERLAP = 0x1       # dspi_packets_emit_check only
+TABLE_CHECKED = 0x1            # table_flags of the _resident calls: the caller warrants the table; no entry check, no wait
 SRC_SPDIF, SRC_PCM16, SRC_PCM24 = 1, 16, 24
 SRC_LINK = 2         # dspi_process_patched / dspi_patched_bytes only
 MAX_VIEWS = 8
@@ -202,6 +203,13 @@ def lib() -> C.CDLL:
         L.dspi_packets_emit_check.argtypes = [vp, vp, vp, u32, u32, C.c_uint64, u32, C.POINTER(C.c_uint64)]
         L.dspi_packets_emit.argtypes = [vp, vp, u32, u32, vp, vp, vp, C.c_uint64, u32]
         L.dspi_debug_packets_emit_launch.argtypes = [vp, vp, u32, u32, vp, vp, vp, u32]
+    if hasattr(L, "dspi_process_packets_resident"):      # (ABI 8 + resident packet tables: detected by symbol; with it the three other _resident calls)
+        L.dspi_packets_check_resident.argtypes = [vp, vp, vp, u32, u32, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.dspi_packets_emit_check_resident.argtypes = [vp, vp, vp, u32, u32, C.c_uint64, u32, C.POINTER(C.c_uint64)]
+        L.dspi_process_packets_resident.argtypes = [vp, vp, C.c_uint64, vp, vp, u32, u32, C.POINTER(_Out), vp, u32, u32]
+        L.dspi_packets_emit_resident.argtypes = [vp, vp, u32, u32, vp, vp, vp, C.c_uint64, u32, u32]
+        L.dspi_debug_table_check_launch.argtypes = [vp, u32, vp, vp, u32, u32, C.c_uint64]
+        L.dspi_tablecheck_launch_raw.argtypes = [u32, vp, vp, vp, C.c_uint64, u32, u32, C.c_uint64, u32, vp, C.POINTER(C.c_uint64)]      # (no interface: the tests' raw launcher)
     _lib = L
     return L
 
@@ -898,6 +906,49 @@ class Dspi:
     def debug_packets_emit_launch(self, pairs_ptr: int, n_blocks: int, block_len: int, formats_ptr: int, table_ptr: int, arena_ptr: int, tiled: bool = False):
         """dspi_debug_packets_emit_launch: the one launch of packets_emit_device, formats and table already in DEVICE memory and unchecked; asynchronous"""
         self._ck(self.L.dspi_debug_packets_emit_launch(self.h, pairs_ptr, n_blocks, block_len, formats_ptr, table_ptr, arena_ptr, MEM_DEVICE | (OUT_TILED if tiled else 0)), "debug_packets_emit_launch")
+
+    # ---- resident packet tables (include/dspi.h: dspi_process_packets_resident): the twins above with the table in DEVICE memory ----
+    def packets_check_resident(self, bit_depths, table_ptr: int, n_blocks: int, block_len: int, arena_bytes: int):
+        """dspi_packets_check_resident: packets_check on a table in device memory (table_ptr, 16-byte aligned), checked on the GPU and waited for;
+        self.bad_entry as there.  Needs a device."""
+        d = self._depths(bit_depths)
+        bad = C.c_uint64(2 ** 64 - 1)
+        rc = self.L.dspi_packets_check_resident(self.h, d.ctypes.data, table_ptr, n_blocks, block_len, arena_bytes, C.byref(bad))
+        self.bad_entry = None if rc == 0 or bad.value == 2 ** 64 - 1 else bad.value
+        self._ck(rc, "packets_check_resident")
+
+    def packets_emit_check_resident(self, formats, table_ptr: int, n_blocks: int, block_len: int, arena_bytes: int):
+        """dspi_packets_emit_check_resident: packets_emit_check (without the overlap rule) on a table in device memory; self.bad_entry as there"""
+        f = self._formats(formats)
+        bad = C.c_uint64(2 ** 64 - 1)
+        rc = self.L.dspi_packets_emit_check_resident(self.h, f.ctypes.data, table_ptr, n_blocks, block_len, arena_bytes, 0, C.byref(bad))
+        self.bad_entry = None if rc == 0 or bad.value == 2 ** 64 - 1 else bad.value
+        self._ck(rc, "packets_emit_check_resident")
+
+    def process_packets_resident_device(self, arena_ptr: int, arena_bytes: int, bit_depths, table_ptr: int, n_blocks: int, block_len: int, pairs_ptr: int = 0, sub_ptr: int = 0,
+                                        peaks_ptr: int = 0, words_ptr: int = 0, tiled: bool = False, enabled_only: bool = False, spdif: bool = False, wire: bool = False,
+                                        clip_ptr: int = 0, checked: bool = False):
+        """dspi_process_packets_resident: process_packets_device with the table in device memory (the depths stay a host array).  checked=False:
+        the entries are checked on the GPU first and the call waits for that answer; checked=True (DSPI_TABLE_CHECKED): the caller warrants that
+        packets_check_resident accepted this table with these arguments and that no stream was resumed since; fully asynchronous, see sync()."""
+        d = self._depths(bit_depths)
+        out = _Out(pairs_ptr or None, sub_ptr or None, peaks_ptr or None, clip_ptr or None)
+        self._ck(self.L.dspi_process_packets_resident(self.h, arena_ptr, arena_bytes, d.ctypes.data, table_ptr, n_blocks, block_len, C.byref(out), words_ptr or None,
+                                                      MEM_DEVICE | (OUT_TILED if tiled else 0) | (OUT_ENABLED_ONLY if enabled_only else 0) | (OUT_SPDIF if spdif else 0) |
+                                                      (OUT_WIRE if wire else 0) | (OUT_CLIP_FLAGS if clip_ptr else 0), TABLE_CHECKED if checked else 0), "process_packets_resident")
+
+    def packets_emit_resident_device(self, pairs_ptr: int, n_blocks: int, block_len: int, formats, table_ptr: int, arena_ptr: int, arena_bytes: int, tiled: bool = False,
+                                     checked: bool = False):
+        """dspi_packets_emit_resident: packets_emit_device with the table in device memory (the formats stay a host array); checked as in
+        process_packets_resident_device, the warrant being packets_emit_check_resident's"""
+        f = self._formats(formats)
+        self._ck(self.L.dspi_packets_emit_resident(self.h, pairs_ptr, n_blocks, block_len, f.ctypes.data, table_ptr, arena_ptr, arena_bytes, MEM_DEVICE | (OUT_TILED if tiled else 0),
+                                                   TABLE_CHECKED if checked else 0), "packets_emit_resident")
+
+    def debug_table_check_launch(self, kind: int, kinds_ptr: int, table_ptr: int, n_blocks: int, block_len: int, arena_bytes: int):
+        """dspi_debug_table_check_launch: the checker's one launch alone (kind 0: input table and depths, 1: emit table and formats; both in
+        DEVICE memory); the answer is not read; asynchronous"""
+        self._ck(self.L.dspi_debug_table_check_launch(self.h, kind, kinds_ptr, table_ptr, n_blocks, block_len, arena_bytes), "debug_table_check_launch")
 
     def pdm_restart(self, stream: int = ALL):
         self._ck(self.L.dspi_pdm_restart(self.h, stream), "pdm_restart")

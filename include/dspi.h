@@ -84,7 +84,9 @@ extern "C" {
                               * 8 + chained devices: detect by symbol (dspi_process_linked; with it dspi_wire_decode, dspi_wire_view_of, dspi_link_kinds, dspi_wire_view, dspi_link, DSPI_LINK_*; additions only);
                               * 8 + the patch bay: detect by symbol (dspi_process_patched; with it dspi_patched_bytes, dspi_patch, DSPI_SRC_LINK, DSPI_MAX_VIEWS; additions only);
                               * 8 + the meter bridge: detect by symbol (dspi_meters_update; with it dspi_meters_alarms, dspi_status_all, dspi_clear_clips_list; additions only);
-                              * 8 + input from a packet table: detect by symbol (dspi_process_packets; with it dspi_packets_check; additions only) */
+                              * 8 + input from a packet table: detect by symbol (dspi_process_packets; with it dspi_packets_check; additions only)
+                              * 8 + resident packet tables: detect by symbol (dspi_process_packets_resident; with it the three other _resident
+                              *   calls; additions only) */
 
 /* flavours: values equal the firmware's platform ids (config.h:269-270) */
 #define DSPI_FLAVOR_RP2040_Q28 0   /* 7 channels, 5 outputs, int32 Q28, 2048-sample delay lines */
@@ -1190,6 +1192,7 @@ int dspi_process_patched(dspi_ctx *ctx, const void *in, const uint8_t *sources,
  * s * n_blocks + k of the entry refused, and is not written otherwise.
  * LEFT OUT: arenas in host memory; tables in device memory; S/PDIF and linked sources in the same call (the patch bay keeps those); a
  * packet-table OUTPUT (a packetiser); per-packet lengths (block_len is one number per call); an option of dspi_host.
+ * (Tables in device memory are left out of THIS call only: dspi_process_packets_resident, "resident packet tables" below, takes them.)
  * The ABI stays 8: detect by symbol (dspi_process_packets; with it dspi_packets_check; additions only). */
 int dspi_packets_check(const dspi_ctx *ctx, const uint8_t *bit_depths, const uint64_t *table, uint32_t n_blocks, uint32_t block_len,
                        uint64_t arena_bytes, uint64_t *bad_entry /* may be NULL: s * n_blocks + k of the first entry refused */);
@@ -1365,6 +1368,7 @@ int dspi_debug_packets_intake(dspi_ctx *ctx, const void *arena, uint64_t arena_b
  * takes the index of the entry refused, and is not written otherwise.
  * LEFT OUT of the packetiser: the sub channel; wire-layout and S/PDIF sources; 16-bit packets; per-packet lengths; tables in device memory; a
  * fused process-and-emit call; an option of dspi_host.
+ * (Tables in device memory are left out of THIS call only: dspi_packets_emit_resident, "resident packet tables" below, takes them.)
  * The ABI stays 8: detect by symbol (dspi_packets_emit; with it dspi_packets_emit_check; additions only). */
 #define DSPI_PACKET_SKIP UINT64_MAX        /* a table entry that emits nothing */
 #define DSPI_EMIT_CHECK_OVERLAP 0x1u       /* dspi_packets_emit_check only */
@@ -1377,6 +1381,55 @@ int dspi_packets_emit(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_blocks, ui
  * Asynchronous on the context's stream.  For timing (tools/bench_packets_out.py); comes with dspi_packets_emit. */
 int dspi_debug_packets_emit_launch(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_blocks, uint32_t block_len, const uint8_t *formats,
                                    const uint64_t *table, void *arena, uint32_t flags);
+
+/* ---- resident packet tables: both packet calls on a table that lies in device memory ---------------------------------------------------------- */
+/* A fleet host whose arena is a ring repeats its table from call to call, and often builds it on the GPU.  The four calls below are
+ * dspi_packets_check, dspi_packets_emit_check, dspi_process_packets and dspi_packets_emit with ONE difference: `table` is DEVICE memory, 16-byte
+ * aligned (every hipMalloc is), and is read where it lies: it does not travel.  The table's layout, the entry rule, the meaning of every other
+ * argument and every output are those of the host-table calls.  bit_depths and formats stay HOST memory, uint8 [dspi_num_streams]: their
+ * n bytes go up with the call as before, and refusal 3 and the preamp rule are applied on the host as before.  DSPI_MEM_DEVICE is required in
+ * flags of both audio calls (dspi_packets_emit_resident has no CPU path).
+ * THE ENTRY CHECK RUNS ON THE GPU (refusal 5: the first illegal entry of an active stream in table order).
+ *   table_flags == 0, the default route: the call launches the checker on the context's stream, WAITS for its 8-byte answer, and refuses or
+ *             proceeds.  The code, the message (entry index, stream, pair, packet) and *bad_entry are exactly what the host-table call gives for
+ *             the same table.  The call therefore waits for everything the context queued earlier; what it launches afterwards is asynchronous as
+ *             ever.  The table must be complete ON THE CONTEXT'S STREAM when the call is made — written there (dspi_hip_stream), or synchronised
+ *             by the caller — and must not be written before the call's work has finished.
+ *   DSPI_TABLE_CHECKED: no check, no wait, and no upload beyond the n depth / format bytes: the call is fully asynchronous.  THE CALLER WARRANTS
+ *             that dspi_packets_check_resident (dspi_packets_emit_check_resident) accepted THIS table with THESE depths (formats), lengths and
+ *             arena_bytes, and that no stream has been resumed, booted active or added since: a paused stream's row was never looked at.  A
+ *             violated warrant is out-of-bounds access on the device, reads (input) or WRITES (emit) — nothing looks at the entries again, exactly
+ *             as with dspi_debug_packets_emit_launch.  The ring-arena host: check once, then DSPI_TABLE_CHECKED every call until a stream is resumed.
+ * REFUSALS, in this order (a refused call writes nothing and advances nothing):
+ *   1. to 4.  as in the host-table call; with the flag rule of 1: DSPI_MEM_DEVICE missing, and a bit of table_flags other than DSPI_TABLE_CHECKED
+ *   then DSPI_E_NODEVICE on a host-only context
+ *   then DSPI_E_INVAL   a table that is not 16-byte aligned; in dspi_packets_emit_resident the host-table call's pointer alignments and its
+ *                       limit of 2^31 - 1 workgroups
+ *   5.        as in the host-table call, on the default route only
+ *   then, in dspi_process_packets_resident, DSPI_E_UNSUPPORTED: the preamp's refusal, and whatever dspi_process_mixed refuses after it
+ * The two check calls apply the same refusals up to and including 5 (no arena, no pairs, no out) and wait like the default route; *bad_entry is
+ * written at refusal 5 only.  check_flags must be 0: DSPI_EMIT_CHECK_OVERLAP is DSPI_E_INVAL, overlap detection sorts on the CPU and stays with
+ * host tables.  Neither works on a host-only context.
+ * LEFT OUT: overlap detection on device tables; depth and format vectors in device memory; a check fused into the packet kernels; arenas in
+ * host memory; an option of dspi_host.
+ * The ABI stays 8: detect by symbol (dspi_process_packets_resident; with it the other three and dspi_debug_table_check_launch; additions only). */
+#define DSPI_TABLE_CHECKED 0x1u            /* table_flags: the caller warrants the table; no entry check, no wait */
+int dspi_packets_check_resident(dspi_ctx *ctx, const uint8_t *bit_depths, const uint64_t *table /* DEVICE */, uint32_t n_blocks,
+                                uint32_t block_len, uint64_t arena_bytes, uint64_t *bad_entry /* may be NULL */);
+int dspi_packets_emit_check_resident(dspi_ctx *ctx, const uint8_t *formats, const uint64_t *table /* DEVICE */, uint32_t n_blocks,
+                                     uint32_t block_len, uint64_t arena_bytes, uint32_t check_flags /* must be 0 */,
+                                     uint64_t *bad_entry /* may be NULL */);
+int dspi_process_packets_resident(dspi_ctx *ctx, const void *arena, uint64_t arena_bytes, const uint8_t *bit_depths,
+                                  const uint64_t *table /* DEVICE */, uint32_t n_blocks, uint32_t block_len, const dspi_out *out,
+                                  uint32_t *pdm_words /* may be NULL */, uint32_t flags, uint32_t table_flags);
+int dspi_packets_emit_resident(dspi_ctx *ctx, const int32_t *pairs, uint32_t n_blocks, uint32_t block_len, const uint8_t *formats,
+                               const uint64_t *table /* DEVICE */, void *arena, uint64_t arena_bytes, uint32_t flags, uint32_t table_flags);
+/* The checker's one launch alone (dspi_tablecheck.hip), asynchronous on the context's stream; the answer stays in the context's own word and is
+ * not read.  kind 0: an input table [dspi_num_streams][n_blocks], kinds = the depths; kind 1: an emit table, kinds = the formats.  kinds and
+ * table are DEVICE memory, the kinds valid (they are not checked).  For timing (tools/bench_packets_resident.py); comes with
+ * dspi_process_packets_resident. */
+int dspi_debug_table_check_launch(dspi_ctx *ctx, uint32_t kind, const uint8_t *kinds, const uint64_t *table, uint32_t n_blocks,
+                                  uint32_t block_len, uint64_t arena_bytes);
 
 #ifdef __cplusplus
 }
